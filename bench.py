@@ -27,6 +27,11 @@ Extra objects in the line:
                 and `frac_reference_equivalent` SURVEY.md 8d's count of what the reference executes (120)
   collective    N>1 (or --force-collective): ranks seen by torch.distributed, per-rank mean MLP launch time,
                 all-gather time per frame
+
+--dump-outputs DIR writes what the timed path handed its caller in the LAST timed step as DIR/<name>.npy (float32, or
+float64 where the path computes in float64): c3 the frame's rgb / depth / acc; a training workload the step's render
+outputs, its loss and the parameters after the optimiser step.  The inputs are seeded, so two builds run with the same
+arguments can be compared output for output.
 """
 import argparse
 import json
@@ -57,6 +62,7 @@ METRIC = "rays/sec (+ ms/800\u00b2 frame @64 samples) at 1/2/4/8 MI355X; PSNR vs
 W = H = 800
 NEAR, FAR = 2.0, 6.0            # nerf/configs/lego.json:10-11
 NC, NF = 64, 128
+DUMP_MAX_BYTES = 64 << 20       # --dump-outputs: every workload's last step fits whole (c3: 12.8 MB), so nothing is sampled
 
 
 def pose_degrees(radius, theta, phi):
@@ -82,6 +88,19 @@ def make_models(dev):
             m.output_layer_sigma.weight.mul_(50.0)
             m.output_layer_sigma.bias.add_(5.0)
     return coarse, fine
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one out_dir/<name>.npy per tensor of `arrays` (float64 kept, every other dtype as float32).
+    Called after the timed region; refuses to write more than DUMP_MAX_BYTES in all."""
+    host = {name: t.detach().cpu().numpy().astype(np.float64 if t.dtype == torch.float64 else np.float32)
+            for name, t in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES} byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 class MlpTimer:
@@ -163,12 +182,13 @@ def newest_profile(suffix: str):
     return max(found)[1] if found else None
 
 
-def train_workload(args, world, rank, dev, workload=None, steps=None, warmup=None):
+def train_workload(args, world, rank, dev, workload=None, steps=None, warmup=None, dump_dir=None):
     """Secondary workloads (not the headline line): one training step per `step`, data-parallel over ranks
     (each rank its own batch = weak scaling) with one flat RCCL all-reduce of the renderer gradients.
       c4          pi_GAN generator step, 128x128, batch 32 per GPU, Nc=12 Nf=24 (BASELINE config C4)
       c5          pi_GAN training step, 256x256, batch 4 per GPU, Nc=24 Nf=48 (BASELINE config C5)
-      nerf_train  nerf/train_nerf.py step: 1024 rays per GPU, 64+128 samples, coarse+fine NeRF, Adam"""
+      nerf_train  nerf/train_nerf.py step: 1024 rays per GPU, 64+128 samples, coarse+fine NeRF, Adam
+    dump_dir: write the last timed step's outputs there (dump_outputs)"""
     from mirender import dist as mdist, fields, pigan, render_core, train
     torch.manual_seed(rank)
     reduce_events, timed = [], [False]       # (start, end) stream events around every timed step's gradient all-reduce
@@ -192,6 +212,7 @@ def train_workload(args, world, rank, dev, workload=None, steps=None, warmup=Non
         params = list(gen.parameters())
         opt = torch.optim.Adam(params, lr=5e-5, betas=(0.0, 0.9))
         torch.manual_seed(1000 + rank)         # ... its own latents (its share of the global batch) on each
+        np.random.seed(1000 + rank)            # and its own camera poses (the Renderer draws them from NumPy's global RNG)
         z = torch.randn(b, 256, device=dev)
         rays_per_step = b * res * res
         # SURVEY.md 8d counts what the reference executes: coarse forward + 3 x the fine pass's Nc + Nf points (+ the D-step's
@@ -203,16 +224,20 @@ def train_workload(args, world, rank, dev, workload=None, steps=None, warmup=Non
         evals_executed = 3 * (nc + nf) + ((nc + nf) if c5 else 0)
         flops = rays_per_step * evals * fields.FLOPS_PER_POINT[fields.FILM_SIREN_NERF]
 
-        def step(i):
+        def step(i, keep=False):
+            kept = {}
             if c5:
                 with torch.no_grad():
-                    gen(z, seed=500 + i)                                             # fake images for the D step
+                    kept["fake_image"] = gen(z, seed=500 + i)                         # fake images for the D step
+                if not keep:
+                    kept.clear()
             img = gen(z, seed=100 + i)
             loss = torch.nn.functional.softplus(-img.mean(dim=(1, 2, 3))).mean()   # stand-in for -D(G(z))
             opt.zero_grad(set_to_none=True)
             loss.backward()
             mdist.allreduce_grads(params, timing=reduce_events if timed[0] else None)
             opt.step()
+            return dict(kept, image=img.detach(), loss=loss.detach()) if keep else None
         name = (f"pi_GAN training step {res}x{res}, batch 4/GPU, 24+48 samples (BASELINE config C5): D-step generator forward "
                 "+ G-step fwd+bwd+Adam, RCCL grad all-reduce" if c5 else
                 "pi_GAN generator training step 128x128, batch 32/GPU, 12+24 samples (BASELINE config C4), fwd+bwd+Adam")
@@ -233,13 +258,15 @@ def train_workload(args, world, rank, dev, workload=None, steps=None, warmup=Non
         evals = evals_executed = 3 * (nc + nc + nf)                      # two fields: nothing repeats
         flops = rays_per_step * evals * fields.FLOPS_PER_POINT[fields.NERF]
 
-        def step(i):
+        def step(i, keep=False):
             outs = render_core.render_rays(rays, NEAR, FAR, coarse, fine, nc, nf, seed=i)
             loss, _psnr = train.nerf_loss(outs, tgt[:, :3], tgt[:, 3], use_alpha=True, use_fine_model=True)  # train_nerf.py:158-167
             opt.zero_grad(set_to_none=True)
             loss.backward()
             mdist.allreduce_grads(params, timing=reduce_events if timed[0] else None)
             opt.step()
+            names = ("rgb_c", "depth_c", "acc_c", "rgb_f", "depth_f", "acc_f")
+            return dict({k: t.detach() for k, t in zip(names, outs)}, loss=loss.detach()) if keep else None
         name = "nerf/train_nerf.py step: 1024 rays/GPU, 64+128 samples, coarse+fine NeRF 8x256, fwd+bwd+fused Adam"
 
     def sync():
@@ -258,10 +285,14 @@ def train_workload(args, world, rank, dev, workload=None, steps=None, warmup=Non
     timed[0] = True
     t0 = time.perf_counter()
     for i in range(steps):
-        step(settle + warmup + i)
+        # only the last step of a dumping run keeps its outputs: every other step frees them as it always has (the pi_GAN
+        # steps' allocator pattern, see above)
+        last = step(settle + warmup + i, keep=dump_dir is not None and i == steps - 1)
     sync()
     mine_s = elapsed = time.perf_counter() - t0
     timed[0] = False
+    if dump_dir is not None:
+        dump_outputs(dump_dir, dict(last, params=torch.cat([p.detach().reshape(-1) for p in params])))
     per_rank_step_ms, per_rank_reduce_ms = [mine_s / steps * 1e3], [None]
     if reduce_events:
         per_rank_reduce_ms = [sum(a.elapsed_time(b) for a, b in reduce_events) / len(reduce_events)]
@@ -415,7 +446,11 @@ def main():
                          "all-reduce anyway (mirender.dist.FORCE_COLLECTIVE), so the collective code runs on a one-GPU box")
     ap.add_argument("--workload", default="c3", choices=["c3", "c4", "c5", "nerf_train"],
                     help="c3 (default, the headline line) | c4 | c5 | nerf_train (secondary training workloads)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: this process has not touched the GPU (importing torch does not initialise
@@ -447,7 +482,7 @@ def main():
         dist.init_process_group("nccl", device_id=dev)
         mdist.FORCE_COLLECTIVE = True
     if args.workload != "c3":
-        line = train_workload(args, world, rank, dev)
+        line = train_workload(args, world, rank, dev, dump_dir=args.dump_outputs if rank == 0 else None)
         if rank == 0:
             print(json.dumps(line), flush=True)
         if dist.is_initialized():
@@ -490,6 +525,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert bool(torch.isfinite(out[0]).all())
+    if args.dump_outputs and rank == 0:          # every rank holds the whole frame after the all-gather
+        dump_outputs(args.dump_outputs, {"rgb": out[0], "depth": out[1], "acc": out[2]})
 
     # roofline of the dominant kernel, from the events recorded inside the timed region (this rank)
     flops_pt = fields.FLOPS_PER_POINT[fields.NERF]

@@ -7,8 +7,14 @@ through the C-ABI, checked against the oracle and the committed fixtures.
 import os
 import sys
 
-import numpy as np
-import pytest
+# Before anything loads torch: the fp32 CPU oracle is compared with fixtures recorded from the reference
+# (tests/golden/make_golden.py, which pins the same branch).  MKL's default sgemm kernels depend on the host's CPU vendor,
+# ISA and thread count and move those results by up to 3e-4 between hosts; the strict AVX2 branch gives the same bits on
+# every AVX2 host at any thread count.
+os.environ["MKL_CBWR"] = "AVX2,STRICT"
+
+import numpy as np  # noqa: E402
+import pytest  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "msra-practice-project_amd")

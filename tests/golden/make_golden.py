@@ -25,8 +25,13 @@ import contextlib
 import os
 import sys
 
-import numpy as np
-import torch
+# MKL's default sgemm kernels depend on the host's CPU vendor, ISA and thread count (fp32 results move by up to 3e-4
+# between hosts); its strict AVX2 branch gives the same bits on every AVX2 host at any thread count.  tests/conftest.py
+# pins the same branch.
+os.environ["MKL_CBWR"] = "AVX2,STRICT"
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))

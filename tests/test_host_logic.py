@@ -176,6 +176,26 @@ def test_bench_spawns_its_own_ranks(monkeypatch):
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
 
 
+def test_bench_dump_outputs_writes_npy_within_the_cap(tmp_path, monkeypatch):
+    """--dump-outputs writes one float32 .npy per array (float64 stays float64), refuses more than 64 MB, and a
+    --steps that would time nothing is rejected before anything touches the GPU."""
+    import sys
+    import bench
+    src = {"rgb": torch.linspace(0, 1, 6, dtype=torch.float16).reshape(2, 3), "loss": torch.tensor(0.25, dtype=torch.float64)}
+    bench.dump_outputs(str(tmp_path / "out"), src)
+    rgb, loss = np.load(tmp_path / "out" / "rgb.npy"), np.load(tmp_path / "out" / "loss.npy")
+    assert rgb.dtype == np.float32 and rgb.shape == (2, 3) and np.array_equal(rgb, src["rgb"].float().numpy())
+    assert loss.dtype == np.float64 and loss.shape == () and float(loss) == 0.25
+    with pytest.raises(ValueError, match="limit"):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": torch.zeros(bench.DUMP_MAX_BYTES // 4 + 1)})
+    assert not (tmp_path / "big").exists()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0", "--dump-outputs", str(tmp_path / "none")])
+    monkeypatch.setattr(torch.cuda, "set_device", lambda *_: (_ for _ in ()).throw(AssertionError("touched the GPU")))
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert e.value.code == 2
+
+
 def _rebuild_from_attrs(kind_name, layers):
     """A torch module tree whose layer objects carry exactly what tests/golden/ref_layer_attrs.json recorded from the
     reference's own classes (class name, activation_name, w_0, the module after a Linear in its Sequential)."""
