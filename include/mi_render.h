@@ -28,6 +28,7 @@ extern "C" {
 #define MI_OK 0
 #define MI_EINVAL (-1)   /* bad argument (shape, kind, null pointer) */
 #define MI_EHIP (-2)     /* HIP runtime error at launch */
+#define MI_ERANGE (-3)   /* marching cubes: level outside [min, max] of the volume */
 
 /* Field MLP kinds (state-dict layouts: SURVEY.md §8a a6-a8). */
 #define MI_FIELD_NERF 0                   /* nerf/nerf.py:52-94   NeRF            */
@@ -262,6 +263,23 @@ int mi_adam_step(int n_fields, const int* kinds, float* const* params, const flo
                  float* const* exp_avg_sq, const int64_t* numel, float step_size, float one_minus_beta1, float beta2,
                  float one_minus_beta2, float eps, float bias_correction2_sqrt, float* const* packed_fwd,
                  float* const* packed_bwd, void* stream);
+
+/* ---- marching cubes (mesh_stages.hip): the mesh half of create_mesh, pi_GAN/utils.py:109-180 ---------
+ * skimage.measure.marching_cubes_lewiner(volume, level, spacing, gradient_direction, allow_degenerate=True) on a
+ * C-contiguous fp32 device volume [nx, ny, nz] (nz fastest); every axis >= 2.  Two calls on one stream, one workspace
+ * of mi_mc_workspace_bytes (needs no GPU; about 2 bytes per voxel):
+ *   mi_marching_cubes_count  sweeps the volume, returns the vertex and triangle counts (synchronises the stream);
+ *                            MI_ERANGE when level is outside [min, max] of the volume, MI_EINVAL when V >= 2^31;
+ *   mi_marching_cubes_emit   with the same volume, level and workspace: verts[V,3] (f32, axis order of the volume,
+ *                            times spacing[3]), faces[F,3] (int32), normals[V,3], values[V].  descent != 0 gives
+ *                            skimage's default winding, 0 its 'ascent' winding.
+ * The output is identical from run to run: vertices in order of owning voxel then axis, triangles in order of cube. */
+int64_t mi_mc_workspace_bytes(int64_t nx, int64_t ny, int64_t nz);
+int mi_marching_cubes_count(const float* volume, int64_t nx, int64_t ny, int64_t nz, double level, void* workspace,
+                            int64_t* n_verts, int64_t* n_faces, void* stream);
+int mi_marching_cubes_emit(const float* volume, int64_t nx, int64_t ny, int64_t nz, double level, const double* spacing,
+                           int descent, void* workspace, float* verts, int* faces, float* normals, float* values,
+                           void* stream);
 
 /* ---- measurement hooks (bench.py) ---------------------------------------------------- */
 

@@ -23,9 +23,10 @@ SOURCES = {
     "render_stages.hip": ["-ffp-contract=off"],
     "eval_stages.hip": ["-ffp-contract=off"],
     "adam_step.hip": [],
+    "mesh_stages.hip": [],
     "api.hip": [],
 }
-HEADERS = ["field_layout.h", "mi_common.h", "mi_math.h", "field_mlp_device.h", os.path.join("..", "..", "include", "mi_render.h")]
+HEADERS = ["field_layout.h", "mi_common.h", "mesh_cube.h", "mi_math.h", "field_mlp_device.h", os.path.join("..", "..", "include", "mi_render.h")]
 
 
 def _stale(target, deps):
