@@ -1,15 +1,15 @@
-// adam_step.hip - the optimiser step of nerf/train_nerf.py:98,168 (torch.optim.Adam, betas (0.9, 0.999), no weight
-// decay, no amsgrad) for the parameters of up to two fields, FUSED with the refresh of their packed MFMA weight
-// streams (gfx950).
+// adam_step.hip - writers of the packed weight streams (field_layout.h) of every field kind (gfx950): the pack kernel,
+// and the optimiser step of nerf/train_nerf.py:98,168 (torch.optim.Adam, betas (0.9, 0.999), no weight decay, no amsgrad)
+// for the parameters of up to two fields, FUSED with the refresh of their streams.
 //
-// After a torch optimiser step the renderer has to repack both streams of each model (forward order, and the
-// transposed order of the backward chain: field_layout.h) from the updated parameters: two optimiser-side launches
-// and four pack launches per step, on a step that is launch-bound at the reference's 1024-ray batch.  Here one
-// launch does all of it: thread = one parameter element; it applies Adam to (p, m, v) and SCATTERS the new value to
-// every position of the two streams that holds it, by inverting the item tables (an element sits in at most a few
-// items: its K block of the forward stream, its K block of the transposed stream, a VEC / PLAIN piece for biases,
-// head rows and K = 3 columns).  Padding entries of the streams never change, so they are written once by the
-// ordinary pack kernels and left alone.
+// pack_kernel writes a whole stream, forward or transposed, from the parameter tensors (mi_field_pack /
+// mi_field_pack_bwd).  After a torch optimiser step the renderer would have to repack both streams of each model that
+// way: two optimiser-side launches and four pack launches per step, on a step that is launch-bound at the reference's
+// 1024-ray batch.  adam_pack_kernel does all of it in one launch: thread = one parameter element; it applies Adam to
+// (p, m, v) and SCATTERS the new value to every position of the two streams that holds it, by inverting the item tables
+// (an element sits in at most a few items: its K block of the forward stream, its K block of the transposed stream, a
+// VEC / PLAIN piece for biases, head rows and K = 3 columns).  Padding entries of the streams never change, so they are
+// written once by pack_kernel and left alone.
 //
 // Arithmetic follows torch's multi-tensor Adam op by op (torch/optim/adam.py:_multi_tensor_adam): lerp of exp_avg,
 // mul + addcmul of exp_avg_sq, sqrt / bias_correction2_sqrt + eps, addcdiv with -lr / bias_correction1; the scalars
@@ -17,14 +17,57 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "field_layout.h"
+#include "field_kinds.h"
 #include "mi_common.h"
 
 namespace mi {
 
-__constant__ PackTable c_fwd[5] = {build_nerf(), build_siren_nerf(), build_film(true), build_film(false), build_tiny_nerf()};
-__constant__ PackTable c_bwd[5] = {build_nerf_bwd(), build_siren_nerf_bwd(), build_film_bwd(true), build_film_bwd(false),
-                                   build_tiny_nerf_bwd()};
+// the only device copies of the item tables
+__constant__ PackTable c_fwd[MI_FIELD_KINDS] = {kFieldKinds[0].fwd, kFieldKinds[1].fwd, kFieldKinds[2].fwd, kFieldKinds[3].fwd,
+                                                kFieldKinds[4].fwd};
+__constant__ PackTable c_bwd[MI_FIELD_KINDS] = {kFieldKinds[0].bwd, kFieldKinds[1].bwd, kFieldKinds[2].bwd, kFieldKinds[3].bwd,
+                                                kFieldKinds[4].bwd};
+
+struct PackSrc { const float* p[2 * kMaxLayers]; };
+
+// grid: (32, n_items); block 256.  One block row per item of the kind's forward (dir = STREAM_FWD) or transposed table.
+__global__ void pack_kernel(int kind, int dir, PackSrc src_params, float* __restrict__ dst, float w0) {
+    const PackTable& t = dir == STREAM_FWD ? c_fwd[kind] : c_bwd[kind];
+    const int it = blockIdx.y;
+    if (it >= t.n_items) return;
+    if (it == 0 && blockIdx.x == 0) {                        // the trailer piece: hyper-parameters (field_layout.h:kTrailer)
+        float* tr = dst + packed_body_floats(t);
+        tr[threadIdx.x] = threadIdx.x == 0 ? w0 : (threadIdx.x == 1 ? w0 * w0 : 0.f);
+    }
+    const PackItem item = t.item[it];
+    float* out = dst + t.dst_off[it];
+    const float* src = src_params.p[item.param];
+    if (item.type == ITEM_CHUNK) {
+        const int total = item.mb * 1024;
+        for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += 32 * 256) {
+            int q = idx & 3, lane = (idx >> 2) & 63, rm = idx >> 8;
+            int m = rm % item.mb, rg = rm / item.mb;
+            int row = 32 * m + (lane & 31);
+            int c = 8 * rg + 4 * (lane >> 5) + q;
+            float v = 0.f;
+            if (row < item.rows_valid && c < item.n_valid)
+                v = src[(int64_t)row * item.ld + item.offset + (int64_t)c * item.stride];
+            out[idx] = v;
+        }
+    } else if (blockIdx.x == 0) {
+        const int f = threadIdx.x;  // 256 features per piece
+        if (item.type == ITEM_VEC) out[vec_slot(f)] = f < item.n_valid ? src[item.offset + (int64_t)f * item.stride] : 0.f;
+        else out[f] = f < item.n_valid ? src[f] : 0.f;
+    }
+}
+
+int launch_pack(int kind, StreamDir dir, const float* const* params, int n_params, float w0, float* packed, hipStream_t stream) {
+    PackSrc src{};
+    for (int i = 0; i < n_params && i < 2 * kMaxLayers; ++i) src.p[i] = params[i];
+    const PackTable& t = dir == STREAM_FWD ? kFieldKinds[kind].fwd : kFieldKinds[kind].bwd;
+    hipLaunchKernelGGL(pack_kernel, dim3(32, t.n_items), dim3(256), 0, stream, kind, (int)dir, src, packed, w0);
+    return check_launch("pack_kernel");
+}
 
 constexpr int kAdamMaxParams = 48;      // two fields of up to 24 tensors
 constexpr int kAdamMaxHits = 16;        // stream items per parameter tensor the kernel's hit lists hold
@@ -41,11 +84,9 @@ constexpr int max_items_per_param(const PackTable& t) {
     return worst;
 }
 constexpr int max_items_per_param_all() {
-    const PackTable all[10] = {build_nerf(), build_siren_nerf(), build_film(true), build_film(false), build_tiny_nerf(),
-                               build_nerf_bwd(), build_siren_nerf_bwd(), build_film_bwd(true), build_film_bwd(false),
-                               build_tiny_nerf_bwd()};
     int worst = 0;
-    for (int k = 0; k < 10; ++k) { const int n = max_items_per_param(all[k]); worst = n > worst ? n : worst; }
+    for (const FieldKind& k : kFieldKinds)
+        for (const PackTable* t : {&k.fwd, &k.bwd}) { const int n = max_items_per_param(*t); worst = n > worst ? n : worst; }
     return worst;
 }
 static_assert(max_items_per_param_all() <= kAdamMaxHits, "adam_pack_kernel: a parameter sits in more stream items than hit_f / hit_b hold");

@@ -5,7 +5,7 @@
 #include <stdio.h>
 
 #include "../../include/mi_render.h"
-#include "field_layout.h"
+#include "field_kinds.h"
 #include "mi_common.h"
 
 namespace mi {
@@ -32,26 +32,6 @@ int check_launch(const char* what) {
     }
     return MI_OK;
 }
-
-// implemented in field_mlp.hip / field_mlp_bwd.hip
-const PackTable* host_table(int kind);
-const PackTable* host_table_bwd(int kind);
-static const int kNumLayers[MI_FIELD_KINDS] = {12, 12, 11, 11, 7};
-// multiply-accumulates of the linear layers per point (a6, a7, a8)
-static const int64_t kMacs[MI_FIELD_KINDS] = {591488, 559616, 526848, 526080, 248448};
-// (out, in) of every linear layer in mi_field_pack order (nerf/nerf.py:59-73, 128-146; pi_GAN/modules.py:76-94)
-static const int kLayerDims[MI_FIELD_KINDS][12][2] = {
-    {{256, 60}, {256, 256}, {256, 256}, {256, 256}, {256, 256}, {256, 316}, {256, 256}, {256, 256}, {256, 256}, {128, 280}, {1, 256}, {3, 128}},
-    {{256, 3}, {256, 256}, {256, 256}, {256, 256}, {256, 256}, {256, 259}, {256, 256}, {256, 256}, {256, 256}, {128, 259}, {1, 256}, {3, 128}},
-    {{256, 3}, {256, 256}, {256, 256}, {256, 256}, {256, 256}, {256, 256}, {256, 256}, {256, 256}, {1, 256}, {256, 259}, {3, 256}, {0, 0}},
-    {{256, 3}, {256, 256}, {256, 256}, {256, 256}, {256, 256}, {256, 256}, {256, 256}, {256, 256}, {1, 256}, {256, 256}, {3, 256}, {0, 0}},
-    {{256, 60}, {256, 256}, {256, 256}, {256, 256}, {128, 280}, {1, 256}, {3, 128}, {0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}}};
-
-static bool bad_kind(int kind) {
-    if (kind < 0 || kind >= MI_FIELD_KINDS) { set_error("unknown field kind %d", kind); return true; }
-    return false;
-}
-static bool is_film(int kind) { return kind == MI_FIELD_FILM_SIREN_NERF || kind == MI_FIELD_FILM_SIREN_NERF_NODIR; }
 
 static int eval_common(int kind, const float* packed, const float* film, const float* a, const float* z,
                        int64_t n_groups, int64_t ppg, int64_t rpg, int S, int mode, float* out, hipStream_t s,
@@ -82,14 +62,15 @@ extern "C" {
 int mi_abi_version(void) { return 4; }
 const char* mi_last_error(void) { return g_err; }
 
-int mi_field_num_params(int kind) { return bad_kind(kind) ? MI_EINVAL : 2 * kNumLayers[kind]; }
-int64_t mi_field_packed_floats(int kind) { return bad_kind(kind) ? MI_EINVAL : packed_floats(*host_table(kind)); }
-int64_t mi_field_macs(int kind) { return bad_kind(kind) ? MI_EINVAL : kMacs[kind]; }
+int mi_field_num_params(int kind) { return bad_kind(kind) ? MI_EINVAL : 2 * kFieldKinds[kind].n_layers; }
+int64_t mi_field_packed_floats(int kind) { return bad_kind(kind) ? MI_EINVAL : packed_floats(kFieldKinds[kind].fwd); }
+int64_t mi_field_macs(int kind) { return bad_kind(kind) ? MI_EINVAL : kFieldKinds[kind].macs(); }
 int mi_field_param_shape(int kind, int index, int64_t* rows, int64_t* cols) {
     if (bad_kind(kind)) return MI_EINVAL;
-    if (index < 0 || index >= 2 * kNumLayers[kind] || !rows || !cols) { set_error("mi_field_param_shape: bad arguments"); return MI_EINVAL; }
-    *rows = kLayerDims[kind][index / 2][0];
-    *cols = (index & 1) ? 1 : kLayerDims[kind][index / 2][1];
+    const FieldKind& k = kFieldKinds[kind];
+    if (index < 0 || index >= 2 * k.n_layers || !rows || !cols) { set_error("mi_field_param_shape: bad arguments"); return MI_EINVAL; }
+    *rows = k.dims[index / 2][0];
+    *cols = (index & 1) ? 1 : k.dims[index / 2][1];
     return MI_OK;
 }
 
@@ -108,14 +89,14 @@ static int check_w0(int kind, float w_0, const char* fn) {
 int mi_field_pack(int kind, const float* const* params, int n_params, float w_0, float* packed, void* stream) {
     if (bad_kind(kind)) return MI_EINVAL;
     if (!params || !packed) { set_error("null pointer argument"); return MI_EINVAL; }
-    if (n_params != 2 * kNumLayers[kind]) {
-        set_error("kind %d expects %d parameter tensors, got %d", kind, 2 * kNumLayers[kind], n_params);
+    if (n_params != 2 * kFieldKinds[kind].n_layers) {
+        set_error("kind %d expects %d parameter tensors, got %d", kind, 2 * kFieldKinds[kind].n_layers, n_params);
         return MI_EINVAL;
     }
     for (int i = 0; i < n_params; ++i)
         if (!params[i]) { set_error("parameter %d is null", i); return MI_EINVAL; }
     if (int rc = check_w0(kind, w_0, "mi_field_pack")) return rc;
-    return launch_pack(kind, params, n_params, w_0, packed, (hipStream_t)stream);
+    return launch_pack(kind, STREAM_FWD, params, n_params, w_0, packed, (hipStream_t)stream);
 }
 
 int mi_field_eval_points(int kind, const float* packed, const float* film, const float* x, int64_t n_groups,
@@ -299,17 +280,17 @@ int mi_composite_bwd(int64_t n, int n_samples, const float* raw, const float* z,
     return launch_composite_bwd(n, n_samples, raw, z, rays, g_rgb, g_depth, g_acc, g_weights, g_raw, (hipStream_t)stream);
 }
 
-int64_t mi_field_packed_bwd_floats(int kind) { return bad_kind(kind) ? MI_EINVAL : packed_floats(*host_table_bwd(kind)); }
+int64_t mi_field_packed_bwd_floats(int kind) { return bad_kind(kind) ? MI_EINVAL : packed_floats(kFieldKinds[kind].bwd); }
 
 int mi_field_pack_bwd(int kind, const float* const* params, int n_params, float w_0, float* packed_bwd, void* stream) {
     if (bad_kind(kind)) return MI_EINVAL;
-    if (!params || !packed_bwd || n_params != 2 * kNumLayers[kind]) { set_error("mi_field_pack_bwd: bad arguments"); return MI_EINVAL; }
+    if (!params || !packed_bwd || n_params != 2 * kFieldKinds[kind].n_layers) { set_error("mi_field_pack_bwd: bad arguments"); return MI_EINVAL; }
     if (int rc = check_w0(kind, w_0, "mi_field_pack_bwd")) return rc;
-    return launch_pack_bwd(kind, params, n_params, w_0, packed_bwd, (hipStream_t)stream);
+    return launch_pack(kind, STREAM_BWD, params, n_params, w_0, packed_bwd, (hipStream_t)stream);
 }
 
-int64_t mi_field_train_acts_floats(int kind) { return bad_kind(kind) ? MI_EINVAL : train_acts_floats(kind); }
-int64_t mi_field_train_grads_floats(int kind) { return bad_kind(kind) ? MI_EINVAL : train_grads_floats(kind); }
+int64_t mi_field_train_acts_floats(int kind) { return bad_kind(kind) ? MI_EINVAL : region_total(kFieldKinds[kind].acts); }
+int64_t mi_field_train_grads_floats(int kind) { return bad_kind(kind) ? MI_EINVAL : region_total(kFieldKinds[kind].grads); }
 int64_t mi_field_bwd_partial_floats(int64_t points) { return bwd_partial_floats(points); }
 
 int mi_field_eval_rays_train(int kind, const float* packed, const float* film, const float* rays, const float* z,
@@ -317,7 +298,6 @@ int mi_field_eval_rays_train(int kind, const float* packed, const float* film, c
                              void* stream) {
     if (n_samples <= 0 || !acts) { set_error("mi_field_eval_rays_train: bad arguments"); return MI_EINVAL; }
     if (bad_kind(kind)) return MI_EINVAL;
-    if (train_acts_floats(kind) < 0) { set_error("kind %d has no training path yet", kind); return MI_EINVAL; }
     return eval_common(kind, packed, film, rays, z, n_groups, rays_per_group * n_samples, rays_per_group, n_samples, 1,
                        raw, (hipStream_t)stream, acts);
 }
@@ -326,7 +306,6 @@ int mi_field_eval_points_train(int kind, const float* packed, const float* film,
                                int64_t points_per_group, float* out, float* acts, void* stream) {
     if (!acts) { set_error("mi_field_eval_points_train: bad arguments"); return MI_EINVAL; }
     if (bad_kind(kind)) return MI_EINVAL;
-    if (train_acts_floats(kind) < 0) { set_error("kind %d has no training path yet", kind); return MI_EINVAL; }
     return eval_common(kind, packed, film, x, nullptr, n_groups, points_per_group, 0, 1, 0, out, (hipStream_t)stream, acts);
 }
 
@@ -340,8 +319,8 @@ int mi_field_backward(int kind, const float* packed_bwd, const float* film, cons
                       const float* const* params, int n_params, float* grad_film, void* stream) {
     if (bad_kind(kind)) return MI_EINVAL;
     if (!packed_bwd || !acts || !grads_ws || !raw || !g_raw || !partial_ws || !grad_params ||
-        n_params != 2 * kNumLayers[kind]) { set_error("mi_field_backward: bad arguments"); return MI_EINVAL; }
-    const bool film_kind = kind == 2 || kind == 3;
+        n_params != 2 * kFieldKinds[kind].n_layers) { set_error("mi_field_backward: bad arguments"); return MI_EINVAL; }
+    const bool film_kind = is_film(kind);
     for (int i = 0; i < n_params; ++i) {
         if (!grad_params[i]) { set_error("gradient pointer %d is null", i); return MI_EINVAL; }
         if (film_kind && (!params || !params[i])) { set_error("FiLM kinds need parameter pointer %d", i); return MI_EINVAL; }
@@ -411,7 +390,7 @@ int mi_adam_step(int n_fields, const int* kinds, float* const* params, const flo
     for (int f = 0; f < n_fields; ++f) {
         if (bad_kind(kinds[f])) return MI_EINVAL;
         if (!packed_fwd[f]) { set_error("mi_adam_step: field %d has no packed stream", f); return MI_EINVAL; }
-        n_params[f] = 2 * kNumLayers[kinds[f]];
+        n_params[f] = 2 * kFieldKinds[kinds[f]].n_layers;
         total += n_params[f];
     }
     for (int t = 0; t < total; ++t)

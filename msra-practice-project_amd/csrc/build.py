@@ -26,7 +26,7 @@ SOURCES = {
     "mesh_stages.hip": [],
     "api.hip": [],
 }
-HEADERS = ["field_layout.h", "mi_common.h", "mesh_cube.h", "mi_math.h", "field_mlp_device.h", os.path.join("..", "..", "include", "mi_render.h")]
+HEADERS = ["field_layout.h", "field_kinds.h", "mi_common.h", "mesh_cube.h", "mi_math.h", "field_mlp_device.h", os.path.join("..", "..", "include", "mi_render.h")]
 
 
 def _stale(target, deps):

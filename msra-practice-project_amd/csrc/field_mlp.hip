@@ -1,4 +1,4 @@
-// field_mlp.hip - fused radiance-field MLP forward for gfx950 (MI355X), plus the weight packer.
+// field_mlp.hip - fused radiance-field MLP forward for gfx950 (MI355X).
 //
 // What it replaces: the `network(inputs[M,6]) -> [M,4]` call inside run_network
 // (reference nerf/render.py:59-75) for NeRF / SirenNeRF (nerf/nerf.py:52-170), FilmSirenNeRF
@@ -20,80 +20,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "field_kinds.h"
 #include "field_mlp_device.h"
 
 namespace mi {
-
-// ---- packed tables in constant memory (built at compile time) -----------------------------
-__constant__ PackTable c_tab_nerf = build_nerf();
-__constant__ PackTable c_tab_siren = build_siren_nerf();
-__constant__ PackTable c_tab_film = build_film(true);
-__constant__ PackTable c_tab_film_nodir = build_film(false);
-__constant__ PackTable c_tab_tiny = build_tiny_nerf();
-
-static constexpr PackTable h_tab_nerf = build_nerf();
-static constexpr PackTable h_tab_siren = build_siren_nerf();
-static constexpr PackTable h_tab_film = build_film(true);
-static constexpr PackTable h_tab_film_nodir = build_film(false);
-static constexpr PackTable h_tab_tiny = build_tiny_nerf();
-
-const PackTable* host_table(int kind) {
-    switch (kind) {
-        case 0: return &h_tab_nerf;
-        case 1: return &h_tab_siren;
-        case 2: return &h_tab_film;
-        case 3: return &h_tab_film_nodir;
-        case 4: return &h_tab_tiny;
-    }
-    return nullptr;
-}
-
-struct ParamPtrs { const float* p[24]; };
-
-__device__ __forceinline__ const PackTable& dev_table(int kind) {
-    switch (kind) {
-        case 0: return c_tab_nerf;
-        case 1: return c_tab_siren;
-        case 2: return c_tab_film;
-        case 3: return c_tab_film_nodir;
-        default: return c_tab_tiny;
-    }
-}
-
-// grid: (32, n_items); block 256.  One block row per item.
-__global__ void pack_kernel(int kind, ParamPtrs pp, float* __restrict__ dst, float w0) {
-    const PackTable& t = dev_table(kind);
-    const int it = blockIdx.y;
-    if (it >= t.n_items) return;
-    if (it == 0 && blockIdx.x == 0) {                        // the trailer piece: hyper-parameters (field_layout.h:kTrailer)
-        float* tr = dst + packed_body_floats(t);
-        tr[threadIdx.x] = threadIdx.x == 0 ? w0 : (threadIdx.x == 1 ? w0 * w0 : 0.f);
-    }
-    const PackItem item = t.item[it];
-    float* out = dst + t.dst_off[it];
-    const float* src = pp.p[item.param];
-    if (item.type == ITEM_CHUNK) {
-        const int total = item.mb * 1024;
-        for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += 32 * 256) {
-            int q = idx & 3, lane = (idx >> 2) & 63, rm = idx >> 8;
-            int m = rm % item.mb, rg = rm / item.mb;
-            int row = 32 * m + (lane & 31);
-            int c = 8 * rg + 4 * (lane >> 5) + q;
-            float v = 0.f;
-            if (row < item.rows_valid && c < item.n_valid)
-                v = src[(int64_t)row * item.ld + item.offset + (int64_t)c * item.stride];
-            out[idx] = v;
-        }
-    } else if (blockIdx.x == 0) {
-        const int f = threadIdx.x;  // 256 features per piece
-        if (item.type == ITEM_VEC) {
-            float v = f < item.n_valid ? src[item.offset + (int64_t)f * item.stride] : 0.f;
-            out[vec_slot(f)] = v;
-        } else {
-            out[f] = f < item.n_valid ? src[f] : 0.f;
-        }
-    }
-}
 
 // =========================================================================================
 // NeRF (nerf/nerf.py:75-94) and TinyNeRF
@@ -306,7 +236,7 @@ __global__ __launch_bounds__(256, 1) void film_fwd_kernel(MlpArgs a) {
     const int64_t tile = blockIdx.x % a.tiles_per_group;
     Ctx c = make_ctx(smem, a, group);
     // FilmSiren's w_0 (pi_GAN/modules.py:11,73): the first float of the stream's trailer, a uniform (scalar) load
-    constexpr int kBody = USE_DIR ? packed_body_floats(h_tab_film) : packed_body_floats(h_tab_film_nodir);
+    constexpr int kBody = packed_body_floats(kFieldKinds[USE_DIR ? MI_FIELD_FILM_SIREN_NERF : MI_FIELD_FILM_SIREN_NERF_NODIR].fwd);
     c.w0 = a.packed[kBody];
     issue_first_stage<4, 0, true>(c, 0, 0, 0);   // input_layer: bias + 3 columns, FiLM row 0
 
@@ -365,46 +295,33 @@ __global__ __launch_bounds__(256, 1) void film_fwd_kernel(MlpArgs a) {
 }
 
 // ---- host side ---------------------------------------------------------------------------
-int launch_pack(int kind, const float* const* params, int n_params, float w0, float* packed, hipStream_t stream) {
-    const PackTable* t = host_table(kind);
-    ParamPtrs pp{};
-    for (int i = 0; i < n_params && i < 24; ++i) pp.p[i] = params[i];
-    hipLaunchKernelGGL(pack_kernel, dim3(32, t->n_items), dim3(256), 0, stream, kind, pp, packed, w0);
-    return check_launch("pack_kernel");
-}
+// [kind][save]: the inference and the training (layer inputs saved) instance of each kind's kernel
+static const void* const kFwdKernels[MI_FIELD_KINDS][2] = {
+    {(const void*)nerf_fwd_kernel<false, false>, (const void*)nerf_fwd_kernel<false, true>},     // MI_FIELD_NERF
+    {(const void*)siren_fwd_kernel<false>, (const void*)siren_fwd_kernel<true>},                 // MI_FIELD_SIREN_NERF
+    {(const void*)film_fwd_kernel<true, false>, (const void*)film_fwd_kernel<true, true>},       // MI_FIELD_FILM_SIREN_NERF
+    {(const void*)film_fwd_kernel<false, false>, (const void*)film_fwd_kernel<false, true>},     // ..._NODIR
+    {(const void*)nerf_fwd_kernel<true, false>, (const void*)nerf_fwd_kernel<true, true>}};      // MI_FIELD_TINY_NERF
 
 int launch_mlp(int kind, const MlpArgs& a, int64_t n_groups, hipStream_t stream) {
     const int64_t blocks = n_groups * a.tiles_per_group;
     if (blocks <= 0) return 0;
     if (blocks > 0x7fffffffLL) { set_error("too many point tiles (%lld)", (long long)blocks); return -1; }
-    const dim3 grid((unsigned)blocks), block(256);
+    if (bad_kind(kind)) return -1;
     const size_t lds = kLdsFloats * sizeof(float);
     // 148 KiB of dynamic LDS: raise the per-kernel limit once per device (host-side attribute, no device work)
     static PerDeviceOnce attr_once;
     const int arc = attr_once.run([&]() {
-        const void* fns[] = {(const void*)nerf_fwd_kernel<false, false>, (const void*)nerf_fwd_kernel<false, true>,
-                             (const void*)nerf_fwd_kernel<true, false>, (const void*)nerf_fwd_kernel<true, true>,
-                             (const void*)siren_fwd_kernel<false>, (const void*)siren_fwd_kernel<true>,
-                             (const void*)film_fwd_kernel<true, false>, (const void*)film_fwd_kernel<true, true>,
-                             (const void*)film_fwd_kernel<false, false>, (const void*)film_fwd_kernel<false, true>};
-        for (const void* f : fns) {
-            const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return -2; }
-        }
+        for (const auto& k : kFwdKernels)
+            for (const void* f : k) {
+                const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return -2; }
+            }
         return 0;
     });
     if (arc) return arc;
-    const bool sv = a.save != nullptr;
-#define MI_LAUNCH(K) hipLaunchKernelGGL((K), grid, block, lds, stream, a)
-    switch (kind) {
-        case 0: if (sv) MI_LAUNCH((nerf_fwd_kernel<false, true>)); else MI_LAUNCH((nerf_fwd_kernel<false, false>)); break;
-        case 1: if (sv) MI_LAUNCH((siren_fwd_kernel<true>)); else MI_LAUNCH((siren_fwd_kernel<false>)); break;
-        case 2: if (sv) MI_LAUNCH((film_fwd_kernel<true, true>)); else MI_LAUNCH((film_fwd_kernel<true, false>)); break;
-        case 3: if (sv) MI_LAUNCH((film_fwd_kernel<false, true>)); else MI_LAUNCH((film_fwd_kernel<false, false>)); break;
-        case 4: if (sv) MI_LAUNCH((nerf_fwd_kernel<true, true>)); else MI_LAUNCH((nerf_fwd_kernel<true, false>)); break;
-        default: set_error("unknown field kind %d", kind); return -1;
-    }
-#undef MI_LAUNCH
+    void* args[] = {const_cast<MlpArgs*>(&a)};
+    (void)hipLaunchKernel(kFwdKernels[kind][a.save != nullptr], dim3((unsigned)blocks), dim3(256), args, lds, stream);
     return check_launch("field_mlp_fwd");
 }
 

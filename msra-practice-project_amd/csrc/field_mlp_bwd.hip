@@ -17,76 +17,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "field_kinds.h"
 #include "field_mlp_device.h"
 
 #include <type_traits>
 
 namespace mi {
-
-__constant__ PackTable c_tabb_nerf = build_nerf_bwd();
-__constant__ PackTable c_tabb_siren = build_siren_nerf_bwd();
-__constant__ PackTable c_tabb_film = build_film_bwd(true);
-__constant__ PackTable c_tabb_film_nodir = build_film_bwd(false);
-__constant__ PackTable c_tabb_tiny = build_tiny_nerf_bwd();
-
-static constexpr PackTable h_tabb_nerf = build_nerf_bwd();
-static constexpr PackTable h_tabb_siren = build_siren_nerf_bwd();
-static constexpr PackTable h_tabb_film = build_film_bwd(true);
-static constexpr PackTable h_tabb_film_nodir = build_film_bwd(false);
-static constexpr PackTable h_tabb_tiny = build_tiny_nerf_bwd();
-
-const PackTable* host_table_bwd(int kind) {
-    switch (kind) {
-        case 0: return &h_tabb_nerf;
-        case 1: return &h_tabb_siren;
-        case 2: return &h_tabb_film;
-        case 3: return &h_tabb_film_nodir;
-        case 4: return &h_tabb_tiny;
-    }
-    return nullptr;
-}
-
-struct ParamPtrsB { const float* p[24]; };
-
-__device__ __forceinline__ const PackTable& dev_table_bwd(int kind) {
-    switch (kind) {
-        case 0: return c_tabb_nerf;
-        case 1: return c_tabb_siren;
-        case 2: return c_tabb_film;
-        case 3: return c_tabb_film_nodir;
-        default: return c_tabb_tiny;
-    }
-}
-
-__global__ void pack_bwd_kernel(int kind, ParamPtrsB pp, float* __restrict__ dst, float w0) {
-    const PackTable& t = dev_table_bwd(kind);
-    const int it = blockIdx.y;
-    if (it >= t.n_items) return;
-    if (it == 0 && blockIdx.x == 0) {                        // the trailer piece: hyper-parameters (field_layout.h:kTrailer)
-        float* tr = dst + packed_body_floats(t);
-        tr[threadIdx.x] = threadIdx.x == 0 ? w0 : (threadIdx.x == 1 ? w0 * w0 : 0.f);
-    }
-    const PackItem item = t.item[it];
-    float* out = dst + t.dst_off[it];
-    const float* src = pp.p[item.param];
-    if (item.type == ITEM_CHUNK) {
-        const int total = item.mb * 1024;
-        for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += 32 * 256) {
-            int q = idx & 3, lane = (idx >> 2) & 63, rm = idx >> 8;
-            int m = rm % item.mb, rg = rm / item.mb;
-            int row = 32 * m + (lane & 31);
-            int c = 8 * rg + 4 * (lane >> 5) + q;
-            float v = 0.f;
-            if (row < item.rows_valid && c < item.n_valid)
-                v = src[(int64_t)row * item.ld + item.offset + (int64_t)c * item.stride];
-            out[idx] = v;
-        }
-    } else if (blockIdx.x == 0) {
-        const int f = threadIdx.x;
-        if (item.type == ITEM_VEC) out[vec_slot(f)] = f < item.n_valid ? src[item.offset + (int64_t)f * item.stride] : 0.f;
-        else out[f] = f < item.n_valid ? src[f] : 0.f;
-    }
-}
 
 struct BwdArgs {
     const float* packed;     // backward stream
@@ -587,7 +523,7 @@ __global__ __launch_bounds__(256, 1) void film_bwd_kernel(BwdArgs a) {
     Ctx c = make_ctx_raw(smem, a.packed, a.film + group * (kFilmLayers * kFilmRow));
     // fl(w_0^2) of the module's w_0 (pi_GAN/modules.py:11,73) from the backward stream's trailer: the rebuilt derivative
     // factor is +-sqrt(w_0^2 (1 - X^2)); a uniform (scalar) load
-    constexpr int kBody = USE_DIR ? packed_body_floats(h_tabb_film) : packed_body_floats(h_tabb_film_nodir);
+    constexpr int kBody = packed_body_floats(kFieldKinds[USE_DIR ? MI_FIELD_FILM_SIREN_NERF : MI_FIELD_FILM_SIREN_NERF_NODIR].bwd);
     c.w0sq = a.packed[kBody + 1];
     const int64_t P = a.points;
     // rgb head rows x3, sigma row; K blocks 0-1 of hidden_layer_rgb^T; FiLM row 8 -> film slot 0 (row r lives in slot (8 - r) & 1)
@@ -1032,32 +968,6 @@ __global__ __launch_bounds__(256) void reduce_jobs_kernel(ReduceBatch rb) {
 }
 
 // ---- host orchestration ---------------------------------------------------------------------
-int launch_pack_bwd(int kind, const float* const* params, int n_params, float w0, float* packed, hipStream_t stream) {
-    const PackTable* t = host_table_bwd(kind);
-    ParamPtrsB pp{};
-    for (int i = 0; i < n_params && i < 24; ++i) pp.p[i] = params[i];
-    hipLaunchKernelGGL(pack_bwd_kernel, dim3(32, t->n_items), dim3(256), 0, stream, kind, pp, packed, w0);
-    return check_launch("pack_bwd_kernel");
-}
-
-int64_t train_acts_floats(int kind) {
-    switch (kind) {
-        case 0: return region_total(nerf_acts());
-        case 1: return region_total(siren_acts());
-        case 2: case 3: return region_total(film_acts());
-        case 4: return region_total(tiny_acts());
-    }
-    return -1;
-}
-int64_t train_grads_floats(int kind) {
-    switch (kind) {
-        case 0: return region_total(nerf_grads());
-        case 1: return region_total(siren_grads());
-        case 2: case 3: return region_total(film_grads());
-        case 4: return region_total(tiny_grads());
-    }
-    return -1;
-}
 // FiLM scratch: one image's T_l (256x256) and column sums s_l (256) per 256-wide layer, its raw-input columns (256x3, padded)
 constexpr int64_t kFilmLayerScratch = 256 * 256 + 256;       // T_l and s_l of one 256-wide FiLM layer
 int64_t film_partial_floats(int64_t /*n_groups*/, int64_t /*points_per_group*/) {
@@ -1071,7 +981,7 @@ int64_t bwd_partial_floats(int64_t P) {
     // pass's real plan against this figure before it launches anything.
     const int64_t slabs256 = (P + 255) / 256 > 0 ? (P + 255) / 256 : 1;          // BwdBatcher::slabs_for never exceeds this
     int64_t most = 8 * (slabs256 < 32 ? slabs256 : 32) * kFilmLayerScratch + 2 * (slabs256 < 512 ? slabs256 : 512) * 1280 + 4096;
-    for (int kind : {0, 1, 4}) {                                       // the others: every job of the pass at once
+    for (int kind : {MI_FIELD_NERF, MI_FIELD_SIREN_NERF, MI_FIELD_TINY_NERF}) {   // the others: every job of the pass at once
         const int64_t n = batched_partial_floats(kind, P);
         if (n > most) most = n;
     }
@@ -1141,6 +1051,7 @@ struct BwdBatcher {
         }
         if (!partial) return 0;
         constexpr size_t lds = gemm_lds_bytes<CB, WM, WK>();
+        static_assert(lds <= 160 * 1024, "dw_gemm_kernel: this tile shape needs more LDS than a CU has");
         static PerDeviceOnce attr_once;                                               // one per template instance
         const int arc = attr_once.run([&]() {
             if (hipFuncSetAttribute((const void*)dw_gemm_kernel<CB, WM, WK>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1194,11 +1105,11 @@ struct BwdBatcher {
 static int batched_backward(int kind, BwdBatcher& b, const float* acts, float* grads, float* const* gp) {
     const int64_t P = b.P;
     int rc;
-    if (kind == 0 || kind == 4) {
-        const bool tiny = kind == 4;
-        const RegionLayout AL = tiny ? tiny_acts() : nerf_acts(), GL = tiny ? tiny_grads() : nerf_grads();
-        const auto A = [&](int r) { return acts + (int64_t)region_offset(AL, r) * P; };
-        const auto G = [&](int r) { return grads + (int64_t)region_offset(GL, r) * P; };
+    const RegionLayout &AL = kFieldKinds[kind].acts, &GL = kFieldKinds[kind].grads;
+    const auto A = [&](int r) { return acts + (int64_t)region_offset(AL, r) * P; };
+    const auto G = [&](int r) { return grads + (int64_t)region_offset(GL, r) * P; };
+    if (kind == MI_FIELD_NERF || kind == MI_FIELD_TINY_NERF) {
+        const bool tiny = kind == MI_FIELD_TINY_NERF;
         b.gemm<2, 2, 1>(b.g221, G(0), A(0), gp[0], 60, 0, 256, 60, gp[1]);                        // layers_pos.0: dA0 x E_pos
         if (!tiny) {
             for (int l = 1; l <= 7; ++l)
@@ -1217,9 +1128,6 @@ static int batched_backward(int kind, BwdBatcher& b, const float* acts, float* g
             b.thin_job(G(5), 4, 0, 3, A(6), 128, 128, gp[12], 128, 0, false, gp[13]);
         }
     } else {                                                                                      // SirenNeRF
-        const RegionLayout AL = siren_acts(), GL = siren_grads();
-        const auto A = [&](int r) { return acts + (int64_t)region_offset(AL, r) * P; };
-        const auto G = [&](int r) { return grads + (int64_t)region_offset(GL, r) * P; };
         for (int l = 1; l <= 7; ++l)                                                              // input of layer l: X_l
             b.gemm<4, 2, 2>(b.g422, G(l), A(l), gp[2 * l], l == 5 ? 259 : 256, l == 5 ? 3 : 0, 256, 256, gp[2 * l + 1]);
         b.gemm<4, 2, 2>(b.g422, G(8), A(8), gp[16], 256, 0, 256, 256, gp[17]);                    // layers_dir.0 x X8
@@ -1238,7 +1146,35 @@ static int batched_backward(int kind, BwdBatcher& b, const float* acts, float* g
     return b.reduce_all();
 }
 
-// Backward of a NeRF / TinyNeRF field over P points.  grad_params[2i], [2i+1]: device pointers to the weight /
+// A pass's job list is run twice: first as a plan (no scratch, nothing launched) whose scratch need is checked against
+// what mi_field_bwd_partial_floats(P) told the caller to allocate - a planning / execution mismatch would otherwise be an
+// out-of-bounds write by the GEMMs - then for real over `pts` points.  check = false skips the plan (a pass already
+// checked for the same shape).
+template <class Jobs>
+static int plan_then_run(int64_t pts, int64_t P, float* partial, hipStream_t stream, const Jobs& jobs, bool check = true) {
+    if (check) {
+        BwdBatcher plan{pts, nullptr, 0, stream};
+        (void)jobs(plan);
+        const int64_t limit = bwd_partial_floats(P);
+        if (plan.used > limit) {
+            set_error("backward scratch plan (%lld floats) exceeds mi_field_bwd_partial_floats (%lld)", (long long)plan.used,
+                      (long long)limit);
+            return -1;
+        }
+    }
+    BwdBatcher run{pts, partial, 0, stream};
+    return jobs(run);
+}
+
+// [kind]: the backward chain kernel of each kind
+static const void* const kBwdKernels[MI_FIELD_KINDS] = {
+    (const void*)nerf_bwd_kernel<false>,      // MI_FIELD_NERF
+    (const void*)siren_bwd_kernel,            // MI_FIELD_SIREN_NERF
+    (const void*)film_bwd_kernel<true>,       // MI_FIELD_FILM_SIREN_NERF
+    (const void*)film_bwd_kernel<false>,      // MI_FIELD_FILM_SIREN_NERF_NODIR
+    (const void*)nerf_bwd_kernel<true>};      // MI_FIELD_TINY_NERF
+
+// Backward of a field over P points.  grad_params[2i], [2i+1]: device pointers to the weight /
 // bias gradient tensors (torch layout), overwritten.
 int launch_field_backward(int kind, const float* packed_bwd, const float* acts, float* grads, const float* raw,
                           const float* g_raw, int64_t n_groups, int64_t points_per_group, const float* film,
@@ -1246,20 +1182,22 @@ int launch_field_backward(int kind, const float* packed_bwd, const float* acts, 
                           const float* const* params, hipStream_t stream) {
     const int64_t P = n_groups * points_per_group;
     if (P <= 0) return 0;
-    if (kind < 0 || kind > 4) { set_error("unknown field kind %d", kind); return -1; }
+    if (bad_kind(kind)) return -1;
     const size_t lds = kLdsFloats * sizeof(float);
     static PerDeviceOnce attr_once;
     const int arc = attr_once.run([&]() {
-        const void* fns[] = {(const void*)nerf_bwd_kernel<false>, (const void*)nerf_bwd_kernel<true>,
-                             (const void*)siren_bwd_kernel, (const void*)film_bwd_kernel<true>,
-                             (const void*)film_bwd_kernel<false>};
-        for (const void* f : fns)
+        for (const void* f : kBwdKernels)
             if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
                 set_error("hipFuncSetAttribute failed"); return -2;
             }
         return 0;
     });
     if (arc) return arc;
+    const bool film_kind = is_film(kind);
+    if (film_kind && (!film || !film_partial || !grad_film || !params)) {
+        set_error("FiLM backward needs film, the FiLM scratch, grad_film and the parameter pointers");
+        return -1;
+    }
     const int64_t tpg = (points_per_group + 127) / 128;
 #ifdef MI_PROFILE_STAMPS
     unsigned long long* stamps = g_bwd_stamps;
@@ -1267,103 +1205,70 @@ int launch_field_backward(int kind, const float* packed_bwd, const float* acts, 
     unsigned long long* stamps = nullptr;
 #endif
     BwdArgs a{packed_bwd, acts, grads, raw, g_raw, P, film, film_partial, points_per_group, tpg, n_groups * tpg, stamps};
-    const unsigned blocks = (unsigned)((kind == 2 || kind == 3) ? n_groups * tpg : (P + 127) / 128);
+    const unsigned blocks = (unsigned)(film_kind ? n_groups * tpg : (P + 127) / 128);
+    void* args[] = {&a};
+    (void)hipLaunchKernel(kBwdKernels[kind], dim3(blocks), dim3(256), args, lds, stream);
     int rc;
-    if (kind == 0 || kind == 1 || kind == 4) {
-        if (kind == 0) hipLaunchKernelGGL(nerf_bwd_kernel<false>, dim3(blocks), dim3(256), lds, stream, a);
-        else if (kind == 4) hipLaunchKernelGGL(nerf_bwd_kernel<true>, dim3(blocks), dim3(256), lds, stream, a);
-        else hipLaunchKernelGGL(siren_bwd_kernel, dim3(blocks), dim3(256), lds, stream, a);
-        if ((rc = check_launch("backward chain"))) return rc;
-        // dry run first (no launches): the scratch this very pass needs must fit what mi_field_bwd_partial_floats told the
-        // caller to allocate - a planning / execution mismatch would otherwise be an out-of-bounds write by the GEMMs
-        BwdBatcher plan{P, nullptr, 0, stream};
-        (void)batched_backward(kind, plan, acts, grads, gp);
-        if (plan.used > bwd_partial_floats(P)) {
-            set_error("backward scratch plan (%lld floats) exceeds mi_field_bwd_partial_floats (%lld)", (long long)plan.used,
-                      (long long)bwd_partial_floats(P));
-            return -1;
-        }
-        BwdBatcher bb{P, partial, 0, stream};
-        if ((rc = batched_backward(kind, bb, acts, grads, gp))) return rc;
-    } else if (kind == 2 || kind == 3) {
-        const bool use_dir = kind == 2;
-        if (!film || !film_partial || !grad_film || !params) {
-            set_error("FiLM backward needs film, the FiLM scratch, grad_film and the parameter pointers");
-            return -1;
-        }
-        if (use_dir) hipLaunchKernelGGL(film_bwd_kernel<true>, dim3(blocks), dim3(256), lds, stream, a);
-        else hipLaunchKernelGGL(film_bwd_kernel<false>, dim3(blocks), dim3(256), lds, stream, a);
-        if ((rc = check_launch("film_bwd_kernel"))) return rc;
-        constexpr RegionLayout AL = film_acts();
-        const int64_t ppg = points_per_group;
-        // FiLM scratch of the current image: T_l [256][256] + s_l [256] for the eight 256-wide FiLM layers, the K = 3
-        // blocks of layer 0 (xyz) and of layer 8 (dir) as [256][3] (padded to 4), s_0 [256]
-        const auto Tl = [&](int l) { return film_partial + (int64_t)(l - 1) * kFilmLayerScratch; };
-        const auto sl = [&](int l) { return Tl(l) + 256 * 256; };
-        float* T3_0 = film_partial + 8 * kFilmLayerScratch;
-        float* T3_8 = T3_0 + 256 * 4;
-        float* s0 = T3_8 + 256 * 4;
-        const int ld9 = use_dir ? 259 : 256;
-        // Per image g (fixed order, so the sums over images are deterministic): T_g, s_g of every FiLM layer - the eight
-        // 256 x 256 GEMMs of an image are ONE launch (grid.y = layer, a job needs only 32 slabs to give every CU a
-        // workgroup, so 8x fewer partial tiles are written and re-read than with a launch per layer), the K = 3 blocks
-        // one thin launch, one reduction launch for all of them - then per layer
-        // dW += gamma_g (.) T_g, db += gamma_g (.) s_g, d gamma_g = <W, T_g> + b (.) s_g, d beta_g = s_g.
-        for (int64_t g = 0; g < n_groups; ++g) {
-            const auto A = [&](int r) { return acts + (int64_t)region_offset(AL, r) * P + g * ppg * AL.width[r]; };
-            const auto G = [&](int l) { return grads + (int64_t)(256 * l) * P + g * ppg * 256; };
-            const float* frow = film + (g * kFilmLayers) * kFilmRow;
-            float* dfrow = grad_film + (g * kFilmLayers) * kFilmRow;
-            const int first = g == 0;
-            const auto jobs = [&](BwdBatcher& bb) -> int {
-                for (int l = 1; l <= 8; ++l)                                  // FiLM layer l: input X_{l-1} = acts region l
-                    bb.gemm<4, 2, 2>(bb.g422, G(l), A(l), Tl(l), 256, 0, 256, 256, sl(l));
-                bb.thin_job(A(0), 8, 0, 3, G(0), 256, 256, T3_0, 3, 0, true, nullptr, s0);          // input_layer (K = 3: xyz) + s_0
-                if (use_dir) bb.thin_job(A(0), 8, 3, 3, G(8), 256, 256, T3_8, 3, 0, true, nullptr); // hidden_layer_rgb's dir columns
-                int r;
-                if ((r = bb.flush<4, 2, 2>(bb.g422))) return r;
-                if ((r = bb.flush_thin())) return r;
-                return bb.reduce_all();
-            };
-            if (first) {                             // dry run: this image's scratch plan against what the caller was told to allocate
-                BwdBatcher plan{ppg, nullptr, 0, stream};
-                (void)jobs(plan);
-                if (plan.used > bwd_partial_floats(P)) {
-                    set_error("FiLM backward scratch plan (%lld floats) exceeds mi_field_bwd_partial_floats (%lld)",
-                              (long long)plan.used, (long long)bwd_partial_floats(P));
-                    return -1;
-                }
-            }
-            BwdBatcher bb{ppg, partial, 0, stream};
-            if ((rc = jobs(bb))) return rc;
-            FinishBatch fb{};
-            int n_fin = 0, n_heads = 0;
-            fb.first_group = first;
-            const auto finish = [&](const float* t, int tk, const float* sg, int l, int wp, int w_ld, int col0, int bias_part) {
-                fb.job[n_fin++] = FinishJob{t, sg, params[2 * wp], params[2 * wp + 1], frow + l * kFilmRow, gp[2 * wp], gp[2 * wp + 1],
-                                            dfrow + l * kFilmRow, tk, w_ld, col0, bias_part};
-                n_heads += bias_part;
-            };
-            finish(T3_0, 3, s0, 0, 0, 3, 0, 1);                               // input_layer: FiLM layer 0, parameter pair 0
-            for (int l = 1; l <= 7; ++l) finish(Tl(l), 256, sl(l), l, l, 256, 0, 1);      // hidden_layers[l-1]: pair l
-            finish(Tl(8), 256, sl(8), 8, 9, ld9, 0, 1);                       // hidden_layer_rgb: FiLM layer 8, pair 9: [X_7 | dir]
-            if (use_dir) finish(T3_8, 3, sl(8), 8, 9, 259, 256, 0);           // ... its dir columns: chained behind the job above
-            hipLaunchKernelGGL(film_finish_kernel, dim3(256, n_heads), dim3(256), 0, stream, fb);
-        }
-        if ((rc = check_launch("film_finish_kernel"))) return rc;
-        // heads: sigma (param pair 8) on X_7, rgb (pair 10) on X_8 - no FiLM in between, all images at once
-        const auto A = [&](int r) { return acts + (int64_t)region_offset(AL, r) * P; };
-        const float* dpre = grads + (int64_t)(9 * 256) * P;
-        for (int pass = 0; pass < 2; ++pass) {                        // 0: plan only (scratch check), 1: launch
-            BwdBatcher hb{P, pass ? partial : nullptr, 0, stream};
-            hb.thin_job(dpre, 4, 3, 1, A(8), 256, 256, gp[16], 256, 0, false, gp[17]);                        // sigma x X_7
-            hb.thin_job(dpre, 4, 0, 3, A(9), 256, 256, gp[20], 256, 0, false, gp[21]);                        // rgb x X_8
-            if ((rc = hb.flush_thin())) return rc;
-            if (!pass && hb.used > bwd_partial_floats(P)) { set_error("FiLM head scratch plan exceeds mi_field_bwd_partial_floats"); return -1; }
-            if ((rc = hb.reduce_all())) return rc;
-        }
+    if ((rc = check_launch("backward chain"))) return rc;
+    if (!film_kind)
+        return plan_then_run(P, P, partial, stream, [&](BwdBatcher& bb) { return batched_backward(kind, bb, acts, grads, gp); });
+
+    const bool use_dir = kFieldKinds[kind].use_dir;
+    constexpr RegionLayout AL = film_acts();
+    const int64_t ppg = points_per_group;
+    // FiLM scratch of the current image: T_l [256][256] + s_l [256] for the eight 256-wide FiLM layers, the K = 3
+    // blocks of layer 0 (xyz) and of layer 8 (dir) as [256][3] (padded to 4), s_0 [256]
+    const auto Tl = [&](int l) { return film_partial + (int64_t)(l - 1) * kFilmLayerScratch; };
+    const auto sl = [&](int l) { return Tl(l) + 256 * 256; };
+    float* T3_0 = film_partial + 8 * kFilmLayerScratch;
+    float* T3_8 = T3_0 + 256 * 4;
+    float* s0 = T3_8 + 256 * 4;
+    const int ld9 = use_dir ? 259 : 256;
+    // Per image g (fixed order, so the sums over images are deterministic): T_g, s_g of every FiLM layer - the eight
+    // 256 x 256 GEMMs of an image are ONE launch (grid.y = layer, a job needs only 32 slabs to give every CU a
+    // workgroup, so 8x fewer partial tiles are written and re-read than with a launch per layer), the K = 3 blocks
+    // one thin launch, one reduction launch for all of them - then per layer
+    // dW += gamma_g (.) T_g, db += gamma_g (.) s_g, d gamma_g = <W, T_g> + b (.) s_g, d beta_g = s_g.
+    for (int64_t g = 0; g < n_groups; ++g) {
+        const auto A = [&](int r) { return acts + (int64_t)region_offset(AL, r) * P + g * ppg * AL.width[r]; };
+        const auto G = [&](int l) { return grads + (int64_t)(256 * l) * P + g * ppg * 256; };
+        const float* frow = film + (g * kFilmLayers) * kFilmRow;
+        float* dfrow = grad_film + (g * kFilmLayers) * kFilmRow;
+        const auto jobs = [&](BwdBatcher& bb) -> int {
+            for (int l = 1; l <= 8; ++l)                                  // FiLM layer l: input X_{l-1} = acts region l
+                bb.gemm<4, 2, 2>(bb.g422, G(l), A(l), Tl(l), 256, 0, 256, 256, sl(l));
+            bb.thin_job(A(0), 8, 0, 3, G(0), 256, 256, T3_0, 3, 0, true, nullptr, s0);          // input_layer (K = 3: xyz) + s_0
+            if (use_dir) bb.thin_job(A(0), 8, 3, 3, G(8), 256, 256, T3_8, 3, 0, true, nullptr); // hidden_layer_rgb's dir columns
+            int r;
+            if ((r = bb.flush<4, 2, 2>(bb.g422))) return r;
+            if ((r = bb.flush_thin())) return r;
+            return bb.reduce_all();
+        };
+        if ((rc = plan_then_run(ppg, P, partial, stream, jobs, g == 0))) return rc;   // the plan: first image only
+        FinishBatch fb{};
+        int n_fin = 0, n_heads = 0;
+        fb.first_group = g == 0;
+        const auto finish = [&](const float* t, int tk, const float* sg, int l, int wp, int w_ld, int col0, int bias_part) {
+            fb.job[n_fin++] = FinishJob{t, sg, params[2 * wp], params[2 * wp + 1], frow + l * kFilmRow, gp[2 * wp], gp[2 * wp + 1],
+                                        dfrow + l * kFilmRow, tk, w_ld, col0, bias_part};
+            n_heads += bias_part;
+        };
+        finish(T3_0, 3, s0, 0, 0, 3, 0, 1);                               // input_layer: FiLM layer 0, parameter pair 0
+        for (int l = 1; l <= 7; ++l) finish(Tl(l), 256, sl(l), l, l, 256, 0, 1);      // hidden_layers[l-1]: pair l
+        finish(Tl(8), 256, sl(8), 8, 9, ld9, 0, 1);                       // hidden_layer_rgb: FiLM layer 8, pair 9: [X_7 | dir]
+        if (use_dir) finish(T3_8, 3, sl(8), 8, 9, 259, 256, 0);           // ... its dir columns: chained behind the job above
+        hipLaunchKernelGGL(film_finish_kernel, dim3(256, n_heads), dim3(256), 0, stream, fb);
     }
-    return 0;
+    if ((rc = check_launch("film_finish_kernel"))) return rc;
+    // heads: sigma (param pair 8) on X_7, rgb (pair 10) on X_8 - no FiLM in between, all images at once
+    const auto A = [&](int r) { return acts + (int64_t)region_offset(AL, r) * P; };
+    const float* dpre = grads + (int64_t)(9 * 256) * P;
+    return plan_then_run(P, P, partial, stream, [&](BwdBatcher& hb) {
+        hb.thin_job(dpre, 4, 3, 1, A(8), 256, 256, gp[16], 256, 0, false, gp[17]);                        // sigma x X_7
+        hb.thin_job(dpre, 4, 0, 3, A(9), 256, 256, gp[20], 256, 0, false, gp[21]);                        // rgb x X_8
+        const int r = hb.flush_thin();
+        return r ? r : hb.reduce_all();
+    });
 }
 
 static int64_t batched_partial_floats(int kind, int64_t P) {

@@ -70,12 +70,11 @@ struct MlpArgs {
 #define MI_STAMP(a, i) do { } while (0)
 #endif
 
-// host launchers (field_mlp.hip, render_stages.hip)
-int launch_pack(int kind, const float* const* params, int n_params, float w0, float* packed, hipStream_t stream);
+// The two packed weight streams of a field kind (field_layout.h): forward order, and transposed for the backward chain.
+enum StreamDir : int { STREAM_FWD = 0, STREAM_BWD = 1 };
+
+// host launchers (field_mlp.hip, field_mlp_bwd.hip, render_stages.hip, eval_stages.hip, adam_step.hip)
 int launch_mlp(int kind, const MlpArgs& a, int64_t n_groups, hipStream_t stream);
-int launch_pack_bwd(int kind, const float* const* params, int n_params, float w0, float* packed, hipStream_t stream);
-int64_t train_acts_floats(int kind);
-int64_t train_grads_floats(int kind);
 int64_t bwd_partial_floats(int64_t P);
 int64_t film_partial_floats(int64_t n_groups, int64_t points_per_group);
 int launch_field_backward(int kind, const float* packed_bwd, const float* acts, float* grads, const float* raw,
@@ -101,6 +100,8 @@ int launch_nerf_loss(int64_t n, const float* rgb_c, const float* acc_c, const fl
                      float* g_acc_f, float* workspace, float* out, hipStream_t stream);
 int launch_ray_bank(int width, int height, double focal, const float* poses, const float* rgba, int white_bkgd,
                     int64_t images, float* out, int compute_f64, hipStream_t stream);
+int launch_pack(int kind, StreamDir dir, const float* const* params, int n_params, float w0, float* packed,
+                hipStream_t stream);
 int launch_adam_step(int n_fields, const int* kinds, const int* n_params, float* const* params, const float* const* grads,
                      float* const* exp_avg, float* const* exp_avg_sq, const int64_t* numel, float step_size,
                      float one_minus_beta1, float beta2, float one_minus_beta2, float eps, float bc2_sqrt,

@@ -44,7 +44,7 @@ def main():
         c = collections.Counter()
         for x in asm[i:j]:
             m = re.match(r"\s+(\S+)", x)
-            if m:
+            if m and m.group(1) != "...":             # "...": objdump's zero padding up to the next kernel
                 c[m.group(1)] += 1
         sl = sum(v for k, v in c.items() if k.startswith("scratch_load"))
         ss = sum(v for k, v in c.items() if k.startswith("scratch_store"))
