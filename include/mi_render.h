@@ -210,6 +210,64 @@ int mi_field_backward(int kind, const float* packed_bwd, const float* film, cons
                       float* partial_ws, float* film_partial_ws, float* const* grad_params,
                       const float* const* params, int n_params, float* grad_film, void* stream);
 
+/* ---- training pair: render_rays forward + backward in two calls (train_path.hip) ----------------------------------
+ * One iteration of nerf/train_nerf.py:151-168 from C (render_rays, the loss, loss.backward(), optimizer.step()), or the
+ * generator backward of pi_GAN/modules.py:159-161: mi_render_rays_train -> mi_nerf_loss (or the caller's own loss) ->
+ * mi_render_rays_backward -> mi_adam_step.  The pair restates what autograd does for render_rays in Python
+ * (msra-practice-project_amd/mirender/autograd.py) and gives the same bits.
+ *
+ * Each pass (coarse: Nc samples per ray; fine: Nc + Nf with two fields, the Nf new depths with one shared field) is cut
+ * into ray ranges of at most range_points points: whole rays; for FiLM kinds whole groups per range, or equal parts of
+ * one group when one image alone is larger.  `saved` keeps the layer inputs of the leading ranges that fit in
+ * saved_bytes (coarse pass first, each pass stopping at the first range that does not fit; any size, 0 included, gives
+ * the same results); the backward re-runs the forward of every other range into its own workspace.
+ *
+ * mi_render_train_saved_bytes: what keeps every range (4 * mi_field_train_acts_floats * n * samples, summed over the
+ * passes).  shared != 0: one field for both passes.
+ * mi_render_backward_workspace_bytes: the backward's workspace for the given range split (n = n_groups*rays_per_group). */
+int64_t mi_render_train_saved_bytes(int kind_coarse, int kind_fine, int shared, int64_t n, int n_coarse, int n_fine);
+int64_t mi_render_backward_workspace_bytes(int kind_coarse, int kind_fine, int shared, int64_t n_groups,
+                                           int64_t rays_per_group, int n_coarse, int n_fine, int64_t range_points_coarse,
+                                           int64_t range_points_fine);
+
+/* render_rays (nerf/render.py:106-147) with autograd's saved state: mi_render_rays' arguments and outputs, bit-identical
+ * to it, plus the range split and the saved buffer.  The workspace (mi_render_workspace_bytes, and when both passes
+ * share one field - same kind, same packed pointer - mi_render_shared_field_extra_bytes on top, else MI_EINVAL) holds
+ * the forward's state afterwards: hand it to mi_render_rays_backward unchanged, with `saved`. */
+int mi_render_rays_train(int kind_coarse, const float* packed_coarse, int kind_fine, const float* packed_fine,
+                         const float* film, const float* rays, int64_t n_groups, int64_t rays_per_group, float near_,
+                         float far_, int n_coarse, int n_fine, const float* z_lin, const float* u_lin, const float* t_rand,
+                         uint64_t seed, uint64_t ray0, float* rgb_c, float* depth_c, float* acc_c, float* rgb_f,
+                         float* depth_f, float* acc_f, void* workspace, int64_t workspace_bytes,
+                         int64_t range_points_coarse, int64_t range_points_fine, void* saved, int64_t saved_bytes,
+                         void* stream);
+
+/* The backward of mi_render_rays_train (render_rays' part of loss.backward(), nerf/train_nerf.py:167): the six output
+ * cotangents [n,3] / [n] (any may be NULL = no gradient) -> parameter gradients and the FiLM-table gradient.
+ *   packed_* / packed_bwd_*: the fields' forward and transposed streams (mi_field_pack / mi_field_pack_bwd)
+ *   params_*      HOST arrays of the parameter tensors (FiLM kinds; may be NULL for the others)
+ *   film, rays, sizes, range points, workspace, saved: exactly as given to mi_render_rays_train (the depths come from
+ *                 the workspace, so near / far and the linspace tables are not needed again)
+ *   grad_params_* HOST arrays of mi_field_num_params device pointers, OVERWRITTEN.  A field that receives no cotangent
+ *                 is left untouched and may pass NULL.  One shared field: both passes' sum goes to grad_params_coarse
+ *                 (grad_params_fine is not used).
+ *   grad_film     [n_groups,9,512] (FiLM kinds), OVERWRITTEN with the sum of both passes' FiLM gradients
+ *   bwd_workspace mi_render_backward_workspace_bytes
+ *   fields_written HOST, optional: MI_WROTE_* bits of what was written; known from the NULL pattern, no synchronisation */
+#define MI_WROTE_COARSE 1
+#define MI_WROTE_FINE 2
+#define MI_WROTE_FILM 4
+int mi_render_rays_backward(int kind_coarse, const float* packed_coarse, const float* packed_bwd_coarse,
+                            const float* const* params_coarse, int kind_fine, const float* packed_fine,
+                            const float* packed_bwd_fine, const float* const* params_fine, const float* film,
+                            const float* rays, int64_t n_groups, int64_t rays_per_group, int n_coarse, int n_fine,
+                            int64_t range_points_coarse, int64_t range_points_fine, const void* workspace,
+                            int64_t workspace_bytes, const void* saved, int64_t saved_bytes, const float* g_rgb_c,
+                            const float* g_depth_c, const float* g_acc_c, const float* g_rgb_f, const float* g_depth_f,
+                            const float* g_acc_f, float* const* grad_params_coarse, float* const* grad_params_fine,
+                            float* grad_film, void* bwd_workspace, int64_t bwd_workspace_bytes, int* fields_written,
+                            void* stream);
+
 /* ---- evaluation stages (frame metrics, density grids) --------------------- */
 
 /* Frame metrics of nerf/test_nerf.py:102-105: mean squared error (psnr = -10 log10 mse) and

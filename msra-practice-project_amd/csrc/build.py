@@ -24,6 +24,7 @@ SOURCES = {
     "eval_stages.hip": ["-ffp-contract=off"],
     "adam_step.hip": [],
     "mesh_stages.hip": [],
+    "train_path.hip": [],
     "api.hip": [],
 }
 HEADERS = ["field_layout.h", "field_kinds.h", "mi_common.h", "mesh_cube.h", "mi_math.h", "field_mlp_device.h", os.path.join("..", "..", "include", "mi_render.h")]
@@ -96,22 +97,26 @@ def build(force=False, verbose=True, always=()):
 
 
 def build_host_example(verbose=True):
-    """tests/cabi/cabi_host: a C++ program that uses the library through include/mi_render.h alone (no Python, no torch) -
-    the link line a C / C++ host of the ABI uses.  Test infrastructure (tests/test_gpu_cabi_host.py runs it)."""
+    """tests/cabi/cabi_host and tests/cabi/cabi_train_host: C++ programs that use the library through include/mi_render.h
+    alone (no Python, no torch) - the link line a C / C++ host of the ABI uses.  Test infrastructure
+    (tests/test_gpu_cabi_host.py and tests/test_gpu_cabi_train.py run them).  Returns cabi_host's path."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     root = os.path.dirname(PKG)
-    src = os.path.join(root, "tests", "cabi", "cabi_host.cpp")
-    out = os.path.join(root, "tests", "cabi", "cabi_host")
-    if _stale(out, [src, OUT, os.path.join(root, "include", "mi_render.h")]):
-        cmd = [hipcc, "-O2", "-std=c++17", "-Wall", "-I", os.path.join(root, "include"), src, "-L", os.path.dirname(OUT), "-lmirender",
-               "-Wl,-rpath,$ORIGIN/../../msra-practice-project_amd/mirender", "-o", out]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.check_call(cmd, timeout=600)
-        print(f"[build] {os.path.relpath(out, root)}: LINKED against libmirender.so", flush=True)
-    else:
-        print(f"[build] {os.path.relpath(out, root)}: REUSED", flush=True)
-    return out
+    outs = []
+    for name in ("cabi_host", "cabi_train_host"):
+        src = os.path.join(root, "tests", "cabi", name + ".cpp")
+        out = os.path.join(root, "tests", "cabi", name)
+        if _stale(out, [src, OUT, os.path.join(root, "include", "mi_render.h")]):
+            cmd = [hipcc, "-O2", "-std=c++17", "-Wall", "-I", os.path.join(root, "include"), src, "-L", os.path.dirname(OUT),
+                   "-lmirender", "-Wl,-rpath,$ORIGIN/../../msra-practice-project_amd/mirender", "-o", out]
+            if verbose:
+                print(" ".join(cmd), flush=True)
+            subprocess.check_call(cmd, timeout=600)
+            print(f"[build] {os.path.relpath(out, root)}: LINKED against libmirender.so", flush=True)
+        else:
+            print(f"[build] {os.path.relpath(out, root)}: REUSED", flush=True)
+        outs.append(out)
+    return outs[0]
 
 
 if __name__ == "__main__":

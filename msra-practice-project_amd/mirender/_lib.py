@@ -66,6 +66,14 @@ SIGNATURES = {
     "mi_field_film_partial_floats": (_i64, [_i64, _i64]),
     "mi_field_backward": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, ctypes.POINTER(_vp),
                                  ctypes.POINTER(_vp), _int, _vp, _vp]),
+    "mi_render_train_saved_bytes": (_i64, [_int, _int, _int, _i64, _int, _int]),
+    "mi_render_backward_workspace_bytes": (_i64, [_int, _int, _int, _i64, _i64, _int, _int, _i64, _i64]),
+    "mi_render_rays_train": (_int, [_int, _vp, _int, _vp, _vp, _vp, _i64, _i64, _f32, _f32, _int, _int, _vp, _vp, _vp,
+                                    _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp]),
+    "mi_render_rays_backward": (_int, [_int, _vp, _vp, ctypes.POINTER(_vp), _int, _vp, _vp, ctypes.POINTER(_vp), _vp, _vp,
+                                       _i64, _i64, _int, _int, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp,
+                                       _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp, _i64,
+                                       ctypes.POINTER(_int), _vp]),
     "mi_mc_workspace_bytes": (_i64, [_i64, _i64, _i64]),
     "mi_marching_cubes_count": (_int, [_vp, _i64, _i64, _i64, _f64, _vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _vp]),
     "mi_marching_cubes_emit": (_int, [_vp, _i64, _i64, _i64, _f64, ctypes.POINTER(_f64), _int, _vp, _vp, _vp, _vp, _vp,
