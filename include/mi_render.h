@@ -152,7 +152,13 @@ int mi_sample_pdf(int64_t n, int n_bins, int n_samples, const float* bins, const
  *   workspace: mi_render_workspace_bytes(n, Nc, Nf) bytes; workspace_bytes = what the caller really provided.
  *   When both passes share one field (same kind, same packed pointer) and the workspace also holds
  *   mi_render_shared_field_extra_bytes(n, Nc, Nf) more, the fine pass evaluates the Nf new depths only (mi_merge_raw);
- *   with Nf = 0 it aliases the coarse outputs.  Results are bit-identical either way. */
+ *   with Nf = 0 it aliases the coarse outputs.  Results are bit-identical either way.
+ *   The coarse outputs are optional: rgb_c = NULL says the coarse colours are not wanted, and then depth_c and acc_c may
+ *   each be NULL too (with rgb_c, all three are needed).  The fine outputs, rays and the workspace are not optional.
+ *   Without rgb_c and with two different fields (kind or packed pointer), the coarse pass runs the coarse field's
+ *   sigma-only forward, where the kind has one (NeRF, SirenNeRF, TinyNeRF), and a composite that forms the weights (and
+ *   depth_c / acc_c when asked for) from sigma alone.  The fine outputs, and depth_c / acc_c, are the same bits as those
+ *   of a call with all six outputs. */
 int64_t mi_render_workspace_bytes(int64_t n, int n_coarse, int n_fine);
 int64_t mi_render_shared_field_extra_bytes(int64_t n, int n_coarse, int n_fine);
 int mi_render_rays(int kind_coarse, const float* packed_coarse, int kind_fine, const float* packed_fine,

@@ -35,7 +35,7 @@ int check_launch(const char* what) {
 
 static int eval_common(int kind, const float* packed, const float* film, const float* a, const float* z,
                        int64_t n_groups, int64_t ppg, int64_t rpg, int S, int mode, float* out, hipStream_t s,
-                       float* save = nullptr) {
+                       float* save = nullptr, bool sigma_only = false) {
     if (bad_kind(kind)) return MI_EINVAL;
     if (!packed || !a || !out || (mode == 1 && !z)) { set_error("null pointer argument"); return MI_EINVAL; }
     if (is_film(kind) && !film) { set_error("FiLM kind needs a film table"); return MI_EINVAL; }
@@ -50,7 +50,7 @@ static int eval_common(int kind, const float* packed, const float* film, const f
 #else
     args.stamps = nullptr;
 #endif
-    return launch_mlp(kind, args, n_groups, s);
+    return launch_mlp(kind, args, n_groups, s, sigma_only);
 }
 
 }  // namespace mi
@@ -210,7 +210,9 @@ int mi_render_rays(int kind_coarse, const float* packed_coarse, int kind_fine, c
                    float* depth_f, float* acc_f, void* workspace, int64_t workspace_bytes, void* stream) {
     if (n_groups < 0 || rays_per_group < 0 || n_coarse < 1 || n_fine < 0) { set_error("mi_render_rays: bad sizes"); return MI_EINVAL; }
     if (n_groups * rays_per_group == 0) return MI_OK;          // no rays: nothing to launch, no buffer is touched
-    if (!workspace || !rays || !rgb_c || !depth_c || !acc_c || !rgb_f || !depth_f || !acc_f) {
+    // the coarse outputs are optional: rgb_c NULL = the coarse colours are not wanted, and then depth_c / acc_c each may be
+    // NULL too; with rgb_c, all three
+    if (!workspace || !rays || (rgb_c && (!depth_c || !acc_c)) || !rgb_f || !depth_f || !acc_f) {
         set_error("mi_render_rays: null pointer argument");
         return MI_EINVAL;
     }
@@ -229,28 +231,42 @@ int mi_render_rays(int kind_coarse, const float* packed_coarse, int kind_fine, c
     float* w_c = take(n * n_coarse);
     float* z_f = take(n * (int64_t)S);
     float* raw_f = take(n * (int64_t)S * 4);
+    const bool shared = kind_fine == kind_coarse && packed_fine == packed_coarse;
+    // Without the coarse colours and with a coarse field of its own, the coarse pass only feeds sample_fine its weights,
+    // which depend on sigma alone: the sigma-only forward writes sigma [n,Nc] compactly at the start of raw_c's region.
+    // A shared field's coarse raw values are merged into the fine pass (or are its outputs with Nf = 0): whole forward.
+    const bool sigma_only = !rgb_c && !shared && has_sigma_only_kernel(kind_coarse);
     int rc;
     if ((rc = mi_sample_coarse(n, near_, far_, n_coarse, z_lin, t_rand, seed, ray0, z_c, stream))) return rc;
     hipStream_t hs = (hipStream_t)stream;
     if (g_mlp_ev[0]) (void)hipEventRecord(g_mlp_ev[0], hs);
-    if ((rc = mi_field_eval_rays(kind_coarse, packed_coarse, film, rays, z_c, n_groups, rays_per_group, n_coarse, raw_c,
-                                 stream))) return rc;
+    if (sigma_only) {
+        if ((rc = eval_common(kind_coarse, packed_coarse, film, rays, z_c, n_groups, rays_per_group * n_coarse, rays_per_group,
+                              n_coarse, 1, raw_c, hs, nullptr, true))) return rc;
+    } else if ((rc = mi_field_eval_rays(kind_coarse, packed_coarse, film, rays, z_c, n_groups, rays_per_group, n_coarse, raw_c,
+                                        stream))) {
+        return rc;
+    }
     if (g_mlp_ev[1]) (void)hipEventRecord(g_mlp_ev[1], hs);
-    if ((rc = mi_composite(n, n_coarse, raw_c, z_c, rays, rgb_c, depth_c, acc_c, w_c, stream))) return rc;
-    if (n_fine == 0 && kind_fine == kind_coarse && packed_fine == packed_coarse) {
+    if (n_fine == 0 && shared) {
         // render.py:140-145 with Nf = 0 and one model: sort(z_coarse) == z_coarse, so the second pass would
-        // re-evaluate identical inputs; alias its outputs instead.
-        hipStream_t s = (hipStream_t)stream;
-        if (hipMemcpyAsync(rgb_f, rgb_c, n * 3 * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess ||
-            hipMemcpyAsync(depth_f, depth_c, n * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess ||
-            hipMemcpyAsync(acc_f, acc_c, n * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) {
-            set_error("mi_render_rays: output alias copy failed");
-            return MI_EHIP;
-        }
+        // re-evaluate identical inputs: the coarse pass's composite IS the fine outputs, and the coarse
+        // outputs asked for are copies of them.
+        if ((rc = mi_composite(n, n_coarse, raw_c, z_c, rays, rgb_f, depth_f, acc_f, w_c, stream))) return rc;
+        const struct { float* dst; const float* src; int64_t floats; } alias[3] = {
+            {rgb_c, rgb_f, n * 3}, {depth_c, depth_f, n}, {acc_c, acc_f, n}};
+        for (const auto& c : alias)
+            if (c.dst && hipMemcpyAsync(c.dst, c.src, c.floats * sizeof(float), hipMemcpyDeviceToDevice, hs) != hipSuccess) {
+                set_error("mi_render_rays: output alias copy failed");
+                return MI_EHIP;
+            }
         return MI_OK;
     }
-    if (kind_fine == kind_coarse && packed_fine == packed_coarse &&
-        workspace_bytes >= base_bytes + mi_render_shared_field_extra_bytes(n, n_coarse, n_fine)) {
+    if (rgb_c) rc = mi_composite(n, n_coarse, raw_c, z_c, rays, rgb_c, depth_c, acc_c, w_c, stream);
+    else if (sigma_only) rc = launch_composite_weights(n, n_coarse, raw_c, 1, z_c, rays, depth_c, acc_c, w_c, hs);
+    else rc = launch_composite_weights(n, n_coarse, raw_c + 3, 4, z_c, rays, depth_c, acc_c, w_c, hs);     // raw's sigma channel
+    if (rc) return rc;
+    if (shared && workspace_bytes >= base_bytes + mi_render_shared_field_extra_bytes(n, n_coarse, n_fine)) {
         // One field for both passes: Nc of the fine pass's Nc + Nf points are the coarse pass's points - evaluate the Nf
         // new ones only and merge (render_stages.hip: merge_raw_kernel).  Needs the extra workspace regions; a caller
         // that did not provide them gets the plain path below (same results).

@@ -30,8 +30,15 @@ namespace mi {
 // =========================================================================================
 // SAVE = training forward: every linear layer's input is also written to HBM ([point][feature] rows,
 // region table nerf_acts()/tiny_acts() in field_layout.h) for the backward pass.
-template <bool TINY, bool SAVE>
+// SIGMA_ONLY = density forward: the trunk and the sigma head, then the wave ends (store_sigma).  Up to sigma it executes
+// the inference instance's instructions, so sigma has the same bits.
+template <bool TINY, bool SAVE, bool SIGMA_ONLY>
 __global__ __launch_bounds__(256, 1) void nerf_fwd_kernel(MlpArgs a) {
+    static_assert(!(SAVE && SIGMA_ONLY), "the training forward needs the colour branch");
+    constexpr FieldKind K = kFieldKinds[TINY ? MI_FIELD_TINY_NERF : MI_FIELD_NERF];
+    // the stage the last trunk layer issues behind it: the colour branch's first, none if the wave stops at sigma
+    constexpr int kNextAux = SIGMA_ONLY ? 0 : K.branch_aux_pieces();
+    constexpr int kNextBlock = SIGMA_ONLY ? 0 : K.branch_block_pieces();
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int64_t group = blockIdx.x / a.tiles_per_group;
     const int64_t tile = blockIdx.x % a.tiles_per_group;
@@ -107,7 +114,7 @@ __global__ __launch_bounds__(256, 1) void nerf_fwd_kernel(MlpArgs a) {
         slot ^= 1;
         MI_STAMP(a, 15);
         // layers_pos[7] (+ sigma head pieces)
-        fwd_layer<8, 8, false, 1, 32, false, ACT_RELU, SAVE, true, 8>(c, slot, 0, 0, 0.f, 0.f, 0.f, sel_x, acc, X, nullptr,
+        fwd_layer<8, 8, false, kNextAux, kNextBlock, false, ACT_RELU, SAVE, true, 8>(c, slot, 0, 0, 0.f, 0.f, 0.f, sel_x, acc, X, nullptr,
                                                                       rows(region_offset(RL, 8), 256, SW0 + 7), rows(region_offset(RL, 7), 256));    // H8
         {
             const float* aux = smem + kLdsAux0 + slot * kLdsAux;
@@ -115,11 +122,13 @@ __global__ __launch_bounds__(256, 1) void nerf_fwd_kernel(MlpArgs a) {
         }
         slot ^= 1;
         MI_STAMP(a, 17);
-        // layers_dir[0]: linear
-        fwd_layer<8, 8, false, 5, 16, false, ACT_LINEAR, SAVE, true, 8>(c, slot, 0, 0, 0.f, 0.f, 0.f, sel_x, acc, X, nullptr,
-                                                                        rows(region_offset(RL, 9), 256), rows(region_offset(RL, 8), 256));  // G
-        slot ^= 1;
-        MI_STAMP(a, 19);
+        if constexpr (!SIGMA_ONLY) {
+            // layers_dir[0]: linear
+            fwd_layer<8, 8, false, 5, 16, false, ACT_LINEAR, SAVE, true, 8>(c, slot, 0, 0, 0.f, 0.f, 0.f, sel_x, acc, X, nullptr,
+                                                                            rows(region_offset(RL, 9), 256), rows(region_offset(RL, 8), 256));  // G
+            slot ^= 1;
+            MI_STAMP(a, 19);
+        }
     } else {
         // layers_pos[1], [2], [3] (+ sigma head pieces), then the dir layer's 5 aux pieces
         fwd_layer<8, 8, false, 1, 32, false, ACT_RELU, SAVE, true, 8>(c, slot, 0, 0, 0.f, 0.f, 0.f, sel_x, acc, X, nullptr,
@@ -128,13 +137,17 @@ __global__ __launch_bounds__(256, 1) void nerf_fwd_kernel(MlpArgs a) {
         fwd_layer<8, 8, false, 3, 32, false, ACT_RELU, SAVE, true, 8>(c, slot, 0, 0, 0.f, 0.f, 0.f, sel_x, acc, X, nullptr,
                                                                       rows(region_offset(RL, 3), 256, SW0 + 2), rows(region_offset(RL, 2), 256));
         slot ^= 1;
-        fwd_layer<8, 8, false, 5, 16, false, ACT_RELU, SAVE, true, 8>(c, slot, 0, 0, 0.f, 0.f, 0.f, sel_x, acc, X, nullptr,
+        fwd_layer<8, 8, false, kNextAux, kNextBlock, false, ACT_RELU, SAVE, true, 8>(c, slot, 0, 0, 0.f, 0.f, 0.f, sel_x, acc, X, nullptr,
                                                                       rows(region_offset(RL, 4), 256, SW0 + 3), rows(region_offset(RL, 3), 256));
         {
             const float* aux = smem + kLdsAux0 + slot * kLdsAux;
             sigma = fmaxf(head_dot<8>(X, aux, 1, c.h) + aux[2 * kPiece], 0.f);
         }
         slot ^= 1;
+    }
+    if constexpr (SIGMA_ONLY) {
+        store_sigma(a, pt, c.h, sigma);
+        return;
     }
     // layers_dir[1] (TinyNeRF: layers_dir[0]): [h(256) | PE_dir(24)] -> 128, relu; then rgb head
     fwd_layer<9, 4, false, 0, 0, false, ACT_RELU, SAVE, false, 8>(c, slot, 0, 0, 0.f, 0.f, 0.f, sel_dir, acc, X, nullptr,
@@ -152,8 +165,12 @@ __global__ __launch_bounds__(256, 1) void nerf_fwd_kernel(MlpArgs a) {
 // =========================================================================================
 // SirenNeRF (nerf/nerf.py:153-170): sin(30 * linear) layers on raw xyz / dir
 // =========================================================================================
-template <bool SAVE>
+template <bool SAVE, bool SIGMA_ONLY>
 __global__ __launch_bounds__(256, 1) void siren_fwd_kernel(MlpArgs a) {
+    static_assert(!(SAVE && SIGMA_ONLY), "the training forward needs the colour branch");
+    constexpr FieldKind K = kFieldKinds[MI_FIELD_SIREN_NERF];
+    constexpr int kNextAux = SIGMA_ONLY ? 0 : K.branch_aux_pieces();      // as in nerf_fwd_kernel
+    constexpr int kNextBlock = SIGMA_ONLY ? 0 : K.branch_block_pieces();
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int64_t group = blockIdx.x / a.tiles_per_group;
     const int64_t tile = blockIdx.x % a.tiles_per_group;
@@ -204,11 +221,15 @@ __global__ __launch_bounds__(256, 1) void siren_fwd_kernel(MlpArgs a) {
     slot ^= 1;
     fwd_layer<8, 8, false, 3, 32, false, ACT_SIN30, SAVE, false, 0>(c, slot, 0, 0, 0.f, 0.f, 0.f, sel_x, acc, X, nullptr, sin_rows(7), none);  // [6]
     slot ^= 1;
-    fwd_layer<8, 8, false, 1, 32, false, ACT_SIN30, SAVE, false, 0>(c, slot, 0, 0, 0.f, 0.f, 0.f, sel_x, acc, X, nullptr, sin_rows(8), none);  // [7] + sigma head
+    fwd_layer<8, 8, false, kNextAux, kNextBlock, false, ACT_SIN30, SAVE, false, 0>(c, slot, 0, 0, 0.f, 0.f, 0.f, sel_x, acc, X, nullptr, sin_rows(8), none);  // [7] + sigma head
     float sigma;
     {
         const float* aux = smem + kLdsAux0 + slot * kLdsAux;
         sigma = fmaxf(head_dot<8>(X, aux, 1, c.h) + aux[2 * kPiece], 0.f);
+    }
+    if constexpr (SIGMA_ONLY) {
+        store_sigma(a, pt, c.h, sigma);
+        return;
     }
     slot ^= 1;
     const SaveRows g_rows{SAVE ? region(9) : nullptr, 256, pt.p, pt.valid};
@@ -295,25 +316,38 @@ __global__ __launch_bounds__(256, 1) void film_fwd_kernel(MlpArgs a) {
 }
 
 // ---- host side ---------------------------------------------------------------------------
-// [kind][save]: the inference and the training (layer inputs saved) instance of each kind's kernel
-static const void* const kFwdKernels[MI_FIELD_KINDS][2] = {
-    {(const void*)nerf_fwd_kernel<false, false>, (const void*)nerf_fwd_kernel<false, true>},     // MI_FIELD_NERF
-    {(const void*)siren_fwd_kernel<false>, (const void*)siren_fwd_kernel<true>},                 // MI_FIELD_SIREN_NERF
-    {(const void*)film_fwd_kernel<true, false>, (const void*)film_fwd_kernel<true, true>},       // MI_FIELD_FILM_SIREN_NERF
-    {(const void*)film_fwd_kernel<false, false>, (const void*)film_fwd_kernel<false, true>},     // ..._NODIR
-    {(const void*)nerf_fwd_kernel<true, false>, (const void*)nerf_fwd_kernel<true, true>}};      // MI_FIELD_TINY_NERF
+// [kind][variant]: the inference, the training (layer inputs saved) and the sigma-only instance of each kind's kernel.
+// The FiLM kinds have no sigma-only instance (their caller, pi_GAN, renders both passes with one field and needs the
+// coarse colours for the merge): has_sigma_only_kernel() is false for them.
+enum FwdVariant : int { FWD_INFER = 0, FWD_SAVE = 1, FWD_SIGMA = 2 };
+static const void* const kFwdKernels[MI_FIELD_KINDS][3] = {
+    {(const void*)nerf_fwd_kernel<false, false, false>, (const void*)nerf_fwd_kernel<false, true, false>,
+     (const void*)nerf_fwd_kernel<false, false, true>},                                                     // MI_FIELD_NERF
+    {(const void*)siren_fwd_kernel<false, false>, (const void*)siren_fwd_kernel<true, false>,
+     (const void*)siren_fwd_kernel<false, true>},                                                           // MI_FIELD_SIREN_NERF
+    {(const void*)film_fwd_kernel<true, false>, (const void*)film_fwd_kernel<true, true>, nullptr},         // MI_FIELD_FILM_SIREN_NERF
+    {(const void*)film_fwd_kernel<false, false>, (const void*)film_fwd_kernel<false, true>, nullptr},       // ..._NODIR
+    {(const void*)nerf_fwd_kernel<true, false, false>, (const void*)nerf_fwd_kernel<true, true, false>,
+     (const void*)nerf_fwd_kernel<true, false, true>}};                                                     // MI_FIELD_TINY_NERF
 
-int launch_mlp(int kind, const MlpArgs& a, int64_t n_groups, hipStream_t stream) {
+bool has_sigma_only_kernel(int kind) { return kind >= 0 && kind < MI_FIELD_KINDS && kFwdKernels[kind][FWD_SIGMA]; }
+
+int launch_mlp(int kind, const MlpArgs& a, int64_t n_groups, hipStream_t stream, bool sigma_only) {
     const int64_t blocks = n_groups * a.tiles_per_group;
     if (blocks <= 0) return 0;
     if (blocks > 0x7fffffffLL) { set_error("too many point tiles (%lld)", (long long)blocks); return -1; }
     if (bad_kind(kind)) return -1;
+    if (sigma_only && (a.save || !has_sigma_only_kernel(kind))) {
+        set_error("kind %d has no sigma-only forward%s", kind, a.save ? " with saved layer inputs" : "");
+        return -1;
+    }
     const size_t lds = kLdsFloats * sizeof(float);
     // 148 KiB of dynamic LDS: raise the per-kernel limit once per device (host-side attribute, no device work)
     static PerDeviceOnce attr_once;
     const int arc = attr_once.run([&]() {
         for (const auto& k : kFwdKernels)
             for (const void* f : k) {
+                if (!f) continue;
                 const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
                 if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return -2; }
             }
@@ -321,7 +355,8 @@ int launch_mlp(int kind, const MlpArgs& a, int64_t n_groups, hipStream_t stream)
     });
     if (arc) return arc;
     void* args[] = {const_cast<MlpArgs*>(&a)};
-    (void)hipLaunchKernel(kFwdKernels[kind][a.save != nullptr], dim3((unsigned)blocks), dim3(256), args, lds, stream);
+    const int variant = sigma_only ? FWD_SIGMA : a.save ? FWD_SAVE : FWD_INFER;
+    (void)hipLaunchKernel(kFwdKernels[kind][variant], dim3((unsigned)blocks), dim3(256), args, lds, stream);
     return check_launch("field_mlp_fwd");
 }
 

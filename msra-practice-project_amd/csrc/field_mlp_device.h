@@ -643,6 +643,11 @@ __device__ __forceinline__ void store_out(const MlpArgs& a, const PointIn& pt, i
     if (pt.valid && h == 0) reinterpret_cast<f32x4*>(a.out)[pt.p] = f32x4{r, g, b, s};
 }
 
+// sigma-only forward: out is a compact sigma buffer [points] (one float per point, not [points][4])
+__device__ __forceinline__ void store_sigma(const MlpArgs& a, const PointIn& pt, int h, float s) {
+    if (pt.valid && h == 0) a.out[pt.p] = s;
+}
+
 
 // ---- activations <-> HBM in [point][feature] row-major (training: saved layer inputs, gradients) --------
 // Register r of block m on lane (col j, half h) is feature 32m + 8(r>>2) + 4h + (r&3) of point j, so each

@@ -51,7 +51,7 @@ struct MlpArgs {
     const float* film;      // [groups][9][512] or null
     const float* a;         // points x[M,6] (mode 0) or rays [N,2,3] (mode 1)
     const float* z;         // [N,S] (mode 1)
-    float* out;             // [M,4]
+    float* out;             // [M,4]; the sigma-only forward: [M] (sigma alone)
     int64_t points_per_group;
     int64_t rays_per_group;
     int64_t tiles_per_group;
@@ -74,7 +74,9 @@ struct MlpArgs {
 enum StreamDir : int { STREAM_FWD = 0, STREAM_BWD = 1 };
 
 // host launchers (field_mlp.hip, field_mlp_bwd.hip, render_stages.hip, eval_stages.hip, adam_step.hip)
-int launch_mlp(int kind, const MlpArgs& a, int64_t n_groups, hipStream_t stream);
+// sigma_only: the kind's sigma-only instance (has_sigma_only_kernel), which writes sigma alone to a.out [M]
+int launch_mlp(int kind, const MlpArgs& a, int64_t n_groups, hipStream_t stream, bool sigma_only = false);
+bool has_sigma_only_kernel(int kind);
 int64_t bwd_partial_floats(int64_t P);
 int64_t film_partial_floats(int64_t n_groups, int64_t points_per_group);
 int launch_field_backward(int kind, const float* packed_bwd, const float* acts, float* grads, const float* raw,
@@ -87,6 +89,8 @@ int launch_sample_coarse(int64_t n, float near_, float far_, int nc, const float
                          uint64_t seed, uint64_t ray0, float* z, hipStream_t stream);
 int launch_composite(int64_t n, int S, const float* raw, const float* z, const float* rays, float* rgb, float* depth,
                      float* acc, float* weights, hipStream_t stream);
+int launch_composite_weights(int64_t n, int S, const float* sigma, int sigma_stride, const float* z, const float* rays,
+                             float* depth, float* acc, float* weights, hipStream_t stream);
 int launch_composite_bwd(int64_t n, int S, const float* raw, const float* z, const float* rays, const float* g_rgb,
                          const float* g_depth, const float* g_acc, const float* g_w, float* g_raw, hipStream_t stream);
 int64_t image_metrics_workspace_floats(int images, int channels, int H, int W);

@@ -3,6 +3,7 @@
 //   gen_rays_kernel       get_rays                       reference nerf/render.py:7-23
 //   sample_coarse_kernel  stratified depths              nerf/render.py:123-132
 //   composite_kernel      raw_to_outputs                 nerf/render.py:78-103
+//   composite_weights_kernel  its weights (+ depth / acc) from sigma alone, for a coarse pass whose colours are discarded
 //   sample_fine_kernel    sample_pdf + detach/cat/sort   nerf/render.py:27-56, 140-142
 //
 // All arithmetic is fp32 in the reference's operation order (this file is compiled with
@@ -143,6 +144,62 @@ __global__ __launch_bounds__(256) void composite_kernel(int64_t n, int S, const 
         rgb[ray * 3 + 0] = sr + bg; rgb[ray * 3 + 1] = sg + bg; rgb[ray * 3 + 2] = sb + bg;
         depth[ray] = sd;
         acc[ray] = sa;
+    }
+}
+
+// The coarse pass of a renderer that discards the coarse colours: only sigma is read (element e at
+// sigma[e * sigma_stride]: a compact [n,S] buffer with stride 1, or the sigma channel of raw [n,S,4] with raw + 3 and
+// stride 4), the weights [n,S] are written, depth / acc only when non-null.  Same weights, depth and acc bits as
+// composite_kernel: its operations in its order (the colour sums it drops are sums of their own).
+template <int G>
+__global__ __launch_bounds__(256) void composite_weights_kernel(int64_t n, int S, const float* __restrict__ sigma,
+                                                                int sigma_stride, const float* __restrict__ z,
+                                                                const float* __restrict__ rays, float* __restrict__ depth,
+                                                                float* __restrict__ acc, float* __restrict__ weights) {
+    const int lane = threadIdx.x & 63;
+    const int sub = lane & (G - 1);
+    const int64_t groups_per_block = 256 / G;
+    const int64_t ray = (int64_t)blockIdx.x * groups_per_block + threadIdx.x / G;
+    const bool live = ray < n;
+    const int64_t rc = live ? ray : n - 1;
+    const float* rd = rays + rc * 6 + 3;
+    const float nrm = sqrtf((rd[0] * rd[0] + rd[1] * rd[1]) + rd[2] * rd[2]);
+    double T = 1.0;
+    float sd = 0.f, sa = 0.f;
+    for (int k0 = 0; k0 < S; k0 += G) {
+        const int k = k0 + sub;
+        const bool in = k < S;
+        const int kc = in ? k : S - 1;
+        const float sg = sigma[(rc * S + kc) * sigma_stride];
+        const float zk = z[rc * S + kc];
+        const float zn = kc + 1 < S ? z[rc * S + kc + 1] : 0.f;
+        float delta = kc + 1 < S ? zn - zk : 1e10f;
+        delta = delta * nrm;
+        const float alpha = in ? 1.0f - expf(-sg * delta) : 0.f;
+        const float f = in ? (1.0f - alpha) + 1e-10f : 1.f;
+        double p = (double)f;                               // composite_kernel's fp64 product scan
+#pragma unroll
+        for (int o = 1; o < G; o <<= 1) {
+            const double q = __shfl_up(p, o, G);
+            if (sub >= o) p *= q;
+        }
+        double excl = __shfl_up(p, 1, G);
+        if (sub == 0) excl = 1.0;
+        const float w = alpha * (float)(T * excl);
+        T = T * __shfl(p, G - 1, G);
+        if (in) {
+            sd += w * zk; sa += w;
+            if (live) weights[rc * S + k] = w;
+        }
+    }
+    if (!depth && !acc) return;
+#pragma unroll
+    for (int o = G / 2; o > 0; o >>= 1) {
+        sd += __shfl_xor(sd, o, G); sa += __shfl_xor(sa, o, G);
+    }
+    if (live && sub == 0) {
+        if (depth) depth[ray] = sd;
+        if (acc) acc[ray] = sa;
     }
 }
 
@@ -489,6 +546,22 @@ int launch_composite(int64_t n, int S, const float* raw, const float* z, const f
                            rays, rgb, depth, acc, weights);
     }
     return check_launch("composite");
+}
+
+int launch_composite_weights(int64_t n, int S, const float* sigma, int sigma_stride, const float* z, const float* rays,
+                             float* depth, float* acc, float* weights, hipStream_t stream) {
+    if (n <= 0) return 0;
+    if (S > 32) {
+        hipLaunchKernelGGL(composite_weights_kernel<64>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, n, S, sigma,
+                           sigma_stride, z, rays, depth, acc, weights);
+    } else if (S > 16) {
+        hipLaunchKernelGGL(composite_weights_kernel<32>, dim3((unsigned)((n + 7) / 8)), dim3(256), 0, stream, n, S, sigma,
+                           sigma_stride, z, rays, depth, acc, weights);
+    } else {
+        hipLaunchKernelGGL(composite_weights_kernel<16>, dim3((unsigned)((n + 15) / 16)), dim3(256), 0, stream, n, S, sigma,
+                           sigma_stride, z, rays, depth, acc, weights);
+    }
+    return check_launch("composite_weights");
 }
 
 int launch_composite_bwd(int64_t n, int S, const float* raw, const float* z, const float* rays, const float* g_rgb,

@@ -232,9 +232,11 @@ class _Workspace:
 
 def render_rays_fused(pf_c: PackedField, pf_f: PackedField, rays: torch.Tensor, near: float, far: float,
                       n_coarse: int, n_fine: int, film=None, t_rand=None, seed: int = 0, exact_linspace: bool = True,
-                      ray0: int = 0):
+                      ray0: int = 0, coarse_outputs: bool = True):
     """render_rays (render.py:106-147) as one C-ABI call: six launches on the current stream.
-    Returns the reference's 6-tuple."""
+    Returns the reference's 6-tuple.  coarse_outputs=False: the caller discards the coarse pass's outputs, which come back
+    as None; with two different fields the library then runs the coarse field's sigma-only forward (mi_render_rays).
+    The fine outputs are the same bits either way."""
     lib = _lib.load()
     dev = pf_c.device
     rays = _f32c(rays, dev).reshape(-1, 2, 3)
@@ -244,7 +246,8 @@ def render_rays_fused(pf_c: PackedField, pf_f: PackedField, rays: torch.Tensor, 
         t_rand = _f32c(t_rand, dev)
         if tuple(t_rand.shape) != (n, n_coarse):
             raise _lib.MiRenderError(f"t_rand must be [{n},{n_coarse}]")
-    outs = [torch.empty(s, dtype=torch.float32, device=dev) for s in ((n, 3), (n,), (n,), (n, 3), (n,), (n,))]
+    outs = [torch.empty(s, dtype=torch.float32, device=dev) if coarse_outputs or k >= 3 else None
+            for k, s in enumerate(((n, 3), (n,), (n,), (n, 3), (n,), (n,)))]
     ws_bytes = lib.mi_render_workspace_bytes(n, n_coarse, n_fine)
     if pf_c is pf_f and n_fine > 0:
         # one field for both passes: with room for z_samples / their raw values / the merge positions the library evaluates

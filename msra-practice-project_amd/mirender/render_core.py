@@ -112,6 +112,14 @@ def render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, fi
     so a frame rendered in pieces (chunks, GPUs) gets the jitter it would get in one call.
     `film` [b,9,512] (FiLM fields only) renders b images in one call: rays are b equal consecutive groups and
     group g uses film[g]; by default the model's own film_params (one image) are used like the reference."""
+    return _render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, fine_sample_num, t_rand=t_rand,
+                        seed=seed, film=film, ray0=ray0)
+
+
+def _render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, fine_sample_num, *,
+                 t_rand=None, seed=None, film=None, ray0=0, coarse_outputs=True):
+    """render_rays; coarse_outputs=False lets the fused inference path skip what only the coarse outputs need
+    (ops.render_rays_fused), which may then return None in their slots.  The fine outputs are the same bits."""
     dev = _device_of(coarse_model, fine_model, rays=rays)
     rays = torch.as_tensor(rays).to(device=dev, dtype=torch.float32).reshape(-1, 2, 3).contiguous()
     nc, nf = int(coarse_sample_num), int(fine_sample_num)
@@ -145,7 +153,8 @@ def render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, fi
         if needs_grad:
             from . import autograd
             return autograd.render_rays_train(pf_c, pf_f, rays, near, far, nc, nf, film, t_rand, seed or 0, ray0)
-        return ops.render_rays_fused(pf_c, pf_f, rays, near, far, nc, nf, film, t_rand, seed or 0, ray0=ray0)
+        return ops.render_rays_fused(pf_c, pf_f, rays, near, far, nc, nf, film, t_rand, seed or 0, ray0=ray0,
+                                     coarse_outputs=coarse_outputs)
 
     # generic path: sampling / compositing kernels around an arbitrary callable (or a mixed pair: one fused kind, one
     # callable).  Differentiable like the reference's torch ops (render.py:59-103): the callable's graph reaches `raw`,
@@ -177,7 +186,8 @@ def _render_image_device(width, height, focal, pose, near, far, coarse_model, fi
         m = min(step, ray0 + n_rays - i)
         rays = ops.gen_rays(width, height, focal, pose, dev, i, m)
         tr = None if t_rand is None else t_rand[i - ray0:i - ray0 + m]   # row k of t_rand <-> ray ray0 + k
-        out = render_rays(rays, near, far, coarse_model, fine_model, nc, nf, t_rand=tr, seed=seed, ray0=i)
+        out = _render_rays(rays, near, far, coarse_model, fine_model, nc, nf, t_rand=tr, seed=seed, ray0=i,
+                           coarse_outputs=False)
         parts.append(out[3:6])
     if not parts:                                          # an empty ray range (a rank of a group larger than the frame)
         return (torch.empty((0, 3), dtype=torch.float32, device=dev), torch.empty(0, dtype=torch.float32, device=dev),

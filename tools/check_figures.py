@@ -121,7 +121,35 @@ def checks(s):
         (r"generator\s+step ([\d.]+) s \(([\d.]+) of peak on the 108", [tr["c4"]["ms_per_step"] / 1e3, tr["c4"]["frac"]]),
         (r"256² training step ([\d.]+) s per GPU \(([\d.]+)\)", [tr["c5"]["ms_per_step"] / 1e3, tr["c5"]["frac"]]),
     ]
+    r5 = sigma_only_sources()
+    design += [
+        (r"the\s+coarse launch takes ([\d.]+) ms against ([\d.]+) ms before, ([\d.]+) TFLOP/s executed = ([\d.]+) of the peak, as efficient as the\s+whole forward; the fine launch is unchanged \(([\d.]+) ms against ([\d.]+) ms\)",
+         [r5["coarse"]["branch"], r5["coarse"]["main"], r5["sigma_tflops"], r5["sigma_tflops"] / PEAK, r5["fine"]["branch"], r5["fine"]["main"]]),
+        (r"alternating on one MI355X\): ([\d ]+) / ([\d ]+) / ([\d ]+) rays/s before against ([\d ]+) / ([\d ]+) / ([\d ]+)\s+after, \+([\d.]+) % on every pair",
+         [*r5["value"]["main"], *r5["value"]["branch"], r5["min_gain_pct"]]),
+        (r"`roofline.frac` rises from ([\d.]+) to\s+([\d.]+), but only", [r5["frac"]["main"], r5["frac"]["branch"]]),
+    ]
     return [("DESIGN.md", design), ("README.md", readme)]
+
+
+def sigma_only_sources():
+    """The sigma-only coarse pass: mean coarse / fine MLP launch of each build from the kernel traces (the
+    launches alternate coarse, fine), and the alternating bench pairs."""
+    out = {"coarse": {}, "fine": {}, "value": {"main": [], "branch": []}, "frac": {}}
+    for b in ("main", "branch"):
+        with open(os.path.join(ROOT, f"profiles/r05_sigma_only_c3_kernel_trace_{b}.csv")) as f:
+            rows = sorted((r for r in csv.DictReader(f) if "nerf_fwd_kernel" in r["Kernel_Name"]), key=lambda r: int(r["Start_Timestamp"]))
+        d = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6 for r in rows]
+        out["coarse"][b], out["fine"][b] = sum(d[0::2]) / len(d[0::2]), sum(d[1::2]) / len(d[1::2])
+    with open(os.path.join(ROOT, "profiles/r05_sigma_only_bench_pairs.log")) as f:
+        runs = [json.loads(ln) for ln in f if ln.startswith("{")]
+    for r in runs:
+        out["value"][r["build"]].append(r["line"]["value"])
+        out["frac"].setdefault(r["build"], []).append(r["line"]["roofline"]["frac"])
+    out["frac"] = {b: sum(v) / len(v) for b, v in out["frac"].items()}
+    out["min_gain_pct"] = min(100 * (b / m - 1) for m, b in zip(out["value"]["main"], out["value"]["branch"]))
+    out["sigma_tflops"] = 2 * 489728 * 640000 * 64 / (out["coarse"]["branch"] * 1e-3) / 1e12
+    return out
 
 
 def _format_like(text: str, value: float) -> str:

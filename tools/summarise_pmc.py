@@ -8,7 +8,7 @@ import csv, glob, json, os, shutil, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1] if len(sys.argv) > 1 else "r01"
 out_dir = os.path.join(ROOT, "profiles")
-KERNEL = "nerf_fwd_kernel<false, false>"
+KERNEL = "nerf_fwd_kernel<false, false, false>"   # the inference instance: the fine launch (the coarse one is <false, false, true>)
 
 
 def newest(pattern):
@@ -65,7 +65,7 @@ derived = {
 json.dump({
     "command": "bash tools/profile_round.sh (rocprofv3 --pmc <group> --kernel-trace --output-format csv -- python3 "
                "bench.py --steps 1 --warmup 0 --no-cpu-baseline; one pass per counter group)",
-    "kernel": "mi::nerf_fwd_kernel<false,false>",
+    "kernel": "mi::nerf_fwd_kernel<false, false, false>",
     "launch_points": [l["points"] for l in launches], "launch_ms": [l["ms"] for l in launches],
     "counters": counters, "derived_fine_launch": derived}, open(os.path.join(out_dir, f"{tag}_pmc_nerf_fwd.json"), "w"), indent=1)
 print(json.dumps(derived, indent=1))
