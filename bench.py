@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Headline benchmark: rays/s of the ray-march + field-MLP + alpha-composite path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W          (N > 1 without WORLD_SIZE: spawns its own N ranks)
-    python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]   (N > 1 without WORLD_SIZE: spawns its own N ranks)
+    python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W [--full]
 
 One step = one synthetic 800x800 frame (640 000 rays) rendered with 64 coarse + 128 fine samples per ray
 through separate coarse / fine NeRF 8x256 models (BASELINE.json config C3, nerf/configs/lego.json) by the
@@ -11,10 +11,15 @@ weights and rays resident in HBM before the timed region.  With N > 1 the frame'
 contiguous ranges (one process per GPU) and reassembled by one RCCL all-gather per frame, so total work
 is fixed: scaling = "strong".  Rank 0 prints ONE JSON line.
 
-Extra objects in the line:
+A plain run does only what the headline figure needs: set-up, W warm-up steps, K timed steps, --dump-outputs, the line.
+Extra objects in its line, all taken from the timed steps themselves:
   roofline      fused field-MLP kernel (nerf_fwd_kernel) timed with HIP events around its launches inside
                 the timed region; achieved = algorithmic FLOPs (2 x 591 488 MACs per point)
                 per launch / mean launch duration, peak = 157.3 TFLOP/s fp32 MFMA (MI355X_MICROARCH.md)
+  collective    N>1 (or --force-collective): ranks seen by torch.distributed, per-rank mean MLP launch time,
+                all-gather time per frame
+
+--full adds what takes runs of its own, after the timed steps (each can be left out with its --no-* option):
   frame64       the "800^2 frame @ 64 samples" figure of BASELINE.json's metric (Nc=64, Nf=0, one model)
   cpu_baseline  the CPU oracle (oracle/render_ref.py, PyTorch CPU, all host cores) on a bounded sample of
                 the same workload, rank 0, N=1 only; with it `psnr_vs_ref`: held-out-view PSNR of a TinyNeRF fitted
@@ -25,8 +30,6 @@ Extra objects in the line:
                 renderer evaluates the fine pass's Nf new depths only: `frac` / `frac_executed` count what
                 this renderer executes (C4: 108 evaluation-equivalents per ray) - the figure to hold against MFMA-busy -
                 and `frac_reference_equivalent` SURVEY.md 8d's count of what the reference executes (120)
-  collective    N>1 (or --force-collective): ranks seen by torch.distributed, per-rank mean MLP launch time,
-                all-gather time per frame
 
 --dump-outputs DIR writes what the timed path handed its caller in the LAST timed step as DIR/<name>.npy (float32, or
 float64 where the path computes in float64): c3 the frame's rgb / depth / acc; a training workload the step's render
@@ -436,11 +439,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what takes runs of its own: the 64-sample frame, the "
+                         "secondary training workloads and (N=1) the CPU baseline with psnr_vs_ref")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and psnr_vs_ref")
     ap.add_argument("--no-frame64", action="store_true",
-                    help="skip the secondary 64-sample frame (profiling runs: keeps every nerf_fwd_kernel launch in the "
-                         "trace one of the timed step's two launches, so rocprofv3's average matches roofline.avg_launch_ms)")
-    ap.add_argument("--no-train", action="store_true", help="skip the secondary training workloads folded into the N=1 line")
+                    help="with --full: skip the secondary 64-sample frame (profiling runs: keeps every nerf_fwd_kernel launch "
+                         "in the trace one of the timed step's two launches, so rocprofv3's average matches "
+                         "roofline.avg_launch_ms)")
+    ap.add_argument("--no-train", action="store_true", help="with --full: skip the secondary training workloads")
     ap.add_argument("--force-collective", action="store_true",
                     help="N=1 only: initialise a one-rank nccl (RCCL) group and issue the frame's all-gather / the gradient "
                          "all-reduce anyway (mirender.dist.FORCE_COLLECTIVE), so the collective code runs on a one-GPU box")
@@ -555,7 +562,7 @@ def main():
 
     # the "800^2 frame @ 64 samples" figure: Nc=64, Nf=0, fine model = coarse model (second pass aliased)
     f64_s = None
-    if not args.no_frame64:
+    if args.full and not args.no_frame64:
         sync()
         t1 = time.perf_counter()
         reps = max(2, args.steps)
@@ -583,14 +590,14 @@ def main():
                       "note": "one all_gather_into_tensor of packed [n_local, 5] fp32 per frame, issued after the last "
                               "composite kernel (no overlap: the frame is not complete before that)"}
 
-    # The secondary training workloads inside this (driver-timed) run, after the frame's workspace is freed - at EVERY N, so
-    # that the driver's own 1/2/4/8-GPU command also times what BASELINE.json's north_star asks of 8 GPUs: the pi_GAN
+    # --full: the secondary training workloads inside this run, after the frame's workspace is freed - at EVERY N, so that
+    # `--gpus 1/2/4/8 --full` also times what BASELINE.json's north_star asks of 8 GPUs: the pi_GAN
     # 256x256 training step (config C5: 4 images per GPU, D-step forward + G-step) and the nerf 1024-rays-per-GPU step, both
     # data-parallel with ONE flat RCCL all-reduce of the renderer gradients per step (pi_GAN/train.py:50,52's DataParallel
     # replaced), the all-reduce timed on its own.  Weak scaling (per-GPU work fixed): efficiency = ms_per_step(1) / ms_per_step(N).
     # C4 (batch 32 on one GPU) is a single-GPU configuration and stays at N = 1.
     train = None
-    if not args.no_train:
+    if args.full and not args.no_train:
         del out
         from mirender import ops
         ops._Workspace.release()
@@ -639,7 +646,7 @@ def main():
             line["collective"] = collective
         if train is not None:
             line["train"] = train
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline()
             line["gpu_over_cpu"] = rays_per_s / line["cpu_baseline"]["value"]
             line["psnr_vs_ref"] = psnr_vs_ref(dev)

@@ -17,8 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def run_bench(*args):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-frame64", "--no-train",
-                        *args], capture_output=True, text=True, timeout=500)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args], capture_output=True, text=True, timeout=500)
     assert r.returncode == 0, r.stderr[-3000:]
     return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
 
@@ -30,6 +29,9 @@ def test_dump_is_the_frame_of_the_last_timed_step(tmp_path):
     steps, warmup = 2, 1
     line = run_bench("--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(tmp_path))
     assert line["steps"] == steps and line["warmup"] == warmup
+    # a plain run is lean: what takes runs of its own waits for --full
+    assert not {"frame64", "train", "cpu_baseline", "gpu_over_cpu", "psnr_vs_ref"} & set(line), sorted(line)
+    assert line["roofline"]["launches"] == 2 * steps
     got = {n: np.load(tmp_path / f"{n}.npy") for n in ("rgb", "depth", "acc")}
     assert sorted(os.listdir(tmp_path)) == ["acc.npy", "depth.npy", "rgb.npy"]
     assert got["rgb"].shape == (bench.H, bench.W, 3) and got["depth"].shape == got["acc"].shape == (bench.H, bench.W, 1)

@@ -96,7 +96,7 @@ def test_two_ranks_one_device_frame_and_training_step():
 
 @pytest.mark.timeout(600)
 def test_the_drivers_two_gpu_command_end_to_end():
-    """`python bench.py --gpus 2 ...` exactly as the driver's scaling run starts it (the script spawns its own two ranks through
+    """`python bench.py --gpus 2 ... --full` as a scaling run starts it (the script spawns its own two ranks through
     torch.distributed.run), with both ranks on this box's one device (MI_BENCH_REHEARSAL=2: gloo, the pi_GAN images shrunk so that
     two steps fit next to whatever this test process holds): ONE JSON line comes back, the frame was ray-sharded over two ranks, and
     its `train` object holds the nerf step and the C5 step with two ranks' step times and gradient all-reduce times."""
@@ -107,7 +107,8 @@ def test_the_drivers_two_gpu_command_end_to_end():
     torch.cuda.empty_cache()
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["MI_BENCH_REHEARSAL"] = "2"
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--no-frame64"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--full",
+                        "--no-frame64"],
                        env=env, capture_output=True, text=True, timeout=560)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -1,5 +1,5 @@
-"""Copy the rocprofv3 outputs of tools/profile_round.sh from gpurun_out/ into profiles/ and derive the
-per-launch figures bench.py's roofline.traffic reads (profiles/rNN_pmc_nerf_fwd.json).
+"""Copy the rocprofv3 outputs of tools/profile_round.sh from its output folder ($PROFILE_OUT, default profile_out/) into
+profiles/ and derive the per-launch figures bench.py's roofline.traffic reads (profiles/rNN_pmc_nerf_fwd.json).
 
 FETCH_SIZE / WRITE_SIZE count KiB; on gfx950 FETCH_SIZE under-reports by 2x (MI355X_MICROARCH.md, HBM / rocprofv3
 section).  Both the raw and the corrected figures are written out."""
@@ -8,23 +8,24 @@ import csv, glob, json, os, shutil, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1] if len(sys.argv) > 1 else "r01"
 out_dir = os.path.join(ROOT, "profiles")
+run_dir = os.path.join(ROOT, os.environ.get("PROFILE_OUT", "profile_out"))      # what tools/profile_round.sh wrote
 KERNEL = "nerf_fwd_kernel<false, false, false>"   # the inference instance: the fine launch (the coarse one is <false, false, true>)
 
 
 def newest(pattern):
-    files = glob.glob(os.path.join(ROOT, "gpurun_out", pattern), recursive=True)
+    files = glob.glob(os.path.join(run_dir, pattern), recursive=True)
     return max(files, key=os.path.getmtime) if files else None
 
 
 stats = newest("prof_stats/**/*kernel_stats.csv")
 if stats:
     shutil.copy(stats, os.path.join(out_dir, f"{tag}_bench_c3_kernel_stats.csv"))
-bench = os.path.join(ROOT, "gpurun_out", "bench.log")
+bench = os.path.join(run_dir, "bench.log")
 if os.path.exists(bench):
     shutil.copy(bench, os.path.join(out_dir, f"{tag}_bench_n1.log"))
 
 counters, launches = {}, None
-for d in sorted(glob.glob(os.path.join(ROOT, "gpurun_out", "pmc_*"))):
+for d in sorted(glob.glob(os.path.join(run_dir, "pmc_*"))):
     if not os.path.isdir(d):
         continue
     f = max(glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True), key=os.path.getmtime)
@@ -45,7 +46,7 @@ for d in sorted(glob.glob(os.path.join(ROOT, "gpurun_out", "pmc_*"))):
                 counters.setdefault(name, []).append(v)
 
 if not counters:
-    sys.exit("no PMC passes found under gpurun_out/")
+    sys.exit(f"no PMC passes found under {run_dir}")
 i = max(range(len(launches)), key=lambda j: launches[j]["points"])      # the fine pass: most points
 pts, ms = launches[i]["points"], launches[i]["ms"]
 g = lambda n: counters[n][i]
@@ -74,7 +75,7 @@ print(json.dumps(derived, indent=1))
 # ---- training workloads: per-kernel HBM traffic and MFMA-busy fraction over the traced run (profile_round.sh) ----
 def train_summary(wl):
     per_kernel = {}
-    for d in sorted(glob.glob(os.path.join(ROOT, "gpurun_out", f"pmct_{wl}_*"))):
+    for d in sorted(glob.glob(os.path.join(run_dir, f"pmct_{wl}_*"))):
         if not os.path.isdir(d):
             continue
         f = max(glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True), key=os.path.getmtime)
@@ -100,9 +101,9 @@ def train_summary(wl):
     stats = newest(f"prof_stats_{wl}/**/*kernel_stats.csv")
     if stats:
         shutil.copy(stats, os.path.join(out_dir, f"{tag}_bench_{wl}_kernel_stats.csv"))
-    log = os.path.join(ROOT, "gpurun_out", f"bench_{wl}.log")              # the unprofiled run of tools/profile_round.sh
+    log = os.path.join(run_dir, f"bench_{wl}.log")              # the unprofiled run of tools/profile_round.sh
     if not os.path.exists(log):
-        log = os.path.join(ROOT, "gpurun_out", f"prof_stats_{wl}.log")
+        log = os.path.join(run_dir, f"prof_stats_{wl}.log")
     if os.path.exists(log):
         line = [l for l in open(log) if l.startswith("{")]
         if line:
