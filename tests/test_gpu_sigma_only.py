@@ -5,8 +5,8 @@ different fields the coarse pass then feeds nothing but sample_fine's weights, w
 runs the coarse field's sigma-only forward (the trunk and the sigma head) and a weights-only composite.  Sigma is final
 before the colour branch starts, so the fine outputs must be the SAME BITS as those of a call that asks for all six:
 
-* NeRF / TinyNeRF / SirenNeRF pairs, 64 + 128 and small odd sample counts, point counts that leave a partial 128-point
-  tile, seeded jitter and t_rand;
+* NeRF / TinyNeRF / SirenNeRF pairs, 64 + 128 and small odd sample counts, 65 coarse samples (two passes of the
+  weights-only composite: its carry of T), point counts that leave a partial 128-point tile, seeded jitter and t_rand;
 * depth_c / acc_c asked for while rgb_c is NULL: bit-equal to the all-six call's;
 * the fallbacks (one shared field, Nf = 0 with one field, a FiLM pair) give the same bits too;
 * render_image / render_image_dist equal render_rays(...)[3:6]."""
@@ -61,7 +61,7 @@ def _assert_same(a, b):
 @pytest.mark.parametrize("kind,n,nc,nf,jitter", [("nerf", 257, 64, 128, "seed"), ("nerf", 33, 5, 3, "t_rand"),
                                                  ("tiny_nerf", 130, 7, 11, "seed"), ("tiny_nerf", 64, 64, 128, "t_rand"),
                                                  ("siren_nerf", 101, 9, 0, "t_rand"), ("siren_nerf", 257, 64, 128, "seed"),
-                                                 ("nerf", 1, 3, 1, "seed")])
+                                                 ("nerf", 1, 3, 1, "seed"), ("tiny_nerf", 130, 65, 16, "t_rand")])
 def test_sigma_only_coarse_pass_gives_the_same_fine_bits(kind, n, nc, nf, jitter):
     from mirender import fields, ops
     pf_c, pf_f = fields.as_packed_field(_field(kind, 5)), fields.as_packed_field(_field(kind, 6))

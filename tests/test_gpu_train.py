@@ -36,6 +36,16 @@ def model(kind, sd):
     return m.to(dev())
 
 
+def _assert_close_last_and_interior(got, ref):
+    """2e-5 of the largest gradient, the last sample of a ray and the samples before it each on their own scale: the
+    last delta is 1e10 |d| (render.py:94), so d/dsigma of a last sample with sigma == 0 is about 1e10, and on that scale
+    every other element would pass as 0 (per element against float64: test_gpu_composite_stages.py)."""
+    for part in (slice(-1, None), slice(0, -1)):
+        g, r = got[:, part], ref[:, part]
+        if r.numel():
+            assert float((g - r).abs().max()) <= 2e-5 * max(1.0, float(r.abs().max())), part
+
+
 @pytest.mark.parametrize("S", [1, 13, 64, 192])
 def test_composite_bwd_vs_oracle_autograd(S):
     from mirender import autograd as A
@@ -52,15 +62,14 @@ def test_composite_bwd_vs_oracle_autograd(S):
     rays = torch.from_numpy(np.stack([np.zeros_like(rd), rd], 1)).to(dev())
     got = A._composite_bwd(torch.from_numpy(raw).to(dev()), torch.from_numpy(z).to(dev()), rays,
                            g[0].to(dev()), g[1].to(dev()), g[2].to(dev())).cpu()
-    scale = float(rt.grad.abs().max())
-    assert float((got - rt.grad).abs().max()) <= 2e-5 * max(1.0, scale)
+    _assert_close_last_and_interior(got, rt.grad)
     # partial cotangents (None) behave as zeros
     got2 = A._composite_bwd(torch.from_numpy(raw).to(dev()), torch.from_numpy(z).to(dev()), rays, g[0].to(dev()),
                             None, None).cpu()
     rt.grad = None
     rgb, _, _, _ = R.composite(rt, torch.from_numpy(z), torch.from_numpy(rd))
     (rgb * g[0]).sum().backward()
-    assert float((got2 - rt.grad).abs().max()) <= 2e-5 * max(1.0, float(rt.grad.abs().max()))
+    _assert_close_last_and_interior(got2, rt.grad)
 
 
 def _grad_check(case, named_got, g, prefix, tol=2e-4):
