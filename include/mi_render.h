@@ -36,7 +36,15 @@ extern "C" {
 #define MI_FIELD_FILM_SIREN_NERF 2        /* pi_GAN/modules.py:70-118 use_dir=True  */
 #define MI_FIELD_FILM_SIREN_NERF_NODIR 3  /* pi_GAN/modules.py:70-118 use_dir=False */
 #define MI_FIELD_TINY_NERF 4              /* build-defined 4-layer net for BASELINE C1 */
-#define MI_FIELD_KINDS 5
+#define MI_FIELD_KINDS 5                  /* the fixed kinds above */
+/* FilmSirenNeRF(hidden_dim=256, hidden_layers=L, use_dir) for any MI_FIELD_FILM_DEPTH_MIN <= L <= MI_FIELD_FILM_DEPTH_MAX
+ * (pi_GAN/modules.py:73): a kind id outside the fixed kinds, accepted by every entry point that takes a `kind`.  Its state
+ * dict is input_layer, hidden_layers.0 .. L-2, output_layer_sigma.0, hidden_layer_rgb, output_layer_rgb.0 (L + 3 linear
+ * layers) and its FiLM table has mi_field_film_layers(kind) = L + 1 rows.  L = 8 is the network of kinds 2 / 3 and gives
+ * the same bits.  A depth outside the range is MI_EINVAL. */
+#define MI_FIELD_FILM_DEPTH_MIN 4
+#define MI_FIELD_FILM_DEPTH_MAX 12
+#define MI_FIELD_FILM_DEPTH(hidden_layers, use_dir) (0x100 + 2 * (hidden_layers) + ((use_dir) ? 1 : 0))
 
 /* Library / build identification. */
 int mi_abi_version(void);
@@ -51,6 +59,9 @@ int mi_field_num_params(int kind);
 int64_t mi_field_packed_floats(int kind);
 /* Multiply-accumulates of the kind's linear layers per point (roofline accounting). */
 int64_t mi_field_macs(int kind);
+/* Rows of the kind's FiLM table (one gamma|beta row of 512 per FiLM layer): 9 for kinds 2 and 3, hidden_layers + 1 for
+ * MI_FIELD_FILM_DEPTH kinds, 0 for the kinds without FiLM. */
+int mi_field_film_layers(int kind);
 /* Shape of parameter tensor `index` (0 <= index < mi_field_num_params(kind)): weights [rows = out, cols = in], biases
  * [rows = out, cols = 1].  What a host that does not hold an nn.Module needs in order to lay out the tensors it hands to
  * mi_field_pack (the shapes of nerf/nerf.py:59-73, 128-146 and pi_GAN/modules.py:76-94). */
@@ -71,8 +82,8 @@ int mi_field_pack(int kind, const float* const* params, int n_params, float w_0,
 /* network(inputs[M,6]) -> [M,4] = (r,g,b,sigma): replaces the model call inside
  * run_network (nerf/render.py:72-74) for a known kind.
  *   x      [n_groups*points_per_group, 6]  (xyz, view_dir)
- *   film   [n_groups, 9, 512] FiLM table (gamma|beta per layer; pi_GAN/modules.py:96-99)
- *          for FILM kinds, else NULL; group g uses film[g]
+ *   film   [n_groups, mi_field_film_layers(kind), 512] FiLM table (gamma|beta per layer;
+ *          pi_GAN/modules.py:96-99) for FILM kinds, else NULL; group g uses film[g]
  *   out    [n_groups*points_per_group, 4] */
 int mi_field_eval_points(int kind, const float* packed, const float* film, const float* x,
                          int64_t n_groups, int64_t points_per_group, float* out, void* stream);
@@ -183,10 +194,12 @@ int mi_field_pack_bwd(int kind, const float* const* params, int n_params, float 
 
 /* Per-point sizes (floats) of the training buffers, or -1 if the kind has no backward yet:
  * acts = layer inputs saved by the training forward; grads = per-layer dA written by the backward chain.
- * mi_field_bwd_partial_floats(points) = scratch for the dW slab partial sums. */
+ * mi_field_bwd_partial_floats(points) = scratch for the dW slab partial sums of the fixed kinds;
+ * mi_field_bwd_partial_floats_kind(kind, points) = the same for any kind (MI_FIELD_FILM_DEPTH kinds deeper than 8 need more). */
 int64_t mi_field_train_acts_floats(int kind);
 int64_t mi_field_train_grads_floats(int kind);
 int64_t mi_field_bwd_partial_floats(int64_t points);
+int64_t mi_field_bwd_partial_floats_kind(int kind, int64_t points);
 
 /* mi_field_eval_rays that also saves every linear layer's input into `acts`
  * [mi_field_train_acts_floats(kind) * points] (points = n_groups*rays_per_group*n_samples). */
@@ -201,16 +214,18 @@ int mi_field_eval_points_train(int kind, const float* packed, const float* film,
 
 /* Backward of network(inputs) over n_groups*points_per_group points: g_raw [points,4] = dL/d(raw) ->
  * parameter gradients (and, for FiLM kinds, the gradient of the FiLM table).
- *   film            [n_groups,9,512] FiLM table of the forward (FiLM kinds) or NULL
+ *   film            [n_groups,mi_field_film_layers(kind),512] FiLM table of the forward (FiLM kinds) or NULL
  *   grad_params     HOST array of n_params device pointers (torch layouts, state-dict order), OVERWRITTEN
  *   params          HOST array of the n_params parameter tensors themselves (FiLM kinds: the FiLM-table
  *                   gradient is formed from the per-image weight-gradient sums, d gamma = <W, dW_image> +
  *                   b . db_image); NULL for the other kinds
- *   grad_film       [n_groups,9,512] (FiLM kinds) or NULL, OVERWRITTEN
+ *   grad_film       [n_groups,mi_field_film_layers(kind),512] (FiLM kinds) or NULL, OVERWRITTEN
  *   grads_ws        [mi_field_train_grads_floats(kind) * points]
- *   partial_ws      [mi_field_bwd_partial_floats(points)]
- *   film_partial_ws [mi_field_film_partial_floats(n_groups, points_per_group)] FiLM scratch (FiLM kinds) or NULL */
+ *   partial_ws      [mi_field_bwd_partial_floats_kind(kind, points)]
+ *   film_partial_ws [mi_field_film_partial_floats_kind(kind, n_groups, points_per_group)] FiLM scratch (FiLM kinds) or
+ *                   NULL; mi_field_film_partial_floats(n_groups, points_per_group) is the value for kinds 2 and 3 */
 int64_t mi_field_film_partial_floats(int64_t n_groups, int64_t points_per_group);
+int64_t mi_field_film_partial_floats_kind(int kind, int64_t n_groups, int64_t points_per_group);
 int mi_field_backward(int kind, const float* packed_bwd, const float* film, const float* acts, float* grads_ws,
                       const float* raw, const float* g_raw, int64_t n_groups, int64_t points_per_group,
                       float* partial_ws, float* film_partial_ws, float* const* grad_params,
@@ -257,7 +272,8 @@ int mi_render_rays_train(int kind_coarse, const float* packed_coarse, int kind_f
  *   grad_params_* HOST arrays of mi_field_num_params device pointers, OVERWRITTEN.  A field that receives no cotangent
  *                 is left untouched and may pass NULL.  One shared field: both passes' sum goes to grad_params_coarse
  *                 (grad_params_fine is not used).
- *   grad_film     [n_groups,9,512] (FiLM kinds), OVERWRITTEN with the sum of both passes' FiLM gradients
+ *   grad_film     [n_groups,mi_field_film_layers(kind),512] (FiLM kinds), OVERWRITTEN with the sum of both passes' FiLM
+ *                 gradients (two FiLM fields of one call share the table, so they have the same depth)
  *   bwd_workspace mi_render_backward_workspace_bytes
  *   fields_written HOST, optional: MI_WROTE_* bits of what was written; known from the NULL pattern, no synchronisation */
 #define MI_WROTE_COARSE 1

@@ -33,6 +33,19 @@ int check_launch(const char* what) {
     return MI_OK;
 }
 
+const FieldKind& field_kind(int kind) {
+    if (is_fixed_kind(kind)) return kFieldKinds[kind];
+    struct DepthKinds {
+        FieldKind k[kFilmDepthMax - kFilmDepthMin + 1][2];
+        DepthKinds() {
+            for (int L = kFilmDepthMin; L <= kFilmDepthMax; ++L)
+                for (int d = 0; d < 2; ++d) k[L - kFilmDepthMin][d] = make_film_kind(L, d != 0);
+        }
+    };
+    static const DepthKinds depth;                       // built once, on first use
+    return depth.k[film_depth(kind) - kFilmDepthMin][kind & 1];
+}
+
 static int eval_common(int kind, const float* packed, const float* film, const float* a, const float* z,
                        int64_t n_groups, int64_t ppg, int64_t rpg, int S, int mode, float* out, hipStream_t s,
                        float* save = nullptr, bool sigma_only = false) {
@@ -45,6 +58,7 @@ static int eval_common(int kind, const float* packed, const float* film, const f
     args.packed = packed; args.film = is_film(kind) ? film : nullptr; args.a = a; args.z = z; args.out = out;
     args.points_per_group = ppg; args.rays_per_group = rpg; args.tiles_per_group = (ppg + 127) / 128;
     args.n_samples = S; args.mode = mode; args.save = save; args.save_points = n_groups * ppg;
+    args.film_depth = film_depth(kind);
 #ifdef MI_PROFILE_STAMPS
     args.stamps = g_stamps;
 #else
@@ -62,12 +76,13 @@ extern "C" {
 int mi_abi_version(void) { return 4; }
 const char* mi_last_error(void) { return g_err; }
 
-int mi_field_num_params(int kind) { return bad_kind(kind) ? MI_EINVAL : 2 * kFieldKinds[kind].n_layers; }
-int64_t mi_field_packed_floats(int kind) { return bad_kind(kind) ? MI_EINVAL : packed_floats(kFieldKinds[kind].fwd); }
-int64_t mi_field_macs(int kind) { return bad_kind(kind) ? MI_EINVAL : kFieldKinds[kind].macs(); }
+int mi_field_num_params(int kind) { return bad_kind(kind) ? MI_EINVAL : 2 * field_kind(kind).n_layers; }
+int64_t mi_field_packed_floats(int kind) { return bad_kind(kind) ? MI_EINVAL : packed_floats(field_kind(kind).fwd); }
+int64_t mi_field_macs(int kind) { return bad_kind(kind) ? MI_EINVAL : field_kind(kind).macs(); }
+int mi_field_film_layers(int kind) { return bad_kind(kind) ? MI_EINVAL : film_layers(kind); }
 int mi_field_param_shape(int kind, int index, int64_t* rows, int64_t* cols) {
     if (bad_kind(kind)) return MI_EINVAL;
-    const FieldKind& k = kFieldKinds[kind];
+    const FieldKind& k = field_kind(kind);
     if (index < 0 || index >= 2 * k.n_layers || !rows || !cols) { set_error("mi_field_param_shape: bad arguments"); return MI_EINVAL; }
     *rows = k.dims[index / 2][0];
     *cols = (index & 1) ? 1 : k.dims[index / 2][1];
@@ -89,8 +104,8 @@ static int check_w0(int kind, float w_0, const char* fn) {
 int mi_field_pack(int kind, const float* const* params, int n_params, float w_0, float* packed, void* stream) {
     if (bad_kind(kind)) return MI_EINVAL;
     if (!params || !packed) { set_error("null pointer argument"); return MI_EINVAL; }
-    if (n_params != 2 * kFieldKinds[kind].n_layers) {
-        set_error("kind %d expects %d parameter tensors, got %d", kind, 2 * kFieldKinds[kind].n_layers, n_params);
+    if (n_params != 2 * field_kind(kind).n_layers) {
+        set_error("kind %d expects %d parameter tensors, got %d", kind, 2 * field_kind(kind).n_layers, n_params);
         return MI_EINVAL;
     }
     for (int i = 0; i < n_params; ++i)
@@ -296,18 +311,19 @@ int mi_composite_bwd(int64_t n, int n_samples, const float* raw, const float* z,
     return launch_composite_bwd(n, n_samples, raw, z, rays, g_rgb, g_depth, g_acc, g_weights, g_raw, (hipStream_t)stream);
 }
 
-int64_t mi_field_packed_bwd_floats(int kind) { return bad_kind(kind) ? MI_EINVAL : packed_floats(kFieldKinds[kind].bwd); }
+int64_t mi_field_packed_bwd_floats(int kind) { return bad_kind(kind) ? MI_EINVAL : packed_floats(field_kind(kind).bwd); }
 
 int mi_field_pack_bwd(int kind, const float* const* params, int n_params, float w_0, float* packed_bwd, void* stream) {
     if (bad_kind(kind)) return MI_EINVAL;
-    if (!params || !packed_bwd || n_params != 2 * kFieldKinds[kind].n_layers) { set_error("mi_field_pack_bwd: bad arguments"); return MI_EINVAL; }
+    if (!params || !packed_bwd || n_params != 2 * field_kind(kind).n_layers) { set_error("mi_field_pack_bwd: bad arguments"); return MI_EINVAL; }
     if (int rc = check_w0(kind, w_0, "mi_field_pack_bwd")) return rc;
     return launch_pack(kind, STREAM_BWD, params, n_params, w_0, packed_bwd, (hipStream_t)stream);
 }
 
-int64_t mi_field_train_acts_floats(int kind) { return bad_kind(kind) ? MI_EINVAL : region_total(kFieldKinds[kind].acts); }
-int64_t mi_field_train_grads_floats(int kind) { return bad_kind(kind) ? MI_EINVAL : region_total(kFieldKinds[kind].grads); }
+int64_t mi_field_train_acts_floats(int kind) { return bad_kind(kind) ? MI_EINVAL : region_total(field_kind(kind).acts); }
+int64_t mi_field_train_grads_floats(int kind) { return bad_kind(kind) ? MI_EINVAL : region_total(field_kind(kind).grads); }
 int64_t mi_field_bwd_partial_floats(int64_t points) { return bwd_partial_floats(points); }
+int64_t mi_field_bwd_partial_floats_kind(int kind, int64_t points) { return bad_kind(kind) ? MI_EINVAL : bwd_partial_floats_kind(kind, points); }
 
 int mi_field_eval_rays_train(int kind, const float* packed, const float* film, const float* rays, const float* z,
                              int64_t n_groups, int64_t rays_per_group, int n_samples, float* raw, float* acts,
@@ -329,13 +345,17 @@ int64_t mi_field_film_partial_floats(int64_t n_groups, int64_t points_per_group)
     return film_partial_floats(n_groups, points_per_group);
 }
 
+int64_t mi_field_film_partial_floats_kind(int kind, int64_t n_groups, int64_t points_per_group) {
+    return bad_kind(kind) ? MI_EINVAL : film_partial_floats_kind(kind, n_groups, points_per_group);
+}
+
 int mi_field_backward(int kind, const float* packed_bwd, const float* film, const float* acts, float* grads_ws,
                       const float* raw, const float* g_raw, int64_t n_groups, int64_t points_per_group,
                       float* partial_ws, float* film_partial_ws, float* const* grad_params,
                       const float* const* params, int n_params, float* grad_film, void* stream) {
     if (bad_kind(kind)) return MI_EINVAL;
     if (!packed_bwd || !acts || !grads_ws || !raw || !g_raw || !partial_ws || !grad_params ||
-        n_params != 2 * kFieldKinds[kind].n_layers) { set_error("mi_field_backward: bad arguments"); return MI_EINVAL; }
+        n_params != 2 * field_kind(kind).n_layers) { set_error("mi_field_backward: bad arguments"); return MI_EINVAL; }
     const bool film_kind = is_film(kind);
     for (int i = 0; i < n_params; ++i) {
         if (!grad_params[i]) { set_error("gradient pointer %d is null", i); return MI_EINVAL; }
@@ -406,7 +426,7 @@ int mi_adam_step(int n_fields, const int* kinds, float* const* params, const flo
     for (int f = 0; f < n_fields; ++f) {
         if (bad_kind(kinds[f])) return MI_EINVAL;
         if (!packed_fwd[f]) { set_error("mi_adam_step: field %d has no packed stream", f); return MI_EINVAL; }
-        n_params[f] = 2 * kFieldKinds[kinds[f]].n_layers;
+        n_params[f] = 2 * field_kind(kinds[f]).n_layers;
         total += n_params[f];
     }
     for (int t = 0; t < total; ++t)

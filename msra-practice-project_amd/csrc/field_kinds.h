@@ -10,7 +10,7 @@
 
 namespace mi {
 
-constexpr int kMaxLayers = 12;
+constexpr int kMaxLayers = 15;           // FilmSirenNeRF with hidden_layers = 12 has 15
 
 struct FieldKind {
     int n_layers;                  // linear layers: parameters 2i / 2i+1 are the weight / bias of layer i
@@ -62,6 +62,22 @@ struct FieldKind {
     }
 };
 
+// FilmSirenNeRF(hidden_dim = 256, hidden_layers = L, use_dir) (pi_GAN/modules.py:73-94): L + 3 linear layers
+constexpr FieldKind make_film_kind(int L, bool use_dir) {
+    FieldKind k{};
+    k.n_layers = L + 3;
+    k.dims[0][0] = 256; k.dims[0][1] = 3;
+    for (int l = 1; l < L; ++l) { k.dims[l][0] = 256; k.dims[l][1] = 256; }
+    k.dims[L][0] = 1; k.dims[L][1] = 256;
+    k.dims[L + 1][0] = 256; k.dims[L + 1][1] = use_dir ? 259 : 256;
+    k.dims[L + 2][0] = 3; k.dims[L + 2][1] = 256;
+    k.film = true; k.use_dir = use_dir;
+    k.acts = film_acts_depth(L); k.grads = film_grads_depth(L);
+    k.fwd = build_film(use_dir, L); k.bwd = build_film_bwd(use_dir, L);
+    k.trunk = L; k.sigma_head = L;
+    return k;
+}
+
 // nerf/nerf.py:59-73, 128-146; pi_GAN/modules.py:76-94; TinyNeRF is build-defined (BASELINE C1)
 inline constexpr FieldKind kFieldKinds[MI_FIELD_KINDS] = {
     // MI_FIELD_NERF
@@ -90,6 +106,30 @@ static_assert(kFieldKinds[MI_FIELD_SIREN_NERF].macs() == 559616, "SirenNeRF MACs
 static_assert(kFieldKinds[MI_FIELD_FILM_SIREN_NERF].macs() == 526848, "FilmSirenNeRF MACs per point");
 static_assert(kFieldKinds[MI_FIELD_FILM_SIREN_NERF_NODIR].macs() == 526080, "FilmSirenNeRF (no dir) MACs per point");
 static_assert(kFieldKinds[MI_FIELD_TINY_NERF].macs() == 248448, "TinyNeRF MACs per point");
+// the depth kinds are not table rows (see field_kind() below); their two ends are checked here all the same
+static_assert(region_total(film_acts_depth(8)) == region_total(film_acts()) && region_total(film_grads_depth(8)) == region_total(film_grads()) &&
+              film_grads_depth(8).n == film_grads().n, "depth 8 is the literal layout");
+static_assert(make_film_kind(8, true).macs() == 526848 && make_film_kind(8, false).macs() == 526080, "depth 8 is kinds 2 / 3");
+static_assert(make_film_kind(4, true).macs() == 264704 && make_film_kind(4, false).macs() == 263936, "FilmSirenNeRF depth 4 MACs per point");
+static_assert(make_film_kind(12, true).macs() == 788992 && make_film_kind(12, false).macs() == 788224, "FilmSirenNeRF depth 12 MACs per point");
+static_assert(make_film_kind(4, true).sigma_prefix_ok() && make_film_kind(4, false).sigma_prefix_ok() &&
+                  make_film_kind(12, true).sigma_prefix_ok() && make_film_kind(12, false).sigma_prefix_ok(),
+              "every FiLM depth's stream puts the sigma path's weights first");
+constexpr bool film_closed_forms_ok(int L, bool use_dir) {
+    const FieldKind k = make_film_kind(L, use_dir);
+    if (k.fwd.n_items != film_n_items(L, use_dir, false) || k.bwd.n_items != film_n_items(L, use_dir, true)) return false;
+    if (packed_body_floats(k.fwd) != film_body_floats(L, use_dir, false)) return false;
+    if (packed_body_floats(k.bwd) != film_body_floats(L, use_dir, true)) return false;
+    for (int i = 0; i < k.fwd.n_items; i += 7) {
+        const PickedItem p = film_item(L, use_dir, false, i);
+        if (p.off != k.fwd.dst_off[i] || p.it.param != k.fwd.item[i].param || p.it.type != k.fwd.item[i].type) return false;
+    }
+    const PickedItem q = film_item(L, use_dir, true, k.bwd.n_items - 1);
+    return q.off == k.bwd.dst_off[k.bwd.n_items - 1] && q.it.param == 2 && k.fwd.n_items <= kMaxItems;
+}
+static_assert(film_closed_forms_ok(4, true) && film_closed_forms_ok(4, false) && film_closed_forms_ok(8, true) &&
+                  film_closed_forms_ok(8, false) && film_closed_forms_ok(12, true) && film_closed_forms_ok(12, false),
+              "film_n_items / film_body_floats / film_item restate the tables build_film builds");
 static_assert(kFieldKinds[MI_FIELD_NERF].sigma_macs() == 489728, "NeRF sigma-path MACs per point");
 static_assert(kFieldKinds[MI_FIELD_SIREN_NERF].sigma_macs() == 460544, "SirenNeRF sigma-path MACs per point");
 static_assert(kFieldKinds[MI_FIELD_TINY_NERF].sigma_macs() == 212224, "TinyNeRF sigma-path MACs per point");
@@ -98,12 +138,40 @@ static_assert(kFieldKinds[MI_FIELD_NERF].sigma_prefix_ok() && kFieldKinds[MI_FIE
                   kFieldKinds[MI_FIELD_FILM_SIREN_NERF_NODIR].sigma_prefix_ok() && kFieldKinds[MI_FIELD_TINY_NERF].sigma_prefix_ok(),
               "every kind's stream puts the sigma path's weights first");
 
-constexpr bool is_film(int kind) { return kind >= 0 && kind < MI_FIELD_KINDS && kFieldKinds[kind].film; }
+// ---- MI_FIELD_FILM_DEPTH kinds -------------------------------------------------------------------------------------
+// A depth kind is no row of kFieldKinds and has no table in constant memory (adam_step.hip keeps one PackTable pair per
+// fixed kind there, about 11 KB each; eighteen more do not fit in 64 KB).  The host reads a depth kind's descriptor from
+// field_kind(); the kernels take the depth as a run-time argument and compute stream items with film_item().
+constexpr bool is_depth_id(int kind) { return kind >= 0x100 && kind < 0x200; }
+constexpr int depth_of_id(int kind) { return (kind - 0x100) >> 1; }
+constexpr bool is_depth_kind(int kind) {
+    return is_depth_id(kind) && depth_of_id(kind) >= kFilmDepthMin && depth_of_id(kind) <= kFilmDepthMax;
+}
+static_assert(kFilmDepthMin == MI_FIELD_FILM_DEPTH_MIN && kFilmDepthMax == MI_FIELD_FILM_DEPTH_MAX, "header and layout agree");
+// Depth 8 IS kinds 2 / 3: normalised wherever a kind selects a kernel or a table, so it gives their bits.
+constexpr int canon_kind(int kind) {
+    return is_depth_kind(kind) && depth_of_id(kind) == 8 ? ((kind & 1) ? MI_FIELD_FILM_SIREN_NERF : MI_FIELD_FILM_SIREN_NERF_NODIR) : kind;
+}
+constexpr bool is_fixed_kind(int kind) { return kind >= 0 && kind < MI_FIELD_KINDS; }
+constexpr bool is_film(int kind) { return is_depth_kind(kind) || (is_fixed_kind(kind) && kFieldKinds[kind].film); }
+// hidden_layers of a FiLM kind (8 for kinds 2 / 3), 0 for the others
+constexpr int film_depth(int kind) { return is_depth_kind(kind) ? depth_of_id(kind) : is_film(kind) ? 8 : 0; }
+constexpr bool film_use_dir(int kind) { return is_depth_kind(kind) ? (kind & 1) != 0 : kind == MI_FIELD_FILM_SIREN_NERF; }
+constexpr int film_layers(int kind) { return is_film(kind) ? film_depth(kind) + 1 : 0; }
+constexpr int64_t film_floats(int kind) { return (int64_t)film_layers(kind) * kFilmRow; }   // one group's rows of the FiLM table
 
 // Validates a kind from the C ABI; sets the error message if it names none.
 inline bool bad_kind(int kind) {
-    if (kind < 0 || kind >= MI_FIELD_KINDS) { set_error("unknown field kind %d", kind); return true; }
+    if (is_depth_id(kind) && !is_depth_kind(kind)) {
+        set_error("FiLM depth kind 0x%x: hidden_layers = %d is outside the supported range %d..%d", kind, depth_of_id(kind),
+                  kFilmDepthMin, kFilmDepthMax);
+        return true;
+    }
+    if (!is_fixed_kind(kind) && !is_depth_kind(kind)) { set_error("unknown field kind %d", kind); return true; }
     return false;
 }
+
+// Descriptor of a VALID kind, fixed or depth (api.hip builds the depth kinds' once, on first use).
+const FieldKind& field_kind(int kind);
 
 }  // namespace mi

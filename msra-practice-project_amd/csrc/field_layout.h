@@ -24,7 +24,8 @@ namespace mi {
 constexpr int kPiece = 256;          // floats per DMA piece
 constexpr int kMaxAuxPieces = 8;     // per-layer VEC/PLAIN pieces (LDS aux slot = 8 KiB)
 constexpr int kHidden = 256;
-constexpr int kFilmLayers = 9;
+constexpr int kFilmLayers = 9;         // FiLM rows of the reference's default depth (hidden_layers = 8); depth L has L + 1
+constexpr int kFilmDepthMin = 4, kFilmDepthMax = 12;   // hidden_layers the FiLM kernels run (MI_FIELD_FILM_DEPTH)
 constexpr int kFilmRow = 512;        // gamma[256] | beta[256]
 
 enum ItemType : int { ITEM_VEC = 0, ITEM_PLAIN = 1, ITEM_CHUNK = 2 };
@@ -42,7 +43,7 @@ struct PackItem {
                        // inverse map (parameter element -> stream position) of adam_step.hip needs no division by them
 };
 
-constexpr int kMaxItems = 112;
+constexpr int kMaxItems = 128;        // the depth-12 FiLM forward table has 121
 
 struct PackTable {
     int n_items;
@@ -66,7 +67,10 @@ __host__ __device__ inline int vec_slot(int f) {
 // ---------------------------------------------------------------------------------------
 namespace mi {
 
-struct TableBuilder {
+// Where a recipe's items go: into a whole table (TableSink), or nowhere but item number `want` (PickSink: the FiLM
+// depth kinds' pack / Adam kernels compute the one item they need from (depth, use_dir, i) instead of reading a table
+// per depth out of constant memory).
+struct TableSink {
     PackTable t{};
     int off = 0;
 
@@ -76,6 +80,21 @@ struct TableBuilder {
         t.n_items++;
         off += floats;
     }
+};
+struct PickSink {
+    int want = 0, n = 0, off = 0, it_off = 0;
+    PackItem it{};
+
+    constexpr void push(PackItem i, int floats) {
+        if (n == want) { it = i; it_off = off; }
+        ++n;
+        off += floats;
+    }
+};
+
+template <class Sink>
+struct BuilderT : Sink {
+    using Sink::push;
     // bias of layer i (n outputs)
     constexpr void bias(int layer, int n) { push({ITEM_VEC, 2 * layer + 1, 0, 0, 1, n, 0, 0, 0, 0}, kPiece); }
     // row `row` of weight of layer i as a vector over its n input features starting at col0
@@ -102,6 +121,7 @@ struct TableBuilder {
         }
     }
 };
+using TableBuilder = BuilderT<TableSink>;
 
 // NeRF (nerf/nerf.py:59-73): 0..7 layers_pos, 8,9 layers_dir, 10 output_layer_sigma, 11 output_layer_rgb
 constexpr PackTable build_nerf() {
@@ -145,18 +165,23 @@ constexpr PackTable build_siren_nerf() {
     return b.t;
 }
 
-// FilmSirenNeRF (pi_GAN/modules.py:76-94): 0 input_layer, 1..7 hidden_layers, 8 output_layer_sigma.0,
-// 9 hidden_layer_rgb ([256,259] with dir, [256,256] without), 10 output_layer_rgb.0
-constexpr PackTable build_film(bool use_dir) {
-    TableBuilder b;
+// FilmSirenNeRF (pi_GAN/modules.py:76-94) with hidden_layers = L (the reference's default: 8): 0 input_layer,
+// 1..L-1 hidden_layers, L output_layer_sigma.0, L+1 hidden_layer_rgb ([256,259] with dir, [256,256] without),
+// L+2 output_layer_rgb.0
+template <class B>
+constexpr void film_recipe(B& b, int L, bool use_dir) {
     b.bias(0, 256); b.wcol(0, 3, 0, 256); b.wcol(0, 3, 1, 256); b.wcol(0, 3, 2, 256);
-    for (int l = 1; l <= 6; ++l) { b.bias(l, 256); b.chunks(l, 256, 0, 256, 256, 8); }
-    b.bias(7, 256); b.wrow(8, 256, 0, 0, 256); b.scalars(8, 1); b.chunks(7, 256, 0, 256, 256, 8);
+    for (int l = 1; l <= L - 2; ++l) { b.bias(l, 256); b.chunks(l, 256, 0, 256, 256, 8); }
+    b.bias(L - 1, 256); b.wrow(L, 256, 0, 0, 256); b.scalars(L, 1); b.chunks(L - 1, 256, 0, 256, 256, 8);
     const int ld = use_dir ? 259 : 256;
-    b.bias(9, 256);
-    if (use_dir) { b.wcol(9, ld, 256, 256); b.wcol(9, ld, 257, 256); b.wcol(9, ld, 258, 256); }
-    b.wrow(10, 256, 0, 0, 256); b.wrow(10, 256, 1, 0, 256); b.wrow(10, 256, 2, 0, 256); b.scalars(10, 3);
-    b.chunks(9, ld, 0, 256, 256, 8);
+    b.bias(L + 1, 256);
+    if (use_dir) { b.wcol(L + 1, ld, 256, 256); b.wcol(L + 1, ld, 257, 256); b.wcol(L + 1, ld, 258, 256); }
+    b.wrow(L + 2, 256, 0, 0, 256); b.wrow(L + 2, 256, 1, 0, 256); b.wrow(L + 2, 256, 2, 0, 256); b.scalars(L + 2, 3);
+    b.chunks(L + 1, ld, 0, 256, 256, 8);
+}
+constexpr PackTable build_film(bool use_dir, int L = 8) {
+    TableBuilder b;
+    film_recipe(b, L, use_dir);
     return b.t;
 }
 
@@ -198,13 +223,34 @@ constexpr PackTable build_siren_nerf_bwd() {
     return b.t;
 }
 
-// FilmSirenNeRF: [rgb rows x3 over 256 features] | hidden_layer_rgb^T (h part) with [sigma row] | hidden 6..0 ^T
-constexpr PackTable build_film_bwd(bool use_dir) {
+// FilmSirenNeRF: [rgb rows x3 over 256 features] | hidden_layer_rgb^T (h part) with [sigma row] | hidden L-2..0 ^T
+template <class B>
+constexpr void film_bwd_recipe(B& b, int L, bool use_dir) {
+    b.wrow(L + 2, 256, 0, 0, 256); b.wrow(L + 2, 256, 1, 0, 256); b.wrow(L + 2, 256, 2, 0, 256); b.wrow(L, 256, 0, 0, 256);
+    b.chunks_t(L + 1, use_dir ? 259 : 256, 0, 256, 256, 8);
+    for (int l = L - 1; l >= 1; --l) b.chunks_t(l, 256, 0, 256, 256, 8);
+}
+constexpr PackTable build_film_bwd(bool use_dir, int L = 8) {
     TableBuilder b;
-    b.wrow(10, 256, 0, 0, 256); b.wrow(10, 256, 1, 0, 256); b.wrow(10, 256, 2, 0, 256); b.wrow(8, 256, 0, 0, 256);
-    b.chunks_t(9, use_dir ? 259 : 256, 0, 256, 256, 8);
-    for (int l = 7; l >= 1; --l) b.chunks_t(l, 256, 0, 256, 256, 8);
+    film_bwd_recipe(b, L, use_dir);
     return b.t;
+}
+
+// The FiLM tables are regular in the depth, so their sizes have closed forms and one item can be had without the table:
+// item i of the depth-L forward (transposed: bwd) stream and its float offset, by walking the recipe (at most 121 steps
+// of integer arithmetic, nothing stored).
+constexpr int film_n_items(int L, bool use_dir, bool bwd) { return bwd ? 8 * L + 4 : 9 * L + (use_dir ? 13 : 10); }
+constexpr int film_body_floats(int L, bool use_dir, bool bwd) {
+    // L MFMA layers (hidden 0..L-2, rgb hidden) of eight 32 KiB K blocks + the VEC / PLAIN pieces
+    return (bwd ? 4 : L + (use_dir ? 13 : 10)) * kPiece + L * 8 * 8192;
+}
+struct PickedItem { PackItem it; int off; };
+constexpr PickedItem film_item(int L, bool use_dir, bool bwd, int i) {
+    BuilderT<PickSink> b;
+    b.want = i;
+    if (bwd) film_bwd_recipe(b, L, use_dir);
+    else film_recipe(b, L, use_dir);
+    return {b.it, b.it_off};
 }
 
 // ---- training buffers: per-point row-major regions [points][width], region r at offset_r * points ------
@@ -248,6 +294,20 @@ constexpr RegionLayout film_acts() {
     return L;
 }
 constexpr RegionLayout film_grads() { return {10, {256, 256, 256, 256, 256, 256, 256, 256, 256, 4}}; }
+// With hidden_layers = L there are L + 1 FiLM layers (input, hidden 0..L-2, rgb hidden): acts 0 xin | 1..L+1 X_l,
+// grads 0..L dL/du_l | L+1 head pre-act grads.  The two above are L = 8.
+constexpr RegionLayout film_acts_depth(int L) {
+    RegionLayout R{L + 2, {}};
+    R.width[0] = 8;
+    for (int i = 1; i < L + 2; ++i) R.width[i] = 256;
+    return R;
+}
+constexpr RegionLayout film_grads_depth(int L) {
+    RegionLayout R{L + 2, {}};
+    for (int i = 0; i < L + 1; ++i) R.width[i] = 256;
+    R.width[L + 1] = 4;
+    return R;
+}
 
 // The stream ends with a trailer piece of hyper-parameters the kernels read as wave-uniform scalars: [0] = w_0, the sin layers'
 // frequency (FilmSiren's constructor argument, pi_GAN/modules.py:11,73; 30 for every other kind), [1] = fl(w_0^2) for the

@@ -250,14 +250,21 @@ __global__ __launch_bounds__(256, 1) void siren_fwd_kernel(MlpArgs a) {
 // FilmSirenNeRF (pi_GAN/modules.py:101-118): sin(30 * (gamma * linear + beta)), one FiLM
 // table per group (image)
 // =========================================================================================
-template <bool USE_DIR, bool SAVE>
+// RT_DEPTH: hidden_layers = L is a run-time, wave-uniform value (MlpArgs::film_depth, 4..12: the MI_FIELD_FILM_DEPTH kinds)
+// instead of the literal 8 of kinds 2 / 3, whose instances stay compile-time: one more instance per (USE_DIR, SAVE) serves
+// every depth.  The stream has L - 2 plain hidden layers in the loop, then the two that prefetch the heads' pieces; FiLM
+// layer l saves to region 1 + l; the trailer sits behind a body whose length follows L (so L cannot travel in it).
+template <bool USE_DIR, bool SAVE, bool RT_DEPTH = false>
 __global__ __launch_bounds__(256, 1) void film_fwd_kernel(MlpArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int64_t group = blockIdx.x / a.tiles_per_group;
     const int64_t tile = blockIdx.x % a.tiles_per_group;
-    Ctx c = make_ctx(smem, a, group);
+    const int L = RT_DEPTH ? __builtin_amdgcn_readfirstlane(a.film_depth) : 8;
+    Ctx c = make_ctx_raw(smem, a.packed, a.film + group * ((L + 1) * kFilmRow));
     // FilmSiren's w_0 (pi_GAN/modules.py:11,73): the first float of the stream's trailer, a uniform (scalar) load
-    constexpr int kBody = packed_body_floats(kFieldKinds[USE_DIR ? MI_FIELD_FILM_SIREN_NERF : MI_FIELD_FILM_SIREN_NERF_NODIR].fwd);
+    static_assert(film_body_floats(8, USE_DIR, false) ==
+                  packed_body_floats(kFieldKinds[USE_DIR ? MI_FIELD_FILM_SIREN_NERF : MI_FIELD_FILM_SIREN_NERF_NODIR].fwd));
+    const int kBody = film_body_floats(L, USE_DIR, false);
     c.w0 = a.packed[kBody];
     issue_first_stage<4, 0, true>(c, 0, 0, 0);   // input_layer: bias + 3 columns, FiLM row 0
 
@@ -267,7 +274,7 @@ __global__ __launch_bounds__(256, 1) void film_fwd_kernel(MlpArgs a) {
     const auto sel_x = [&](auto kb) -> const f32x16& { return X[decltype(kb)::value]; };
     const auto film_row = [&](int s) { return smem + kLdsFilm0 + s * kFilmRow; };
     const int64_t SP = a.save_points;
-    // FiLM layer l (0..8): X_l (cosine sign in the lowest bit) -> region 1+l (256 wide, after the 8-wide xin)
+    // FiLM layer l (0..L): X_l (cosine sign in the lowest bit) -> region 1+l (256 wide, after the 8-wide xin)
     const auto film_rows = [&](int l) {
         return SaveRows{SAVE ? a.save + (int64_t)(8 + 256 * l) * SP : nullptr, 256, pt.p, pt.valid};
     };
@@ -293,20 +300,20 @@ __global__ __launch_bounds__(256, 1) void film_fwd_kernel(MlpArgs a) {
     init_acc<8, true>(smem + kLdsAux0, c.h, 1, pt.px, pt.py, pt.pz, acc);
     film_act(0, 0); slot ^= 1;
 #pragma unroll 1
-    for (int l = 1; l <= 5; ++l) {                                                   // hidden_layers[0..4]
+    for (int l = 1; l <= L - 3; ++l) {                                               // hidden_layers[0..L-4]
         fwd_layer<8, 8, false, 1, 32, true, ACT_FILM, SAVE, false, 0>(c, slot, l + 1, 0, 0.f, 0.f, 0.f, sel_x, acc, X, film_row(slot), film_rows(l), none);
         slot ^= 1;
     }
-    fwd_layer<8, 8, false, 3, 32, true, ACT_FILM, SAVE, false, 0>(c, slot, 7, 0, 0.f, 0.f, 0.f, sel_x, acc, X, film_row(slot), film_rows(6), none);  // hidden_layers[5]
+    fwd_layer<8, 8, false, 3, 32, true, ACT_FILM, SAVE, false, 0>(c, slot, L - 1, 0, 0.f, 0.f, 0.f, sel_x, acc, X, film_row(slot), film_rows(L - 2), none);  // hidden_layers[L-3]
     slot ^= 1;
-    fwd_layer<8, 8, false, USE_DIR ? 8 : 5, 32, true, ACT_FILM, SAVE, false, 0>(c, slot, 8, 0, 0.f, 0.f, 0.f, sel_x, acc, X, film_row(slot), film_rows(7), none);  // hidden_layers[6]
+    fwd_layer<8, 8, false, USE_DIR ? 8 : 5, 32, true, ACT_FILM, SAVE, false, 0>(c, slot, L, 0, 0.f, 0.f, 0.f, sel_x, acc, X, film_row(slot), film_rows(L - 1), none);  // hidden_layers[L-2]
     float sigma;
     {
         const float* aux = smem + kLdsAux0 + slot * kLdsAux;
         sigma = fmaxf(head_dot<8>(X, aux, 1, c.h) + aux[2 * kPiece], 0.f);
     }
     slot ^= 1;
-    fwd_layer<8, 8, USE_DIR, 0, 0, false, ACT_FILM, SAVE, false, 0>(c, slot, 0, 1, pt.dx, pt.dy, pt.dz, sel_x, acc, X, film_row(slot), film_rows(8), none);   // hidden_layer_rgb
+    fwd_layer<8, 8, USE_DIR, 0, 0, false, ACT_FILM, SAVE, false, 0>(c, slot, 0, 1, pt.dx, pt.dy, pt.dz, sel_x, acc, X, film_row(slot), film_rows(L), none);   // hidden_layer_rgb
     const float* aux = smem + kLdsAux0 + slot * kLdsAux;
     constexpr int hp = USE_DIR ? 4 : 1;
     const float r = sigmoidf(head_dot<8>(X, aux, hp + 0, c.h) + aux[(hp + 3) * kPiece + 0]);
@@ -330,9 +337,15 @@ static const void* const kFwdKernels[MI_FIELD_KINDS][3] = {
     {(const void*)nerf_fwd_kernel<true, false, false>, (const void*)nerf_fwd_kernel<true, true, false>,
      (const void*)nerf_fwd_kernel<true, false, true>}};                                                     // MI_FIELD_TINY_NERF
 
+// [use_dir][variant]: the run-time-depth FiLM instances (MI_FIELD_FILM_DEPTH kinds other than depth 8, which IS kinds 2 / 3)
+static const void* const kFilmDepthFwdKernels[2][2] = {
+    {(const void*)film_fwd_kernel<false, false, true>, (const void*)film_fwd_kernel<false, true, true>},
+    {(const void*)film_fwd_kernel<true, false, true>, (const void*)film_fwd_kernel<true, true, true>}};
+
 bool has_sigma_only_kernel(int kind) { return kind >= 0 && kind < MI_FIELD_KINDS && kFwdKernels[kind][FWD_SIGMA]; }
 
-int launch_mlp(int kind, const MlpArgs& a, int64_t n_groups, hipStream_t stream, bool sigma_only) {
+int launch_mlp(int kind_in, const MlpArgs& a, int64_t n_groups, hipStream_t stream, bool sigma_only) {
+    const int kind = canon_kind(kind_in);
     const int64_t blocks = n_groups * a.tiles_per_group;
     if (blocks <= 0) return 0;
     if (blocks > 0x7fffffffLL) { set_error("too many point tiles (%lld)", (long long)blocks); return -1; }
@@ -351,12 +364,24 @@ int launch_mlp(int kind, const MlpArgs& a, int64_t n_groups, hipStream_t stream,
                 const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
                 if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return -2; }
             }
+        for (const auto& k : kFilmDepthFwdKernels)
+            for (const void* f : k) {
+                const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return -2; }
+            }
         return 0;
     });
     if (arc) return arc;
     void* args[] = {const_cast<MlpArgs*>(&a)};
     const int variant = sigma_only ? FWD_SIGMA : a.save ? FWD_SAVE : FWD_INFER;
-    (void)hipLaunchKernel(kFwdKernels[kind][variant], dim3((unsigned)blocks), dim3(256), args, lds, stream);
+    const void* fn;
+    if (is_depth_kind(kind)) {
+        if (a.film_depth != film_depth(kind) || !a.film) { set_error("FiLM depth kind 0x%x launched without its depth or table", kind); return -1; }
+        fn = kFilmDepthFwdKernels[film_use_dir(kind)][variant];
+    } else {
+        fn = kFwdKernels[kind][variant];
+    }
+    (void)hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(256), args, lds, stream);
     return check_launch("field_mlp_fwd");
 }
 

@@ -31,11 +31,12 @@ struct BwdArgs {
     const float* raw;        // [P,4] forward outputs (rgb post-sigmoid, sigma post-ReLU)
     const float* g_raw;      // [P,4] dL/d(raw)
     int64_t points;
-    // FiLM kinds: one table [9][512] per group of points_per_group consecutive points
+    // FiLM kinds: one table [film_depth + 1][512] per group of points_per_group consecutive points
     const float* film;
     float* film_partial;     // unused by the chain (kept so the argument block stays stable)
     int64_t points_per_group, tiles_per_group, n_tiles;
     unsigned long long* stamps;   // diagnostic build (-DMI_PROFILE_STAMPS) only: [block][128] s_memtime values (MI_STAMP)
+    int film_depth;          // FiLM kinds: hidden_layers (the run-time-depth chain reads it), else 0
 };
 
 #ifdef MI_PROFILE_STAMPS
@@ -515,19 +516,24 @@ __device__ __forceinline__ void film_chain_layer(Ctx& c, int piece, float s, f32
     mma_layer_fn<8, 8, 0, 0, NEXT_BLOCK, FILM_NEXT, true, !SCALED, LAST>(c, issue_slot, next_film_layer, NoHook{}, sel_x, acc, pre, post, mid);
 }
 
-template <bool USE_DIR>
+// RT_DEPTH: hidden_layers = L at run time (BwdArgs::film_depth, wave-uniform) for the MI_FIELD_FILM_DEPTH kinds; kinds 2 / 3
+// keep the literal 8.  FiLM layers 0..L: the chain runs rgb hidden (L), hidden L-2..0 (L-1..1), input_layer (0).
+template <bool USE_DIR, bool RT_DEPTH = false>
 __global__ __launch_bounds__(256, 1) void film_bwd_kernel(BwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int64_t group = blockIdx.x / a.tiles_per_group;
     const int64_t tile = blockIdx.x % a.tiles_per_group;
-    Ctx c = make_ctx_raw(smem, a.packed, a.film + group * (kFilmLayers * kFilmRow));
+    const int L = RT_DEPTH ? __builtin_amdgcn_readfirstlane(a.film_depth) : 8;
+    Ctx c = make_ctx_raw(smem, a.packed, a.film + group * ((L + 1) * kFilmRow));
     // fl(w_0^2) of the module's w_0 (pi_GAN/modules.py:11,73) from the backward stream's trailer: the rebuilt derivative
     // factor is +-sqrt(w_0^2 (1 - X^2)); a uniform (scalar) load
-    constexpr int kBody = packed_body_floats(kFieldKinds[USE_DIR ? MI_FIELD_FILM_SIREN_NERF : MI_FIELD_FILM_SIREN_NERF_NODIR].bwd);
+    static_assert(film_body_floats(8, USE_DIR, true) ==
+                  packed_body_floats(kFieldKinds[USE_DIR ? MI_FIELD_FILM_SIREN_NERF : MI_FIELD_FILM_SIREN_NERF_NODIR].bwd));
+    const int kBody = film_body_floats(L, USE_DIR, true);
     c.w0sq = a.packed[kBody + 1];
     const int64_t P = a.points;
-    // rgb head rows x3, sigma row; K blocks 0-1 of hidden_layer_rgb^T; FiLM row 8 -> film slot 0 (row r lives in slot (8 - r) & 1)
-    issue_first_stage<4, 32, true>(c, 0, 0, 8);
+    // rgb head rows x3, sigma row; K blocks 0-1 of hidden_layer_rgb^T; FiLM row L -> film slot 0 (row r lives in slot (L - r) & 1)
+    issue_first_stage<4, 32, true>(c, 0, 0, L);
 
     const int64_t local = tile * 128 + c.wave * 32 + (c.lane & 31);
     const bool valid = local < a.points_per_group;
@@ -536,15 +542,15 @@ __global__ __launch_bounds__(256, 1) void film_bwd_kernel(BwdArgs a) {
     const f32x4 o = reinterpret_cast<const f32x4*>(a.raw)[p];
     const float d0 = g.x * o.x * (1.f - o.x), d1 = g.y * o.y * (1.f - o.y), d2 = g.z * o.z * (1.f - o.z);
     const float ds = o.w > 0.f ? g.w : 0.f;
-    if (valid && c.h == 0) reinterpret_cast<f32x4*>(a.grads + (int64_t)(9 * 256) * P)[p] = f32x4{d0, d1, d2, ds};
+    if (valid && c.h == 0) reinterpret_cast<f32x4*>(a.grads + (int64_t)((L + 1) * 256) * P)[p] = f32x4{d0, d1, d2, ds};
 
     f32x16 X[8], acc[8];
-    const auto film_row = [&](int r) { return smem + kLdsFilm0 + ((8 - r) & 1) * kFilmRow; };       // FiLM row r's LDS slot
+    const auto film_row = [&](int r) { return smem + kLdsFilm0 + ((L - r) & 1) * kFilmRow; };       // FiLM row r's LDS slot
     const auto C = [&](int l) { return a.acts + (int64_t)(8 + 256 * l) * P; };    // saved X_l rows: C_l is rebuilt from them
     const auto dU = [&](int l) { return a.grads + (int64_t)(256 * l) * P; };
     f32x4 ring[32];                                            // a layer's C quarters, loaded a K block or more ahead
-    {   // the first epilogue's rows (X_8) now, while the first weight stage is still on its way
-        const f32x4* crow = reinterpret_cast<const f32x4*>(C(8) + p * 256 + 4 * c.h);
+    {   // the first epilogue's rows (X_L) now, while the first weight stage is still on its way
+        const f32x4* crow = reinterpret_cast<const f32x4*>(C(L) + p * 256 + 4 * c.h);
 #pragma unroll
         for (int j = 0; j < 32; ++j) ring[j] = crow[(j / 4) * 8 + (j % 4) * 2];
     }
@@ -566,32 +572,32 @@ __global__ __launch_bounds__(256, 1) void film_bwd_kernel(BwdArgs a) {
     MI_STAMP(a, 0);
     film_bwd_first<8>(acc, X, ring, c.w0sq);                                                             // hidden_layer_rgb: X = dU_8
     MI_STAMP(a, 1);
-    // Chain layer j multiplies by FiLM row j + 1 (slot (7 - j) & 1) and DMAs row j - what layer j - 1 multiplies by -
-    // into the other slot.  j = 7 starts from the sigma head's row (aux slot 0, piece 3).
+    // Chain layer j multiplies by FiLM row j + 1 (slot (L - 1 - j) & 1) and DMAs row j - what layer j - 1 multiplies by -
+    // into the other slot.  j = L - 1 starts from the sigma head's row (aux slot 0, piece 3).
 #if defined(MI_PROFILE_STAMPS) && defined(MI_STAMP_LAYER) && MI_STAMP_LAYER == 7
     if (a.stamps) c.rowst = a.stamps + (int64_t)blockIdx.x * 128 + 32;                          // rows of layer 7: 32..64
 #endif
-    film_chain_layer<32, true, true, false>(c, 3, ds, acc, X, ring, C(7), dU(7), dU(8), p, 0, 7, film_row(8));
+    film_chain_layer<32, true, true, false>(c, 3, ds, acc, X, ring, C(L - 1), dU(L - 1), dU(L), p, 0, L - 1, film_row(L));
 #if defined(MI_PROFILE_STAMPS) && defined(MI_STAMP_LAYER) && MI_STAMP_LAYER == 7
     if (c.rowst) { MI_ROW_STAMP(c); }
     c.rowst = nullptr;
 #endif
     MI_STAMP(a, 2);
 #pragma unroll 1
-    for (int j = 6; j >= 1; --j) {                                                               // hidden_layers[5..0]
+    for (int j = L - 2; j >= 1; --j) {                                                           // hidden_layers[L-3..0]
 #ifdef MI_PROFILE_STAMPS
 #if !defined(MI_STAMP_LAYER) || MI_STAMP_LAYER != 7
         if (j == 4 && a.stamps) c.rowst = a.stamps + (int64_t)blockIdx.x * 128 + 32;            // rows of layer j = 4: 32..64
 #endif
 #endif
-        film_chain_layer<32, false, true, false>(c, 0, 0.f, acc, X, ring, C(j), dU(j), dU(j + 1), p, (7 - j) & 1, j, film_row(j + 1));
+        film_chain_layer<32, false, true, false>(c, 0, 0.f, acc, X, ring, C(j), dU(j), dU(j + 1), p, (L - 1 - j) & 1, j, film_row(j + 1));
 #ifdef MI_PROFILE_STAMPS
         if (c.rowst) { MI_ROW_STAMP(c); }
         c.rowst = nullptr;
-        if (threadIdx.x == 0 && a.stamps) a.stamps[(int64_t)blockIdx.x * 128 + 3 + (6 - j)] = __builtin_amdgcn_s_memtime();   // 3..8
+        if (threadIdx.x == 0 && a.stamps) a.stamps[(int64_t)blockIdx.x * 128 + 3 + (L - 2 - j)] = __builtin_amdgcn_s_memtime();   // 3..L
 #endif
     }
-    film_chain_layer<0, false, false, true>(c, 0, 0.f, acc, X, ring, C(0), dU(0), dU(1), p, 1, 0, film_row(1));   // input_layer
+    film_chain_layer<0, false, false, true>(c, 0, 0.f, acc, X, ring, C(0), dU(0), dU(1), p, (L - 1) & 1, 0, film_row(1));   // input_layer
     MI_STAMP(a, 9);
 }
 
@@ -600,7 +606,7 @@ __global__ __launch_bounds__(256, 1) void film_bwd_kernel(BwdArgs a) {
 //   dW[f][col0+k]  (+)= gamma[f] T[f][k]                       (+= for g > 0: images are summed in order)
 //   d gamma_g[f]   (+)= sum_k W[f][col0+k] T[f][k]  (+ b[f] s[f] with the bias part: A = W x + b)
 //   d beta_g[f]      = s[f];   db[f] (+)= gamma[f] s[f]        (bias part only)
-constexpr int kMaxFinishJobs = 10;          // an image's nine FiLM layers + the dir columns of hidden_layer_rgb
+constexpr int kMaxFinishJobs = kFilmDepthMax + 2;   // an image's FiLM layers (at most 13) + the dir columns of hidden_layer_rgb
 struct FinishJob {
     const float* T; const float* s; const float* W; const float* b; const float* film_row;
     float* dW; float* db; float* dfilm_row;
@@ -970,8 +976,11 @@ __global__ __launch_bounds__(256) void reduce_jobs_kernel(ReduceBatch rb) {
 // ---- host orchestration ---------------------------------------------------------------------
 // FiLM scratch: one image's T_l (256x256) and column sums s_l (256) per 256-wide layer, its raw-input columns (256x3, padded)
 constexpr int64_t kFilmLayerScratch = 256 * 256 + 256;       // T_l and s_l of one 256-wide FiLM layer
-int64_t film_partial_floats(int64_t /*n_groups*/, int64_t /*points_per_group*/) {
-    return 8 * kFilmLayerScratch + 2 * 256 * 4 + 256;        // eight layers, two K = 3 blocks, s_0 (launch_field_backward)
+// the L 256-wide FiLM layers of depth L, two K = 3 blocks, s_0 (launch_field_backward)
+static int64_t film_partial_floats_depth(int L) { return L * kFilmLayerScratch + 2 * 256 * 4 + 256; }
+int64_t film_partial_floats(int64_t /*n_groups*/, int64_t /*points_per_group*/) { return film_partial_floats_depth(8); }
+int64_t film_partial_floats_kind(int kind, int64_t /*n_groups*/, int64_t /*points_per_group*/) {
+    return is_film(kind) ? film_partial_floats_depth(film_depth(kind)) : 0;
 }
 
 static int64_t batched_partial_floats(int kind, int64_t P);
@@ -986,6 +995,14 @@ int64_t bwd_partial_floats(int64_t P) {
         if (n > most) most = n;
     }
     return most;
+}
+// ... of any kind: a FiLM image of depth L runs L GEMM jobs, so the depths above 8 can need more than the figure above
+int64_t bwd_partial_floats_kind(int kind, int64_t P) {
+    const int64_t base = bwd_partial_floats(P);
+    if (film_depth(kind) <= 8) return base;
+    const int64_t slabs256 = (P + 255) / 256 > 0 ? (P + 255) / 256 : 1;
+    const int64_t film = film_depth(kind) * (slabs256 < 32 ? slabs256 : 32) * kFilmLayerScratch + 2 * (slabs256 < 512 ? slabs256 : 512) * 1280 + 4096;
+    return film > base ? film : base;
 }
 
 
@@ -1151,11 +1168,11 @@ static int batched_backward(int kind, BwdBatcher& b, const float* acts, float* g
 // out-of-bounds write by the GEMMs - then for real over `pts` points.  check = false skips the plan (a pass already
 // checked for the same shape).
 template <class Jobs>
-static int plan_then_run(int64_t pts, int64_t P, float* partial, hipStream_t stream, const Jobs& jobs, bool check = true) {
+static int plan_then_run(int kind, int64_t pts, int64_t P, float* partial, hipStream_t stream, const Jobs& jobs, bool check = true) {
     if (check) {
         BwdBatcher plan{pts, nullptr, 0, stream};
         (void)jobs(plan);
-        const int64_t limit = bwd_partial_floats(P);
+        const int64_t limit = bwd_partial_floats_kind(kind, P);
         if (plan.used > limit) {
             set_error("backward scratch plan (%lld floats) exceeds mi_field_bwd_partial_floats (%lld)", (long long)plan.used,
                       (long long)limit);
@@ -1173,20 +1190,29 @@ static const void* const kBwdKernels[MI_FIELD_KINDS] = {
     (const void*)film_bwd_kernel<true>,       // MI_FIELD_FILM_SIREN_NERF
     (const void*)film_bwd_kernel<false>,      // MI_FIELD_FILM_SIREN_NERF_NODIR
     (const void*)nerf_bwd_kernel<true>};      // MI_FIELD_TINY_NERF
+static_assert(kFilmDepthMax <= kMaxGemmJobs && kFilmDepthMax + 6 <= kMaxReduceJobs,
+              "an image's FiLM layers are one GEMM batch and, with the thin jobs, one reduction batch");
+// [use_dir]: the run-time-depth FiLM chain (MI_FIELD_FILM_DEPTH kinds other than depth 8)
+static const void* const kFilmDepthBwdKernels[2] = {(const void*)film_bwd_kernel<false, true>, (const void*)film_bwd_kernel<true, true>};
 
 // Backward of a field over P points.  grad_params[2i], [2i+1]: device pointers to the weight /
 // bias gradient tensors (torch layout), overwritten.
-int launch_field_backward(int kind, const float* packed_bwd, const float* acts, float* grads, const float* raw,
+int launch_field_backward(int kind_in, const float* packed_bwd, const float* acts, float* grads, const float* raw,
                           const float* g_raw, int64_t n_groups, int64_t points_per_group, const float* film,
                           float* film_partial, float* grad_film, float* partial, float* const* gp,
                           const float* const* params, hipStream_t stream) {
     const int64_t P = n_groups * points_per_group;
     if (P <= 0) return 0;
-    if (bad_kind(kind)) return -1;
+    if (bad_kind(kind_in)) return -1;
+    const int kind = canon_kind(kind_in);
     const size_t lds = kLdsFloats * sizeof(float);
     static PerDeviceOnce attr_once;
     const int arc = attr_once.run([&]() {
         for (const void* f : kBwdKernels)
+            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+                set_error("hipFuncSetAttribute failed"); return -2;
+            }
+        for (const void* f : kFilmDepthBwdKernels)
             if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
                 set_error("hipFuncSetAttribute failed"); return -2;
             }
@@ -1204,26 +1230,30 @@ int launch_field_backward(int kind, const float* packed_bwd, const float* acts, 
 #else
     unsigned long long* stamps = nullptr;
 #endif
-    BwdArgs a{packed_bwd, acts, grads, raw, g_raw, P, film, film_partial, points_per_group, tpg, n_groups * tpg, stamps};
+    const int L = film_depth(kind);                      // hidden_layers of a FiLM kind: FiLM layers 0..L
+    BwdArgs a{packed_bwd, acts, grads, raw, g_raw, P, film, film_partial, points_per_group, tpg, n_groups * tpg, stamps, L};
     const unsigned blocks = (unsigned)(film_kind ? n_groups * tpg : (P + 127) / 128);
     void* args[] = {&a};
-    (void)hipLaunchKernel(kBwdKernels[kind], dim3(blocks), dim3(256), args, lds, stream);
+    (void)hipLaunchKernel(is_depth_kind(kind) ? kFilmDepthBwdKernels[film_use_dir(kind)] : kBwdKernels[kind], dim3(blocks),
+                          dim3(256), args, lds, stream);
     int rc;
     if ((rc = check_launch("backward chain"))) return rc;
     if (!film_kind)
-        return plan_then_run(P, P, partial, stream, [&](BwdBatcher& bb) { return batched_backward(kind, bb, acts, grads, gp); });
+        return plan_then_run(kind, P, P, partial, stream, [&](BwdBatcher& bb) { return batched_backward(kind, bb, acts, grads, gp); });
 
-    const bool use_dir = kFieldKinds[kind].use_dir;
-    constexpr RegionLayout AL = film_acts();
+    const bool use_dir = film_use_dir(kind);
+    const RegionLayout AL = film_acts_depth(L);
     const int64_t ppg = points_per_group;
-    // FiLM scratch of the current image: T_l [256][256] + s_l [256] for the eight 256-wide FiLM layers, the K = 3
-    // blocks of layer 0 (xyz) and of layer 8 (dir) as [256][3] (padded to 4), s_0 [256]
+    // FiLM scratch of the current image: T_l [256][256] + s_l [256] for the L 256-wide FiLM layers (eight at the reference's
+    // depth), the K = 3 blocks of layer 0 (xyz) and of layer L (dir) as [256][3] (padded to 4), s_0 [256]
     const auto Tl = [&](int l) { return film_partial + (int64_t)(l - 1) * kFilmLayerScratch; };
     const auto sl = [&](int l) { return Tl(l) + 256 * 256; };
-    float* T3_0 = film_partial + 8 * kFilmLayerScratch;
+    float* T3_0 = film_partial + (int64_t)L * kFilmLayerScratch;
     float* T3_8 = T3_0 + 256 * 4;
     float* s0 = T3_8 + 256 * 4;
     const int ld9 = use_dir ? 259 : 256;
+    const int n_film = L + 1;                            // rows of the FiLM table; parameter pairs: hidden l = pair l,
+    const int p_sigma = L, p_rgbh = L + 1, p_rgb = L + 2;   // then the sigma head, hidden_layer_rgb, the rgb head
     // Per image g (fixed order, so the sums over images are deterministic): T_g, s_g of every FiLM layer - the eight
     // 256 x 256 GEMMs of an image are ONE launch (grid.y = layer, a job needs only 32 slabs to give every CU a
     // workgroup, so 8x fewer partial tiles are written and re-read than with a launch per layer), the K = 3 blocks
@@ -1232,19 +1262,19 @@ int launch_field_backward(int kind, const float* packed_bwd, const float* acts, 
     for (int64_t g = 0; g < n_groups; ++g) {
         const auto A = [&](int r) { return acts + (int64_t)region_offset(AL, r) * P + g * ppg * AL.width[r]; };
         const auto G = [&](int l) { return grads + (int64_t)(256 * l) * P + g * ppg * 256; };
-        const float* frow = film + (g * kFilmLayers) * kFilmRow;
-        float* dfrow = grad_film + (g * kFilmLayers) * kFilmRow;
+        const float* frow = film + (g * n_film) * kFilmRow;
+        float* dfrow = grad_film + (g * n_film) * kFilmRow;
         const auto jobs = [&](BwdBatcher& bb) -> int {
-            for (int l = 1; l <= 8; ++l)                                  // FiLM layer l: input X_{l-1} = acts region l
+            for (int l = 1; l <= L; ++l)                                  // FiLM layer l: input X_{l-1} = acts region l
                 bb.gemm<4, 2, 2>(bb.g422, G(l), A(l), Tl(l), 256, 0, 256, 256, sl(l));
             bb.thin_job(A(0), 8, 0, 3, G(0), 256, 256, T3_0, 3, 0, true, nullptr, s0);          // input_layer (K = 3: xyz) + s_0
-            if (use_dir) bb.thin_job(A(0), 8, 3, 3, G(8), 256, 256, T3_8, 3, 0, true, nullptr); // hidden_layer_rgb's dir columns
+            if (use_dir) bb.thin_job(A(0), 8, 3, 3, G(L), 256, 256, T3_8, 3, 0, true, nullptr); // hidden_layer_rgb's dir columns
             int r;
             if ((r = bb.flush<4, 2, 2>(bb.g422))) return r;
             if ((r = bb.flush_thin())) return r;
             return bb.reduce_all();
         };
-        if ((rc = plan_then_run(ppg, P, partial, stream, jobs, g == 0))) return rc;   // the plan: first image only
+        if ((rc = plan_then_run(kind, ppg, P, partial, stream, jobs, g == 0))) return rc;   // the plan: first image only
         FinishBatch fb{};
         int n_fin = 0, n_heads = 0;
         fb.first_group = g == 0;
@@ -1254,18 +1284,18 @@ int launch_field_backward(int kind, const float* packed_bwd, const float* acts, 
             n_heads += bias_part;
         };
         finish(T3_0, 3, s0, 0, 0, 3, 0, 1);                               // input_layer: FiLM layer 0, parameter pair 0
-        for (int l = 1; l <= 7; ++l) finish(Tl(l), 256, sl(l), l, l, 256, 0, 1);      // hidden_layers[l-1]: pair l
-        finish(Tl(8), 256, sl(8), 8, 9, ld9, 0, 1);                       // hidden_layer_rgb: FiLM layer 8, pair 9: [X_7 | dir]
-        if (use_dir) finish(T3_8, 3, sl(8), 8, 9, 259, 256, 0);           // ... its dir columns: chained behind the job above
+        for (int l = 1; l <= L - 1; ++l) finish(Tl(l), 256, sl(l), l, l, 256, 0, 1);  // hidden_layers[l-1]: pair l
+        finish(Tl(L), 256, sl(L), L, p_rgbh, ld9, 0, 1);                  // hidden_layer_rgb: FiLM layer L, pair L+1: [X_{L-1} | dir]
+        if (use_dir) finish(T3_8, 3, sl(L), L, p_rgbh, 259, 256, 0);      // ... its dir columns: chained behind the job above
         hipLaunchKernelGGL(film_finish_kernel, dim3(256, n_heads), dim3(256), 0, stream, fb);
     }
     if ((rc = check_launch("film_finish_kernel"))) return rc;
-    // heads: sigma (param pair 8) on X_7, rgb (pair 10) on X_8 - no FiLM in between, all images at once
+    // heads: sigma (param pair L) on X_{L-1}, rgb (pair L+2) on X_L - no FiLM in between, all images at once
     const auto A = [&](int r) { return acts + (int64_t)region_offset(AL, r) * P; };
-    const float* dpre = grads + (int64_t)(9 * 256) * P;
-    return plan_then_run(P, P, partial, stream, [&](BwdBatcher& hb) {
-        hb.thin_job(dpre, 4, 3, 1, A(8), 256, 256, gp[16], 256, 0, false, gp[17]);                        // sigma x X_7
-        hb.thin_job(dpre, 4, 0, 3, A(9), 256, 256, gp[20], 256, 0, false, gp[21]);                        // rgb x X_8
+    const float* dpre = grads + (int64_t)(n_film * 256) * P;
+    return plan_then_run(kind, P, P, partial, stream, [&](BwdBatcher& hb) {
+        hb.thin_job(dpre, 4, 3, 1, A(L), 256, 256, gp[2 * p_sigma], 256, 0, false, gp[2 * p_sigma + 1]);   // sigma x X_{L-1}
+        hb.thin_job(dpre, 4, 0, 3, A(L + 1), 256, 256, gp[2 * p_rgb], 256, 0, false, gp[2 * p_rgb + 1]);   // rgb x X_L
         const int r = hb.flush_thin();
         return r ? r : hb.reduce_all();
     });

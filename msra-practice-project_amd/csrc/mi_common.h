@@ -48,7 +48,7 @@ public:
 // arguments of the fused field-MLP kernels (field_mlp.hip)
 struct MlpArgs {
     const float* packed;    // packed weight stream (field_layout.h)
-    const float* film;      // [groups][9][512] or null
+    const float* film;      // [groups][film_depth + 1][512] or null
     const float* a;         // points x[M,6] (mode 0) or rays [N,2,3] (mode 1)
     const float* z;         // [N,S] (mode 1)
     float* out;             // [M,4]; the sigma-only forward: [M] (sigma alone)
@@ -60,6 +60,7 @@ struct MlpArgs {
     float* save;            // training: saved layer inputs, region r = save + act_offset(r) * save_points
     int64_t save_points;    // points in this launch (row count of every saved region)
     unsigned long long* stamps;   // diagnostic build (-DMI_PROFILE_STAMPS) only: [block][128] s_memtime values
+    int film_depth;         // FiLM kinds: hidden_layers (wave-uniform; the run-time-depth instances read it), else 0
 };
 
 // In-kernel cycle stamps for the diagnostic build (csrc/build.py --profile -> gpurun_tools/libmirender_prof.so);
@@ -79,6 +80,8 @@ int launch_mlp(int kind, const MlpArgs& a, int64_t n_groups, hipStream_t stream,
 bool has_sigma_only_kernel(int kind);
 int64_t bwd_partial_floats(int64_t P);
 int64_t film_partial_floats(int64_t n_groups, int64_t points_per_group);
+int64_t bwd_partial_floats_kind(int kind, int64_t P);                      // ... of any kind (deeper FiLM kinds need more)
+int64_t film_partial_floats_kind(int kind, int64_t n_groups, int64_t points_per_group);
 int launch_field_backward(int kind, const float* packed_bwd, const float* acts, float* grads, const float* raw,
                           const float* g_raw, int64_t n_groups, int64_t points_per_group, const float* film,
                           float* film_partial, float* grad_film, float* partial, float* const* gp,

@@ -86,8 +86,6 @@ struct Accumulator {
 };
 
 // ---- ray ranges (autograd._chunk_ranges) --------------------------------------------------------------------------
-constexpr int64_t kFilmFloats = (int64_t)kFilmLayers * kFilmRow;   // one group's row of the FiLM table
-
 struct Ranges {
     bool film = false, parts = false;
     int64_t n = 0, groups = 1, rpg = 0, step = 1, per_group = 1;
@@ -157,7 +155,7 @@ static void plan_kept(const PassSpec P[2], const Geometry& G, int64_t saved_byte
         kept[p] = 0;
         if (!P[p].exists) continue;
         const Ranges R = make_ranges(P[p].kind, G.n_groups, G.rpg, P[p].S, P[p].range_points);
-        const int64_t per_ray = 4 * region_total(kFieldKinds[P[p].kind].acts) * (int64_t)P[p].S;
+        const int64_t per_ray = 4 * region_total(field_kind(P[p].kind).acts) * (int64_t)P[p].S;
         for (int64_t k = 0, c = R.count(); k < c; ++k) {
             int64_t r0, r1;
             R.get(k, r0, r1);
@@ -171,7 +169,7 @@ static void plan_kept(const PassSpec P[2], const Geometry& G, int64_t saved_byte
 
 static int64_t param_floats(int kind) {
     int64_t f = 0;
-    const FieldKind& k = kFieldKinds[kind];
+    const FieldKind& k = field_kind(kind);
     for (int l = 0; l < k.n_layers; ++l) f += ((int64_t)k.dims[l][0] * k.dims[l][1] + 63) / 64 * 64 + ((int64_t)k.dims[l][0] + 63) / 64 * 64;
     return f;
 }
@@ -188,9 +186,11 @@ struct BwdLayout {
 static BwdLayout bwd_layout(const PassSpec P[2], const Geometry& G) {
     int64_t sz_acts = 0, sz_raw = 0, sz_grads = 0, sz_part = 0, sz_fpart = 0, sz_params = 0;
     bool any_film = false;
+    int64_t film_fl = 0;                           // one group's rows of the FiLM table (two FiLM fields: the same depth)
     for (int p = 0; p < 2; ++p) {
         if (!P[p].exists) continue;
-        const FieldKind& K = kFieldKinds[P[p].kind];
+        if (film_floats(P[p].kind) > film_fl) film_fl = film_floats(P[p].kind);
+        const FieldKind& K = field_kind(P[p].kind);
         const Ranges R = make_ranges(P[p].kind, G.n_groups, G.rpg, P[p].S, P[p].range_points);
         // every range has the shape of the first, the last, or (parts of images) the last part of an image
         const int64_t probes[3] = {0, R.count() - 1, R.parts ? R.per_group - 1 : 0};
@@ -202,10 +202,10 @@ static BwdLayout bwd_layout(const PassSpec P[2], const Geometry& G) {
             sz_acts = pts * region_total(K.acts) > sz_acts ? pts * region_total(K.acts) : sz_acts;
             sz_raw = pts * 4 > sz_raw ? pts * 4 : sz_raw;
             sz_grads = pts * region_total(K.grads) > sz_grads ? pts * region_total(K.grads) : sz_grads;
-            const int64_t bp = bwd_partial_floats(pts);
+            const int64_t bp = bwd_partial_floats_kind(P[p].kind, pts);
             sz_part = bp > sz_part ? bp : sz_part;
             if (R.film) {
-                const int64_t fp = film_partial_floats(ng, pts / ng);
+                const int64_t fp = film_partial_floats_kind(P[p].kind, ng, pts / ng);
                 sz_fpart = fp > sz_fpart ? fp : sz_fpart;
             }
         }
@@ -221,8 +221,8 @@ static BwdLayout bwd_layout(const PassSpec P[2], const Geometry& G) {
     L.g_raw_s = take(G.shared ? n * G.nf * 4 : 0);
     L.range_params = take(sz_params);
     L.fine_total = take(G.shared && G.nf > 0 ? param_floats(P[0].kind) : 0);
-    L.film_pass = take(any_film ? G.n_groups * kFilmFloats : 0);
-    L.film_row = take(any_film ? kFilmFloats : 0);
+    L.film_pass = take(any_film ? G.n_groups * film_fl : 0);
+    L.film_row = take(any_film ? film_fl : 0);
     L.acts = take(sz_acts);
     L.raw = take(sz_raw);
     L.grads = take(sz_grads);
@@ -258,6 +258,11 @@ static State carve_state(void* workspace, const Geometry& G) {
 static int check_common(const char* fn, int kind_c, int kind_f, int64_t n_groups, int64_t rpg, int nc, int nf,
                         int64_t rp_c, int64_t rp_f) {
     if (bad_kind(kind_c) || bad_kind(kind_f)) return MI_EINVAL;
+    if (is_film(kind_c) && is_film(kind_f) && film_layers(kind_c) != film_layers(kind_f)) {
+        set_error("%s: the two FiLM fields of one call share the FiLM table, so they need the same depth (%d and %d rows)", fn,
+                  film_layers(kind_c), film_layers(kind_f));
+        return MI_EINVAL;
+    }
     if (n_groups < 0 || rpg < 0 || nc < 3 || nf < 0) {
         set_error("%s: bad sizes (need n_groups, rays_per_group >= 0, Nc >= 3, Nf >= 0)", fn);
         return MI_EINVAL;
@@ -289,7 +294,8 @@ static int check_state(const char* fn, const Geometry& G, int64_t workspace_byte
 static int forward_pass(const PassSpec& P, const Geometry& G, const float* packed, const float* film, const float* rays,
                         const float* z, float* raw, int64_t kept, float*& saved, void* stream) {
     const Ranges R = make_ranges(P.kind, G.n_groups, G.rpg, P.S, P.range_points);
-    const int64_t acts = region_total(kFieldKinds[P.kind].acts);
+    const int64_t acts = region_total(field_kind(P.kind).acts);
+    const int64_t film_fl = film_floats(P.kind);   // one group's rows of the FiLM table
     const int S = P.S;
     int64_t r_done = 0;
     int rc;
@@ -297,20 +303,20 @@ static int forward_pass(const PassSpec& P, const Geometry& G, const float* packe
         int64_t r0, r1, g0, ng;
         R.get(k, r0, r1);
         range_groups(R, r0, r1, g0, ng);
-        if ((rc = mi_field_eval_rays_train(P.kind, packed, R.film ? film + g0 * kFilmFloats : nullptr, rays + r0 * 6,
+        if ((rc = mi_field_eval_rays_train(P.kind, packed, R.film ? film + g0 * film_fl : nullptr, rays + r0 * 6,
                                            z + r0 * S, ng, (r1 - r0) / ng, S, raw + r0 * S * 4, saved, stream))) return rc;
         saved += acts * (r1 - r0) * S;
         r_done = r1;
     }
     if (r_done < R.n && R.film && r_done % R.rpg) {
         const int64_t r_next = (r_done / R.rpg + 1) * R.rpg;
-        if ((rc = mi_field_eval_rays(P.kind, packed, film + (r_done / R.rpg) * kFilmFloats, rays + r_done * 6, z + r_done * S,
+        if ((rc = mi_field_eval_rays(P.kind, packed, film + (r_done / R.rpg) * film_fl, rays + r_done * 6, z + r_done * S,
                                      1, r_next - r_done, S, raw + r_done * S * 4, stream))) return rc;
         r_done = r_next;
     }
     if (r_done < R.n) {
         const int64_t ng = R.film ? (R.n - r_done) / R.rpg : 1;
-        if ((rc = mi_field_eval_rays(P.kind, packed, R.film ? film + (r_done / R.rpg) * kFilmFloats : nullptr,
+        if ((rc = mi_field_eval_rays(P.kind, packed, R.film ? film + (r_done / R.rpg) * film_fl : nullptr,
                                      rays + r_done * 6, z + r_done * S, ng, (R.n - r_done) / ng, S, raw + r_done * S * 4,
                                      stream))) return rc;
     }
@@ -319,7 +325,7 @@ static int forward_pass(const PassSpec& P, const Geometry& G, const float* packe
 
 // Parameter-gradient pointers of a kind laid out in a scratch region (param_floats order).
 static void scratch_params(int kind, float* base, float* out[2 * kMaxLayers]) {
-    const FieldKind& k = kFieldKinds[kind];
+    const FieldKind& k = field_kind(kind);
     for (int l = 0; l < k.n_layers; ++l) {
         out[2 * l] = base;
         base += ((int64_t)k.dims[l][0] * k.dims[l][1] + 63) / 64 * 64;
@@ -329,7 +335,7 @@ static void scratch_params(int kind, float* base, float* out[2 * kMaxLayers]) {
 }
 
 static int64_t param_numel(int kind, int i) {
-    const FieldKind& k = kFieldKinds[kind];
+    const FieldKind& k = field_kind(kind);
     return (i & 1) ? k.dims[i / 2][0] : (int64_t)k.dims[i / 2][0] * k.dims[i / 2][1];
 }
 
@@ -349,8 +355,9 @@ struct PassIO {
 static int backward_pass(const PassSpec& P, const Geometry& G, const PassIO& io, const float* film, const float* rays,
                          float* const* dst, float* film_dst, float* bws, const BwdLayout& L, void* stream) {
     const Ranges R = make_ranges(P.kind, G.n_groups, G.rpg, P.S, P.range_points);
-    const FieldKind& K = kFieldKinds[P.kind];
+    const FieldKind& K = field_kind(P.kind);
     const int n_params = 2 * K.n_layers;
+    const int64_t film_fl = film_floats(P.kind);   // one group's rows of the FiLM table
     const int64_t acts_f = region_total(K.acts);
     const int S = P.S;
     hipStream_t hs = (hipStream_t)stream;
@@ -364,8 +371,8 @@ static int backward_pass(const PassSpec& P, const Geometry& G, const PassIO& io,
         range_groups(R, r0, r1, g0, ng);
         const int64_t pts = (r1 - r0) * S;
         const bool add_to_row = R.film && (r1 - r0) < R.rpg && r0 % R.rpg != 0;   // a later part of one image
-        const float* f_c = R.film ? film + g0 * kFilmFloats : nullptr;
-        float* g_c = !R.film ? nullptr : add_to_row ? bws + L.film_row : film_dst + g0 * kFilmFloats;
+        const float* f_c = R.film ? film + g0 * film_fl : nullptr;
+        float* g_c = !R.film ? nullptr : add_to_row ? bws + L.film_row : film_dst + g0 * film_fl;
         const float* acts;
         const float* raw_k;
         if (k < io.kept) {
@@ -385,7 +392,7 @@ static int backward_pass(const PassSpec& P, const Geometry& G, const PassIO& io,
         if (k > 0) {                                   // _foreach_add_(total, out); a later part adds to its image's row
             Accumulator acc(hs);
             for (int i = 0; i < n_params; ++i) acc.add(dst[i], range_out[i], param_numel(P.kind, i));
-            if (add_to_row) acc.add(film_dst + g0 * kFilmFloats, bws + L.film_row, kFilmFloats);
+            if (add_to_row) acc.add(film_dst + g0 * film_fl, bws + L.film_row, film_fl);
             if ((rc = acc.flush())) return rc;
         }
     }
@@ -401,9 +408,9 @@ extern "C" {
 int64_t mi_render_train_saved_bytes(int kind_coarse, int kind_fine, int shared, int64_t n, int n_coarse, int n_fine) {
     if (bad_kind(kind_coarse) || bad_kind(kind_fine)) return MI_EINVAL;
     if (n < 0 || n_coarse < 1 || n_fine < 0) { set_error("mi_render_train_saved_bytes: bad sizes"); return MI_EINVAL; }
-    const int64_t coarse = region_total(kFieldKinds[kind_coarse].acts) * n * n_coarse;
-    const int64_t second = shared ? region_total(kFieldKinds[kind_coarse].acts) * n * n_fine
-                                  : region_total(kFieldKinds[kind_fine].acts) * n * ((int64_t)n_coarse + n_fine);
+    const int64_t coarse = region_total(field_kind(kind_coarse).acts) * n * n_coarse;
+    const int64_t second = shared ? region_total(field_kind(kind_coarse).acts) * n * n_fine
+                                  : region_total(field_kind(kind_fine).acts) * n * ((int64_t)n_coarse + n_fine);
     return 4 * (coarse + second);
 }
 
@@ -504,7 +511,7 @@ int mi_render_rays_backward(int kind_coarse, const float* packed_coarse, const f
     const bool runs[2] = {run_c, shared ? run_f : want_f};
     bool film_written = false;
     for (int f = 0; f < (shared ? 1 : 2); ++f) {
-        const int np = 2 * kFieldKinds[kinds[f]].n_layers;
+        const int np = 2 * field_kind(kinds[f]).n_layers;
         const char* which = f ? "fine" : "coarse";
         if (is_film(kinds[f])) {
             if (!film) { set_error("%s: FiLM kind needs a film table", fn); return MI_EINVAL; }
@@ -538,7 +545,7 @@ int mi_render_rays_backward(int kind_coarse, const float* packed_coarse, const f
         for (int64_t k = 0; k < kept[0]; ++k) {
             int64_t r0, r1;
             R.get(k, r0, r1);
-            saved_pass[1] += region_total(kFieldKinds[P[0].kind].acts) * (r1 - r0) * P[0].S;
+            saved_pass[1] += region_total(field_kind(P[0].kind).acts) * (r1 - r0) * P[0].S;
         }
     }
     const State st = carve_state(const_cast<void*>(workspace), G);
@@ -565,7 +572,7 @@ int mi_render_rays_backward(int kind_coarse, const float* packed_coarse, const f
             if ((rc = backward_pass(P[1], G, io, film, rays, grad_params_fine, film_dst, bws, L, stream))) return rc;
             if (film_written && is_film(kind_fine)) {          // grad_film = coarse pass + fine pass
                 Accumulator acc(hs);
-                acc.add(grad_film, bws + L.film_pass, n_groups * kFilmFloats);
+                acc.add(grad_film, bws + L.film_pass, n_groups * film_floats(kind_coarse));
                 if ((rc = acc.flush())) return rc;
             }
             film_written |= is_film(kind_fine);
@@ -606,9 +613,9 @@ int mi_render_rays_backward(int kind_coarse, const float* packed_coarse, const f
         if ((rc = backward_pass(P[1], G, io_s, film, rays, fine_total, film_kind ? bws + L.film_pass : nullptr, bws, L,
                                 stream))) return rc;
         Accumulator acc(hs);                                   // _foreach_add_(grads_c, grads_f); grad_film += fine pass's
-        for (int i = 0; i < 2 * kFieldKinds[kind_coarse].n_layers; ++i)
+        for (int i = 0; i < 2 * field_kind(kind_coarse).n_layers; ++i)
             acc.add(grad_params_coarse[i], fine_total[i], param_numel(kind_coarse, i));
-        if (film_kind) acc.add(grad_film, bws + L.film_pass, n_groups * kFilmFloats);
+        if (film_kind) acc.add(grad_film, bws + L.film_pass, n_groups * film_floats(kind_coarse));
         if ((rc = acc.flush())) return rc;
     }
     if (fields_written) *fields_written = MI_WROTE_COARSE | (is_film(kind_coarse) ? MI_WROTE_FILM : 0);

@@ -30,6 +30,7 @@ SIGNATURES = {
     "mi_field_num_params": (_int, [_int]),
     "mi_field_packed_floats": (_i64, [_int]),
     "mi_field_macs": (_i64, [_int]),
+    "mi_field_film_layers": (_int, [_int]),
     "mi_field_param_shape": (_int, [_int, _int, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     "mi_field_pack": (_int, [_int, ctypes.POINTER(_vp), _int, _f32, _vp, _vp]),
     "mi_field_eval_points": (_int, [_int, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
@@ -61,9 +62,11 @@ SIGNATURES = {
     "mi_field_train_acts_floats": (_i64, [_int]),
     "mi_field_train_grads_floats": (_i64, [_int]),
     "mi_field_bwd_partial_floats": (_i64, [_i64]),
+    "mi_field_bwd_partial_floats_kind": (_i64, [_int, _i64]),
     "mi_field_eval_rays_train": (_int, [_int, _vp, _vp, _vp, _vp, _i64, _i64, _int, _vp, _vp, _vp]),
     "mi_field_eval_points_train": (_int, [_int, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     "mi_field_film_partial_floats": (_i64, [_i64, _i64]),
+    "mi_field_film_partial_floats_kind": (_i64, [_int, _i64, _i64]),
     "mi_field_backward": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, ctypes.POINTER(_vp),
                                  ctypes.POINTER(_vp), _int, _vp, _vp]),
     "mi_render_train_saved_bytes": (_i64, [_int, _int, _int, _i64, _int, _int]),

@@ -57,7 +57,7 @@ def _max_points_per_chunk(pf) -> int:
 def _groups(pf, film, n_rays):
     if not fields.is_film(pf.kind):
         return None, 1, n_rays
-    f = film.detach().to(device=pf.device, dtype=torch.float32).contiguous().reshape(-1, 9, 512)
+    f = film.detach().to(device=pf.device, dtype=torch.float32).contiguous().reshape(-1, fields.film_layers(pf.kind), 512)
     if n_rays % f.shape[0]:
         raise _lib.MiRenderError("rays must split evenly over the FiLM groups (images)")
     return f, f.shape[0], n_rays // f.shape[0]
@@ -200,9 +200,9 @@ def _field_backward(pf: fields.PackedField, rays, z, raw, g_raw, film, saved=Non
             # a part of an image adds to that image's row; the first part (and whole groups) overwrite
             add_to_row = part_of_group and r0 % rpg != 0
             g_c = torch.empty_like(f_c) if add_to_row else g_film[g0:g0 + ng]
-            fp = torch.empty(lib.mi_field_film_partial_floats(ng, ppg), dtype=torch.float32, device=dev)
+            fp = torch.empty(lib.mi_field_film_partial_floats_kind(pf.kind, ng, ppg), dtype=torch.float32, device=dev)
         gws, gws_g = _guarded(grads_f * pts, dev)
-        part, part_g = _guarded(lib.mi_field_bwd_partial_floats(pts), dev)
+        part, part_g = _guarded(lib.mi_field_bwd_partial_floats_kind(pf.kind, pts), dev)
         out = [torch.empty_like(p) for p in pf.params]
         if k in saved:
             acts_c, raw_c = saved.pop(k), raw[r0:r1]

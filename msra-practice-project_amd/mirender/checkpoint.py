@@ -56,11 +56,13 @@ def nerf_models(check_point: dict, device="cuda"):
 
 
 def pigan_generator(check_point: dict, output_size: int, device="cuda", **renderer_kw) -> "pigan.Generator":
-    """Generator (pi_GAN/modules.py:165) rebuilt from a pi_GAN/train.py checkpoint dict: input_dim and use_dir come
-    from the stored shapes; the renderer's settings are not part of a state dict and are passed by the caller."""
+    """Generator (pi_GAN/modules.py:165) rebuilt from a pi_GAN/train.py checkpoint dict: input_dim, use_dir and the
+    field's depth (hidden_layers = its hidden_layers.N entries + 1) come from the stored keys and shapes; the renderer's
+    settings are not part of a state dict and are passed by the caller."""
     sd = check_point["generator"]
     input_dim = sd["mapping_network.input_layer.0.weight"].shape[1]
     use_dir = sd["film_siren_nerf.hidden_layer_rgb.weight"].shape[1] == 259
-    gen = pigan.Generator(input_dim, output_size, use_dir=use_dir, **renderer_kw)
+    hidden_layers = 1 + sum(1 for k in sd if k.startswith("film_siren_nerf.hidden_layers.") and k.endswith(".weight"))
+    gen = pigan.Generator(input_dim, output_size, use_dir=use_dir, hidden_layers=hidden_layers, **renderer_kw)
     gen.load_state_dict(sd)
     return gen.to(device)

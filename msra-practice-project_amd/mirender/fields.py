@@ -50,17 +50,89 @@ SPECS = {
     TINY_NERF: [("layers_pos.0", (256, 60))] + [(f"layers_pos.{i}", (256, 256)) for i in (1, 2, 3)]
                + [("layers_dir.0", (128, 280)), ("output_layer_sigma", (1, 256)), ("output_layer_rgb", (3, 128))],
 }
-MACS = {k: sum(o * i for _, (o, i) in v) for k, v in SPECS.items()}
-FLOPS_PER_POINT = {k: 2 * v for k, v in MACS.items()}   # 2 x MACs of the linear layers
+
+# FilmSirenNeRF(hidden_dim=256, hidden_layers=L) for any FILM_DEPTH_MIN <= L <= FILM_DEPTH_MAX (pi_GAN/modules.py:73): kind
+# ids outside the five fixed kinds, MI_FIELD_FILM_DEPTH(L, use_dir) of include/mi_render.h.  L = 8 is kinds 2 / 3 and is
+# always named by them here.  SPECS stays the dict of the fixed kinds; spec_of(kind) serves every kind.
+FILM_DEPTH_MIN, FILM_DEPTH_MAX = 4, 12
+
+
+def film_depth_kind(hidden_layers: int, use_dir: bool = True) -> int:
+    """The kind of FilmSirenNeRF(hidden_layers=L, use_dir=...): kinds 2 / 3 for L = 8, else MI_FIELD_FILM_DEPTH(L, use_dir)."""
+    L = int(hidden_layers)
+    if not FILM_DEPTH_MIN <= L <= FILM_DEPTH_MAX:
+        raise _lib.MiRenderError(f"FilmSirenNeRF(hidden_layers={hidden_layers}): the fused kernels run hidden_layers "
+                                 f"{FILM_DEPTH_MIN}..{FILM_DEPTH_MAX}")
+    if L == 8:
+        return FILM_SIREN_NERF if use_dir else FILM_SIREN_NERF_NODIR
+    return 0x100 + 2 * L + (1 if use_dir else 0)
+
+
+def is_depth_kind(kind: int) -> bool:
+    return 0x100 <= kind < 0x200 and FILM_DEPTH_MIN <= (kind - 0x100) >> 1 <= FILM_DEPTH_MAX
 
 
 def is_film(kind: int) -> bool:
-    return kind in (FILM_SIREN_NERF, FILM_SIREN_NERF_NODIR)
+    return kind in (FILM_SIREN_NERF, FILM_SIREN_NERF_NODIR) or is_depth_kind(kind)
+
+
+def film_depth(kind: int) -> int:
+    """hidden_layers of a FiLM kind (8 for kinds 2 / 3), 0 for the others."""
+    return (kind - 0x100) >> 1 if is_depth_kind(kind) else 8 if is_film(kind) else 0
+
+
+def film_use_dir(kind: int) -> bool:
+    return bool(kind & 1) if is_depth_kind(kind) else kind == FILM_SIREN_NERF
+
+
+def film_layers(kind: int) -> int:
+    """Rows of the kind's FiLM table (mi_field_film_layers): hidden_layers + 1, 0 for the kinds without FiLM."""
+    return film_depth(kind) + 1 if is_film(kind) else 0
+
+
+def spec_of(kind: int) -> list:
+    """(key, (out, in)) per linear layer of any kind, fixed or depth (the reference's layout, pi_GAN/modules.py:76-94)."""
+    if kind in SPECS:
+        return SPECS[kind]
+    if not is_depth_kind(kind):
+        raise _lib.MiRenderError(f"unknown field kind {kind}")
+    L = film_depth(kind)
+    return ([("input_layer", (256, 3))] + [(f"hidden_layers.{i}", (256, 256)) for i in range(L - 1)]
+            + [("output_layer_sigma.0", (1, 256)), ("hidden_layer_rgb", (256, 259 if film_use_dir(kind) else 256)),
+               ("output_layer_rgb.0", (3, 256))])
+
+
+def kind_name(kind: int) -> str:
+    if kind in KIND_NAMES:
+        return KIND_NAMES[kind]
+    return f"film_siren_nerf_depth{film_depth(kind)}" + ("" if film_use_dir(kind) else "_nodir")
+
+
+def all_kinds() -> list:
+    """Every kind with kernels: the fixed kinds, then the depth kinds (depth 8 is among the fixed)."""
+    return list(SPECS) + [film_depth_kind(L, d) for L in range(FILM_DEPTH_MIN, FILM_DEPTH_MAX + 1) if L != 8
+                          for d in (True, False)]
+
+
+class _PerKind(dict):
+    """Per-kind figures: the fixed kinds are plain entries, a depth kind's is computed from its spec on first use."""
+
+    def __init__(self, fn):
+        super().__init__({k: fn(k) for k in SPECS})
+        self._fn = fn
+
+    def __missing__(self, kind):
+        self[kind] = v = self._fn(kind)
+        return v
+
+
+MACS = _PerKind(lambda k: sum(o * i for _, (o, i) in spec_of(k)))
+FLOPS_PER_POINT = _PerKind(lambda k: 2 * MACS[k])   # SURVEY.md §8d: 2 x MACs of the linear layers
 
 
 def _shapes(kind):
     out = {}
-    for key, (o, i) in SPECS[kind]:
+    for key, (o, i) in spec_of(kind):
         out[key + ".weight"] = (o, i)
         out[key + ".bias"] = (o,)
     return out
@@ -69,7 +141,7 @@ def _shapes(kind):
 def detect_kind(named_params: dict) -> int | None:
     """Match a {name: tensor} mapping against the known layouts (exact key set and shapes)."""
     got = {k: tuple(v.shape) for k, v in named_params.items()}
-    for kind in SPECS:
+    for kind in all_kinds():
         if got == _shapes(kind):
             return kind
     return None
@@ -110,7 +182,7 @@ def film_w0(model, kind: int) -> float:
     if hasattr(model, "mi_w_0"):
         return float(model.mi_w_0)
     try:
-        return float(getattr(_layer_module(model, SPECS[kind][0][0]), "w_0", W_0))
+        return float(getattr(_layer_module(model, spec_of(kind)[0][0]), "w_0", W_0))
     except (AttributeError, IndexError, KeyError, TypeError):
         return W_0
 
@@ -128,7 +200,7 @@ def hyper_mismatch(model, kind: int) -> str | None:
       our own leaves (`_Leaf`)               carry `mi_activation`
     Anything else (a user's nn.Linear stack with its own forward, a subclass with another nonlinearity) says nothing
     about its activation, so it is not claimed."""
-    for key, _ in SPECS[kind]:
+    for key, _ in spec_of(kind):
         want = expected_activation(kind, key)
         try:
             mod = _layer_module(model, key)
@@ -156,7 +228,7 @@ def hyper_mismatch(model, kind: int) -> str | None:
         else:
             return f"{key}: {type(mod).__name__} does not name its activation"
         if have != want:
-            return f"{key}: activation {have!r}, the fused {KIND_NAMES[kind]} kernel applies {want!r}"
+            return f"{key}: activation {have!r}, the fused {kind_name(kind)} kernel applies {want!r}"
     return None
 
 
@@ -256,7 +328,8 @@ def _replica_named(model) -> dict:
     """torch.nn.DataParallel (pi_GAN/train.py:50) runs forward on per-device REPLICAS whose parameters are plain
     tensor attributes (broadcast copies that still carry autograd history back to the originals), so
     named_parameters() is empty there.  Walk the known layouts' attribute paths instead."""
-    for kind, spec in SPECS.items():
+    for kind in all_kinds():
+        spec = spec_of(kind)
         named = {}
         try:
             for key, _ in spec:
@@ -289,7 +362,7 @@ def as_packed_field(model) -> PackedField | None:
             # module's own forward between the sampling / compositing kernels, correct but orders of magnitude slower
             # than the fused kernels.  Said once per model (the verdict is cached and NOT re-checked if a layer's
             # attributes change later: INTEGRATION.md)
-            warnings.warn(f"{type(model).__name__} has the parameter layout of {KIND_NAMES[kind]} but is not claimed by the "
+            warnings.warn(f"{type(model).__name__} has the parameter layout of {kind_name(kind)} but is not claimed by the "
                           f"fused kernels ({why}); it is rendered through the generic path (its own forward)",
                           RuntimeWarning, stacklevel=3)
             kind = None
@@ -299,7 +372,7 @@ def as_packed_field(model) -> PackedField | None:
         if not next(iter(named.values())).is_cuda:
             raise _lib.MiRenderError("the fused renderer needs the model on a ROCm device (model.cuda())")
         params = []
-        for key, _ in SPECS[kind]:
+        for key, _ in spec_of(kind):
             params += [named[key + ".weight"], named[key + ".bias"]]
         pf = PackedField(kind, params, film_w0(model, kind))
         _field_cache[model] = pf
@@ -307,15 +380,17 @@ def as_packed_field(model) -> PackedField | None:
 
 
 def film_table(model) -> torch.Tensor:
-    """[1,9,512] FiLM table from FilmSirenNeRF.film_params (list of 9 (gamma, beta) pairs set by
-    set_film_params, pi_GAN/modules.py:96-99).  Raises ValueError like the reference
+    """[1,rows,512] FiLM table from FilmSirenNeRF.film_params (list of rows = hidden_layers + 1 (gamma, beta) pairs set by
+    set_film_params, pi_GAN/modules.py:96-99; 9 for the reference's default depth).  Raises ValueError like the reference
     (modules.py:106-107) when unset."""
     fp = getattr(model, "film_params", None)
     if fp is None:
         raise ValueError
     if isinstance(fp, torch.Tensor):
-        return fp.reshape(-1, 9, 512)
-    return torch.cat([torch.cat([g.reshape(-1), b.reshape(-1)]) for g, b in fp]).reshape(1, 9, 512)
+        kind = detect_kind(dict(model.named_parameters())) if isinstance(model, torch.nn.Module) else None
+        return fp.reshape(-1, film_layers(kind) if kind is not None and is_film(kind) else 9, 512)
+    rows = len(fp)                        # a pair per FiLM layer; the kernels' entry points check it against the kind
+    return torch.cat([torch.cat([g.reshape(-1), b.reshape(-1)]) for g, b in fp]).reshape(1, rows, 512)
 
 
 def eval_points(pf: PackedField, x: torch.Tensor, film: torch.Tensor | None = None) -> torch.Tensor:
@@ -329,7 +404,7 @@ def eval_points(pf: PackedField, x: torch.Tensor, film: torch.Tensor | None = No
     if is_film(pf.kind):
         if film is None:
             raise ValueError
-        film = film.detach().to(device=pf.device, dtype=torch.float32).contiguous().reshape(-1, 9, 512)
+        film = film.detach().to(device=pf.device, dtype=torch.float32).contiguous().reshape(-1, film_layers(pf.kind), 512)
         groups = film.shape[0]
         if x.shape[0] % groups:
             raise _lib.MiRenderError("points must split evenly over the FiLM groups")
@@ -356,7 +431,7 @@ class _FusedField(torch.nn.Module):
 
     def __init__(self):
         super().__init__()
-        for key, (o, i) in SPECS[self.KIND]:
+        for key, (o, i) in spec_of(self.KIND):
             self._register(key, torch.nn.Parameter(torch.empty(o, i)), torch.nn.Parameter(torch.zeros(o)))
         self.reset_parameters()
 
@@ -433,8 +508,9 @@ class SirenNeRF(_FusedField):
 class FilmSirenNeRF(_FusedField):
     """pi_GAN/modules.py:70-118, same constructor arguments (:73).  FiLM parameters are per-image state set by
     set_film_params (modules.py:96-99) or passed to forward, as in the reference.  `c` and `w_0` shape the initialisation
-    (modules.py:27-31) and w_0 is the frequency the fused kernels run with; the fused kernels exist for the reference's own
-    topology (hidden_dim 256, 8 layers) - other sizes have no kernel here and raise."""
+    (modules.py:27-31) and w_0 is the frequency the fused kernels run with; the fused kernels exist for hidden_dim 256 and
+    hidden_layers FILM_DEPTH_MIN..FILM_DEPTH_MAX (8, the reference's default, is kinds 2 / 3; the others are the
+    MI_FIELD_FILM_DEPTH kinds) - other sizes have no kernel here and raise."""
     KIND = FILM_SIREN_NERF
 
     def __new__(cls, hidden_dim=256, hidden_layers=8, c=6, w_0=30, use_dir=True):
@@ -443,10 +519,12 @@ class FilmSirenNeRF(_FusedField):
         return super().__new__(cls)
 
     def __init__(self, hidden_dim=256, hidden_layers=8, c=6, w_0=30, use_dir=True):
-        if (hidden_dim, hidden_layers) != (256, 8):
+        if hidden_dim != 256:
             raise _lib.MiRenderError(f"FilmSirenNeRF(hidden_dim={hidden_dim}, hidden_layers={hidden_layers}): the fused kernels "
-                                     "implement the reference's default topology (256, 8) only; build the reference's own "
-                                     "module for other sizes - render_rays drives it through the generic path")
+                                     "implement hidden_dim 256 only; build the reference's own module for other widths - "
+                                     "render_rays drives it through the generic path")
+        self.KIND = film_depth_kind(hidden_layers, use_dir)      # raises outside FILM_DEPTH_MIN..FILM_DEPTH_MAX
+        self.n_layers = hidden_layers - 1                        # len(hidden_layers), pi_GAN/modules.py:94
         if not (float(w_0) > 0.0 and math.isfinite(float(w_0))):
             raise _lib.MiRenderError(f"FilmSirenNeRF(w_0={w_0}): need a finite w_0 > 0")
         self.c, self.mi_w_0 = c, float(w_0)       # before super().__init__: reset_parameters reads them
@@ -456,7 +534,7 @@ class FilmSirenNeRF(_FusedField):
         self.film_params = None
 
     def reset_parameters(self):
-        for key, (o, i) in SPECS[self.KIND]:
+        for key, (o, i) in spec_of(self.KIND):
             lay = self._layer(key)
             if key in ("output_layer_sigma.0", "output_layer_rgb.0"):   # torch.nn.Linear default
                 b = 1 / math.sqrt(i)
@@ -493,9 +571,10 @@ def field_from_state_dict(sd: dict, device="cuda", w_0: float = W_0) -> torch.nn
     kind = detect_kind(sd)
     if kind is None:
         raise _lib.MiRenderError("state dict does not match a known field layout")
-    cls = {NERF: NeRF, SIREN_NERF: SirenNeRF, FILM_SIREN_NERF: FilmSirenNeRF,
-           FILM_SIREN_NERF_NODIR: FilmSirenNeRFNoDir, TINY_NERF: TinyNeRF}[kind]
-    m = cls(w_0=w_0) if is_film(kind) else cls()
+    if is_film(kind):
+        m = FilmSirenNeRF(hidden_layers=film_depth(kind), w_0=w_0, use_dir=film_use_dir(kind))
+    else:
+        m = {NERF: NeRF, SIREN_NERF: SirenNeRF, TINY_NERF: TinyNeRF}[kind]()
     m.load_state_dict({k: torch.as_tensor(np.asarray(v)) if not isinstance(v, torch.Tensor) else v
                        for k, v in sd.items()})
     return m.to(device)

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .fields import PackedField, is_film
+from .fields import PackedField, film_layers, is_film
 
 
 def _f32c(t, device):
@@ -177,7 +177,7 @@ def _film_for(pf: PackedField, film, n_rays):
         return None, 1, n_rays
     if film is None:
         raise ValueError
-    film = _f32c(film, pf.device).reshape(-1, 9, 512)
+    film = _f32c(film, pf.device).reshape(-1, film_layers(pf.kind), 512)
     groups = film.shape[0]
     if n_rays % groups:
         raise _lib.MiRenderError("rays must split evenly over the FiLM groups (images)")

@@ -32,13 +32,14 @@ def camera_pos_to_transform_matrix(radius, theta, phi):
 
 
 def render_batch(model, film, poses, width, height, focal, near, far, n_coarse, n_fine, t_rand=None, seed=None):
-    """b images [b,H,W,3] (fine rgb, autograd graph attached) from one FiLM field, film [b,9,512], b poses."""
+    """b images [b,H,W,3] (fine rgb, autograd graph attached) from one FiLM field, film [b,rows,512] (rows = hidden_layers + 1),
+    b poses."""
     pf = fields.as_packed_field(model)
     dev = pf.device
     b = len(poses)
     rays = torch.cat([ops.gen_rays(width, height, focal, p, dev) for p in poses])
     out = render_core.render_rays(rays, near, far, model, model, n_coarse, n_fine, t_rand=t_rand, seed=seed,
-                                  film=film.reshape(b, 9, 512))
+                                  film=film.reshape(b, fields.film_layers(pf.kind), 512))
     return out[3].reshape(b, height, width, 3)
 
 
@@ -83,7 +84,7 @@ class Renderer:
 
 
 class MappingNetwork(torch.nn.Module):
-    """pi_GAN/modules.py:34-68: z -> 9 x (gamma | beta); state-dict keys as the reference's."""
+    """pi_GAN/modules.py:34-68: z -> (output_layers + 1) x (gamma | beta); state-dict keys as the reference's."""
 
     def __init__(self, input_dim=256, output_dim=256, output_layers=8, hidden_dim=256, hidden_layers=3):
         super().__init__()
@@ -108,16 +109,17 @@ class Generator(torch.nn.Module):
     """pi_GAN/modules.py:165-197 with the batch rendered in one launch sequence."""
 
     def __init__(self, input_dim, output_size, near=0.1, far=1.9, fov=12, coarse_samples=64, fine_samples=128,
-                 horizontal_std=0.3, vertical_std=0.15, use_dir=True):
+                 horizontal_std=0.3, vertical_std=0.15, use_dir=True, hidden_layers=8):
         super().__init__()
         self.input_dim = input_dim
-        self.film_siren_nerf = fields.FilmSirenNeRF(use_dir=use_dir)
-        self.mapping_network = MappingNetwork(input_dim=input_dim)
+        # the field's depth and the mapping network's heads go together: hidden_layers + 1 FiLM rows (modules.py:52-54)
+        self.film_siren_nerf = fields.FilmSirenNeRF(hidden_layers=hidden_layers, use_dir=use_dir)
+        self.mapping_network = MappingNetwork(input_dim=input_dim, output_layers=hidden_layers)
         self.renderer = Renderer(output_size, output_size, near, far, fov, coarse_samples, fine_samples,
                                  horizontal_std, vertical_std)
 
     def forward(self, input_tensor, thetas=None, phis=None, t_rand=None, seed=None):
-        film = self.mapping_network(input_tensor)                               # [b,9,512]
+        film = self.mapping_network(input_tensor)                               # [b,hidden_layers+1,512]
         img = self.renderer.render_batch(self.film_siren_nerf, film, thetas, phis, t_rand, seed)
         return img.permute(0, 3, 1, 2).contiguous()                             # [b,3,H,W] (modules.py:182-183)
 

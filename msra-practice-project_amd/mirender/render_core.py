@@ -110,7 +110,7 @@ def render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, fi
     """nerf/render.py:106-147.  rays [N,2,3] -> (rgb_c, depth_c, acc_c, rgb_f, depth_f, acc_f).
     `ray0`: index of rays[0] in the caller's full ray list; the seeded jitter is keyed by (seed, ray0 + k, sample),
     so a frame rendered in pieces (chunks, GPUs) gets the jitter it would get in one call.
-    `film` [b,9,512] (FiLM fields only) renders b images in one call: rays are b equal consecutive groups and
+    `film` [b,rows,512] (FiLM fields only; rows = hidden_layers + 1, 9 for the default depth) renders b images in one call: rays are b equal consecutive groups and
     group g uses film[g]; by default the model's own film_params (one image) are used like the reference."""
     return _render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, fine_sample_num, t_rand=t_rand,
                         seed=seed, film=film, ray0=ray0)
