@@ -169,7 +169,10 @@ int mi_sample_pdf(int64_t n, int n_bins, int n_samples, const float* bins, const
  *   Without rgb_c and with two different fields (kind or packed pointer), the coarse pass runs the coarse field's
  *   sigma-only forward, where the kind has one (NeRF, SirenNeRF, TinyNeRF), and a composite that forms the weights (and
  *   depth_c / acc_c when asked for) from sigma alone.  The fine outputs, and depth_c / acc_c, are the same bits as those
- *   of a call with all six outputs. */
+ *   of a call with all six outputs.  That coarse pass runs front to back in windows of samples and stops evaluating the
+ *   field along a ray once the ray's transmittance has reached zero: every later weight is exactly 0 whatever the field
+ *   returns there, so no output bit depends on it - except that a non-finite sigma behind a zero transmittance no longer
+ *   reaches the outputs as NaN.  All launches stay asynchronous, with host-known grid sizes (stream capture works). */
 int64_t mi_render_workspace_bytes(int64_t n, int n_coarse, int n_fine);
 int64_t mi_render_shared_field_extra_bytes(int64_t n, int n_coarse, int n_fine);
 int mi_render_rays(int kind_coarse, const float* packed_coarse, int kind_fine, const float* packed_fine,

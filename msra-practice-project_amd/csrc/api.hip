@@ -59,12 +59,51 @@ static int eval_common(int kind, const float* packed, const float* film, const f
     args.points_per_group = ppg; args.rays_per_group = rpg; args.tiles_per_group = (ppg + 127) / 128;
     args.n_samples = S; args.mode = mode; args.save = save; args.save_points = n_groups * ppg;
     args.film_depth = film_depth(kind);
+    args.live_rays = nullptr; args.live_count = nullptr; args.n_rays = 0; args.win_k0 = 0; args.win_log2 = 0;
 #ifdef MI_PROFILE_STAMPS
     args.stamps = g_stamps;
 #else
     args.stamps = nullptr;
 #endif
     return launch_mlp(kind, args, n_groups, s, sigma_only);
+}
+
+// Samples per window of the sigma-only coarse pass of mi_render_rays (a power of two that divides 128, the point tile).
+#ifndef MI_COARSE_WINDOW_LOG2
+#define MI_COARSE_WINDOW_LOG2 3
+#endif
+constexpr int kCoarseWindowLog2 = MI_COARSE_WINDOW_LOG2;
+constexpr int kCoarseWindow = 1 << kCoarseWindowLog2;
+static_assert(kCoarseWindow >= 1 && 128 % kCoarseWindow == 0, "a tile is 128 / kCoarseWindow rays x one window");
+
+// The sigma-only coarse pass, front to back in windows of kCoarseWindow samples: window r evaluates the field at its
+// samples of the rays that are still live, then the resumable weights composite (render_stages.hip) writes the window's
+// weights and drops every ray whose transmittance has reached zero - all its later weights are exactly 0 whatever the
+// field says there, so the field is not asked.  Same weights / depth_c / acc_c bits as one whole pass.  Everything is
+// launched with worst-case grids from host values only (no read-back: graph-capturable); `scratch` is the part of raw_c's
+// region behind the compact sigma buffer: two live lists [n] and one count per window.
+static int coarse_sigma_windows(int kind, const float* packed, const float* rays, const float* z_c, int64_t n, int n_coarse,
+                                float* sigma, int* scratch, float* depth_c, float* acc_c, float* w_c, hipStream_t hs) {
+    const int rounds = (n_coarse + kCoarseWindow - 1) / kCoarseWindow;
+    int* list[2] = {scratch, scratch + n};
+    int* counts = scratch + 2 * n;
+    if (hipMemsetAsync(counts, 0, sizeof(int) * rounds, hs) != hipSuccess) { set_error("mi_render_rays: hipMemsetAsync failed"); return MI_EHIP; }
+    MlpArgs args = {};
+    args.packed = packed; args.a = rays; args.z = z_c; args.out = sigma;
+    args.n_samples = n_coarse; args.mode = 1; args.n_rays = n; args.win_log2 = kCoarseWindowLog2;
+    for (int r = 0; r < rounds; ++r) {
+        const int k0 = r * kCoarseWindow, k1 = k0 + kCoarseWindow < n_coarse ? k0 + kCoarseWindow : n_coarse;
+        const bool last = r == rounds - 1;
+        args.live_rays = r ? list[r & 1] : nullptr;          // window 0: every ray
+        args.live_count = r ? counts + r : nullptr;
+        args.win_k0 = k0;
+        int rc;
+        if ((rc = launch_mlp_window(kind, args, hs))) return rc;
+        if ((rc = launch_composite_weights_window(n, n_coarse, sigma, z_c, rays, depth_c, acc_c, w_c, args.live_rays,
+                                                  args.live_count, last ? nullptr : list[(r + 1) & 1],
+                                                  last ? nullptr : counts + r + 1, k0, k1, hs))) return rc;
+    }
+    return MI_OK;
 }
 
 }  // namespace mi
@@ -250,12 +289,19 @@ int mi_render_rays(int kind_coarse, const float* packed_coarse, int kind_fine, c
     // Without the coarse colours and with a coarse field of its own, the coarse pass only feeds sample_fine its weights,
     // which depend on sigma alone: the sigma-only forward writes sigma [n,Nc] compactly at the start of raw_c's region.
     // A shared field's coarse raw values are merged into the fine pass (or are its outputs with Nf = 0): whole forward.
+    // The other three quarters of the region hold the windowed pass's live lists and counts: 2 n + ceil(Nc / window) ints
+    // <= 3 n Nc floats whenever Nc >= 2.
     const bool sigma_only = !rgb_c && !shared && has_sigma_only_kernel(kind_coarse);
     int rc;
     if ((rc = mi_sample_coarse(n, near_, far_, n_coarse, z_lin, t_rand, seed, ray0, z_c, stream))) return rc;
     hipStream_t hs = (hipStream_t)stream;
     if (g_mlp_ev[0]) (void)hipEventRecord(g_mlp_ev[0], hs);
-    if (sigma_only) {
+    // more than one window, and ray indices that fit the live lists' ints: the windowed pass (weights included)
+    const bool windowed = sigma_only && n_coarse > kCoarseWindow && n <= 0x7fffffffLL;
+    if (windowed) {
+        if ((rc = coarse_sigma_windows(kind_coarse, packed_coarse, rays, z_c, n, n_coarse, raw_c, (int*)(raw_c + n * n_coarse),
+                                       depth_c, acc_c, w_c, hs))) return rc;
+    } else if (sigma_only) {
         if ((rc = eval_common(kind_coarse, packed_coarse, film, rays, z_c, n_groups, rays_per_group * n_coarse, rays_per_group,
                               n_coarse, 1, raw_c, hs, nullptr, true))) return rc;
     } else if ((rc = mi_field_eval_rays(kind_coarse, packed_coarse, film, rays, z_c, n_groups, rays_per_group, n_coarse, raw_c,
@@ -278,6 +324,7 @@ int mi_render_rays(int kind_coarse, const float* packed_coarse, int kind_fine, c
         return MI_OK;
     }
     if (rgb_c) rc = mi_composite(n, n_coarse, raw_c, z_c, rays, rgb_c, depth_c, acc_c, w_c, stream);
+    else if (windowed) rc = MI_OK;                                   // coarse_sigma_windows wrote w_c / depth_c / acc_c
     else if (sigma_only) rc = launch_composite_weights(n, n_coarse, raw_c, 1, z_c, rays, depth_c, acc_c, w_c, hs);
     else rc = launch_composite_weights(n, n_coarse, raw_c + 3, 4, z_c, rays, depth_c, acc_c, w_c, hs);     // raw's sigma channel
     if (rc) return rc;

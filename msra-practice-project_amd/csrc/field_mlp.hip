@@ -32,22 +32,32 @@ namespace mi {
 // region table nerf_acts()/tiny_acts() in field_layout.h) for the backward pass.
 // SIGMA_ONLY = density forward: the trunk and the sigma head, then the wave ends (store_sigma).  Up to sigma it executes
 // the inference instance's instructions, so sigma has the same bits.
-template <bool TINY, bool SAVE, bool SIGMA_ONLY>
+// WINDOW = the sigma-only instance over one window of samples of the live rays (load_window_point): a block whose tile lies
+// past the live count returns before it issues any LDS DMA.
+template <bool TINY, bool SAVE, bool SIGMA_ONLY, bool WINDOW = false>
 __global__ __launch_bounds__(256, 1) void nerf_fwd_kernel(MlpArgs a) {
     static_assert(!(SAVE && SIGMA_ONLY), "the training forward needs the colour branch");
+    static_assert(!WINDOW || SIGMA_ONLY, "windows exist for the sigma-only coarse pass");
     constexpr FieldKind K = kFieldKinds[TINY ? MI_FIELD_TINY_NERF : MI_FIELD_NERF];
     // the stage the last trunk layer issues behind it: the colour branch's first, none if the wave stops at sigma
     constexpr int kNextAux = SIGMA_ONLY ? 0 : K.branch_aux_pieces();
     constexpr int kNextBlock = SIGMA_ONLY ? 0 : K.branch_block_pieces();
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int64_t group = blockIdx.x / a.tiles_per_group;
-    const int64_t tile = blockIdx.x % a.tiles_per_group;
+    const int64_t group = WINDOW ? 0 : blockIdx.x / a.tiles_per_group;
+    const int64_t tile = WINDOW ? blockIdx.x : blockIdx.x % a.tiles_per_group;
+    int64_t live = 0;
+    if constexpr (WINDOW) {
+        live = window_live_count(a);
+        if (tile * (128 >> a.win_log2) >= live) return;
+    }
     Ctx c = make_ctx(smem, a, group);
     MI_STAMP(a, 0);
     issue_first_stage<1, 32, false>(c, 0, 0, 0);   // layer 0: bias + K block 0 (PE features 0..31)
 
-    const PointIn pt = load_point(a.mode, a.a, a.z, group, a.points_per_group, a.rays_per_group, a.n_samples,
-                                  tile * 128 + c.wave * 32 + (c.lane & 31));
+    PointIn pt;
+    if constexpr (WINDOW) pt = load_window_point(a, tile, live, c.wave * 32 + (c.lane & 31));
+    else pt = load_point(a.mode, a.a, a.z, group, a.points_per_group, a.rays_per_group, a.n_samples,
+                         tile * 128 + c.wave * 32 + (c.lane & 31));
     f32x16 pe[2], pd[1], X[8], acc[8];
     float* scr = smem + kLdsChunk0 + kLdsChunk + c.wave * 2048;   // chunk buffer 1 is idle until stage 1
     posenc_blocks<2>(scr, c.lane, c.h, pt.px, pt.py, pt.pz, 60, pe);
@@ -165,20 +175,28 @@ __global__ __launch_bounds__(256, 1) void nerf_fwd_kernel(MlpArgs a) {
 // =========================================================================================
 // SirenNeRF (nerf/nerf.py:153-170): sin(30 * linear) layers on raw xyz / dir
 // =========================================================================================
-template <bool SAVE, bool SIGMA_ONLY>
+template <bool SAVE, bool SIGMA_ONLY, bool WINDOW = false>
 __global__ __launch_bounds__(256, 1) void siren_fwd_kernel(MlpArgs a) {
     static_assert(!(SAVE && SIGMA_ONLY), "the training forward needs the colour branch");
+    static_assert(!WINDOW || SIGMA_ONLY, "windows exist for the sigma-only coarse pass");
     constexpr FieldKind K = kFieldKinds[MI_FIELD_SIREN_NERF];
     constexpr int kNextAux = SIGMA_ONLY ? 0 : K.branch_aux_pieces();      // as in nerf_fwd_kernel
     constexpr int kNextBlock = SIGMA_ONLY ? 0 : K.branch_block_pieces();
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int64_t group = blockIdx.x / a.tiles_per_group;
-    const int64_t tile = blockIdx.x % a.tiles_per_group;
+    const int64_t group = WINDOW ? 0 : blockIdx.x / a.tiles_per_group;
+    const int64_t tile = WINDOW ? blockIdx.x : blockIdx.x % a.tiles_per_group;
+    int64_t live = 0;
+    if constexpr (WINDOW) {                        // as in nerf_fwd_kernel
+        live = window_live_count(a);
+        if (tile * (128 >> a.win_log2) >= live) return;
+    }
     Ctx c = make_ctx(smem, a, group);
     issue_first_stage<4, 0, false>(c, 0, 0, 0);   // layers_pos[0]: bias + 3 weight columns (K = 3, VALU)
 
-    const PointIn pt = load_point(a.mode, a.a, a.z, group, a.points_per_group, a.rays_per_group, a.n_samples,
-                                  tile * 128 + c.wave * 32 + (c.lane & 31));
+    PointIn pt;
+    if constexpr (WINDOW) pt = load_window_point(a, tile, live, c.wave * 32 + (c.lane & 31));
+    else pt = load_point(a.mode, a.a, a.z, group, a.points_per_group, a.rays_per_group, a.n_samples,
+                         tile * 128 + c.wave * 32 + (c.lane & 31));
     f32x16 X[8], acc[8];
     const auto sel_x = [&](auto kb) -> const f32x16& { return X[decltype(kb)::value]; };
     constexpr RegionLayout RL = siren_acts();
@@ -323,19 +341,20 @@ __global__ __launch_bounds__(256, 1) void film_fwd_kernel(MlpArgs a) {
 }
 
 // ---- host side ---------------------------------------------------------------------------
-// [kind][variant]: the inference, the training (layer inputs saved) and the sigma-only instance of each kind's kernel.
+// [kind][variant]: the inference, the training (layer inputs saved), the sigma-only and the windowed sigma-only instance
+// of each kind's kernel.
 // The FiLM kinds have no sigma-only instance (their caller, pi_GAN, renders both passes with one field and needs the
 // coarse colours for the merge): has_sigma_only_kernel() is false for them.
-enum FwdVariant : int { FWD_INFER = 0, FWD_SAVE = 1, FWD_SIGMA = 2 };
-static const void* const kFwdKernels[MI_FIELD_KINDS][3] = {
+enum FwdVariant : int { FWD_INFER = 0, FWD_SAVE = 1, FWD_SIGMA = 2, FWD_SIGMA_WINDOW = 3 };
+static const void* const kFwdKernels[MI_FIELD_KINDS][4] = {
     {(const void*)nerf_fwd_kernel<false, false, false>, (const void*)nerf_fwd_kernel<false, true, false>,
-     (const void*)nerf_fwd_kernel<false, false, true>},                                                     // MI_FIELD_NERF
+     (const void*)nerf_fwd_kernel<false, false, true>, (const void*)nerf_fwd_kernel<false, false, true, true>},   // MI_FIELD_NERF
     {(const void*)siren_fwd_kernel<false, false>, (const void*)siren_fwd_kernel<true, false>,
-     (const void*)siren_fwd_kernel<false, true>},                                                           // MI_FIELD_SIREN_NERF
-    {(const void*)film_fwd_kernel<true, false>, (const void*)film_fwd_kernel<true, true>, nullptr},         // MI_FIELD_FILM_SIREN_NERF
-    {(const void*)film_fwd_kernel<false, false>, (const void*)film_fwd_kernel<false, true>, nullptr},       // ..._NODIR
+     (const void*)siren_fwd_kernel<false, true>, (const void*)siren_fwd_kernel<false, true, true>},           // MI_FIELD_SIREN_NERF
+    {(const void*)film_fwd_kernel<true, false>, (const void*)film_fwd_kernel<true, true>, nullptr, nullptr},    // MI_FIELD_FILM_SIREN_NERF
+    {(const void*)film_fwd_kernel<false, false>, (const void*)film_fwd_kernel<false, true>, nullptr, nullptr},  // ..._NODIR
     {(const void*)nerf_fwd_kernel<true, false, false>, (const void*)nerf_fwd_kernel<true, true, false>,
-     (const void*)nerf_fwd_kernel<true, false, true>}};                                                     // MI_FIELD_TINY_NERF
+     (const void*)nerf_fwd_kernel<true, false, true>, (const void*)nerf_fwd_kernel<true, false, true, true>}};    // MI_FIELD_TINY_NERF
 
 // [use_dir][variant]: the run-time-depth FiLM instances (MI_FIELD_FILM_DEPTH kinds other than depth 8, which IS kinds 2 / 3)
 static const void* const kFilmDepthFwdKernels[2][2] = {
@@ -344,20 +363,10 @@ static const void* const kFilmDepthFwdKernels[2][2] = {
 
 bool has_sigma_only_kernel(int kind) { return kind >= 0 && kind < MI_FIELD_KINDS && kFwdKernels[kind][FWD_SIGMA]; }
 
-int launch_mlp(int kind_in, const MlpArgs& a, int64_t n_groups, hipStream_t stream, bool sigma_only) {
-    const int kind = canon_kind(kind_in);
-    const int64_t blocks = n_groups * a.tiles_per_group;
-    if (blocks <= 0) return 0;
-    if (blocks > 0x7fffffffLL) { set_error("too many point tiles (%lld)", (long long)blocks); return -1; }
-    if (bad_kind(kind)) return -1;
-    if (sigma_only && (a.save || !has_sigma_only_kernel(kind))) {
-        set_error("kind %d has no sigma-only forward%s", kind, a.save ? " with saved layer inputs" : "");
-        return -1;
-    }
-    const size_t lds = kLdsFloats * sizeof(float);
-    // 148 KiB of dynamic LDS: raise the per-kernel limit once per device (host-side attribute, no device work)
+// 148 KiB of dynamic LDS: raise the per-kernel limit once per device (host-side attribute, no device work)
+static int raise_lds_limit(size_t lds) {
     static PerDeviceOnce attr_once;
-    const int arc = attr_once.run([&]() {
+    return attr_once.run([&]() {
         for (const auto& k : kFwdKernels)
             for (const void* f : k) {
                 if (!f) continue;
@@ -371,7 +380,20 @@ int launch_mlp(int kind_in, const MlpArgs& a, int64_t n_groups, hipStream_t stre
             }
         return 0;
     });
-    if (arc) return arc;
+}
+
+int launch_mlp(int kind_in, const MlpArgs& a, int64_t n_groups, hipStream_t stream, bool sigma_only) {
+    const int kind = canon_kind(kind_in);
+    const int64_t blocks = n_groups * a.tiles_per_group;
+    if (blocks <= 0) return 0;
+    if (blocks > 0x7fffffffLL) { set_error("too many point tiles (%lld)", (long long)blocks); return -1; }
+    if (bad_kind(kind)) return -1;
+    if (sigma_only && (a.save || !has_sigma_only_kernel(kind))) {
+        set_error("kind %d has no sigma-only forward%s", kind, a.save ? " with saved layer inputs" : "");
+        return -1;
+    }
+    const size_t lds = kLdsFloats * sizeof(float);
+    if (const int arc = raise_lds_limit(lds)) return arc;
     void* args[] = {const_cast<MlpArgs*>(&a)};
     const int variant = sigma_only ? FWD_SIGMA : a.save ? FWD_SAVE : FWD_INFER;
     const void* fn;
@@ -383,6 +405,25 @@ int launch_mlp(int kind_in, const MlpArgs& a, int64_t n_groups, hipStream_t stre
     }
     (void)hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(256), args, lds, stream);
     return check_launch("field_mlp_fwd");
+}
+
+int launch_mlp_window(int kind_in, const MlpArgs& a, hipStream_t stream) {
+    const int kind = canon_kind(kind_in);
+    if (bad_kind(kind)) return -1;
+    if (a.save || a.film || !has_sigma_only_kernel(kind) || a.win_log2 < 0 || a.win_log2 > 7 || a.win_k0 < 0 ||
+        a.win_k0 >= a.n_samples || a.n_rays > 0x7fffffffLL) {
+        set_error("kind %d: bad windowed sigma-only launch", kind);
+        return -1;
+    }
+    const int64_t per_tile = 128 >> a.win_log2;
+    const int64_t blocks = (a.n_rays + per_tile - 1) / per_tile;        // worst case: every ray live
+    if (blocks <= 0) return 0;
+    if (blocks > 0x7fffffffLL) { set_error("too many point tiles (%lld)", (long long)blocks); return -1; }
+    const size_t lds = kLdsFloats * sizeof(float);
+    if (const int arc = raise_lds_limit(lds)) return arc;
+    void* args[] = {const_cast<MlpArgs*>(&a)};
+    (void)hipLaunchKernel(kFwdKernels[kind][FWD_SIGMA_WINDOW], dim3((unsigned)blocks), dim3(256), args, lds, stream);
+    return check_launch("field_mlp_fwd_window");
 }
 
 }  // namespace mi

@@ -614,6 +614,35 @@ __device__ __forceinline__ PointIn load_point(int mode, const float* __restrict_
     return o;
 }
 
+// Windowed point source of the sigma-only forward: a tile is 128 >> win_log2 entries of the live list x one window of
+// samples [win_k0, win_k0 + 2^win_log2) of each.  `count` = live entries (uniform, > tile's first entry).  A point's
+// row stays ray * S + k and its inputs are mode 1's expressions, so its sigma does not depend on the tiling.
+__device__ __forceinline__ PointIn load_window_point(const MlpArgs& a, int64_t tile, int64_t count, int i) {
+    PointIn o;
+    const int S = a.n_samples;
+    const int64_t entry = tile * (128 >> a.win_log2) + (i >> a.win_log2);
+    const int k = a.win_k0 + (i & ((1 << a.win_log2) - 1));
+    o.valid = entry < count && k < S;
+    const int64_t ec = entry < count ? entry : count - 1;
+    const int64_t ray = a.live_rays ? (int64_t)a.live_rays[ec] : ec;
+    o.p = ray * S + (k < S ? k : S - 1);
+    const float* r = a.a + ray * 6;
+    const float zz = a.z[o.p];
+    const float d0 = r[3], d1 = r[4], d2 = r[5];
+    o.px = __fadd_rn(r[0], __fmul_rn(d0, zz));
+    o.py = __fadd_rn(r[1], __fmul_rn(d1, zz));
+    o.pz = __fadd_rn(r[2], __fmul_rn(d2, zz));
+    const float nrm = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(d0, d0), __fmul_rn(d1, d1)), __fmul_rn(d2, d2)));
+    o.dx = d0 / nrm; o.dy = d1 / nrm; o.dz = d2 / nrm;
+    return o;
+}
+
+// live entries of a windowed launch (block-uniform): the device count the previous window's composite left, or n_rays
+__device__ __forceinline__ int64_t window_live_count(const MlpArgs& a) {
+    if (!a.live_count) return a.n_rays;
+    return __builtin_amdgcn_readfirstlane(__hip_atomic_load(a.live_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+}
+
 __device__ __forceinline__ Ctx make_ctx_raw(float* smem, const float* packed, const float* film_group) {
     Ctx c;
     c.smem = smem;

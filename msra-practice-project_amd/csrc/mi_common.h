@@ -61,6 +61,12 @@ struct MlpArgs {
     int64_t save_points;    // points in this launch (row count of every saved region)
     unsigned long long* stamps;   // diagnostic build (-DMI_PROFILE_STAMPS) only: [block][128] s_memtime values
     int film_depth;         // FiLM kinds: hidden_layers (wave-uniform; the run-time-depth instances read it), else 0
+    // windowed sigma-only forward (launch_mlp_window): samples [win_k0, win_k0 + 2^win_log2) of the rays in a live list
+    const int* live_rays;   // [live count] ray indices, any order; null = rays 0..n_rays-1
+    const int* live_count;  // device count of live_rays; null = n_rays
+    int64_t n_rays;         // rays of the call (the worst-case live count the grid is sized for)
+    int win_k0;
+    int win_log2;
 };
 
 // In-kernel cycle stamps for the diagnostic build (csrc/build.py --profile -> gpurun_tools/libmirender_prof.so);
@@ -78,6 +84,9 @@ enum StreamDir : int { STREAM_FWD = 0, STREAM_BWD = 1 };
 // sigma_only: the kind's sigma-only instance (has_sigma_only_kernel), which writes sigma alone to a.out [M]
 int launch_mlp(int kind, const MlpArgs& a, int64_t n_groups, hipStream_t stream, bool sigma_only = false);
 bool has_sigma_only_kernel(int kind);
+// the sigma-only instance over a window of samples of the live rays (a.live_rays / a.live_count / a.n_rays / a.win_*;
+// a.a = rays, a.z and a.out [n_rays, n_samples]); the grid covers n_rays, blocks past the live count return at once
+int launch_mlp_window(int kind, const MlpArgs& a, hipStream_t stream);
 int64_t bwd_partial_floats(int64_t P);
 int64_t film_partial_floats(int64_t n_groups, int64_t points_per_group);
 int64_t bwd_partial_floats_kind(int kind, int64_t P);                      // ... of any kind (deeper FiLM kinds need more)
@@ -94,6 +103,12 @@ int launch_composite(int64_t n, int S, const float* raw, const float* z, const f
                      float* acc, float* weights, hipStream_t stream);
 int launch_composite_weights(int64_t n, int S, const float* sigma, int sigma_stride, const float* z, const float* rays,
                              float* depth, float* acc, float* weights, hipStream_t stream);
+// composite_weights over samples [0, k1) of the live rays, k1 > k0 the end of the window just evaluated: writes the weights
+// of [k0, k1), appends the rays that can still contribute behind k1 to live_out, finishes the others (zero weights behind
+// k1, depth / acc); live_out null = the last window, every ray is finished
+int launch_composite_weights_window(int64_t n, int S, const float* sigma, const float* z, const float* rays, float* depth,
+                                    float* acc, float* weights, const int* live_in, const int* count_in, int* live_out,
+                                    int* count_out, int k0, int k1, hipStream_t stream);
 int launch_composite_bwd(int64_t n, int S, const float* raw, const float* z, const float* rays, const float* g_rgb,
                          const float* g_depth, const float* g_acc, const float* g_w, float* g_raw, hipStream_t stream);
 int64_t image_metrics_workspace_floats(int images, int channels, int H, int W);

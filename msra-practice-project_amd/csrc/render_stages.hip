@@ -203,6 +203,94 @@ __global__ __launch_bounds__(256) void composite_weights_kernel(int64_t n, int S
     }
 }
 
+// composite_weights_kernel in resumable form, for a coarse pass evaluated front to back in windows of samples
+// (mi_render_rays): the call behind the window [k0, k1) runs composite_weights_kernel's passes over samples [0, k1) of
+// every live ray - the same G, the same scans, the same order, a sample >= k1 standing in as w = 0 - and writes the
+// weights of [k0, k1).  Then it decides the ray:
+//   * D, the fp64 running product in front of sample k1, is <= 2^-151: every later sample's (float)(T * excl) is 0.0f
+//     whatever its sigma is.  The factors f = (1-alpha)+1e-10f are <= 1 (sigma >= 0, ascending depths), so the exact
+//     product can only fall; the scans' products of <= 2G factors differ from the exact ones by a relative 2^-45 at most,
+//     far inside the factor 2 between 2^-151 and the largest double that still rounds to 0.0f, 2^-150.  Such a ray is
+//     FINISHED: zero weights behind k1, depth / acc from the sums so far - composite_weights_kernel adds w * z = 0 and
+//     w = 0 for those samples, which changes no bit of either sum.  Nothing behind k1 is read: no field evaluation there.
+//   * otherwise the ray goes to live_out for the next window (one atomic per block; the list's order is arbitrary and
+//     touches no output: a ray's results depend on its own samples alone).
+// live_out null = the last window (k1 = S): every ray is finished.  Blocks past the live count return at once.
+// Recomputing [0, k0) from the stored sigma instead of carrying T and the partial sums costs a few reads of a buffer
+// that the pass just wrote and keeps the partition of samples into scans trivially the one-pass kernel's.
+template <int G>
+__global__ __launch_bounds__(256) void composite_weights_window_kernel(
+    int64_t n, int S, const float* __restrict__ sigma, const float* __restrict__ z, const float* __restrict__ rays,
+    float* __restrict__ depth, float* __restrict__ acc, float* __restrict__ weights, const int* __restrict__ live_in,
+    const int* __restrict__ count_in, int* __restrict__ live_out, int* __restrict__ count_out, int k0, int k1) {
+    constexpr int kIter = 8;                          // entries per G-lane group: (256 / G) * kIter entries per block
+    constexpr int kPerBlock = 256 / G * kIter;
+    __shared__ int s_keep[kPerBlock];
+    __shared__ int s_n, s_base;
+    const int64_t count = count_in ? (int64_t)*count_in : n;
+    const int64_t first = (int64_t)blockIdx.x * kPerBlock;
+    if (first >= count) return;
+    if (threadIdx.x == 0) s_n = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int sub = lane & (G - 1);
+    for (int it = 0; it < kIter; ++it) {
+        const int64_t entry = first + (int64_t)it * (256 / G) + threadIdx.x / G;
+        const bool live = entry < count;
+        const int64_t rc = live ? (live_in ? (int64_t)live_in[entry] : entry) : 0;
+        const float* rd = rays + rc * 6 + 3;
+        const float nrm = sqrtf((rd[0] * rd[0] + rd[1] * rd[1]) + rd[2] * rd[2]);
+        double T = 1.0, D = 1.0;
+        float sd = 0.f, sa = 0.f;
+        for (int kk = 0; kk < k1; kk += G) {
+            const int k = kk + sub;
+            const bool in = k < k1;
+            const int kc = in ? k : k1 - 1;
+            const float sg = sigma[rc * S + kc];
+            const float zk = z[rc * S + kc];
+            const float zn = kc + 1 < S ? z[rc * S + kc + 1] : 0.f;
+            float delta = kc + 1 < S ? zn - zk : 1e10f;
+            delta = delta * nrm;
+            const float alpha = in ? 1.0f - expf(-sg * delta) : 0.f;
+            const float f = in ? (1.0f - alpha) + 1e-10f : 1.f;
+            double p = (double)f;                               // composite_kernel's fp64 product scan
+#pragma unroll
+            for (int o = 1; o < G; o <<= 1) {
+                const double q = __shfl_up(p, o, G);
+                if (sub >= o) p *= q;
+            }
+            double excl = __shfl_up(p, 1, G);
+            if (sub == 0) excl = 1.0;
+            const float w = alpha * (float)(T * excl);
+            if (kk + G >= k1) D = T * __shfl(p, k1 - 1 - kk, G);     // the product in front of sample k1
+            T = T * __shfl(p, G - 1, G);
+            if (in) {
+                sd += w * zk; sa += w;
+                if (live && k >= k0) weights[rc * S + k] = w;
+            }
+        }
+        const bool done = !live_out || D <= 0x1p-151;
+        if (live && !done && sub == 0) s_keep[atomicAdd(&s_n, 1)] = (int)rc;
+        if (live && done)
+            for (int k = k1 + sub; k < S; k += G) weights[rc * S + k] = 0.f;
+        if (done && (depth || acc)) {
+#pragma unroll
+            for (int o = G / 2; o > 0; o >>= 1) {
+                sd += __shfl_xor(sd, o, G); sa += __shfl_xor(sa, o, G);
+            }
+            if (live && sub == 0) {
+                if (depth) depth[rc] = sd;
+                if (acc) acc[rc] = sa;
+            }
+        }
+    }
+    if (!live_out) return;
+    __syncthreads();
+    if (threadIdx.x == 0) s_base = s_n ? atomicAdd(count_out, s_n) : 0;
+    __syncthreads();
+    for (int i = threadIdx.x; i < s_n; i += 256) live_out[s_base + i] = s_keep[i];
+}
+
 // ---------------------------------------------------------------------------------------
 // composite backward (autograd of raw_to_outputs, render.py:91-101): G lanes per ray, lane = sample.
 //   Gk = sum_c g_rgb[c]*(c_k[c]-1) + g_depth*z_k + g_acc        (dL/dw_k; rgb carries +1-acc)
@@ -562,6 +650,25 @@ int launch_composite_weights(int64_t n, int S, const float* sigma, int sigma_str
                            sigma_stride, z, rays, depth, acc, weights);
     }
     return check_launch("composite_weights");
+}
+
+int launch_composite_weights_window(int64_t n, int S, const float* sigma, const float* z, const float* rays, float* depth,
+                                    float* acc, float* weights, const int* live_in, const int* count_in, int* live_out,
+                                    int* count_out, int k0, int k1, hipStream_t stream) {
+    if (n <= 0) return 0;
+    // the G of launch_composite_weights for this S: the scans must see its partition of the samples
+    // grid: the worst case, every ray live; (256 / G) * 8 entries per block
+    if (S > 32) {
+        hipLaunchKernelGGL(composite_weights_window_kernel<64>, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, stream, n, S,
+                           sigma, z, rays, depth, acc, weights, live_in, count_in, live_out, count_out, k0, k1);
+    } else if (S > 16) {
+        hipLaunchKernelGGL(composite_weights_window_kernel<32>, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, stream, n, S,
+                           sigma, z, rays, depth, acc, weights, live_in, count_in, live_out, count_out, k0, k1);
+    } else {
+        hipLaunchKernelGGL(composite_weights_window_kernel<16>, dim3((unsigned)((n + 127) / 128)), dim3(256), 0, stream, n, S,
+                           sigma, z, rays, depth, acc, weights, live_in, count_in, live_out, count_out, k0, k1);
+    }
+    return check_launch("composite_weights_window");
 }
 
 int launch_composite_bwd(int64_t n, int S, const float* raw, const float* z, const float* rays, const float* g_rgb,
