@@ -33,6 +33,18 @@ int check_launch(const char* what) {
     return MI_OK;
 }
 
+int copy_render_outputs(const char* fn, int64_t n, float* rgb_dst, float* depth_dst, float* acc_dst, const float* rgb_src,
+                        const float* depth_src, const float* acc_src, hipStream_t stream) {
+    const struct { float* dst; const float* src; int64_t floats; } copies[3] = {
+        {rgb_dst, rgb_src, n * 3}, {depth_dst, depth_src, n}, {acc_dst, acc_src, n}};
+    for (const auto& c : copies)
+        if (c.dst && hipMemcpyAsync(c.dst, c.src, c.floats * sizeof(float), hipMemcpyDeviceToDevice, stream) != hipSuccess) {
+            set_error("%s: output alias copy failed", fn);
+            return MI_EHIP;
+        }
+    return MI_OK;
+}
+
 const FieldKind& field_kind(int kind) {
     if (is_fixed_kind(kind)) return kFieldKinds[kind];
     struct DepthKinds {
@@ -241,20 +253,11 @@ int mi_sample_pdf(int64_t n, int n_bins, int n_samples, const float* bins, const
 }
 
 int64_t mi_render_workspace_bytes(int64_t n, int n_coarse, int n_fine) {
-    const int64_t S = (int64_t)n_coarse + n_fine;
-    // z_c[n,Nc] raw_c[n,Nc,4] w_c[n,Nc] z_f[n,S] raw_f[n,S,4]; each region 256-byte aligned
-    int64_t f = 0;
-    auto add = [&](int64_t x) { f += (x + 63) / 64 * 64; };
-    add(n * n_coarse); add(n * n_coarse * 4); add(n * n_coarse); add(n * S); add(n * S * 4);
-    return f * (int64_t)sizeof(float);
+    return RenderWorkspace(n, n_coarse, n_fine).base_bytes();
 }
 
 int64_t mi_render_shared_field_extra_bytes(int64_t n, int n_coarse, int n_fine) {
-    // z_samples[n,Nf] raw_samples[n,Nf,4] pos[n,Nc+Nf] behind the regions of mi_render_workspace_bytes
-    int64_t f = 0;
-    auto add = [&](int64_t x) { f += (x + 63) / 64 * 64; };
-    add(n * n_fine); add(n * n_fine * 4); add(n * ((int64_t)n_coarse + n_fine));
-    return f * (int64_t)sizeof(float);
+    return RenderWorkspace(n, n_coarse, n_fine).shared_extra_bytes();
 }
 
 int mi_render_rays(int kind_coarse, const float* packed_coarse, int kind_fine, const float* packed_fine,
@@ -272,19 +275,15 @@ int mi_render_rays(int kind_coarse, const float* packed_coarse, int kind_fine, c
     }
     const int64_t n = n_groups * rays_per_group;
     const int S = n_coarse + n_fine;
-    const int64_t base_bytes = mi_render_workspace_bytes(n, n_coarse, n_fine);
+    const RenderWorkspace layout(n, n_coarse, n_fine);
+    const int64_t base_bytes = layout.base_bytes();
     if (workspace_bytes < base_bytes) {
         set_error("mi_render_rays: workspace of %lld bytes, mi_render_workspace_bytes says %lld", (long long)workspace_bytes,
                   (long long)base_bytes);
         return MI_EINVAL;
     }
-    float* ws = (float*)workspace;
-    auto take = [&](int64_t x) { float* p = ws; ws += (x + 63) / 64 * 64; return p; };
-    float* z_c = take(n * n_coarse);
-    float* raw_c = take(n * n_coarse * 4);
-    float* w_c = take(n * n_coarse);
-    float* z_f = take(n * (int64_t)S);
-    float* raw_f = take(n * (int64_t)S * 4);
+    const RenderWorkspace::Regions ws = layout.carve(workspace);
+    float *z_c = ws.z_c, *raw_c = ws.raw_c, *w_c = ws.w_c, *z_f = ws.z_f, *raw_f = ws.raw_f;
     const bool shared = kind_fine == kind_coarse && packed_fine == packed_coarse;
     // Without the coarse colours and with a coarse field of its own, the coarse pass only feeds sample_fine its weights,
     // which depend on sigma alone: the sigma-only forward writes sigma [n,Nc] compactly at the start of raw_c's region.
@@ -314,27 +313,19 @@ int mi_render_rays(int kind_coarse, const float* packed_coarse, int kind_fine, c
         // re-evaluate identical inputs: the coarse pass's composite IS the fine outputs, and the coarse
         // outputs asked for are copies of them.
         if ((rc = mi_composite(n, n_coarse, raw_c, z_c, rays, rgb_f, depth_f, acc_f, w_c, stream))) return rc;
-        const struct { float* dst; const float* src; int64_t floats; } alias[3] = {
-            {rgb_c, rgb_f, n * 3}, {depth_c, depth_f, n}, {acc_c, acc_f, n}};
-        for (const auto& c : alias)
-            if (c.dst && hipMemcpyAsync(c.dst, c.src, c.floats * sizeof(float), hipMemcpyDeviceToDevice, hs) != hipSuccess) {
-                set_error("mi_render_rays: output alias copy failed");
-                return MI_EHIP;
-            }
-        return MI_OK;
+        return copy_render_outputs("mi_render_rays", n, rgb_c, depth_c, acc_c, rgb_f, depth_f, acc_f, hs);
     }
     if (rgb_c) rc = mi_composite(n, n_coarse, raw_c, z_c, rays, rgb_c, depth_c, acc_c, w_c, stream);
     else if (windowed) rc = MI_OK;                                   // coarse_sigma_windows wrote w_c / depth_c / acc_c
     else if (sigma_only) rc = launch_composite_weights(n, n_coarse, raw_c, 1, z_c, rays, depth_c, acc_c, w_c, hs);
     else rc = launch_composite_weights(n, n_coarse, raw_c + 3, 4, z_c, rays, depth_c, acc_c, w_c, hs);     // raw's sigma channel
     if (rc) return rc;
-    if (shared && workspace_bytes >= base_bytes + mi_render_shared_field_extra_bytes(n, n_coarse, n_fine)) {
+    if (shared && workspace_bytes >= base_bytes + layout.shared_extra_bytes()) {
         // One field for both passes: Nc of the fine pass's Nc + Nf points are the coarse pass's points - evaluate the Nf
         // new ones only and merge (render_stages.hip: merge_raw_kernel).  Needs the extra workspace regions; a caller
         // that did not provide them gets the plain path below (same results).
-        float* z_s = take(n * n_fine);
-        float* raw_s = take(n * (int64_t)n_fine * 4);
-        int* pos = (int*)take(n * (int64_t)S);
+        float *z_s = ws.z_s, *raw_s = ws.raw_s;
+        int* pos = ws.pos;
         if ((rc = mi_sample_fine_pos(n, near_, far_, n_coarse, n_fine, z_lin, u_lin, z_c, w_c, z_s, z_f, pos, stream))) return rc;
         if (g_mlp_ev[2]) (void)hipEventRecord(g_mlp_ev[2], hs);
         if ((rc = mi_field_eval_rays(kind_fine, packed_fine, film, rays, z_s, n_groups, rays_per_group, n_fine, raw_s, stream)))

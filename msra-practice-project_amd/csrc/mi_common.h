@@ -23,6 +23,9 @@ __device__ __forceinline__ void static_for(F&& f) {
 // error plumbing for the C ABI (api.hip)
 void set_error(const char* fmt, ...);
 int check_launch(const char* what);
+// one field with Nf = 0: the fine outputs and the coarse outputs are one composite's; copies it to every non-null dst
+int copy_render_outputs(const char* fn, int64_t n, float* rgb_dst, float* depth_dst, float* acc_dst, const float* rgb_src,
+                        const float* depth_src, const float* acc_src, hipStream_t stream);
 
 // hipFuncSetAttribute configures the CURRENT device's copy of a kernel, so "once" means once per device ordinal:
 // a process that drives several GPUs (DataParallel's thread per replica, pi_GAN/train.py:50) sets it on each.
@@ -42,6 +45,38 @@ public:
         const int rc = f();
         if (rc == 0) done_[dev >> 6].fetch_or(bit, std::memory_order_release);
         return rc;
+    }
+};
+
+// floats rounded up to whole 64-float (256-byte) blocks: every workspace region starts on one
+constexpr int64_t align64(int64_t x) { return (x + 63) / 64 * 64; }
+
+// The workspace of mi_render_rays / mi_render_rays_train for n rays of Nc + Nf samples: the five regions of
+// mi_render_workspace_bytes, then the three that one field for both passes adds (mi_render_shared_field_extra_bytes).
+struct RenderWorkspace {
+    struct Regions {
+        float *z_c, *raw_c, *w_c, *z_f, *raw_f;       // [n,Nc] [n,Nc,4] [n,Nc] [n,S] [n,S,4]
+        float *z_s, *raw_s;                           // [n,Nf] [n,Nf,4]
+        int* pos;                                     // [n,S]
+    };
+    static constexpr int kBase = 5, kAll = 8;
+    int64_t floats[kAll];
+    RenderWorkspace(int64_t n, int nc, int nf)
+        : floats{n * nc, n * nc * 4, n * nc, n * ((int64_t)nc + nf), n * ((int64_t)nc + nf) * 4,
+                 n * nf, n * nf * 4, n * ((int64_t)nc + nf)} {}
+    int64_t bytes(int first, int last) const {
+        int64_t f = 0;
+        for (int i = first; i < last; ++i) f += align64(floats[i]);
+        return f * (int64_t)sizeof(float);
+    }
+    int64_t base_bytes() const { return bytes(0, kBase); }
+    int64_t shared_extra_bytes() const { return bytes(kBase, kAll); }
+    // the shared-field regions lie behind base_bytes(): theirs to use only in a workspace that holds them
+    Regions carve(void* base) const {
+        float* p[kAll];
+        float* ws = (float*)base;
+        for (int i = 0; i < kAll; ++i) { p[i] = ws; ws += align64(floats[i]); }
+        return {p[0], p[1], p[2], p[3], p[4], p[5], p[6], (int*)p[7]};
     }
 };
 

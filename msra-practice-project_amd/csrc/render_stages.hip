@@ -4,7 +4,14 @@
 //   sample_coarse_kernel  stratified depths              nerf/render.py:123-132
 //   composite_kernel      raw_to_outputs                 nerf/render.py:78-103
 //   composite_weights_kernel  its weights (+ depth / acc) from sigma alone, for a coarse pass whose colours are discarded
+//   composite_weights_window_kernel  the same, resumable window by window
+//   composite_bwd_kernel  autograd of raw_to_outputs
 //   sample_fine_kernel    sample_pdf + detach/cat/sort   nerf/render.py:27-56, 140-142
+//   sample_pdf_kernel     sample_pdf alone
+//
+// Each computation is stated once: every compositing kernel takes its weights and transmittances from composite_pass
+// (with sample_delta and ray_norm) under the G that dispatch_G picks, and both sampling kernels draw through
+// normalise_pdf and draw_inverse_cdf.
 //
 // All arithmetic is fp32 in the reference's operation order (this file is compiled with
 // -ffp-contract=off so a*b+c stays two roundings like the un-fused torch/NumPy ops).
@@ -87,144 +94,141 @@ __global__ void sample_coarse_kernel(int64_t n, float near_, float far_, int nc,
 }
 
 // ---------------------------------------------------------------------------------------
-// composite: G lanes per ray (G = 16/32/64), lane = sample, passes of G samples with the
-// transmittance carried between passes.  alpha = 1-exp(-sigma*delta*|d|),
-// T = exclusive prod(1-alpha+1e-10), w = alpha*T; rgb = sum w c + (1-acc) (white background).
+// composite (raw_to_outputs): G lanes per ray (G = 16/32/64), lane = sample, passes of G samples with the transmittance
+// carried between passes.  alpha = 1-exp(-sigma*delta*|d|), T = exclusive prod(1-alpha+1e-10), w = alpha*T;
+// rgb = sum w c + (1-acc) (white background).  Every kernel that needs weights or transmittances - the two one-pass
+// forwards, the windowed forward, sweep 1 of the backward - gets them from composite_pass below and from nowhere else,
+// so they all hold the same bits for the same samples under the same G.
 // ---------------------------------------------------------------------------------------
+__device__ __forceinline__ float ray_norm(const float* rays, int64_t ray) {
+    const float* rd = rays + ray * 6 + 3;
+    return sqrtf((rd[0] * rd[0] + rd[1] * rd[1]) + rd[2] * rd[2]);
+}
+
+// delta * |d| of sample kc of a ray's S depths, zp = the address of its own depth: the distance to the next sample,
+// "infinity" behind the last one
+__device__ __forceinline__ float sample_delta(const float* zp, int S, int kc, float nrm) {
+    const float zk = zp[0];
+    const float zn = kc + 1 < S ? zp[1] : 0.f;
+    const float delta = kc + 1 < S ? zn - zk : 1e10f;
+    return delta * nrm;
+}
+
+struct PassOut {
+    float w;        // alpha * trans
+    float trans;    // the transmittance in front of the sample, (float)(T * exclusive product)
+    double p;       // inclusive product of the pass's factors up to this lane; lane G-1 holds the whole pass's
+};
+
+// One pass of G samples, lane `sub` holding one (in = false: a lane past the row's end, the factor 1 and w = 0), T the
+// product of all earlier passes.  The running product is kept in fp64 and rounded to fp32 per sample, as ATen's CPU
+// cumprod does (accumulate type of float is double).  The caller carries T = T * __shfl(p, G - 1, G).
 template <int G>
-__global__ __launch_bounds__(256) void composite_kernel(int64_t n, int S, const float* __restrict__ raw,
-                                                        const float* __restrict__ z, const float* __restrict__ rays,
-                                                        float* __restrict__ rgb, float* __restrict__ depth,
-                                                        float* __restrict__ acc, float* __restrict__ weights) {
+__device__ __forceinline__ PassOut composite_pass(int sub, bool in, float sigma, float delta, double T) {
+    const float alpha = in ? 1.0f - expf(-sigma * delta) : 0.f;
+    const float f = in ? (1.0f - alpha) + 1e-10f : 1.f;
+    double p = (double)f;
+#pragma unroll
+    for (int o = 1; o < G; o <<= 1) {
+        const double q = __shfl_up(p, o, G);
+        if (sub >= o) p *= q;
+    }
+    double excl = __shfl_up(p, 1, G);
+    if (sub == 0) excl = 1.0;
+    const float trans = (float)(T * excl);
+    return {alpha * trans, trans, p};
+}
+
+// The one-pass forward.  kColour: src = raw [n,S,4], all five sums, rgb / depth / acc written, weights when non-null.
+// Otherwise the coarse pass of a renderer that discards the coarse colours: only sigma is read (element e at
+// src[e * sigma_stride]: a compact [n,S] buffer with stride 1, or the sigma channel of raw with raw + 3 and stride 4),
+// the weights [n,S] are written, depth / acc only when non-null (the colour sums it drops are sums of their own).
+template <int G, bool kColour>
+__device__ __forceinline__ void composite_rows(int64_t n, int S, const float* src, int sigma_stride,
+                                               const float* z, const float* rays,
+                                               float* rgb, float* depth,
+                                               float* acc, float* weights) {
     const int lane = threadIdx.x & 63;
     const int sub = lane & (G - 1);
     const int64_t groups_per_block = 256 / G;
     const int64_t ray = (int64_t)blockIdx.x * groups_per_block + threadIdx.x / G;
     const bool live = ray < n;
     const int64_t rc = live ? ray : n - 1;
-    const float* rd = rays + rc * 6 + 3;
-    const float nrm = sqrtf((rd[0] * rd[0] + rd[1] * rd[1]) + rd[2] * rd[2]);
+    const float nrm = ray_norm(rays, rc);
     double T = 1.0;
     float sr = 0.f, sg = 0.f, sb = 0.f, sd = 0.f, sa = 0.f;
     for (int k0 = 0; k0 < S; k0 += G) {
         const int k = k0 + sub;
         const bool in = k < S;
         const int kc = in ? k : S - 1;
-        const float4 c = reinterpret_cast<const float4*>(raw)[rc * S + kc];
-        const float zk = z[rc * S + kc];
-        const float zn = kc + 1 < S ? z[rc * S + kc + 1] : 0.f;
-        float delta = kc + 1 < S ? zn - zk : 1e10f;
-        delta = delta * nrm;
-        const float alpha = in ? 1.0f - expf(-c.w * delta) : 0.f;
-        const float f = in ? (1.0f - alpha) + 1e-10f : 1.f;
-        // inclusive product scan inside the G-lane group.  The running product is kept in fp64 and
-        // rounded to fp32 per sample, as ATen's CPU cumprod does (accumulate type of float is double).
-        double p = (double)f;
-#pragma unroll
-        for (int o = 1; o < G; o <<= 1) {
-            const double q = __shfl_up(p, o, G);
-            if (sub >= o) p *= q;
-        }
-        double excl = __shfl_up(p, 1, G);
-        if (sub == 0) excl = 1.0;
-        const float w = alpha * (float)(T * excl);
-        T = T * __shfl(p, G - 1, G);
+        float4 c;
+        if constexpr (kColour) c = reinterpret_cast<const float4*>(src)[rc * S + kc];
+        else c.w = src[(rc * S + kc) * sigma_stride];
+        const float* zp = z + (rc * S + kc);
+        const float zk = *zp;
+        const PassOut o = composite_pass<G>(sub, in, c.w, sample_delta(zp, S, kc, nrm), T);
+        T = T * __shfl(o.p, G - 1, G);
         if (in) {
-            sr += w * c.x; sg += w * c.y; sb += w * c.z; sd += w * zk; sa += w;
-            if (weights && live) weights[rc * S + k] = w;
+            if constexpr (kColour) { sr += o.w * c.x; sg += o.w * c.y; sb += o.w * c.z; }
+            sd += o.w * zk; sa += o.w;
+            if ((!kColour || weights) && live) weights[rc * S + k] = o.w;
         }
     }
+    if (!kColour && !depth && !acc) return;
 #pragma unroll
     for (int o = G / 2; o > 0; o >>= 1) {
-        sr += __shfl_xor(sr, o, G); sg += __shfl_xor(sg, o, G); sb += __shfl_xor(sb, o, G);
+        if constexpr (kColour) { sr += __shfl_xor(sr, o, G); sg += __shfl_xor(sg, o, G); sb += __shfl_xor(sb, o, G); }
         sd += __shfl_xor(sd, o, G); sa += __shfl_xor(sa, o, G);
     }
     if (live && sub == 0) {
-        const float bg = 1.0f - sa;
-        rgb[ray * 3 + 0] = sr + bg; rgb[ray * 3 + 1] = sg + bg; rgb[ray * 3 + 2] = sb + bg;
-        depth[ray] = sd;
-        acc[ray] = sa;
+        if constexpr (kColour) {
+            const float bg = 1.0f - sa;
+            rgb[ray * 3 + 0] = sr + bg; rgb[ray * 3 + 1] = sg + bg; rgb[ray * 3 + 2] = sb + bg;
+        }
+        if (kColour || depth) depth[ray] = sd;
+        if (kColour || acc) acc[ray] = sa;
     }
 }
 
-// The coarse pass of a renderer that discards the coarse colours: only sigma is read (element e at
-// sigma[e * sigma_stride]: a compact [n,S] buffer with stride 1, or the sigma channel of raw [n,S,4] with raw + 3 and
-// stride 4), the weights [n,S] are written, depth / acc only when non-null.  Same weights, depth and acc bits as
-// composite_kernel: its operations in its order (the colour sums it drops are sums of their own).
+// the two forms under the names kernel traces know them by
+template <int G>
+__global__ __launch_bounds__(256) void composite_kernel(int64_t n, int S, const float* __restrict__ raw,
+                                                        const float* __restrict__ z, const float* __restrict__ rays,
+                                                        float* __restrict__ rgb, float* __restrict__ depth,
+                                                        float* __restrict__ acc, float* __restrict__ weights) {
+    composite_rows<G, true>(n, S, raw, 4, z, rays, rgb, depth, acc, weights);
+}
+
 template <int G>
 __global__ __launch_bounds__(256) void composite_weights_kernel(int64_t n, int S, const float* __restrict__ sigma,
                                                                 int sigma_stride, const float* __restrict__ z,
                                                                 const float* __restrict__ rays, float* __restrict__ depth,
                                                                 float* __restrict__ acc, float* __restrict__ weights) {
-    const int lane = threadIdx.x & 63;
-    const int sub = lane & (G - 1);
-    const int64_t groups_per_block = 256 / G;
-    const int64_t ray = (int64_t)blockIdx.x * groups_per_block + threadIdx.x / G;
-    const bool live = ray < n;
-    const int64_t rc = live ? ray : n - 1;
-    const float* rd = rays + rc * 6 + 3;
-    const float nrm = sqrtf((rd[0] * rd[0] + rd[1] * rd[1]) + rd[2] * rd[2]);
-    double T = 1.0;
-    float sd = 0.f, sa = 0.f;
-    for (int k0 = 0; k0 < S; k0 += G) {
-        const int k = k0 + sub;
-        const bool in = k < S;
-        const int kc = in ? k : S - 1;
-        const float sg = sigma[(rc * S + kc) * sigma_stride];
-        const float zk = z[rc * S + kc];
-        const float zn = kc + 1 < S ? z[rc * S + kc + 1] : 0.f;
-        float delta = kc + 1 < S ? zn - zk : 1e10f;
-        delta = delta * nrm;
-        const float alpha = in ? 1.0f - expf(-sg * delta) : 0.f;
-        const float f = in ? (1.0f - alpha) + 1e-10f : 1.f;
-        double p = (double)f;                               // composite_kernel's fp64 product scan
-#pragma unroll
-        for (int o = 1; o < G; o <<= 1) {
-            const double q = __shfl_up(p, o, G);
-            if (sub >= o) p *= q;
-        }
-        double excl = __shfl_up(p, 1, G);
-        if (sub == 0) excl = 1.0;
-        const float w = alpha * (float)(T * excl);
-        T = T * __shfl(p, G - 1, G);
-        if (in) {
-            sd += w * zk; sa += w;
-            if (live) weights[rc * S + k] = w;
-        }
-    }
-    if (!depth && !acc) return;
-#pragma unroll
-    for (int o = G / 2; o > 0; o >>= 1) {
-        sd += __shfl_xor(sd, o, G); sa += __shfl_xor(sa, o, G);
-    }
-    if (live && sub == 0) {
-        if (depth) depth[ray] = sd;
-        if (acc) acc[ray] = sa;
-    }
+    composite_rows<G, false>(n, S, sigma, sigma_stride, z, rays, nullptr, depth, acc, weights);
 }
 
-// composite_weights_kernel in resumable form, for a coarse pass evaluated front to back in windows of samples
-// (mi_render_rays): the call behind the window [k0, k1) runs composite_weights_kernel's passes over samples [0, k1) of
-// every live ray - the same G, the same scans, the same order, a sample >= k1 standing in as w = 0 - and writes the
-// weights of [k0, k1).  Then it decides the ray:
+// The weights form made resumable, for a coarse pass evaluated front to back in windows of samples (mi_render_rays): the
+// call behind the window [k0, k1) runs the passes over samples [0, k1) of every live ray under dispatch_G's G for S, a
+// sample >= k1 standing in as w = 0, and writes the weights of [k0, k1).  Then it decides the ray:
 //   * D, the fp64 running product in front of sample k1, is <= 2^-151: every later sample's (float)(T * excl) is 0.0f
 //     whatever its sigma is.  The factors f = (1-alpha)+1e-10f are <= 1 (sigma >= 0, ascending depths), so the exact
 //     product can only fall; the scans' products of <= 2G factors differ from the exact ones by a relative 2^-45 at most,
 //     far inside the factor 2 between 2^-151 and the largest double that still rounds to 0.0f, 2^-150.  Such a ray is
-//     FINISHED: zero weights behind k1, depth / acc from the sums so far - composite_weights_kernel adds w * z = 0 and
+//     FINISHED: zero weights behind k1, depth / acc from the sums so far - the one-pass kernel adds w * z = 0 and
 //     w = 0 for those samples, which changes no bit of either sum.  Nothing behind k1 is read: no field evaluation there.
 //   * otherwise the ray goes to live_out for the next window (one atomic per block; the list's order is arbitrary and
 //     touches no output: a ray's results depend on its own samples alone).
 // live_out null = the last window (k1 = S): every ray is finished.  Blocks past the live count return at once.
 // Recomputing [0, k0) from the stored sigma instead of carrying T and the partial sums costs a few reads of a buffer
-// that the pass just wrote and keeps the partition of samples into scans trivially the one-pass kernel's.
+// that the pass just wrote and keeps the partition of samples into passes the one-pass kernel's.
+constexpr int kWindowIter = 8;                        // entries per G-lane group: (256 / G) * kWindowIter entries per block
+
 template <int G>
 __global__ __launch_bounds__(256) void composite_weights_window_kernel(
     int64_t n, int S, const float* __restrict__ sigma, const float* __restrict__ z, const float* __restrict__ rays,
     float* __restrict__ depth, float* __restrict__ acc, float* __restrict__ weights, const int* __restrict__ live_in,
     const int* __restrict__ count_in, int* __restrict__ live_out, int* __restrict__ count_out, int k0, int k1) {
-    constexpr int kIter = 8;                          // entries per G-lane group: (256 / G) * kIter entries per block
-    constexpr int kPerBlock = 256 / G * kIter;
+    constexpr int kPerBlock = 256 / G * kWindowIter;
     __shared__ int s_keep[kPerBlock];
     __shared__ int s_n, s_base;
     const int64_t count = count_in ? (int64_t)*count_in : n;
@@ -234,12 +238,11 @@ __global__ __launch_bounds__(256) void composite_weights_window_kernel(
     __syncthreads();
     const int lane = threadIdx.x & 63;
     const int sub = lane & (G - 1);
-    for (int it = 0; it < kIter; ++it) {
+    for (int it = 0; it < kWindowIter; ++it) {
         const int64_t entry = first + (int64_t)it * (256 / G) + threadIdx.x / G;
         const bool live = entry < count;
         const int64_t rc = live ? (live_in ? (int64_t)live_in[entry] : entry) : 0;
-        const float* rd = rays + rc * 6 + 3;
-        const float nrm = sqrtf((rd[0] * rd[0] + rd[1] * rd[1]) + rd[2] * rd[2]);
+        const float nrm = ray_norm(rays, rc);
         double T = 1.0, D = 1.0;
         float sd = 0.f, sa = 0.f;
         for (int kk = 0; kk < k1; kk += G) {
@@ -248,25 +251,12 @@ __global__ __launch_bounds__(256) void composite_weights_window_kernel(
             const int kc = in ? k : k1 - 1;
             const float sg = sigma[rc * S + kc];
             const float zk = z[rc * S + kc];
-            const float zn = kc + 1 < S ? z[rc * S + kc + 1] : 0.f;
-            float delta = kc + 1 < S ? zn - zk : 1e10f;
-            delta = delta * nrm;
-            const float alpha = in ? 1.0f - expf(-sg * delta) : 0.f;
-            const float f = in ? (1.0f - alpha) + 1e-10f : 1.f;
-            double p = (double)f;                               // composite_kernel's fp64 product scan
-#pragma unroll
-            for (int o = 1; o < G; o <<= 1) {
-                const double q = __shfl_up(p, o, G);
-                if (sub >= o) p *= q;
-            }
-            double excl = __shfl_up(p, 1, G);
-            if (sub == 0) excl = 1.0;
-            const float w = alpha * (float)(T * excl);
-            if (kk + G >= k1) D = T * __shfl(p, k1 - 1 - kk, G);     // the product in front of sample k1
-            T = T * __shfl(p, G - 1, G);
+            const PassOut o = composite_pass<G>(sub, in, sg, sample_delta(z + (rc * S + kc), S, kc, nrm), T);
+            if (kk + G >= k1) D = T * __shfl(o.p, k1 - 1 - kk, G);     // the product in front of sample k1
+            T = T * __shfl(o.p, G - 1, G);
             if (in) {
-                sd += w * zk; sa += w;
-                if (live && k >= k0) weights[rc * S + k] = w;
+                sd += o.w * zk; sa += o.w;
+                if (live && k >= k0) weights[rc * S + k] = o.w;
             }
         }
         const bool done = !live_out || D <= 0x1p-151;
@@ -298,9 +288,9 @@ __global__ __launch_bounds__(256) void composite_weights_window_kernel(
 //                 division-free first-order recurrence R_k = Gk alpha_k + f_k R_{k+1}
 //   dL/dsigma_k = dL/dalpha_k * delta_k * (1-alpha_k);   dL/dc_k = g_rgb * w_k
 // f_k = 1-alpha_k+1e-10.  z and rays carry no gradient (z_samples is detached, render.py:141).
-// Sweep 1 (passes of G samples, front to back): the transmittance T_k as in composite_kernel (fp64 product
-// scan), parked in the output's .w slot.  Sweep 2 (back to front): R by a reverse scan of the affine maps
-// (f_k, Gk alpha_k) inside the pass, carried between passes.
+// Sweep 1 (passes of G samples, front to back): the forward's transmittance T_k (composite_pass), parked in the
+// output's .w slot.  Sweep 2 (back to front): R by a reverse scan of the affine maps (f_k, Gk alpha_k) inside the
+// pass, carried between passes.
 // ---------------------------------------------------------------------------------------
 template <int G>
 __global__ __launch_bounds__(256) void composite_bwd_kernel(int64_t n, int S, const float* __restrict__ raw,
@@ -316,8 +306,7 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(int64_t n, int S, co
     const int64_t ray = (int64_t)blockIdx.x * (256 / G) + threadIdx.x / G;
     const bool live = ray < n;
     const int64_t rc = live ? ray : n - 1;
-    const float* rd = rays + rc * 6 + 3;
-    const float nrm = sqrtf((rd[0] * rd[0] + rd[1] * rd[1]) + rd[2] * rd[2]);
+    const float nrm = ray_norm(rays, rc);
     const float gr = g_rgb ? g_rgb[rc * 3 + 0] : 0.f, gg = g_rgb ? g_rgb[rc * 3 + 1] : 0.f,
                 gb = g_rgb ? g_rgb[rc * 3 + 2] : 0.f;
     const float gd = g_depth ? g_depth[rc] : 0.f, ga = g_acc ? g_acc[rc] : 0.f;
@@ -330,18 +319,9 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(int64_t n, int S, co
         const int k = pass * G + sub;
         const bool in = k < S;
         const int kc = in ? k : S - 1;
-        const float delta = (kc + 1 < S ? zr[kc + 1] - zr[kc] : 1e10f) * nrm;
-        const float alpha = in ? 1.0f - expf(-rw[kc].w * delta) : 0.f;
-        double p = in ? (double)((1.0f - alpha) + 1e-10f) : 1.0;
-#pragma unroll
-        for (int o = 1; o < G; o <<= 1) {
-            const double q = __shfl_up(p, o, G);
-            if (sub >= o) p *= q;
-        }
-        double excl = __shfl_up(p, 1, G);
-        if (sub == 0) excl = 1.0;
-        if (in && live) out[k].w = (float)(T * excl);
-        T = T * __shfl(p, G - 1, G);
+        const PassOut o = composite_pass<G>(sub, in, rw[kc].w, sample_delta(zr + kc, S, kc, nrm), T);
+        if (in && live) out[k].w = o.trans;
+        T = T * __shfl(o.p, G - 1, G);
     }
     float carry = 0.f;                                   // R at the first sample of the pass behind this one
     for (int pass = passes - 1; pass >= 0; --pass) {
@@ -350,7 +330,7 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(int64_t n, int S, co
         const int kc = in ? k : S - 1;
         const float4 c = rw[kc];
         const float zk = zr[kc];
-        const float delta = (kc + 1 < S ? zr[kc + 1] - zk : 1e10f) * nrm;
+        const float delta = sample_delta(zr + kc, S, kc, nrm);
         const float e = expf(-c.w * delta);
         const float alpha = 1.0f - e;
         const float Tk = in && live ? out[kc].w : 0.f;
@@ -433,9 +413,39 @@ __device__ __forceinline__ uint64_t sort_key(float v, int i) {
 }
 
 // ---------------------------------------------------------------------------------------
+// The inverse-CDF draw of sample_pdf (render.py:27-56), one wave per ray, in two parts around cdf_like_cumsum.
+// pdf[j] = (w[j] + 1e-5) / sum_j (w[j] + 1e-5), j < nw: strided partial sums, xor reduction, one division per entry.
+// ---------------------------------------------------------------------------------------
+__device__ __forceinline__ void normalise_pdf(const float* __restrict__ w, int nw, int lane, float* pdf) {
+    float part = 0.f;
+    for (int j = lane; j < nw; j += 64) part += w[j] + 1e-5f;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
+    for (int j = lane; j < nw; j += 64) pdf[j] = (w[j] + 1e-5f) / part;
+}
+
+// the sample at u: idx = #(cdf <= u) (searchsorted right=True on the ascending cdf [nb]), both neighbours clamped into
+// the table, a cdf step below 1e-5 replaced by 1, then the lerp between the two bins
+__device__ __forceinline__ float draw_inverse_cdf(const float* cdf, const float* bins, int nb, float u) {
+    int lo_i = 0, hi_i = nb;
+    while (lo_i < hi_i) {
+        const int mid = (lo_i + hi_i) >> 1;
+        if (cdf[mid] <= u) lo_i = mid + 1; else hi_i = mid;
+    }
+    const int below = lo_i - 1 > 0 ? lo_i - 1 : 0;
+    const int above = lo_i < nb - 1 ? lo_i : nb - 1;
+    const float c0 = cdf[below], c1 = cdf[above];
+    float denom = c1 - c0;
+    if (denom < 1e-5f) denom = 1.f;
+    const float t = (u - c0) / denom;
+    const float b0 = bins[below], b1 = bins[above];
+    return b0 + t * (b1 - b0);
+}
+
+// ---------------------------------------------------------------------------------------
 // sample_fine: one wave per ray.  bins = mids of the coarse linspace, w = weights[1:-1]+1e-5,
-// pdf = w/sum(w), cdf = [0, cumsum(pdf)] with the running sum in fp64 rounded per entry like
-// torch.cumsum on CPU; u = linspace(0,1,Nf); idx = #(cdf <= u) (searchsorted right=True); guarded lerp;
+// pdf = w/sum(w) (normalise_pdf), cdf = [0, cumsum(pdf)] with the running sum in fp64 rounded per entry like
+// torch.cumsum on CPU; u = linspace(0,1,Nf), each drawn by draw_inverse_cdf;
 // then z_fine = sort(cat(z_coarse, z_samples)) by full rank counting (no sortedness assumed; -0 ranks before +0).
 // LDS per wave: cdf[Nc] | bins[Nc] | zall[Nc+Nf] | zout[Nc+Nf] (the sorted row, stored coalesced)
 // ---------------------------------------------------------------------------------------
@@ -462,14 +472,8 @@ __global__ __launch_bounds__(256) void sample_fine_kernel(int64_t n, float near_
     for (int64_t ray = (int64_t)blockIdx.x * 4 + wave; ray < n; ray += (int64_t)gridDim.x * 4) {
         const float* wr = weights + ray * nc;
         const float* zc = z_coarse + ray * nc;
-        // sum of (w + 1e-5)
-        float part = 0.f;
-        for (int j = lane; j < nw; j += 64) part += wr[j + 1] + 1e-5f;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
-        const float total = part;
-        // pdf into zall (scratch), then per-entry sequential prefix = torch.cumsum order
-        for (int j = lane; j < nw; j += 64) zall[j] = (wr[j + 1] + 1e-5f) / total;
+        // pdf of the interior weights into zall (scratch), then per-entry sequential prefix = torch.cumsum order
+        normalise_pdf(wr + 1, nw, lane, zall);
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         cdf_like_cumsum(zall, cdf, nb, lane);
@@ -478,21 +482,7 @@ __global__ __launch_bounds__(256) void sample_fine_kernel(int64_t n, float near_
         // coarse depths first, then inverse-CDF samples
         for (int j = lane; j < nc; j += 64) zall[j] = zc[j];
         for (int s = lane; s < nf; s += 64) {
-            const float u = u_lin ? u_lin[s] : linspace_at(0.f, 1.f, nf, s);
-            int lo_i = 0, hi_i = nb;                 // count of cdf entries <= u  (cdf ascending)
-            while (lo_i < hi_i) {
-                const int mid = (lo_i + hi_i) >> 1;
-                if (cdf[mid] <= u) lo_i = mid + 1; else hi_i = mid;
-            }
-            const int idx = lo_i;
-            const int below = idx - 1 > 0 ? idx - 1 : 0;
-            const int above = idx < nb - 1 ? idx : nb - 1;
-            const float c0 = cdf[below], c1 = cdf[above];
-            float denom = c1 - c0;
-            if (denom < 1e-5f) denom = 1.f;
-            const float t = (u - c0) / denom;
-            const float b0 = bins[below], b1 = bins[above];
-            const float zs = b0 + t * (b1 - b0);
+            const float zs = draw_inverse_cdf(cdf, bins, nb, u_lin ? u_lin[s] : linspace_at(0.f, 1.f, nf, s));
             zall[nc + s] = zs;
             if (z_samples) z_samples[ray * nf + s] = zs;
         }
@@ -550,7 +540,7 @@ __global__ __launch_bounds__(256) void sample_fine_kernel(int64_t n, float near_
 
 // ---------------------------------------------------------------------------------------
 // sample_pdf as a free-standing function (render.py:27-56) on arbitrary per-ray bins: one wave per ray,
-// same arithmetic as sample_fine_kernel without the merge.  bins [n,nb], weights [n,nb-1] -> out [n,ns].
+// sample_fine_kernel's draw without the merge.  bins [n,nb], weights [n,nb-1] -> out [n,ns].
 // LDS per wave: cdf[nb] | pdf[nb]
 // ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void sample_pdf_kernel(int64_t n, int nb, int ns, const float* __restrict__ bins,
@@ -564,32 +554,14 @@ __global__ __launch_bounds__(256) void sample_pdf_kernel(int64_t n, int nb, int 
     for (int64_t ray = (int64_t)blockIdx.x * 4 + wave; ray < n; ray += (int64_t)gridDim.x * 4) {
         const float* wr = weights + ray * nw;
         const float* br = bins + ray * nb;
-        float part = 0.f;
-        for (int j = lane; j < nw; j += 64) part += wr[j] + 1e-5f;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
-        for (int j = lane; j < nw; j += 64) pdf[j] = (wr[j] + 1e-5f) / part;
+        normalise_pdf(wr, nw, lane, pdf);
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         cdf_like_cumsum(pdf, cdf, nb, lane);
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        for (int s = lane; s < ns; s += 64) {
-            const float u = u_lin ? u_lin[s] : linspace_at(0.f, 1.f, ns, s);
-            int lo_i = 0, hi_i = nb;
-            while (lo_i < hi_i) {
-                const int mid = (lo_i + hi_i) >> 1;
-                if (cdf[mid] <= u) lo_i = mid + 1; else hi_i = mid;
-            }
-            const int below = lo_i - 1 > 0 ? lo_i - 1 : 0;
-            const int above = lo_i < nb - 1 ? lo_i : nb - 1;
-            const float c0 = cdf[below], c1 = cdf[above];
-            float denom = c1 - c0;
-            if (denom < 1e-5f) denom = 1.f;
-            const float t = (u - c0) / denom;
-            const float b0 = br[below], b1 = br[above];
-            out[ray * ns + s] = b0 + t * (b1 - b0);
-        }
+        for (int s = lane; s < ns; s += 64)
+            out[ray * ns + s] = draw_inverse_cdf(cdf, br, nb, u_lin ? u_lin[s] : linspace_at(0.f, 1.f, ns, s));
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     }
@@ -620,35 +592,41 @@ int launch_sample_coarse(int64_t n, float near_, float far_, int nc, const float
     return check_launch("sample_coarse");
 }
 
+// The lanes per ray of every compositing kernel for rows of S samples, as a compile-time constant: f(integral_constant<G>).
+// One choice for all of them: the windowed forward and the backward must cut the samples into the one-pass forward's passes.
+template <class F>
+static void dispatch_G(int S, F&& f) {
+    if (S > 32) f(std::integral_constant<int, 64>{});
+    else if (S > 16) f(std::integral_constant<int, 32>{});
+    else f(std::integral_constant<int, 16>{});
+}
+
+// blocks of 256 threads for n rays (or worst-case list entries), `iter` of them per G-lane group
+template <int G>
+static dim3 ray_grid(int64_t n, int iter = 1) {
+    const int64_t per_block = 256 / G * iter;
+    return dim3((unsigned)((n + per_block - 1) / per_block));
+}
+
 int launch_composite(int64_t n, int S, const float* raw, const float* z, const float* rays, float* rgb, float* depth,
                      float* acc, float* weights, hipStream_t stream) {
     if (n <= 0) return 0;
-    if (S > 32) {
-        hipLaunchKernelGGL(composite_kernel<64>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, n, S, raw, z,
-                           rays, rgb, depth, acc, weights);
-    } else if (S > 16) {
-        hipLaunchKernelGGL(composite_kernel<32>, dim3((unsigned)((n + 7) / 8)), dim3(256), 0, stream, n, S, raw, z,
-                           rays, rgb, depth, acc, weights);
-    } else {
-        hipLaunchKernelGGL(composite_kernel<16>, dim3((unsigned)((n + 15) / 16)), dim3(256), 0, stream, n, S, raw, z,
-                           rays, rgb, depth, acc, weights);
-    }
+    dispatch_G(S, [&](auto g) {
+        constexpr int G = decltype(g)::value;
+        hipLaunchKernelGGL(composite_kernel<G>, ray_grid<G>(n), dim3(256), 0, stream, n, S, raw, z, rays, rgb, depth, acc,
+                           weights);
+    });
     return check_launch("composite");
 }
 
 int launch_composite_weights(int64_t n, int S, const float* sigma, int sigma_stride, const float* z, const float* rays,
                              float* depth, float* acc, float* weights, hipStream_t stream) {
     if (n <= 0) return 0;
-    if (S > 32) {
-        hipLaunchKernelGGL(composite_weights_kernel<64>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, n, S, sigma,
-                           sigma_stride, z, rays, depth, acc, weights);
-    } else if (S > 16) {
-        hipLaunchKernelGGL(composite_weights_kernel<32>, dim3((unsigned)((n + 7) / 8)), dim3(256), 0, stream, n, S, sigma,
-                           sigma_stride, z, rays, depth, acc, weights);
-    } else {
-        hipLaunchKernelGGL(composite_weights_kernel<16>, dim3((unsigned)((n + 15) / 16)), dim3(256), 0, stream, n, S, sigma,
-                           sigma_stride, z, rays, depth, acc, weights);
-    }
+    dispatch_G(S, [&](auto g) {
+        constexpr int G = decltype(g)::value;
+        hipLaunchKernelGGL(composite_weights_kernel<G>, ray_grid<G>(n), dim3(256), 0, stream, n, S, sigma, sigma_stride, z,
+                           rays, depth, acc, weights);
+    });
     return check_launch("composite_weights");
 }
 
@@ -656,29 +634,22 @@ int launch_composite_weights_window(int64_t n, int S, const float* sigma, const 
                                     float* acc, float* weights, const int* live_in, const int* count_in, int* live_out,
                                     int* count_out, int k0, int k1, hipStream_t stream) {
     if (n <= 0) return 0;
-    // the G of launch_composite_weights for this S: the scans must see its partition of the samples
-    // grid: the worst case, every ray live; (256 / G) * 8 entries per block
-    if (S > 32) {
-        hipLaunchKernelGGL(composite_weights_window_kernel<64>, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, stream, n, S,
+    dispatch_G(S, [&](auto g) {                          // grid: the worst case, every ray live
+        constexpr int G = decltype(g)::value;
+        hipLaunchKernelGGL(composite_weights_window_kernel<G>, ray_grid<G>(n, kWindowIter), dim3(256), 0, stream, n, S,
                            sigma, z, rays, depth, acc, weights, live_in, count_in, live_out, count_out, k0, k1);
-    } else if (S > 16) {
-        hipLaunchKernelGGL(composite_weights_window_kernel<32>, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, stream, n, S,
-                           sigma, z, rays, depth, acc, weights, live_in, count_in, live_out, count_out, k0, k1);
-    } else {
-        hipLaunchKernelGGL(composite_weights_window_kernel<16>, dim3((unsigned)((n + 127) / 128)), dim3(256), 0, stream, n, S,
-                           sigma, z, rays, depth, acc, weights, live_in, count_in, live_out, count_out, k0, k1);
-    }
+    });
     return check_launch("composite_weights_window");
 }
 
 int launch_composite_bwd(int64_t n, int S, const float* raw, const float* z, const float* rays, const float* g_rgb,
                          const float* g_depth, const float* g_acc, const float* g_w, float* g_raw, hipStream_t stream) {
     if (n <= 0) return 0;
-    const int G = S <= 16 ? 16 : (S <= 32 ? 32 : 64);
-    const dim3 grid((unsigned)((n * G + 255) / 256)), block(256);
-    if (G == 16) hipLaunchKernelGGL((composite_bwd_kernel<16>), grid, block, 0, stream, n, S, raw, z, rays, g_rgb, g_depth, g_acc, g_w, g_raw);
-    else if (G == 32) hipLaunchKernelGGL((composite_bwd_kernel<32>), grid, block, 0, stream, n, S, raw, z, rays, g_rgb, g_depth, g_acc, g_w, g_raw);
-    else hipLaunchKernelGGL((composite_bwd_kernel<64>), grid, block, 0, stream, n, S, raw, z, rays, g_rgb, g_depth, g_acc, g_w, g_raw);
+    dispatch_G(S, [&](auto g) {
+        constexpr int G = decltype(g)::value;
+        hipLaunchKernelGGL(composite_bwd_kernel<G>, ray_grid<G>(n), dim3(256), 0, stream, n, S, raw, z, rays, g_rgb, g_depth,
+                           g_acc, g_w, g_raw);
+    });
     return check_launch("composite_bwd");
 }
 

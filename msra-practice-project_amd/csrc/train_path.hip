@@ -167,10 +167,15 @@ static void plan_kept(const PassSpec P[2], const Geometry& G, int64_t saved_byte
     }
 }
 
+static int64_t param_numel(int kind, int i) {
+    const FieldKind& k = field_kind(kind);
+    return (i & 1) ? k.dims[i / 2][0] : (int64_t)k.dims[i / 2][0] * k.dims[i / 2][1];
+}
+
+// a scratch copy of a kind's parameter gradients: tensor after tensor, each starting on a 64-float block
 static int64_t param_floats(int kind) {
     int64_t f = 0;
-    const FieldKind& k = field_kind(kind);
-    for (int l = 0; l < k.n_layers; ++l) f += ((int64_t)k.dims[l][0] * k.dims[l][1] + 63) / 64 * 64 + ((int64_t)k.dims[l][0] + 63) / 64 * 64;
+    for (int i = 0; i < 2 * field_kind(kind).n_layers; ++i) f += align64(param_numel(kind, i));
     return f;
 }
 
@@ -214,7 +219,7 @@ static BwdLayout bwd_layout(const PassSpec P[2], const Geometry& G) {
     }
     BwdLayout L{};
     int64_t f = 0;
-    auto take = [&](int64_t x) { const int64_t o = f; f += (x + 63) / 64 * 64; return o; };
+    auto take = [&](int64_t x) { const int64_t o = f; f += align64(x); return o; };
     const int64_t n = G.n;
     L.g_raw_c = take(n * G.nc * 4);
     L.g_raw_f = take(n * (int64_t)(G.nc + G.nf) * 4);
@@ -232,27 +237,10 @@ static BwdLayout bwd_layout(const PassSpec P[2], const Geometry& G) {
     return L;
 }
 
-// The forward's state in the mi_render_rays workspace (its region order; one field adds z_samples, raw_samples, pos).
-struct State {
-    float *z_c, *raw_c, *w_c, *z_f, *raw_f, *z_s, *raw_s;
-    int* pos;
-};
+// The forward's state in the mi_render_rays workspace (one field adds z_samples, raw_samples, pos).
+using State = RenderWorkspace::Regions;
 
-static State carve_state(void* workspace, const Geometry& G) {
-    float* ws = (float*)workspace;
-    auto take = [&](int64_t x) { float* p = ws; ws += (x + 63) / 64 * 64; return p; };
-    const int64_t n = G.n, S = G.nc + G.nf;
-    State st;
-    st.z_c = take(n * G.nc);
-    st.raw_c = take(n * G.nc * 4);
-    st.w_c = take(n * G.nc);
-    st.z_f = take(n * S);
-    st.raw_f = take(n * S * 4);
-    st.z_s = take(n * G.nf);
-    st.raw_s = take(n * G.nf * 4);
-    st.pos = (int*)take(n * S);
-    return st;
-}
+static State carve_state(void* workspace, const Geometry& G) { return RenderWorkspace(G.n, G.nc, G.nf).carve(workspace); }
 
 // Checks shared by the size queries and both entry points.  shared: one field for both passes.
 static int check_common(const char* fn, int kind_c, int kind_f, int64_t n_groups, int64_t rpg, int nc, int nf,
@@ -275,8 +263,8 @@ static int check_common(const char* fn, int kind_c, int kind_f, int64_t n_groups
 }
 
 static int check_state(const char* fn, const Geometry& G, int64_t workspace_bytes, const void* saved, int64_t saved_bytes) {
-    int64_t need = mi_render_workspace_bytes(G.n, G.nc, G.nf);
-    if (G.shared) need += mi_render_shared_field_extra_bytes(G.n, G.nc, G.nf);
+    const RenderWorkspace layout(G.n, G.nc, G.nf);
+    const int64_t need = layout.base_bytes() + (G.shared ? layout.shared_extra_bytes() : 0);
     if (workspace_bytes < need) {
         set_error("%s: workspace of %lld bytes, need %lld (mi_render_workspace_bytes%s)", fn, (long long)workspace_bytes,
                   (long long)need, G.shared ? " + mi_render_shared_field_extra_bytes: one field for both passes" : "");
@@ -325,18 +313,10 @@ static int forward_pass(const PassSpec& P, const Geometry& G, const float* packe
 
 // Parameter-gradient pointers of a kind laid out in a scratch region (param_floats order).
 static void scratch_params(int kind, float* base, float* out[2 * kMaxLayers]) {
-    const FieldKind& k = field_kind(kind);
-    for (int l = 0; l < k.n_layers; ++l) {
-        out[2 * l] = base;
-        base += ((int64_t)k.dims[l][0] * k.dims[l][1] + 63) / 64 * 64;
-        out[2 * l + 1] = base;
-        base += ((int64_t)k.dims[l][0] + 63) / 64 * 64;
+    for (int i = 0; i < 2 * field_kind(kind).n_layers; ++i) {
+        out[i] = base;
+        base += align64(param_numel(kind, i));
     }
-}
-
-static int64_t param_numel(int kind, int i) {
-    const FieldKind& k = field_kind(kind);
-    return (i & 1) ? k.dims[i / 2][0] : (int64_t)k.dims[i / 2][0] * k.dims[i / 2][1];
 }
 
 struct PassIO {
@@ -459,14 +439,7 @@ int mi_render_rays_train(int kind_coarse, const float* packed_coarse, int kind_f
     if ((rc = forward_pass(P[0], G, packed_coarse, film, rays, st.z_c, st.raw_c, kept[0], sv, stream))) return rc;
     if ((rc = mi_composite(n, n_coarse, st.raw_c, st.z_c, rays, rgb_c, depth_c, acc_c, st.w_c, stream))) return rc;
     if (shared && n_fine == 0) {                   // the fine pass IS the coarse pass (mi_render_rays aliases it)
-        hipStream_t s = (hipStream_t)stream;
-        if (hipMemcpyAsync(rgb_f, rgb_c, n * 3 * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess ||
-            hipMemcpyAsync(depth_f, depth_c, n * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess ||
-            hipMemcpyAsync(acc_f, acc_c, n * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) {
-            set_error("%s: output alias copy failed", fn);
-            return MI_EHIP;
-        }
-        return MI_OK;
+        return copy_render_outputs(fn, n, rgb_f, depth_f, acc_f, rgb_c, depth_c, acc_c, (hipStream_t)stream);
     }
     if (shared) {                                  // the Nf new depths only, merged into sorted order
         if ((rc = mi_sample_fine_pos(n, near_, far_, n_coarse, n_fine, z_lin, u_lin, st.z_c, st.w_c, st.z_s, st.z_f, st.pos,

@@ -272,6 +272,24 @@ def test_sample_fine_sorts_signed_and_repeated_depths(mi):
     assert torch.equal(zf, ref)
 
 
+@pytest.mark.parametrize("n,nc,nf", [(5, 5, 3), (5, 67, 130)])
+def test_sample_pdf_equals_sample_fine_draw(mi, n, nc, nf):
+    """The two sampling kernels share one draw: sample_pdf on the mids of the coarse linspace and the interior weights
+    returns the bits of sample_fine's z_samples.  Positive rows, one all-zero row, one single spike; the larger shape
+    has more than one 64-lane stride in both the pdf loop and the draw loop."""
+    near, far = 2.0, 6.0
+    w = synth.t_rand(n, nc, seed=17).clone()
+    w[1] = 0.0
+    w[3] = 0.0
+    w[3, nc // 2] = 1.0
+    zc, _ = R.stratified_z(n, near, far, nc, synth.t_rand(n, nc, 5))
+    z_lin = mi.ops.linspace_table(near, far, nc, dev())
+    bins = (0.5 * (z_lin[1:] + z_lin[:-1])).expand(n, nc - 1)
+    _, zs = mi.ops.sample_fine(to_dev(zc), to_dev(w), near, far, nf, want_samples=True)
+    got = mi.ops.sample_pdf(bins, to_dev(w[:, 1:-1]), nf)
+    assert torch.equal(got.view(torch.int32), zs.view(torch.int32))
+
+
 # ------------------------------------------------------------------ fused field MLP
 KINDS = ["nerf", "siren_nerf", "film_siren_nerf", "film_siren_nerf_nodir"]
 
