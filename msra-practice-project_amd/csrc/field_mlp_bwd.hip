@@ -996,12 +996,19 @@ int64_t bwd_partial_floats(int64_t P) {
     }
     return most;
 }
-// ... of any kind: a FiLM image of depth L runs L GEMM jobs, so the depths above 8 can need more than the figure above
+// ... of any kind.  A FiLM image of depth L runs L GEMM jobs of at most ceil(256 / L) slabs each (BwdBatcher::slabs_for):
+// 256 job-slabs at depths 4 and 8, but 260 / 258 / 259 at depths 5 / 6 / 7 and up to 264 (depth 12) above 8, so the figure
+// above, written for eight jobs of 32 slabs, does not state every depth's plan.  At depths 5 to 7 it is still large enough:
+// the extra job-slabs (at most 4 x 65 792 floats) start at 9 217 points, where the NeRF plan in its maximum is already more
+// than a million floats above the FiLM term (tests/test_cabi_train_sizes.py replays the planner against this query for
+// every depth).  This one is the planner's worst case for the depth itself, never less than the figure above.
 int64_t bwd_partial_floats_kind(int kind, int64_t P) {
     const int64_t base = bwd_partial_floats(P);
-    if (film_depth(kind) <= 8) return base;
+    const int L = film_depth(kind);
+    if (!L) return base;
     const int64_t slabs256 = (P + 255) / 256 > 0 ? (P + 255) / 256 : 1;
-    const int64_t film = film_depth(kind) * (slabs256 < 32 ? slabs256 : 32) * kFilmLayerScratch + 2 * (slabs256 < 512 ? slabs256 : 512) * 1280 + 4096;
+    const int64_t cap = (256 + L - 1) / L;
+    const int64_t film = L * (slabs256 < cap ? slabs256 : cap) * kFilmLayerScratch + 2 * (slabs256 < 512 ? slabs256 : 512) * 1280 + 4096;
     return film > base ? film : base;
 }
 

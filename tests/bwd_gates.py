@@ -1,8 +1,9 @@
-"""Stage gates of the field backward (test_gpu_bwd_stages.py, test_bwd_gates_host.py): torch only.
+"""Stage gates of the field backward (test_gpu_bwd_stages.py, test_gpu_bwd_stages_depth.py, test_bwd_gates_host.py):
+torch only.
 
 The training buffers are mirrored from csrc/field_layout.h (`ACTS`, `GRADS`, the switch-bit decoder), every network is
-written down once as a list of linear layers (`network`), and each stage of the backward is rebuilt in float64 from the
-kernels' OWN inputs to that stage:
+written down once as a list of linear layers (`network`; the FiLM depth kinds from their depth, `film_depth_network`), and
+each stage of the backward is rebuilt in float64 from the kernels' OWN inputs to that stage:
 
   A  saving forward   every saved row from the saved input of its layer (no compounding through the network)
   B  chain            every dA region from the kernel's dA of the layers it feeds and the saved rows
@@ -13,6 +14,7 @@ reference from absolute values (|W| |X|, |W|^T |dA|, |dA|^T |X|).  Every gate le
 from __future__ import annotations
 
 import math
+import re
 from collections import namedtuple
 
 import numpy as np
@@ -21,10 +23,50 @@ import torch
 from mirender.fields import KIND_NAMES
 from oracle import parity
 
-KIND_IDS = {name: k for k, name in KIND_NAMES.items()}          # kind name -> the C ABI's kind number
+
+# ---- FiLM depth kinds ------------------------------------------------------------------------------------------------
+# FilmSirenNeRF(hidden_layers = L) for L = 4..12 is named film_depth_L{L}_dir / film_depth_L{L}_nodir here and is
+# MI_FIELD_FILM_DEPTH(L, use_dir) of include/mi_render.h at the C ABI.  L = 8 under these names is the same network as the
+# fixed kinds film_siren_nerf / film_siren_nerf_nodir, described a second time (test_bwd_gates_host.py holds the two equal).
+_DEPTH_NAME = re.compile(r"film_depth_L(\d+)_(dir|nodir)$")
+DEPTH_MIN, DEPTH_MAX = 4, 12
+
+
+def depth_name(L: int, use_dir: bool) -> str:
+    return f"film_depth_L{L}_{'dir' if use_dir else 'nodir'}"
+
+
+def depth_of(kind: str):
+    """(hidden_layers, use_dir) of a FiLM kind name, fixed (8) or depth; None for the kinds without FiLM."""
+    if kind in ("film_siren_nerf", "film_siren_nerf_nodir"):
+        return 8, kind == "film_siren_nerf"
+    m = _DEPTH_NAME.match(kind)
+    if not m or not DEPTH_MIN <= int(m.group(1)) <= DEPTH_MAX:
+        return None
+    return int(m.group(1)), m.group(2) == "dir"
+
+
+class _PerKind(dict):
+    """A table over the fixed kinds that computes a depth kind's entry from its name (and does not keep it: iterating the
+    table always gives the fixed kinds only)."""
+
+    def __init__(self, fixed, depth_entry):
+        super().__init__(fixed)
+        self._depth_entry = depth_entry
+
+    def __missing__(self, kind):
+        d = depth_of(kind)
+        if d is None:
+            raise KeyError(kind)
+        return self._depth_entry(*d)
+
+
+# kind name -> the C ABI's kind number
+KIND_IDS = _PerKind({name: k for k, name in KIND_NAMES.items()}, lambda L, use_dir: 0x100 + 2 * L + (1 if use_dir else 0))
 
 U = 2.0 ** -24                 # unit roundoff of fp32
-W0 = 30.0                      # sin layers' frequency (the synth FiLM fields use the module default too)
+W0 = 30.0                      # sin layers' frequency: the default of the reference functions below; the GPU tests hand them
+#                                the packed field's own w_0 (a FiLM module's constructor argument)
 
 # Stage constants, in units of U, calibrated on an MI355X over every case of test_gpu_bwd_stages.py: the worst achieved
 # error was 7.5 u (|W||X| + |b|) in stage A, 7.5 u |act'| |W|^T|dA| in stage B and 1.4 u sqrt(L) |dA|^T|X| in stage C
@@ -38,7 +80,7 @@ COS_BAND = 1e-3                # the saved cosine sign is only claimed where |co
 # ---- training buffers (csrc/field_layout.h) -------------------------------------------------------------------------
 # Per-point row-major regions [points][width]; region r starts at (sum of the widths before it) * points.
 _NERF_GRADS = [(f"dA{l}", 256) for l in range(9)] + [("dA9", 128), ("heads", 4)]
-ACTS = {
+ACTS = _PerKind({
     # E_pos(60 + pad) | H1..H8 post-ReLU | G = layers_dir.0 out | E_dir(24 + pad) | H_d | switches of H1..H8 | of H_d
     "nerf": ([("E_pos", 64)] + [(f"H{l}", 256) for l in range(1, 9)] + [("G", 256), ("E_dir", 32), ("H_d", 128)]
              + [(f"S{l}", 8) for l in range(1, 9)] + [("S_d", 4)]),
@@ -48,14 +90,16 @@ ACTS = {
     "siren_nerf": [("xin", 8)] + [(f"X{l}", 256) for l in range(1, 9)] + [("G", 256), ("X_d", 128)],
     # xin | X_l of FiLM layer l = 0..8, encoded like SirenNeRF's
     "film_siren_nerf": [("xin", 8)] + [(f"X{l}", 256) for l in range(9)],
-}
+    # field_layout.h:film_acts_depth(L): xin | X_0 .. X_L
+}, lambda L, use_dir: [("xin", 8)] + [(f"X{l}", 256) for l in range(L + 1)])
 ACTS["film_siren_nerf_nodir"] = ACTS["film_siren_nerf"]
-GRADS = {
+GRADS = _PerKind({
     "nerf": _NERF_GRADS,
     "tiny_nerf": [(f"dA{l}", 256) for l in range(4)] + [("dA4", 128), ("heads", 4)],
     "siren_nerf": _NERF_GRADS,
     "film_siren_nerf": [(f"dU{l}", 256) for l in range(9)] + [("heads", 4)],   # dL/du of FiLM layer l
-}
+    # field_layout.h:film_grads_depth(L): dU_0 .. dU_L | heads
+}, lambda L, use_dir: [(f"dU{l}", 256) for l in range(L + 1)] + [("heads", 4)])
 GRADS["film_siren_nerf_nodir"] = GRADS["film_siren_nerf"]
 
 
@@ -175,7 +219,27 @@ def network(kind: str) -> list:
         return net + [L(9, ins, "film", "X8", "dU8", film=8),
                       L(8, [("X7", 0, 256, 0, "thin", True)], "relu", (3, 4), ("heads", 3, 4)),
                       L(10, [("X8", 0, 256, 0, "thin", True)], "sigmoid", (0, 3), ("heads", 0, 3))]
+    if depth_of(kind) is not None:
+        return film_depth_network(*depth_of(kind))
     raise KeyError(kind)
+
+
+def film_depth_network(n: int, use_dir: bool) -> list:
+    """FilmSirenNeRF(hidden_layers = n): parameter pairs in the order of include/mi_render.h - 0 input_layer, 1..n-1
+    hidden_layers.0..n-2, n output_layer_sigma.0, n + 1 hidden_layer_rgb, n + 2 output_layer_rgb.0.  FiLM layer l (row l of
+    the image's table) saves X_l and writes dU_l: l = 0 the input layer, 1..n-1 the hidden layers, n the rgb hidden layer.
+    Per image the n 256-wide layers are one GEMM launch and the K = 3 blocks one thin launch; the two heads (sigma on
+    X_{n-1}, rgb on X_n) run over all images."""
+    L = Layer
+    net = [L(0, [("xin", 0, 3, 0, "thin_img", True)], "film", "X0", "dU0", film=0)]
+    for l in range(1, n):
+        net.append(L(l, [(f"X{l - 1}", 0, 256, 0, "g422_img", True)], "film", f"X{l}", f"dU{l}", film=l))
+    ins = [(f"X{n - 1}", 0, 256, 0, "g422_img", True)]
+    if use_dir:
+        ins.append(("xin", 3, 6, 256, "thin_img", False))
+    return net + [L(n + 1, ins, "film", f"X{n}", f"dU{n}", film=n),
+                  L(n, [(f"X{n - 1}", 0, 256, 0, "thin", True)], "relu", (3, 4), ("heads", 3, 4)),
+                  L(n + 2, [(f"X{n}", 0, 256, 0, "thin", True)], "sigmoid", (0, 3), ("heads", 0, 3))]
 
 
 # ---- the planner (BwdBatcher::slabs_for / slab_pts_for, csrc/field_mlp_bwd.hip) ----------------------------------------
@@ -210,6 +274,20 @@ def group_plan(kind: str, group: str, P: int):
 def sum_length(kind: str, group: str, P: int) -> int:
     pts, n, _ = group_plan(kind, group, P)
     return pts + n
+
+
+def film_scratch_plan(kind: str, ppg: int, n_img: int) -> int:
+    """Floats of dW scratch the backward of a FiLM kind hands out (launch_field_backward; BwdBatcher::take rounds every
+    request up to 256 floats): the larger of an image's pass - one [256][256] + [256] record per slab and 256-wide layer,
+    one [4][256] record and 4 bias sums per slab and thin job - and the head pass over all images."""
+    jobs, up = group_jobs(kind), lambda n: -(-n // 256) * 256
+
+    def thin(group, P):
+        n = group_plan(kind, group, P)[1]
+        return jobs[group] * (up(1024 * n) + up(4 * n))
+
+    image = jobs["g422_img"] * up(group_plan(kind, "g422_img", ppg)[1] * (256 * 256 + 256)) + thin("thin_img", ppg)
+    return max(image, thin("thin", n_img * ppg))
 
 
 def cap_thresholds(kind: str) -> list:

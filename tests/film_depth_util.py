@@ -16,7 +16,8 @@ import torch
 DEPTHS = (4, 6, 12)                 # the depths with reference-pinned fixtures
 NEAR, FAR, NC, NF = 0.5, 1.5, 8, 16  # the gradient fixture's render_rays call: 64 rays in 2 groups, one shared field
 N_RAYS, N_GROUPS = 64, 2
-SIGMA_HEAD = {"plain": (1.0, 0.0), "medium": (8.0, 2.0)}     # the "" and "medium" head scalings of the F5 family
+# the "", "medium" and sharp head scalings of the F5 family (oracle/synth.py:SIGMA_HEAD)
+SIGMA_HEAD = {"plain": (1.0, 0.0), "medium": (8.0, 2.0), "sharp": (50.0, 5.0)}
 
 
 def kind_of(L: int, use_dir: bool) -> int:
@@ -40,7 +41,8 @@ def _uniform(rng, shape, bound):
 
 
 def state_dict(L: int, use_dir: bool, seed: int, head: str = "plain") -> dict:
-    """Synthetic fp32 state dict; `head`: "plain" (the initialiser's sigma head) or "medium" (x8, +2: oracle/synth.py)."""
+    """Synthetic fp32 state dict; `head`: "plain" (the initialiser's sigma head), "medium" (x8, +2) or "sharp" (x50, +5:
+    oracle/synth.py)."""
     rng = np.random.Generator(np.random.PCG64(seed))
     scale, shift = SIGMA_HEAD[head]
     sd = {}

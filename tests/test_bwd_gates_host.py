@@ -316,3 +316,222 @@ def test_stage_b_gate_rejects_a_flipped_switch_and_a_flipped_sign():
     flipped[i, j] ^= np.uint32(1)
     ref, bound = G.stage_b_ref("sin", dx64, mag, torch.from_numpy(flipped.view(np.float32)))
     assert not G.gate("host B sin", "B host", "dA (one sign flipped)", torch.from_numpy(got), ref, bound, "")
+
+
+# ---- FiLM depth kinds ------------------------------------------------------------------------------------------------
+DEPTH_KINDS = [G.depth_name(L, d) for L in range(G.DEPTH_MIN, G.DEPTH_MAX + 1) for d in (True, False)]
+
+
+@pytest.mark.parametrize("kind", DEPTH_KINDS)
+def test_depth_description_matches_library(kind):
+    """Layout totals, the kind id, the parameter order and shapes (mi_field_param_shape) and the regions every stage reads."""
+    import ctypes
+
+    import film_depth_util as U
+    lib = _lib.load()
+    L, use_dir = G.depth_of(kind)
+    k = G.KIND_IDS[kind]
+    assert k == U.kind_of(L, use_dir)
+    assert G.floats_per_point(G.ACTS[kind]) == lib.mi_field_train_acts_floats(k) == 8 + 256 * (L + 1)
+    assert G.floats_per_point(G.GRADS[kind]) == lib.mi_field_train_grads_floats(k) == 256 * (L + 1) + 4
+    assert lib.mi_field_film_layers(k) == L + 1 and lib.mi_field_num_params(k) == 2 * (L + 3)
+    net = G.network(kind)
+    assert sorted(lay.p for lay in net) == list(range(L + 3))
+    assert sorted(lay.film for lay in net if lay.film is not None) == list(range(L + 1))
+    for lay in net:
+        rows, cols = ctypes.c_int64(), ctypes.c_int64()
+        assert lib.mi_field_param_shape(k, 2 * lay.p, ctypes.byref(rows), ctypes.byref(cols)) == 0
+        assert cols.value == sum(r.c1 - r.c0 for r in lay.ins) == U.spec(L, use_dir)[lay.p][1][1]
+        assert rows.value == (lay.out[1] - lay.out[0] if lay.head else 256) == U.spec(L, use_dir)[lay.p][1][0]
+    used = {r.region for lay in net for r in lay.ins} | {lay.out for lay in net if not lay.head}
+    assert used == {name for name, _ in G.ACTS[kind]}
+    assert {"heads" if lay.head else lay.grad for lay in net} == {name for name, _ in G.GRADS[kind]}
+    jobs = G.group_jobs(kind)
+    assert jobs == {"g422_img": L, "thin_img": 2 if use_dir else 1, "thin": 2}
+    assert G.cap_thresholds(kind) == sorted({256 * -(-256 // L), 131072 if use_dir else 262144, 131072})
+
+
+def _layer_fields(lay):
+    return lay.p, [tuple(r) for r in lay.ins], lay.act, lay.out, lay.grad, lay.film
+
+
+@pytest.mark.parametrize("fixed,use_dir", [("film_siren_nerf", True), ("film_siren_nerf_nodir", False)])
+def test_depth_8_description_equals_the_fixed_kind(fixed, use_dir):
+    """Region by region and job by job: the depth description at L = 8 is the one written out for kinds 2 / 3."""
+    depth = G.depth_name(8, use_dir)
+    assert G.ACTS[depth] == G.ACTS[fixed] and G.GRADS[depth] == G.GRADS[fixed]
+    assert [_layer_fields(a) for a in G.network(depth)] == [_layer_fields(b) for b in G.network(fixed)]
+    assert G.group_jobs(depth) == G.group_jobs(fixed) and G.cap_thresholds(depth) == G.cap_thresholds(fixed)
+    for P in (1, 257, 8187, 8229, 131109, 262181, 128 * 128 * 36):
+        for grp in G.group_jobs(fixed):
+            assert G.group_plan(depth, grp, P) == G.group_plan(fixed, grp, P)
+    assert G.KIND_IDS[depth] == 0x100 + 16 + use_dir and G.KIND_IDS[fixed] == (2 if use_dir else 3)
+    assert sorted(G.KIND_IDS) == sorted(G.ACTS) == ["film_siren_nerf", "film_siren_nerf_nodir", "nerf", "siren_nerf", "tiny_nerf"]
+
+
+def test_depth_planner_mirror():
+    assert G.cap_thresholds(G.depth_name(12, True)) == [5632, 131072]
+    assert G.cap_thresholds(G.depth_name(5, False)) == [13312, 131072, 262144]
+    # five jobs of 52 slabs: 260 job-slabs, more than the 256 of eight jobs of 32
+    assert G.group_plan(G.depth_name(5, False), "g422_img", 13312 + 37) == (288, 47, 52)
+    assert G.group_plan(G.depth_name(5, False), "g422_img", 128 * 128 * 36) == (11360, 52, 52)
+    assert G.group_plan(G.depth_name(12, True), "g422_img", 128 * 128 * 36) == (26816, 22, 22)
+
+
+# A depth network simulated on the CPU: every stage in float64 from the previous stage's fp32 results, rounded to fp32 once -
+# what a faithful kernel may differ from by rounding only - in the buffers and the layout the GPU test reads
+# (test_gpu_bwd_stages.run), so the GPU test's own stage checks judge it.
+KFS = 256 * 256 + 256
+
+
+def _encode_sin(u, w0):
+    """fp32 sin(w0 u) with the sign of cos(w0 u) in its lowest mantissa bit (mi_math.h: cos_sign_into)."""
+    x = torch.sin(w0 * u).float()
+    return ((x.view(torch.int32) & ~1) | (torch.cos(w0 * u) < 0).int()).view(torch.float32)
+
+
+def sim_forward(kind, ppg, n_img, seed, w0=30.0, swap_rows=None, sigma_from=None):
+    """swap_rows = l: FiLM layers l and l + 1 take each other's row; sigma_from: the region the sigma head reads."""
+    import film_depth_util as U
+    L, use_dir = G.depth_of(kind)
+    sd = U.state_dict(L, use_dir, seed=seed, head="medium")
+    params = [sd[key + s] for key, _ in U.spec(L, use_dir) for s in (".weight", ".bias")]
+    film = U.film_rows(n_img, L, seed=seed + 1)
+    P = n_img * ppg
+    acts = torch.zeros(G.floats_per_point(G.ACTS[kind]) * P)
+    A = G.regions(G.ACTS[kind], acts, P)
+    A["xin"][:, :6] = U.sample_points(P, seed=seed + 2)
+    raw = torch.zeros(P, 4)
+    img = torch.arange(P) // ppg
+    for lay in G.network(kind):
+        W, b = params[2 * lay.p].double(), params[2 * lay.p + 1].double()
+        pre = b.unsqueeze(0)
+        for r in lay.ins:
+            region = sigma_from if (sigma_from and lay.act == "relu") else r.region
+            pre = pre + A[region][:, r.c0:r.c1].double() @ lay.weight_cols(W, r).T
+        if lay.act == "film":
+            row = lay.film
+            if swap_rows is not None and row in (swap_rows, swap_rows + 1):
+                row = 2 * swap_rows + 1 - row
+            fr = film[img, row].double()
+            A[lay.out][:] = _encode_sin(fr[:, :256] * pre + fr[:, 256:], w0)
+        elif lay.act == "relu":
+            raw[:, 3:] = torch.clamp(pre, min=0.0).float()
+        else:
+            raw[:, :3] = torch.sigmoid(pre).float()
+    return dict(P=P, ppg=ppg, n_img=n_img, w0=w0, params=params, film=film, A=A, raw=raw)
+
+
+def sim_chain(kind, st, seed):
+    """g_raw (a magnitude per point over four decades), the head gradients and dU of every FiLM layer."""
+    P, ppg, A, params, film = st["P"], st["ppg"], st["A"], st["params"], st["film"]
+    rng = np.random.Generator(np.random.PCG64(seed))
+    st["g_raw"] = torch.from_numpy((rng.normal(size=(P, 4)) * 10.0 ** rng.uniform(-3, 1, size=(P, 1))).astype(np.float32))
+    gws = torch.zeros(G.floats_per_point(G.GRADS[kind]) * P)
+    D = st["D"] = G.regions(G.GRADS[kind], gws, P)
+    D["heads"][:] = G.heads_ref(st["raw"], st["g_raw"])[0].float()
+    img = torch.arange(P) // ppg
+    net = G.network(kind)
+    for lay in sorted((x for x in net if x.act == "film"), key=lambda x: -x.film):
+        dx = torch.zeros(P, 256, dtype=torch.float64)
+        for m in net:
+            for r in m.ins:
+                if r.region != lay.out:
+                    continue
+                dA = D["heads"][:, m.grad[1]:m.grad[2]].double() if m.head else D[m.grad].double() * film[img, m.film, :256].double()
+                dx += dA @ m.weight_cols(params[2 * m.p].double(), r)
+        D[lay.grad][:] = (G.dsin_from_saved(A[lay.out], st["w0"]) * dx).float()
+    return st
+
+
+def sim_weight_grads(kind, st, drop_dw=None, drop_slab=None, drop_dir_job=False):
+    """drop_dw = p: parameter pair p's dW never written; drop_slab = (l, k): slab k of FiLM layer l's GEMM job left out of the
+    last image's sums; drop_dir_job: the thin job of hidden_layer_rgb's dir columns never run."""
+    L, _ = G.depth_of(kind)
+    P, ppg, n_img, A, D, params, film = st["P"], st["ppg"], st["n_img"], st["A"], st["D"], st["params"], st["film"]
+    grads = [torch.zeros_like(p) for p in params]
+    gfilm = torch.zeros_like(film)
+    fp = torch.zeros(L * KFS + 2 * 1024 + 256)
+    base3 = L * KFS
+    for lay in G.network(kind):
+        W, b = params[2 * lay.p].double(), params[2 * lay.p + 1].double()
+        if lay.head:
+            dA, r = D["heads"][:, lay.grad[1]:lay.grad[2]].double(), lay.ins[0]
+            grads[2 * lay.p][:] = (dA.T @ A[r.region].double()).float()
+            grads[2 * lay.p + 1][:] = dA.sum(0).float()
+            continue
+        l, dW, db = lay.film, torch.zeros_like(W), torch.zeros_like(b)
+        for g in range(n_img):
+            keep = torch.ones(ppg, dtype=torch.bool)
+            if drop_slab is not None and drop_slab[0] == l and g == n_img - 1:
+                pts = G.group_plan(kind, "g422_img", ppg)[0]
+                keep[drop_slab[1] * pts:(drop_slab[1] + 1) * pts] = False
+            rows = torch.arange(g * ppg, (g + 1) * ppg)[keep]
+            dU, gam = D[lay.grad][rows].double(), film[g, l, :256].double()
+            s = dU.sum(0).float().double()
+            dg = b * s
+            for r in lay.ins:
+                T = (dU.T @ A[r.region][rows, r.c0:r.c1].double()).float().double()
+                if drop_dir_job and r.group == "thin_img" and not r.bias:
+                    T = torch.zeros_like(T)
+                lay.weight_cols(dW, r)[:] += gam[:, None] * T
+                dg = dg + (lay.weight_cols(W, r) * T).sum(1)
+                if g == n_img - 1:
+                    o = (l - 1) * KFS if T.shape[1] == 256 else (base3 if l == 0 else base3 + 1024)
+                    fp[o:o + T.numel()] = T.flatten().float()
+            if g == n_img - 1:
+                o = base3 + 2048 if l == 0 else (l - 1) * KFS + 65536
+                fp[o:o + 256] = s.float()
+            db += gam * s
+            gfilm[g, l, :256], gfilm[g, l, 256:] = dg.float(), s.float()
+        if drop_dw != lay.p:
+            grads[2 * lay.p][:] = dW.float()
+        grads[2 * lay.p + 1][:] = db.float()
+    return dict(st, grads=grads, grad_film=gfilm, film_partial=fp)
+
+
+def _failed(case):
+    return {(r["stage"], r["qty"]) for r in parity.RECORDS if r.get("case") == case and not r["passed"]}
+
+
+# L = 5 without and L = 12 with the view direction, just past the cap of the image's GEMM jobs (52 and 22 slabs); the larger
+# of the two sizes as one image, which keeps the float64 work of each case at about 13 000 points
+@pytest.mark.parametrize("L,use_dir,ppg,n_img", [(5, False, 13312 + 37, 1), (12, True, 5632 + 37, 2)])
+def test_depth_gates_pass_the_faithful_network_and_reject_each_mistake(L, use_dir, ppg, n_img):
+    import test_gpu_bwd_stages as S
+    kind = G.depth_name(L, use_dir)
+    pts, n_slabs, cap = G.group_plan(kind, "g422_img", ppg)
+    assert pts > 256 and n_slabs < cap == -(-256 // L)
+    fwd = sim_forward(kind, ppg, n_img, seed=L)
+    chain = sim_chain(kind, fwd, seed=L + 1)
+    st = sim_weight_grads(kind, chain)
+    assert S.stage_a("host depth faithful", kind, st) and S.stage_b("host depth faithful", kind, st)
+    assert S.stage_c("host depth faithful", kind, st), sorted(_failed("host depth faithful"))[:3]
+
+    # FiLM rows 2 and 3 swapped: exactly the two layers' saved rows (and their sign bits) leave the bound
+    bad = sim_forward(kind, ppg, n_img, seed=L, swap_rows=2)
+    assert not S.stage_a("host depth rows swapped", kind, bad)
+    assert {q.split(" ")[0] for _, q in _failed("host depth rows swapped")} == {"X2", "X3"}
+
+    # the sigma head fed from X_{L-2}: its raw column only
+    bad = sim_forward(kind, ppg, n_img, seed=L, sigma_from=f"X{L - 2}")
+    assert not S.stage_a("host depth sigma input", kind, bad)
+    assert _failed("host depth sigma input") == {("A forward", f"p{L}")}
+
+    # hidden layer 3's dW never written
+    assert not S.stage_c("host depth dW dropped", kind, sim_weight_grads(kind, chain, drop_dw=3))
+    assert _failed("host depth dW dropped") == {("C FiLM finish", "dW p3")}
+
+    # one slab of FiLM layer 2's job left out of the last image's sums: the sums, and everything the finish makes of them
+    assert not S.stage_c("host depth slab dropped", kind, sim_weight_grads(kind, chain, drop_slab=(2, n_slabs // 2)))
+    failed = _failed("host depth slab dropped")
+    assert {("C FiLM sums", "T layer 2 X1 (last image)"), ("C FiLM sums", "s layer 2 (last image)"), ("C FiLM finish", "dW p2"),
+            ("C FiLM finish", "db p2"), ("C FiLM finish", f"d gamma layer 2 image {n_img - 1}"),
+            ("C FiLM finish", f"d beta layer 2 image {n_img - 1}")} == failed
+
+    # the thin job of the dir columns never run (a network with the view direction only)
+    if use_dir:
+        assert not S.stage_c("host depth dir job dropped", kind, sim_weight_grads(kind, chain, drop_dir_job=True))
+        failed = _failed("host depth dir job dropped")
+        assert ("C FiLM finish", f"dW p{L + 1}") in failed and ("C FiLM sums", f"T layer {L} xin (last image)") in failed
+        assert all(f"p{L + 1}" in q or f"layer {L} " in q for _, q in failed)

@@ -144,3 +144,41 @@ def test_backward_without_cotangents_launches_nothing():
     # no cotangent at all: nothing to do, nothing written (a NULL gradient array is then fine), no device touched
     rc, written = _backward(grads_c=False, grads_f=False, cots=(0,) * 6)
     assert rc == 0 and written == 0
+
+
+# ---- the dW scratch query against the planner, for every FiLM depth --------------------------------------------------
+FILM_DEPTHS = list(range(4, 13))
+
+
+def _film_sizes(kind):
+    import bwd_gates as G
+    caps = [256 * G.group_plan(kind, grp, 1)[2] for grp in G.group_jobs(kind)]
+    return sorted({1, 257, 9217, 128 * 128 * 36, 1 << 21} | {c + d for c in caps for d in (-5, 37)} | {c // 2 + 37 for c in caps})
+
+
+@pytest.mark.parametrize("use_dir", [True, False])
+@pytest.mark.parametrize("depth", FILM_DEPTHS)
+def test_bwd_partial_query_covers_the_planner_at_every_depth(depth, use_dir):
+    """mi_field_bwd_partial_floats_kind against a replay of the planner (bwd_gates.film_scratch_plan: the image pass of
+    `depth` GEMM jobs of at most ceil(256 / depth) slabs and its thin jobs, the head pass over all images) at every size
+    where the plan changes.  Depths 5, 6 and 7 plan 260, 258 and 259 job-slabs where the fixed kinds' figure was written
+    for 256: that figure still covers them, through the NeRF plan in its maximum, which is asserted here as well."""
+    import bwd_gates as G
+    L = lib()
+    kind = G.depth_name(depth, use_dir)
+    k = G.KIND_IDS[kind]
+    assert L.mi_field_film_partial_floats_kind(k, 2, 4096) == depth * (256 * 256 + 256) + 2 * 1024 + 256
+    worst_units = 0
+    for ppg in _film_sizes(kind):
+        for n_img in (1, 2, 3):
+            plan, query = G.film_scratch_plan(kind, ppg, n_img), L.mi_field_bwd_partial_floats_kind(k, n_img * ppg)
+            assert query >= plan, (ppg, n_img, plan, query)
+            assert query >= L.mi_field_bwd_partial_floats(n_img * ppg)
+            if depth <= 8:
+                assert L.mi_field_bwd_partial_floats(n_img * ppg) >= plan, (ppg, n_img)
+            worst_units = max(worst_units, depth * G.group_plan(kind, "g422_img", ppg)[1])
+    assert worst_units == depth * -(-256 // depth)
+    if depth == 8:
+        for P in (1, 8229, 1 << 20):
+            assert L.mi_field_bwd_partial_floats_kind(2 if use_dir else 3, P) == L.mi_field_bwd_partial_floats_kind(k, P) \
+                == L.mi_field_bwd_partial_floats(P)

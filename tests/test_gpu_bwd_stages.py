@@ -15,6 +15,9 @@ The point counts come from the planner's own formulas (bwd_gates.slabs_for / sla
 shorter than the ring, both sides of every slab-count cap of the kind, fewer slabs than the plan asked for, and the
 production sizes (65 536 / 196 608 points of a 1024-ray NeRF step, one 128 x 128 x 36 C4 image per FiLM group).
 
+The FiLM depth kinds (hidden_layers 4..12 other than 8) run the same `run` and the same stage checks from
+test_gpu_bwd_stages_depth.py, which holds their depth x size matrix.
+
 Measured on one MI355X: the 66 cases take 20 s, with a device-memory peak of 34 GiB allocated (40 GiB held by torch's
 cache) - the two 589 824-point FiLM images, 22 GiB of acts + grads; stage B works on blocks of ROWS points to keep its
 float64 temporaries small."""
@@ -79,12 +82,21 @@ def samples_for(ppg):
     return 1
 
 
-def run(kind, ppg, n_img, sharp, seed):
-    """Training forward + backward through the C ABI; returns everything the stages read and wrote."""
+CANARY = 0x5CA1AB1E            # the bit pattern of every float of a workspace's tail (run(..., tail=n))
+
+
+def run(kind, ppg, n_img, sharp, seed, pf=None, film=None, kind_queries=False, tail=0):
+    """Training forward + backward through the C ABI; returns everything the stages read and wrote.
+
+    pf / film: another packed field of the kind's network (a FiLM depth kind, a kind id of the same network, a w_0) and
+    its FiLM table, instead of the synthetic fixed-kind field.  kind_queries: size the two scratch buffers with the _kind
+    queries (the only ones that know a depth kind).  tail: floats of CANARY behind the queried size of acts, grads and both
+    scratch buffers; st["tails"] names the buffers whose tail the two calls changed."""
     from mirender import _lib
     lib = _lib.load()
-    k = G.KIND_IDS[kind]
-    _m, pf = packed(kind, sharp)
+    if pf is None:
+        _m, pf = packed(kind, sharp)
+    k = pf.kind
     S = samples_for(ppg)
     rpg = ppg // S
     n, P = n_img * rpg, n_img * ppg
@@ -94,8 +106,18 @@ def run(kind, ppg, n_img, sharp, seed):
     d = -o / 4.0 + 0.3 * torch.randn(n, 3, device=dev(), generator=g)
     rays = torch.stack([o, d], 1).contiguous()
     z = torch.sort(2.0 + 4.0 * torch.rand(n, S, device=dev(), generator=g), 1).values.contiguous()
-    film = synth.film_params(n_img, seed=seed).to(dev()).contiguous() if kind.startswith("film") else None
-    acts = torch.empty(lib.mi_field_train_acts_floats(k) * P, device=dev())
+    if film is None and kind.startswith("film"):
+        film = synth.film_params(n_img, seed=seed).to(dev()).contiguous()
+    tails = {}
+
+    def buffer(name, floats):
+        assert floats > 0, (name, floats, lib.mi_last_error())
+        t = torch.empty(floats + tail, device=dev())
+        if tail:
+            tails[name] = t[floats:].view(torch.int32).fill_(CANARY)
+        return t[:floats]
+
+    acts = buffer("acts", lib.mi_field_train_acts_floats(k) * P)
     raw = torch.empty(n, S, 4, device=dev())
     stream = _lib.stream_ptr(dev())
     _lib.check(lib.mi_field_eval_rays_train(k, _lib.ptr(pf.refresh()), _lib.ptr(film), _lib.ptr(rays), _lib.ptr(z),
@@ -105,13 +127,14 @@ def run(kind, ppg, n_img, sharp, seed):
     mag = 10.0 ** (4.0 * torch.rand(n, 1, 1, device=dev(), generator=g) - 3.0)
     mag[::29] = 0.0
     g_raw = (torch.randn(n, S, 4, device=dev(), generator=g) * mag).reshape(P, 4).contiguous()
-    gws = torch.empty(lib.mi_field_train_grads_floats(k) * P, device=dev())
-    part = torch.empty(lib.mi_field_bwd_partial_floats(P), device=dev())
+    gws = buffer("grads", lib.mi_field_train_grads_floats(k) * P)
+    part = buffer("partial", lib.mi_field_bwd_partial_floats_kind(k, P) if kind_queries else lib.mi_field_bwd_partial_floats(P))
     out = [torch.empty_like(p) for p in pf.params]
     arr = (ctypes.c_void_p * len(out))(*[t.data_ptr() for t in out])
     fp = gfilm = par = None
     if film is not None:
-        fp = torch.empty(lib.mi_field_film_partial_floats(n_img, ppg), device=dev())
+        fp = buffer("film partial", lib.mi_field_film_partial_floats_kind(k, n_img, ppg) if kind_queries
+                    else lib.mi_field_film_partial_floats(n_img, ppg))
         gfilm = torch.empty_like(film)
         par = (ctypes.c_void_p * len(out))(*[p.data_ptr() for p in pf.params])
     _lib.check(lib.mi_field_backward(k, _lib.ptr(pf.refresh_bwd()), _lib.ptr(film), _lib.ptr(acts), _lib.ptr(gws),
@@ -119,10 +142,11 @@ def run(kind, ppg, n_img, sharp, seed):
                                      ppg if film is not None else P, _lib.ptr(part), _lib.ptr(fp), arr, par, len(out),
                                      _lib.ptr(gfilm), stream), "mi_field_backward")
     torch.cuda.synchronize()
-    del part
+    touched = [name for name, t in tails.items() if not bool((t == CANARY).all())]
+    del part, tails
     return dict(P=P, ppg=ppg, n_img=n_img, w0=pf.w_0, params=[p.detach() for p in pf.params], film=film,
                 A=G.regions(G.ACTS[kind], acts, P), D=G.regions(G.GRADS[kind], gws, P), raw=raw.reshape(P, 4),
-                g_raw=g_raw, grads=out, film_partial=fp, grad_film=gfilm)
+                g_raw=g_raw, grads=out, film_partial=fp, grad_film=gfilm, rays=rays, z=z, acts=acts, gws=gws, tails=touched)
 
 
 def _images(st, lay):
@@ -270,10 +294,11 @@ KFS = 256 * 256 + 256          # one 256-wide FiLM layer's T_l and s_l in the Fi
 
 
 def _film_scratch(case, st, l, T_parts, s, s_b):
-    """The last image's T_l / s_l as reduce_jobs_kernel left them: T_l [256][256] + s_l [256] for l = 1..8, then the K = 3
-    blocks of layer 0 (xyz) and layer 8 (dir) as [256][3], then s_0."""
+    """The last image's T_l / s_l as reduce_jobs_kernel left them: T_l [256][256] + s_l [256] for l = 1..L (L = 8 for the
+    fixed kinds: one row of the FiLM table less), then the K = 3 blocks of layer 0 (xyz) and layer L (dir) as [256][3],
+    then s_0."""
     fp, ok = st["film_partial"], True
-    base3 = 8 * KFS
+    base3 = (st["film"].shape[1] - 1) * KFS
     for r, T, Tb, L in T_parts:
         if r.c1 - r.c0 == 256:
             got = fp[(l - 1) * KFS:(l - 1) * KFS + 65536].view(256, 256)
