@@ -234,6 +234,37 @@ int mi_field_backward(int kind, const float* packed_bwd, const float* film, cons
                       float* partial_ws, float* film_partial_ws, float* const* grad_params,
                       const float* const* params, int n_params, float* grad_film, void* stream);
 
+/* ---- gradients to the field's inputs and to the rays (ray_grad.hip): opt-in, used by mirender/pose.py --------------
+ * The reference's renderer is plain torch, so `pts = o + d z`, `view = d / |d|` and `dists * |d|`
+ * (nerf/render.py:93,122,134,143) carry a gradient back to `rays` - what camera pose refinement differentiates.  The
+ * three calls below produce it from buffers the training calls above leave behind; nothing above changes its results.
+ *
+ * mi_field_input_grad: dL/d(x) [points,6] (position | view direction, nerf/render.py:72) of the points of ONE
+ * mi_field_backward call, called after it with the same kind / film / acts / grads_ws / n_groups / points_per_group.
+ * `params` = HOST array of the n_params parameter tensors (device pointers, state-dict order), every kind.  g_x is
+ * OVERWRITTEN.  Kinds whose rgb branch takes no direction (use_dir = False) give exactly 0 in columns 3..5.
+ *
+ * mi_field_input_grad_rays: the same gradient for points on rays (mi_field_eval_rays_train's inputs), reduced along
+ * each ray without materialising [points,6]:  g_o = sum_s g_pos,s ;
+ * g_d = sum_s z_s g_pos,s + (I - v v^T) / |d| sum_s g_dir,s with v = d / |d| (render.py:122,134).
+ * g_rays [n,2,3]; accumulate != 0 adds to what it holds (the coarse and the fine pass both contribute to a ray),
+ * 0 overwrites.  One wave owns a ray and no atomics are used: results do not vary from run to run.
+ *
+ * mi_composite_bwd_rays: the part of raw_to_outputs' backward that mi_composite_bwd leaves out (same arguments):
+ * dists = delta_z * |d| (render.py:91-93), so dL/d|d| = sum_s dL/dalpha_s sigma_s delta_z_s exp(-sigma_s delta_z_s |d|)
+ * and g_d = dL/d|d| * d / |d|, the last interval's delta_z = 1e10 included (sigma = 0 there gives an exact 0).
+ * accumulate = 0 writes all six floats of a ray (g_o = 0), otherwise g_d is added to.  n_samples <= 4096.
+ * The depths get no gradient: the stratified ones do not depend on the rays, the resampled ones are detached
+ * (render.py:141). */
+int mi_field_input_grad(int kind, const float* const* params, int n_params, const float* film, const float* acts,
+                        const float* grads_ws, int64_t n_groups, int64_t points_per_group, float* g_x, void* stream);
+int mi_field_input_grad_rays(int kind, const float* const* params, int n_params, const float* film, const float* acts,
+                             const float* grads_ws, const float* rays, const float* z, int64_t n_groups,
+                             int64_t rays_per_group, int n_samples, int accumulate, float* g_rays, void* stream);
+int mi_composite_bwd_rays(int64_t n, int n_samples, const float* raw, const float* z, const float* rays,
+                          const float* g_rgb, const float* g_depth, const float* g_acc, const float* g_weights,
+                          int accumulate, float* g_rays, void* stream);
+
 /* ---- training pair: render_rays forward + backward in two calls (train_path.hip) ----------------------------------
  * One iteration of nerf/train_nerf.py:151-168 from C (render_rays, the loss, loss.backward(), optimizer.step()), or the
  * generator backward of pi_GAN/modules.py:159-161: mi_render_rays_train -> mi_nerf_loss (or the caller's own loss) ->

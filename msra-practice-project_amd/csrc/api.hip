@@ -403,6 +403,52 @@ int mi_field_backward(int kind, const float* packed_bwd, const float* film, cons
                                  film_partial_ws, grad_film, partial_ws, grad_params, params, (hipStream_t)stream);
 }
 
+// shared argument checks of the two input-gradient calls
+static int check_input_grad(const char* fn, int kind, const float* const* params, int n_params, const float* film,
+                            const float* acts, const float* grads_ws, int64_t n_groups, int64_t per_group, const float* out) {
+    if (bad_kind(kind)) return MI_EINVAL;
+    if (!params || !acts || !grads_ws || !out) { set_error("%s: null pointer argument", fn); return MI_EINVAL; }
+    if (n_params != 2 * field_kind(kind).n_layers) {
+        set_error("%s: kind %d expects %d parameter tensors, got %d", fn, kind, 2 * field_kind(kind).n_layers, n_params);
+        return MI_EINVAL;
+    }
+    for (int i = 0; i < n_params; ++i)
+        if (!params[i]) { set_error("%s: parameter %d is null", fn, i); return MI_EINVAL; }
+    if (is_film(kind) && !film) { set_error("%s: FiLM kind needs a film table", fn); return MI_EINVAL; }
+    if (n_groups < 0 || per_group < 0) { set_error("%s: negative size", fn); return MI_EINVAL; }
+    if (!is_film(kind) && n_groups > 1) { set_error("%s: only FiLM kinds have groups (n_groups = %lld)", fn, (long long)n_groups); return MI_EINVAL; }
+    return MI_OK;
+}
+
+int mi_field_input_grad(int kind, const float* const* params, int n_params, const float* film, const float* acts,
+                        const float* grads_ws, int64_t n_groups, int64_t points_per_group, float* g_x, void* stream) {
+    if (int rc = check_input_grad("mi_field_input_grad", kind, params, n_params, film, acts, grads_ws, n_groups,
+                                  points_per_group, g_x)) return rc;
+    return launch_field_input_grad(kind, params, film, acts, grads_ws, n_groups, points_per_group, g_x, (hipStream_t)stream);
+}
+
+int mi_field_input_grad_rays(int kind, const float* const* params, int n_params, const float* film, const float* acts,
+                             const float* grads_ws, const float* rays, const float* z, int64_t n_groups,
+                             int64_t rays_per_group, int n_samples, int accumulate, float* g_rays, void* stream) {
+    if (int rc = check_input_grad("mi_field_input_grad_rays", kind, params, n_params, film, acts, grads_ws, n_groups,
+                                  rays_per_group, g_rays)) return rc;
+    if (!rays || !z) { set_error("mi_field_input_grad_rays: null pointer argument"); return MI_EINVAL; }
+    if (n_samples < 1) { set_error("mi_field_input_grad_rays: n_samples must be positive"); return MI_EINVAL; }
+    return launch_field_input_grad_rays(kind, params, film, acts, grads_ws, rays, z, n_groups, rays_per_group, n_samples,
+                                        accumulate, g_rays, (hipStream_t)stream);
+}
+
+int mi_composite_bwd_rays(int64_t n, int n_samples, const float* raw, const float* z, const float* rays,
+                          const float* g_rgb, const float* g_depth, const float* g_acc, const float* g_weights,
+                          int accumulate, float* g_rays, void* stream) {
+    if (n < 0 || n_samples < 1 || n_samples > 4096 || !raw || !z || !rays || !g_rays) {
+        set_error("mi_composite_bwd_rays: bad arguments (non-null raw, z, rays, g_rays; 1 <= n_samples <= 4096)");
+        return MI_EINVAL;
+    }
+    return launch_composite_bwd_rays(n, n_samples, raw, z, rays, g_rgb, g_depth, g_acc, g_weights, accumulate, g_rays,
+                                     (hipStream_t)stream);
+}
+
 #ifdef MI_PROFILE_STAMPS
 void mi_debug_set_stamps(void* p) { g_stamps = (unsigned long long*)p; g_bwd_stamps = (unsigned long long*)p; }
 #endif

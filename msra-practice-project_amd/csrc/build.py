@@ -19,6 +19,7 @@ COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno
 SOURCES = {
     "field_mlp.hip": [],
     "field_mlp_bwd.hip": [],
+    "ray_grad.hip": [],
     # un-fused mul/add like the torch / NumPy ops these kernels restate
     "render_stages.hip": ["-ffp-contract=off"],
     "eval_stages.hip": ["-ffp-contract=off"],

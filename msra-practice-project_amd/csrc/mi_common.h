@@ -146,6 +146,15 @@ int launch_composite_weights_window(int64_t n, int S, const float* sigma, const 
                                     int* count_out, int k0, int k1, hipStream_t stream);
 int launch_composite_bwd(int64_t n, int S, const float* raw, const float* z, const float* rays, const float* g_rgb,
                          const float* g_depth, const float* g_acc, const float* g_w, float* g_raw, hipStream_t stream);
+int launch_composite_bwd_rays(int64_t n, int S, const float* raw, const float* z, const float* rays, const float* g_rgb,
+                              const float* g_depth, const float* g_acc, const float* g_w, int accumulate, float* g_rays,
+                              hipStream_t stream);
+// ray_grad.hip: dL/d(field inputs) of the points of one launch_field_backward call, from the acts / grads it left behind
+int launch_field_input_grad(int kind, const float* const* params, const float* film, const float* acts, const float* grads,
+                            int64_t n_groups, int64_t points_per_group, float* g_x, hipStream_t stream);
+int launch_field_input_grad_rays(int kind, const float* const* params, const float* film, const float* acts,
+                                 const float* grads, const float* rays, const float* z, int64_t n_groups,
+                                 int64_t rays_per_group, int n_samples, int accumulate, float* g_rays, hipStream_t stream);
 int64_t image_metrics_workspace_floats(int images, int channels, int H, int W);
 int launch_image_metrics(const float* img1, const float* img2, int images, int channels, int H, int W,
                          const float* window, int window_size, float* workspace, float* out, hipStream_t stream);

@@ -1,0 +1,359 @@
+// ray_grad.hip - dL/d(field inputs) and dL/d(rays) on the fused path (gfx950): what the reference's autograd carries back
+// through `network(inputs)` to `pts = o + d z` and `view = d / |d|` (nerf/render.py:93,122,134) - the gradient camera pose
+// refinement is built on.  Opt-in: only mirender/pose.py calls these.
+//
+// The backward chain (field_mlp_bwd.hip) has already written dL/d(pre-activation) of every linear layer as
+// [point][feature] rows into grads_ws (field_layout.h nerf_grads() .. film_grads_depth()); the gradient of a point's six
+// inputs is one more small contraction of the rows of the INPUT-CONSUMING layers with those layers' input columns:
+//
+//   NeRF / TinyNeRF   dE_pos = dA(layers_pos.0) W0[:, :60] (+ dA(layers_pos.5) W5[:, :60], the skip, nerf/nerf.py:84)
+//                     dE_dir = dA(dir layer) Wd[:, 256:280]
+//                     then through the encoding E[6i + c] = sin(2^i x_c), E[6i + 3 + c] = cos(2^i x_c) (nerf/nerf.py:44-49):
+//                     dx_c = sum_i 2^i (E[6i + 3 + c] dE[6i + c] - E[6i + c] dE[6i + 3 + c])
+//   SirenNeRF         dx = dA(layers_pos.0) W0[:, :3] + dA(layers_pos.5) W5[:, :3] (nerf/nerf.py:160),
+//                     dv = dA(layers_dir.1) Wd[:, 256:259]
+//   FilmSirenNeRF     dx = W_input^T (gamma_0 (.) dL/du_0), dv = W_rgb[:, 256:259]^T (gamma_rgb (.) dL/du_rgb) (use_dir), else 0:
+//                     film_bwd_kernel stores dL/du_l = dX_l (.) w_0 cos(w_0 u_l) - the sin derivative is in, gamma is not
+//                     (u = gamma (W x + b) + beta, pi_GAN/modules.py:22-25), so gamma multiplies here.
+//
+// The encoding's sin / cos values are taken from the saved E_pos / E_dir rows (acts regions 0 and 10 / 5): the oracle's
+// autograd multiplies by cos(2^i x) and sin(2^i x) of the very argument the forward used, the saved rows are the forward's
+// values of exactly those (within the forward's own gate), and the point form has no x to recompute them from - acts holds
+// the encoding, not the raw input.
+//
+// Traffic: 1 to 2.5 KiB of dA rows per point (the rows the dW GEMMs also read), next to ~9 KB per point the step already
+// moves; the kernels are bound by those reads, not by arithmetic.  Two kernels:
+//   input_grad_lin_kernel  (sin kinds, 3 + 3 input columns): a wave takes a point per step, lane l owns features
+//                          4l .. 4l + 3 (one coalesced float4 of each dA row), the 3-column weights sit in registers;
+//   input_grad_pe_kernel   (ReLU kinds, 60 + 24 encoding columns): lane = encoding column, the weight columns sit in LDS
+//                          ([256][64] per position layer, [128][32] for the dir layer), a wave takes four points per step
+//                          and reads their dA rows through wave-uniform addresses.
+// The ray form gives every ray to ONE wave, which walks the ray's samples in order, keeps per-lane partial sums and
+// reduces across lanes once per ray: g_o = sum_s g_pos, g_d = sum_s z_s g_pos + (I - v v^T) / |d| sum_s g_dir (v = d / |d|).
+// Lanes 0..5 of that wave write the ray's six floats in one store instruction; no atomics, so a result does not depend
+// on the launch's timing.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "field_kinds.h"
+
+namespace mi {
+
+struct InputGradArgs {
+    const float* dA0; const float* dA5; const float* dAd;     // dA rows of the consuming layers: [P][256] x2, [P][dir_rows]
+    const float* W0; const float* W5; const float* Wd;        // their weights [out][ld]; W5 / Wd null: the kind has none
+    int ld0, ld5, ldd;
+    int col_d;                 // first view-direction (encoding) column of Wd
+    int dir_rows;              // output features of the dir-consuming layer: 128, or 256 (FiLM)
+    const float* film;         // FiLM kinds: [groups][film_rows][512], else null
+    int film_rows, film_dir_row;
+    const float* e_pos; const float* e_dir;                   // ReLU kinds: saved encoding rows [P][64], [P][32]
+    const float* rays; const float* z;                        // ray form: [n,2,3], [n,S]
+    float* out;                // point form: g_x [P,6]; ray form: g_rays [n,2,3]
+    int64_t units;             // ray form: rays; point form: chunks of kChunk points that do not straddle a group
+    int64_t units_per_group;
+    int64_t points_per_group;
+    int n_samples;
+    int accumulate;
+};
+
+constexpr int kChunk = 32;     // points of a point-form unit
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// first point and point count of unit u (wave-uniform), and its FiLM group
+template <bool RAYS>
+__device__ __forceinline__ void unit_points(const InputGradArgs& a, int64_t u, int64_t& p0, int& cnt, int64_t& group) {
+    group = u / a.units_per_group;
+    if constexpr (RAYS) {
+        p0 = u * a.n_samples;
+        cnt = a.n_samples;
+    } else {
+        const int64_t c = u % a.units_per_group;
+        p0 = group * a.points_per_group + c * kChunk;
+        const int64_t left = a.points_per_group - c * kChunk;
+        cnt = left < kChunk ? (int)left : kChunk;
+    }
+}
+
+// Lanes 0..5 write a ray's (g_o | g_d) from the ray's reduced sums (every lane holds them): so = sum g_pos,
+// sz = sum z g_pos, sv = sum g_dir.
+__device__ __forceinline__ void store_ray(const InputGradArgs& a, int64_t ray, int lane, const float (&so)[3],
+                                          const float (&sz)[3], const float (&sv)[3]) {
+    const float* d = a.rays + ray * 6 + 3;
+    const float d0 = d[0], d1 = d[1], d2 = d[2];
+    const float nrm = sqrtf(d0 * d0 + d1 * d1 + d2 * d2);
+    const float v0 = d0 / nrm, v1 = d1 / nrm, v2 = d2 / nrm;
+    const float vg = v0 * sv[0] + v1 * sv[1] + v2 * sv[2];
+    const float g[6] = {so[0], so[1], so[2], sz[0] + (sv[0] - v0 * vg) / nrm, sz[1] + (sv[1] - v1 * vg) / nrm,
+                        sz[2] + (sv[2] - v2 * vg) / nrm};
+    float mine = g[0];
+#pragma unroll
+    for (int j = 1; j < 6; ++j) mine = lane == j ? g[j] : mine;
+    if (lane < 6) {
+        float* o = a.out + ray * 6 + lane;
+        *o = a.accumulate ? *o + mine : mine;
+    }
+}
+
+// =========================================================================================
+// sin kinds: raw xyz / dir inputs, three columns per consuming layer
+// =========================================================================================
+template <bool RAYS>
+__global__ __launch_bounds__(256) void input_grad_lin_kernel(InputGradArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const bool dir_lane = a.Wd && 4 * lane < a.dir_rows;
+    float w0[4][3], w5[4][3], wd[4][3];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const int k = 4 * lane + q;
+            w0[q][j] = a.W0[(int64_t)k * a.ld0 + j];
+            w5[q][j] = a.W5 ? a.W5[(int64_t)k * a.ld5 + j] : 0.f;
+            wd[q][j] = dir_lane ? a.Wd[(int64_t)k * a.ldd + a.col_d + j] : 0.f;
+        }
+    const int64_t stride = (int64_t)gridDim.x * 4;
+    for (int64_t u = (int64_t)blockIdx.x * 4 + wave; u < a.units; u += stride) {
+        int64_t p0, group;
+        int cnt;
+        unit_points<RAYS>(a, u, p0, cnt, group);
+        float4 g0 = {1.f, 1.f, 1.f, 1.f}, gd = {1.f, 1.f, 1.f, 1.f};
+        if (a.film) {                                     // gamma of the input layer and of the rgb hidden layer
+            const float* row = a.film + group * ((int64_t)a.film_rows * kFilmRow);
+            g0 = reinterpret_cast<const float4*>(row)[lane];
+            gd = reinterpret_cast<const float4*>(row + (int64_t)a.film_dir_row * kFilmRow)[lane];
+        }
+        float so[3] = {0.f, 0.f, 0.f}, sz[3] = {0.f, 0.f, 0.f}, sv[3] = {0.f, 0.f, 0.f};
+        for (int s = 0; s < cnt; ++s) {
+            const int64_t p = p0 + s;
+            float4 r = reinterpret_cast<const float4*>(a.dA0 + p * 256)[lane];
+            r.x *= g0.x; r.y *= g0.y; r.z *= g0.z; r.w *= g0.w;
+            float gp[3], gv[3];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) gp[j] = r.x * w0[0][j] + r.y * w0[1][j] + r.z * w0[2][j] + r.w * w0[3][j];
+            if (a.dA5) {
+                const float4 t = reinterpret_cast<const float4*>(a.dA5 + p * 256)[lane];
+#pragma unroll
+                for (int j = 0; j < 3; ++j) gp[j] += t.x * w5[0][j] + t.y * w5[1][j] + t.z * w5[2][j] + t.w * w5[3][j];
+            }
+            float4 t = {0.f, 0.f, 0.f, 0.f};
+            if (dir_lane) t = reinterpret_cast<const float4*>(a.dAd + p * a.dir_rows)[lane];
+            t.x *= gd.x; t.y *= gd.y; t.z *= gd.z; t.w *= gd.w;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) gv[j] = t.x * wd[0][j] + t.y * wd[1][j] + t.z * wd[2][j] + t.w * wd[3][j];
+            if constexpr (RAYS) {
+                const float zs = a.z[p];
+#pragma unroll
+                for (int j = 0; j < 3; ++j) { so[j] += gp[j]; sz[j] += zs * gp[j]; sv[j] += gv[j]; }
+            } else {
+                float mine = 0.f;
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    const float x = wave_sum(gp[j]), v = wave_sum(gv[j]);
+                    mine = lane == j ? x : lane == 3 + j ? v : mine;
+                }
+                if (lane < 6) a.out[p * 6 + lane] = mine;
+            }
+        }
+        if constexpr (RAYS) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) { so[j] = wave_sum(so[j]); sz[j] = wave_sum(sz[j]); sv[j] = wave_sum(sv[j]); }
+            store_ray(a, u, lane, so, sz, sv);
+        }
+    }
+}
+
+// =========================================================================================
+// ReLU kinds: positional encodings, 60 + 24 columns
+// =========================================================================================
+constexpr int kPeThreads = 1024;                  // 16 waves share one copy of the weight columns in LDS
+constexpr int kPePosFloats = 256 * 64, kPeDirFloats = 128 * 32;
+
+// dE[q] += sum_k rows[q][k] * cols[k][lane]: rows through wave-uniform addresses, columns from LDS
+template <int K, int LDW>
+__device__ __forceinline__ void pe_contract(float (&dE)[4], const float* const (&rows)[4], const float* cols, int col) {
+#pragma unroll 2
+    for (int k = 0; k < K; k += 4) {
+        float w[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) w[i] = cols[(k + i) * LDW + col];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float4 r = *reinterpret_cast<const float4*>(rows[q] + k);
+            dE[q] = fmaf(r.x, w[0], dE[q]);
+            dE[q] = fmaf(r.y, w[1], dE[q]);
+            dE[q] = fmaf(r.z, w[2], dE[q]);
+            dE[q] = fmaf(r.w, w[3], dE[q]);
+        }
+    }
+}
+
+template <bool RAYS>
+__global__ __launch_bounds__(kPeThreads) void input_grad_pe_kernel(InputGradArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float* L0 = lds;
+    float* L5 = lds + kPePosFloats;
+    float* Ld = lds + (a.W5 ? 2 : 1) * kPePosFloats;
+    for (int i = threadIdx.x; i < kPePosFloats; i += kPeThreads) {
+        const int k = i >> 6, c = i & 63;
+        L0[i] = c < 60 ? a.W0[(int64_t)k * a.ld0 + c] : 0.f;
+        if (a.W5) L5[i] = c < 60 ? a.W5[(int64_t)k * a.ld5 + c] : 0.f;
+    }
+    for (int i = threadIdx.x; i < kPeDirFloats; i += kPeThreads) {
+        const int k = i >> 5, c = i & 31;
+        Ld[i] = c < 24 ? a.Wd[(int64_t)k * a.ldd + a.col_d + c] : 0.f;
+    }
+    __syncthreads();
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    // lane f <-> encoding feature f = 6 i + c: c < 3 sin(2^i x_c), else cos(2^i x_{c-3}); its partner holds the other one.
+    // d sin(s x) = s cos(s x) dx, d cos(s x) = -s sin(s x) dx: coef = +-2^i times the partner's saved value.
+    const int fi = lane / 6, fc = lane % 6;
+    const bool is_cos = fc >= 3;
+    const int comp = fc % 3;
+    const int mate_p = lane < 60 ? (is_cos ? lane - 3 : lane + 3) : lane;
+    const float coef_p = lane < 60 ? (is_cos ? -(float)(1 << fi) : (float)(1 << fi)) : 0.f;
+    const int dl = lane & 31;
+    const int mate_d = dl < 24 ? (is_cos ? dl - 3 : dl + 3) : dl;             // lanes < 24: same (i, c) as above
+    const float coef_d = lane < 24 ? (is_cos ? -(float)(1 << fi) : (float)(1 << fi)) : 0.f;
+
+    const int64_t stride = (int64_t)gridDim.x * (kPeThreads / 64);
+    for (int64_t u = (int64_t)blockIdx.x * (kPeThreads / 64) + wave; u < a.units; u += stride) {
+        int64_t p0, group;
+        int cnt;
+        unit_points<RAYS>(a, u, p0, cnt, group);
+        float tp = 0.f, tz = 0.f, tv = 0.f;                // ray form: per-lane sums over the ray's samples
+        for (int s0 = 0; s0 < cnt; s0 += 4) {
+            int64_t p[4];
+            const float* r0[4];
+            const float* r5[4];
+            const float* rd[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                p[q] = p0 + (s0 + q < cnt ? s0 + q : cnt - 1);           // past the unit's end: its last point again, masked below
+                r0[q] = a.dA0 + p[q] * 256;
+                r5[q] = a.dA5 ? a.dA5 + p[q] * 256 : nullptr;
+                rd[q] = a.dAd + p[q] * 128;
+            }
+            float dEp[4] = {0.f, 0.f, 0.f, 0.f}, dEd[4] = {0.f, 0.f, 0.f, 0.f};
+            pe_contract<256, 64>(dEp, r0, L0, lane);
+            if (a.W5) pe_contract<256, 64>(dEp, r5, L5, lane);
+            pe_contract<128, 32>(dEd, rd, Ld, dl);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const bool in = s0 + q < cnt;
+                const float ep = a.e_pos[p[q] * 64 + mate_p], ed = a.e_dir[p[q] * 32 + mate_d];
+                const float t = in ? (dEp[q] * ep) * coef_p : 0.f;
+                const float v = in ? (dEd[q] * ed) * coef_d : 0.f;
+                if constexpr (RAYS) {
+                    const float zs = a.z[p[q]];
+                    tp += t; tz += zs * t; tv += v;
+                } else if (in) {                                        // wave-uniform
+                    float mine = 0.f;
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) {
+                        const float x = wave_sum(comp == j ? t : 0.f), w = wave_sum(comp == j ? v : 0.f);
+                        mine = lane == j ? x : lane == 3 + j ? w : mine;
+                    }
+                    if (lane < 6) a.out[p[q] * 6 + lane] = mine;
+                }
+            }
+        }
+        if constexpr (RAYS) {
+            float so[3], sz[3], sv[3];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                so[j] = wave_sum(comp == j ? tp : 0.f);
+                sz[j] = wave_sum(comp == j ? tz : 0.f);
+                sv[j] = wave_sum(comp == j ? tv : 0.f);
+            }
+            store_ray(a, u, lane, so, sz, sv);
+        }
+    }
+}
+
+// =========================================================================================
+// host side
+// =========================================================================================
+static int launch_input_grad(int kind_in, const float* const* params, const float* film, const float* acts,
+                             const float* grads, const float* rays, const float* z, int64_t n_groups, int64_t units_pg,
+                             int n_samples, bool ray_form, int accumulate, float* out, hipStream_t stream) {
+    const int kind = canon_kind(kind_in);
+    const FieldKind& K = field_kind(kind);
+    const int64_t ppg = ray_form ? units_pg * n_samples : units_pg;
+    const int64_t P = n_groups * ppg;
+    if (P == 0) return 0;
+    const auto G = [&](int region) { return grads + (int64_t)region_offset(K.grads, region) * P; };
+    const auto A = [&](int region) { return acts + (int64_t)region_offset(K.acts, region) * P; };
+    InputGradArgs a = {};
+    a.rays = rays; a.z = z; a.out = out; a.n_samples = n_samples; a.accumulate = accumulate;
+    a.points_per_group = ppg;
+    a.units_per_group = ray_form ? units_pg : (ppg + kChunk - 1) / kChunk;
+    a.units = n_groups * a.units_per_group;
+    a.W0 = params[0]; a.ld0 = K.dims[0][1]; a.dA0 = G(0);
+    bool pe = false;
+    if (kind == MI_FIELD_NERF || kind == MI_FIELD_SIREN_NERF) {
+        // layers_pos.5 = [input | h] (nerf/nerf.py:84,160), layers_dir.1 = [h | dir] (grads regions 5 and 9)
+        a.W5 = params[10]; a.ld5 = K.dims[5][1]; a.dA5 = G(5);
+        a.Wd = params[18]; a.ldd = K.dims[9][1]; a.dAd = G(9); a.col_d = 256; a.dir_rows = 128;
+        pe = kind == MI_FIELD_NERF;
+        if (pe) { a.e_pos = A(0); a.e_dir = A(10); }
+    } else if (kind == MI_FIELD_TINY_NERF) {
+        a.Wd = params[8]; a.ldd = K.dims[4][1]; a.dAd = G(4); a.col_d = 256; a.dir_rows = 128;
+        pe = true;
+        a.e_pos = A(0); a.e_dir = A(5);
+    } else {                                              // FiLM: input_layer, hidden_layer_rgb (layer L + 1, FiLM row L)
+        const int L = film_depth(kind);
+        a.film = film; a.film_rows = L + 1; a.film_dir_row = L;
+        if (K.use_dir) { a.Wd = params[2 * (L + 1)]; a.ldd = K.dims[L + 1][1]; a.dAd = G(L); a.col_d = 256; a.dir_rows = 256; }
+    }
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (pe) {
+        const size_t lds = ((a.W5 ? 2 : 1) * kPePosFloats + kPeDirFloats) * sizeof(float);
+        static_assert((2 * kPePosFloats + kPeDirFloats) * sizeof(float) <= 160 * 1024, "the weight columns fit a CU's LDS");
+        const void* fn = ray_form ? (const void*)input_grad_pe_kernel<true> : (const void*)input_grad_pe_kernel<false>;
+        static PerDeviceOnce attr_once[2];
+        const int arc = attr_once[ray_form].run([&]() {
+            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)((2 * kPePosFloats + kPeDirFloats) * sizeof(float))) != hipSuccess) {
+                set_error("hipFuncSetAttribute(input_grad_pe) failed"); return -2;
+            }
+            return 0;
+        });
+        if (arc) return arc;
+        const int64_t per_block = kPeThreads / 64;
+        const int64_t want = (a.units + per_block - 1) / per_block;
+        const dim3 grid((unsigned)(want < cus ? want : cus));
+        if (ray_form) hipLaunchKernelGGL(input_grad_pe_kernel<true>, grid, dim3(kPeThreads), lds, stream, a);
+        else hipLaunchKernelGGL(input_grad_pe_kernel<false>, grid, dim3(kPeThreads), lds, stream, a);
+        return check_launch("input_grad_pe");
+    }
+    const int64_t want = (a.units + 3) / 4, cap = (int64_t)cus * 8;
+    const dim3 grid((unsigned)(want < cap ? want : cap));
+    if (ray_form) hipLaunchKernelGGL(input_grad_lin_kernel<true>, grid, dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(input_grad_lin_kernel<false>, grid, dim3(256), 0, stream, a);
+    return check_launch("input_grad_lin");
+}
+
+int launch_field_input_grad(int kind, const float* const* params, const float* film, const float* acts, const float* grads,
+                            int64_t n_groups, int64_t points_per_group, float* g_x, hipStream_t stream) {
+    return launch_input_grad(kind, params, film, acts, grads, nullptr, nullptr, n_groups, points_per_group, 1, false, 0,
+                             g_x, stream);
+}
+
+int launch_field_input_grad_rays(int kind, const float* const* params, const float* film, const float* acts,
+                                 const float* grads, const float* rays, const float* z, int64_t n_groups,
+                                 int64_t rays_per_group, int n_samples, int accumulate, float* g_rays, hipStream_t stream) {
+    return launch_input_grad(kind, params, film, acts, grads, rays, z, n_groups, rays_per_group, n_samples, true, accumulate,
+                             g_rays, stream);
+}
+
+}  // namespace mi

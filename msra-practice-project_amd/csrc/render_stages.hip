@@ -357,6 +357,84 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(int64_t n, int S, co
 }
 
 // ---------------------------------------------------------------------------------------
+// composite backward towards the ray direction: the part of raw_to_outputs' autograd that composite_bwd_kernel leaves
+// out.  render.py:91-93: dists = delta_z * |d|, alpha = 1 - exp(-sigma * dists), so
+//   dL/d|d| = sum_k ((dL/dalpha_k * exp(-sigma_k dists_k)) * sigma_k) * delta_z_k      (autograd's order of products)
+//   dL/dd   = dL/d|d| * d / |d|                                                         (torch.norm's backward)
+// with dL/dalpha_k exactly as in composite_bwd_kernel (same two sweeps, the transmittances parked in LDS instead of
+// the output).  The last interval's delta_z is 1e10 like the reference's: sigma = 0 gives (x * 0) * 1e10 = 0, sigma > 0
+// gives exp(-huge) = 0, both finite.  z carries no gradient (render.py:141), the origin none from compositing.
+// accumulate = 0 writes the ray's six floats (g_o = 0), otherwise the three of g_d are added to.
+// ---------------------------------------------------------------------------------------
+template <int G>
+__global__ __launch_bounds__(256) void composite_bwd_rays_kernel(int64_t n, int S, const float* __restrict__ raw,
+                                                                 const float* __restrict__ z,
+                                                                 const float* __restrict__ rays,
+                                                                 const float* __restrict__ g_rgb,
+                                                                 const float* __restrict__ g_depth,
+                                                                 const float* __restrict__ g_acc,
+                                                                 const float* __restrict__ g_w, int accumulate,
+                                                                 float* __restrict__ g_rays) {
+    extern __shared__ float s_trans[];                   // [256 / G][S]
+    const int lane = threadIdx.x & 63;
+    const int sub = lane & (G - 1);
+    const int64_t ray = (int64_t)blockIdx.x * (256 / G) + threadIdx.x / G;
+    const bool live = ray < n;
+    const int64_t rc = live ? ray : n - 1;
+    const float nrm = ray_norm(rays, rc);
+    const float gr = g_rgb ? g_rgb[rc * 3 + 0] : 0.f, gg = g_rgb ? g_rgb[rc * 3 + 1] : 0.f,
+                gb = g_rgb ? g_rgb[rc * 3 + 2] : 0.f;
+    const float gd = g_depth ? g_depth[rc] : 0.f, ga = g_acc ? g_acc[rc] : 0.f;
+    const float4* rw = reinterpret_cast<const float4*>(raw) + rc * S;
+    const float* zr = z + rc * S;
+    float* tr = s_trans + (int64_t)(threadIdx.x / G) * S;
+    const int passes = (S + G - 1) / G;
+    double T = 1.0;
+    for (int pass = 0; pass < passes; ++pass) {
+        const int k = pass * G + sub;
+        const bool in = k < S;
+        const int kc = in ? k : S - 1;
+        const PassOut o = composite_pass<G>(sub, in, rw[kc].w, sample_delta(zr + kc, S, kc, nrm), T);
+        if (in) tr[k] = o.trans;
+        T = T * __shfl(o.p, G - 1, G);
+    }
+    float carry = 0.f, gn = 0.f;
+    for (int pass = passes - 1; pass >= 0; --pass) {
+        const int k = pass * G + sub;
+        const bool in = k < S;
+        const int kc = in ? k : S - 1;
+        const float4 c = rw[kc];
+        const float zk = zr[kc];
+        const float dz = kc + 1 < S ? zr[kc + 1] - zk : 1e10f;
+        const float e = expf(-c.w * sample_delta(zr + kc, S, kc, nrm));
+        const float alpha = 1.0f - e;
+        const float Tk = in ? tr[kc] : 0.f;
+        float Gk = gr * (c.x - 1.f) + gg * (c.y - 1.f) + gb * (c.z - 1.f) + gd * zk + ga;
+        if (g_w) Gk += g_w[rc * S + kc];
+        float M = in ? (1.0f - alpha) + 1e-10f : 1.f, A = in ? Gk * alpha : 0.f;
+#pragma unroll
+        for (int o = 1; o < G; o <<= 1) {
+            const float M2 = __shfl_down(M, o, G), A2 = __shfl_down(A, o, G);
+            if (sub + o < G) { A = A + M * A2; M = M * M2; }
+        }
+        const float R = A + M * carry;
+        float Snext = __shfl_down(R, 1, G);
+        if (sub == G - 1) Snext = carry;
+        carry = __shfl(R, 0, G);
+        if (in) gn += ((Tk * (Gk - Snext) * e) * c.w) * dz;
+    }
+#pragma unroll
+    for (int o = G / 2; o > 0; o >>= 1) gn += __shfl_xor(gn, o, G);
+    if (live && sub < 6) {
+        const float* rd = rays + ray * 6 + 3;
+        float* out = g_rays + ray * 6 + sub;
+        const float v = sub < 3 ? 0.f : gn * rd[sub - 3] / nrm;
+        if (!accumulate) *out = v;
+        else if (sub >= 3) *out += v;
+    }
+}
+
+// ---------------------------------------------------------------------------------------
 // cdf[j] = fp32(sum_{i<j} pdf[i]) with the running sum in fp64, j = 0..nb-1, pdf[0..nb-2] in LDS: ATen's CPU cumsum
 // keeps the running sum in the accumulate type of float, i.e. DOUBLE, and rounds every output to fp32
 // (cpu_cum_base_kernel).  A double holds every partial sum of these floats EXACTLY whenever the terms' exponents span
@@ -651,6 +729,18 @@ int launch_composite_bwd(int64_t n, int S, const float* raw, const float* z, con
                            g_acc, g_w, g_raw);
     });
     return check_launch("composite_bwd");
+}
+
+int launch_composite_bwd_rays(int64_t n, int S, const float* raw, const float* z, const float* rays, const float* g_rgb,
+                              const float* g_depth, const float* g_acc, const float* g_w, int accumulate, float* g_rays,
+                              hipStream_t stream) {
+    if (n <= 0) return 0;
+    dispatch_G(S, [&](auto g) {
+        constexpr int G = decltype(g)::value;
+        hipLaunchKernelGGL(composite_bwd_rays_kernel<G>, ray_grid<G>(n), dim3(256), (size_t)(256 / G) * S * sizeof(float),
+                           stream, n, S, raw, z, rays, g_rgb, g_depth, g_acc, g_w, accumulate, g_rays);
+    });
+    return check_launch("composite_bwd_rays");
 }
 
 int launch_sample_pdf(int64_t n, int nb, int ns, const float* bins, const float* weights, const float* u_lin, float* out,

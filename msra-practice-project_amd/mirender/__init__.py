@@ -2,8 +2,9 @@
 
     from mirender import ops, fields, render_core
 
+`mirender.pose` is the opt-in surface whose graph also reaches the rays (camera pose refinement).
 Drop-in modules named `render` live in ../nerf/render.py and ../pi_GAN/render.py.
 """
-from . import _lib, fields, ops, render_core  # noqa: F401
+from . import _lib, fields, ops, pose, render_core  # noqa: F401
 
-__all__ = ["_lib", "fields", "ops", "render_core"]
+__all__ = ["_lib", "fields", "ops", "pose", "render_core"]

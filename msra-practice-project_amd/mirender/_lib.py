@@ -69,6 +69,10 @@ SIGNATURES = {
     "mi_field_film_partial_floats_kind": (_i64, [_int, _i64, _i64]),
     "mi_field_backward": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, ctypes.POINTER(_vp),
                                  ctypes.POINTER(_vp), _int, _vp, _vp]),
+    "mi_field_input_grad": (_int, [_int, ctypes.POINTER(_vp), _int, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
+    "mi_field_input_grad_rays": (_int, [_int, ctypes.POINTER(_vp), _int, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int,
+                                        _vp, _vp]),
+    "mi_composite_bwd_rays": (_int, [_i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp]),
     "mi_render_train_saved_bytes": (_i64, [_int, _int, _int, _i64, _int, _int]),
     "mi_render_backward_workspace_bytes": (_i64, [_int, _int, _int, _i64, _i64, _int, _int, _i64, _i64]),
     "mi_render_rays_train": (_int, [_int, _vp, _int, _vp, _vp, _vp, _i64, _i64, _f32, _f32, _int, _int, _vp, _vp, _vp,

@@ -172,10 +172,14 @@ def _forward_pass(pf: fields.PackedField, rays, z, film, cap: int, all_or_nothin
     return (parts[0] if len(parts) == 1 else torch.cat(parts)), saved
 
 
-def _field_backward(pf: fields.PackedField, rays, z, raw, g_raw, film, saved=None):
+def _field_backward(pf: fields.PackedField, rays, z, raw, g_raw, film, saved=None, input_grad=None):
     """Gradients of one pass: (list of tensors shaped like pf.params, grad of the FiLM table or None).
     `saved` = {range index: layer inputs kept by the forward}; the other ranges re-run the forward first, so
-    memory stays bounded whatever the batch."""
+    memory stays bounded whatever the batch.
+    `input_grad` (mirender.pose only; None leaves this function as it is for every other caller): a tensor that also
+    receives the gradient of the pass's geometric inputs, range by range from the buffers each range's backward leaves
+    behind - g_rays [n,2,3], ADDED to, for points on rays (mi_field_input_grad_rays); g_x [M,6], overwritten, for
+    free-standing points (mi_field_input_grad)."""
     lib = _lib.load()
     dev = pf.device
     grads_f = lib.mi_field_train_grads_floats(pf.kind)
@@ -186,6 +190,8 @@ def _field_backward(pf: fields.PackedField, rays, z, raw, g_raw, film, saved=Non
     g_film = None if f_all is None else torch.empty_like(f_all)
     packed_bwd = pf.refresh_bwd()
     stream = _lib.stream_ptr(dev)
+    srcs = pf._sources() if input_grad is not None else None          # contiguous fp32 views of the live parameters
+
     def one_range(k, r0, r1):
         pts = (r1 - r0) * s
         f_c = g_c = fp = None
@@ -215,6 +221,16 @@ def _field_backward(pf: fields.PackedField, rays, z, raw, g_raw, film, saved=Non
             _lib.check(lib.mi_field_backward(pf.kind, _lib.ptr(packed_bwd), _lib.ptr(f_c), _lib.ptr(acts_c), _lib.ptr(gws),
                                              _lib.ptr(raw_c), _lib.ptr(g_raw[r0:r1]), ng, ppg, _lib.ptr(part),
                                              _lib.ptr(fp), arr, par, len(out), _lib.ptr(g_c), stream), "mi_field_backward")
+            if input_grad is not None:
+                src = (ctypes.c_void_p * len(srcs))(*[t.data_ptr() for t in srcs])
+                if z is None:
+                    _lib.check(lib.mi_field_input_grad(pf.kind, src, len(srcs), _lib.ptr(f_c), _lib.ptr(acts_c), _lib.ptr(gws),
+                                                       ng, ppg, _lib.ptr(input_grad[r0:r1]), stream), "mi_field_input_grad")
+                else:
+                    _lib.check(lib.mi_field_input_grad_rays(pf.kind, src, len(srcs), _lib.ptr(f_c), _lib.ptr(acts_c),
+                                                            _lib.ptr(gws), _lib.ptr(rays[r0:r1]), _lib.ptr(z[r0:r1]), ng,
+                                                            (r1 - r0) // ng, s, 1, _lib.ptr(input_grad[r0:r1]), stream),
+                               "mi_field_input_grad_rays")
         del acts_c
         _check_guard(gws_g, "per-layer gradients (mi_field_train_grads_floats)")
         _check_guard(part_g, "backward scratch (mi_field_bwd_partial_floats)")
@@ -262,6 +278,19 @@ def _composite_bwd(raw, z, rays, g_rgb, g_depth, g_acc, g_w=None):
     return g_raw
 
 
+def _composite_bwd_rays(raw, z, rays, g_rgb, g_depth, g_acc, g_rays, g_w=None):
+    """mirender.pose: adds compositing's gradient to the ray directions (dists = delta_z |d|, render.py:91-93) to g_rays."""
+    lib = _lib.load()
+    dev = raw.device
+    n, s = z.shape
+    c = lambda t: None if t is None else t.detach().to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731
+    g_rgb, g_depth, g_acc, g_w = c(g_rgb), c(g_depth), c(g_acc), c(g_w)
+    with torch.cuda.device(dev):
+        _lib.check(lib.mi_composite_bwd_rays(n, s, _lib.ptr(raw), _lib.ptr(z), _lib.ptr(rays), _lib.ptr(g_rgb),
+                                             _lib.ptr(g_depth), _lib.ptr(g_acc), _lib.ptr(g_w), 1, _lib.ptr(g_rays),
+                                             _lib.stream_ptr(dev)), "mi_composite_bwd_rays")
+
+
 class _RenderRaysFn(torch.autograd.Function):
     """render_rays with autograd.  Two shapes:
 
@@ -307,7 +336,9 @@ class _RenderRaysFn(torch.autograd.Function):
         return rgb_c, depth_c, acc_c, rgb_f, depth_f, acc_f
 
     @staticmethod
-    def backward(ctx, g_rgb_c, g_depth_c, g_acc_c, g_rgb_f, g_depth_f, g_acc_f):
+    def backward(ctx, g_rgb_c, g_depth_c, g_acc_c, g_rgb_f, g_depth_f, g_acc_f, g_rays=None):
+        # g_rays: never passed by autograd; mirender.pose's function calls this with zeros [n,2,3] that additionally receive
+        # the gradient to the rays - from each compositing pass (|d| in the distances) and each field pass (o + d z, d / |d|)
         rays, z_c, raw_c, z_f, raw_f, z_s, raw_s, pos = ctx.saved_tensors
         pf_c, pf_f = ctx.pf_c, ctx.pf_f
         if (pf_c.versions(), pf_f.versions()) != ctx.versions:
@@ -322,24 +353,32 @@ class _RenderRaysFn(torch.autograd.Function):
         if not ctx.shared:
             if want_c:
                 g_raw = _composite_bwd(raw_c, z_c, rays, g_rgb_c, g_depth_c, g_acc_c)
-                grads_c, gfilm_c = _field_backward(pf_c, rays, z_c, raw_c, g_raw, ctx.film, ctx.acts_c)
+                if g_rays is not None:
+                    _composite_bwd_rays(raw_c, z_c, rays, g_rgb_c, g_depth_c, g_acc_c, g_rays)
+                grads_c, gfilm_c = _field_backward(pf_c, rays, z_c, raw_c, g_raw, ctx.film, ctx.acts_c, g_rays)
             if want_f:
                 g_raw = _composite_bwd(raw_f, z_f, rays, g_rgb_f, g_depth_f, g_acc_f)
-                grads_f, gfilm_f = _field_backward(pf_f, rays, z_f, raw_f, g_raw, ctx.film, ctx.acts_f)
+                if g_rays is not None:
+                    _composite_bwd_rays(raw_f, z_f, rays, g_rgb_f, g_depth_f, g_acc_f, g_rays)
+                grads_f, gfilm_f = _field_backward(pf_f, rays, z_f, raw_f, g_raw, ctx.film, ctx.acts_f, g_rays)
         else:
             g_c = _composite_bwd(raw_c, z_c, rays, g_rgb_c, g_depth_c, g_acc_c) if want_c else None
+            if want_c and g_rays is not None:
+                _composite_bwd_rays(raw_c, z_c, rays, g_rgb_c, g_depth_c, g_acc_c, g_rays)
             g_s = None
             if want_f:
                 g_f = _composite_bwd(raw_f, z_f, rays, g_rgb_f, g_depth_f, g_acc_f)
+                if g_rays is not None:
+                    _composite_bwd_rays(raw_f, z_f, rays, g_rgb_f, g_depth_f, g_acc_f, g_rays)
                 if ctx.nf > 0:
                     g_c, g_s = ops.split_grad(g_f, pos, ctx.nc, g_c)      # onto the coarse outputs' own gradient, if any
                 else:
                     g_c = g_f if g_c is None else g_c.add_(g_f)
                 del g_f
             if g_c is not None:
-                grads_c, gfilm_c = _field_backward(pf_c, rays, z_c, raw_c, g_c, ctx.film, ctx.acts_c)
+                grads_c, gfilm_c = _field_backward(pf_c, rays, z_c, raw_c, g_c, ctx.film, ctx.acts_c, g_rays)
             if g_s is not None:
-                grads_f, gfilm_f = _field_backward(pf_f, rays, z_s, raw_s, g_s, ctx.film, ctx.acts_f)
+                grads_f, gfilm_f = _field_backward(pf_f, rays, z_s, raw_s, g_s, ctx.film, ctx.acts_f, g_rays)
         ctx.acts_c = ctx.acts_f = None          # release the saved activations
         if pf_c is pf_f:
             if grads_c is not None and grads_f is not None:
@@ -355,7 +394,7 @@ class _RenderRaysFn(torch.autograd.Function):
             parts = [g for g in (gfilm_c, gfilm_f) if g is not None]
             if parts:
                 g_film = (parts[0] if len(parts) == 1 else parts[0] + parts[1]).reshape(ctx.film.shape)
-        return (None,) * 7 + (g_film, None, None, None) + param_grads
+        return (None, None, g_rays) + (None,) * 4 + (g_film, None, None, None) + param_grads
 
 
 def render_rays_train(pf_c, pf_f, rays, near, far, nc, nf, film, t_rand, seed, ray0=0):
