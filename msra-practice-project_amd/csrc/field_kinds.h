@@ -1,6 +1,10 @@
 // field_kinds.h - the field-kind registry: one compile-time descriptor per MI_FIELD_* kind (include/mi_render.h),
 // indexed by the kind's value.  Everything the host code and the pack / Adam kernels need to know about a kind
-// (its parameter shapes, its packed weight streams, its training buffers) is read from here.
+// (its parameter shapes, its packed weight streams, its training buffers, and its layer GRAPH: which saved input and which
+// weight columns every linear layer multiplies, and where its dA rows live) is read from here.  The graph is stated once,
+// by two builders (with_nerf_graph, make_film_kind), checked at compile time (graph_ok) and read by one host-side walker
+// (for_each_block): the weight-gradient jobs of field_mlp_bwd.hip and the input gradients of ray_grad.hip are derived
+// from it.  Host only: the kernels get pointers and strides, and constant memory holds the PackTables alone.
 #pragma once
 #include <stdint.h>
 
@@ -12,6 +16,30 @@ namespace mi {
 
 constexpr int kMaxLayers = 15;           // FilmSirenNeRF with hidden_layers = 12 has 15
 
+// One input of a linear layer: columns [c0, c1) of an acts region.  The class tells a hidden activation from the raw input.
+enum SrcClass : int {
+    SRC_HIDDEN = 0,            // a whole 256- / 128-wide activation region
+    SRC_XIN,                   // the 8-wide xin row: xyz = columns [0, 3), view direction = [3, 6)
+    SRC_E_POS,                 // positional encoding of xyz: 60 of 64 columns
+    SRC_E_DIR,                 // positional encoding of the direction: 24 of 32 columns
+};
+struct LayerInput {
+    int cls, region, c0, c1;
+    constexpr int width() const { return c1 - c0; }
+    constexpr bool is_pos() const { return cls == SRC_E_POS || (cls == SRC_XIN && c0 == 0); }
+    constexpr bool is_dir() const { return cls == SRC_E_DIR || (cls == SRC_XIN && c0 == 3); }
+};
+// Linear layer i: its one or two concatenated inputs in the order of the weight's columns (an input's weight column offset
+// is the sum of the widths before it), and its dA rows: columns [da_c0, da_c1) of a grads region - the whole region, or for
+// the two heads a column range of the four-wide heads region (rgb 0..2, sigma 3).  In a FiLM kind grads region r holds
+// dL/du of FiLM row r, so da_region is also the layer's row of an image's FiLM table.
+struct LayerGraph {
+    int n_in;
+    LayerInput in[2];
+    int da_region, da_c0, da_c1;
+    bool head;
+};
+
 struct FieldKind {
     int n_layers;                  // linear layers: parameters 2i / 2i+1 are the weight / bias of layer i
     int dims[kMaxLayers][2];       // (out, in) of every linear layer in that order (oracle/fields.py SPECS)
@@ -21,6 +49,13 @@ struct FieldKind {
     PackTable fwd, bwd;            // packed weight streams: forward order, and transposed for the backward chain
     int trunk;                     // layers 0 .. trunk-1 are the density trunk: sigma reads the last one's activation
     int sigma_head;                // the sigma head's layer; every other layer is the colour branch
+    LayerGraph graph[kMaxLayers];  // see LayerGraph; filled by with_nerf_graph / make_film_kind
+
+    constexpr LayerInput hidden_in(int region) const { return {SRC_HIDDEN, region, 0, acts.width[region]}; }
+    constexpr void layer(int i, int da_region, LayerInput a, LayerInput b = {}) {
+        graph[i] = {b.c1 > b.c0 ? 2 : 1, {a, b}, da_region, 0, grads.width[da_region], false};
+    }
+    constexpr void head(int i, int c0, int c1, LayerInput a) { graph[i] = {1, {a, {}}, grads.n - 1, c0, c1, true}; }
 
     // multiply-accumulates of the linear layers per point (a6, a7, a8)
     constexpr int64_t macs() const {
@@ -75,30 +110,50 @@ constexpr FieldKind make_film_kind(int L, bool use_dir) {
     k.acts = film_acts_depth(L); k.grads = film_grads_depth(L);
     k.fwd = build_film(use_dir, L); k.bwd = build_film_bwd(use_dir, L);
     k.trunk = L; k.sigma_head = L;
+    // acts: 0 xin | 1 + l = X_l;  grads: l = dL/du_l | L + 1 heads.  FiLM row l < L is layer l, row L is hidden_layer_rgb
+    k.layer(0, 0, {SRC_XIN, 0, 0, 3});
+    for (int l = 1; l < L; ++l) k.layer(l, l, k.hidden_in(l));
+    k.head(L, 3, 4, k.hidden_in(L));
+    k.layer(L + 1, L, k.hidden_in(L), use_dir ? LayerInput{SRC_XIN, 0, 3, 6} : LayerInput{});
+    k.head(L + 2, 0, 3, k.hidden_in(L + 1));
+    return k;
+}
+
+// NeRF, TinyNeRF, SirenNeRF share one topology: k.trunk position layers (layer l reads acts region l and writes grads region
+// l; the skip layer reads [input | h], nerf/nerf.py:84,160), an optional linear layers_dir.0, the dir layer d = [h | direction]
+// and the two heads (sigma on the trunk's output, rgb on the dir layer's).  sin: the input is the raw xin row (acts region 0)
+// and the dir layer's output is region d + 1; else the encodings E_pos (region 0) and E_dir (region d + 1), output d + 2.
+constexpr int kSkipLayer = 5;
+constexpr FieldKind with_nerf_graph(FieldKind k, bool sin) {
+    const int d = k.n_layers - 3;
+    const LayerInput pos = sin ? LayerInput{SRC_XIN, 0, 0, 3} : LayerInput{SRC_E_POS, 0, 0, 60};
+    const LayerInput dir = sin ? LayerInput{SRC_XIN, 0, 3, 6} : LayerInput{SRC_E_DIR, d + 1, 0, 24};
+    k.layer(0, 0, pos);
+    for (int l = 1; l < d; ++l) {
+        if (l == kSkipLayer && l < k.trunk) k.layer(l, l, pos, k.hidden_in(l));
+        else k.layer(l, l, k.hidden_in(l));
+    }
+    k.layer(d, d, k.hidden_in(d), dir);
+    k.head(d + 1, 3, 4, k.hidden_in(k.trunk));
+    k.head(d + 2, 0, 3, k.hidden_in(d + (sin ? 1 : 2)));
     return k;
 }
 
 // nerf/nerf.py:59-73, 128-146; pi_GAN/modules.py:76-94; TinyNeRF is build-defined (BASELINE C1)
 inline constexpr FieldKind kFieldKinds[MI_FIELD_KINDS] = {
     // MI_FIELD_NERF
-    {12, {{256, 60}, {256, 256}, {256, 256}, {256, 256}, {256, 256}, {256, 316}, {256, 256}, {256, 256}, {256, 256},
-          {128, 280}, {1, 256}, {3, 128}},
-     false, true, nerf_acts(), nerf_grads(), build_nerf(), build_nerf_bwd(), 8, 10},
+    with_nerf_graph({12, {{256, 60}, {256, 256}, {256, 256}, {256, 256}, {256, 256}, {256, 316}, {256, 256}, {256, 256}, {256, 256},
+                          {128, 280}, {1, 256}, {3, 128}},
+                     false, true, nerf_acts(), nerf_grads(), build_nerf(), build_nerf_bwd(), 8, 10, {}}, false),
     // MI_FIELD_SIREN_NERF
-    {12, {{256, 3}, {256, 256}, {256, 256}, {256, 256}, {256, 256}, {256, 259}, {256, 256}, {256, 256}, {256, 256},
-          {128, 259}, {1, 256}, {3, 128}},
-     false, true, siren_acts(), siren_grads(), build_siren_nerf(), build_siren_nerf_bwd(), 8, 10},
-    // MI_FIELD_FILM_SIREN_NERF
-    {11, {{256, 3}, {256, 256}, {256, 256}, {256, 256}, {256, 256}, {256, 256}, {256, 256}, {256, 256}, {1, 256},
-          {256, 259}, {3, 256}},
-     true, true, film_acts(), film_grads(), build_film(true), build_film_bwd(true), 8, 8},
-    // MI_FIELD_FILM_SIREN_NERF_NODIR
-    {11, {{256, 3}, {256, 256}, {256, 256}, {256, 256}, {256, 256}, {256, 256}, {256, 256}, {256, 256}, {1, 256},
-          {256, 256}, {3, 256}},
-     true, false, film_acts(), film_grads(), build_film(false), build_film_bwd(false), 8, 8},
+    with_nerf_graph({12, {{256, 3}, {256, 256}, {256, 256}, {256, 256}, {256, 256}, {256, 259}, {256, 256}, {256, 256}, {256, 256},
+                          {128, 259}, {1, 256}, {3, 128}},
+                     false, true, siren_acts(), siren_grads(), build_siren_nerf(), build_siren_nerf_bwd(), 8, 10, {}}, true),
+    make_film_kind(8, true),       // MI_FIELD_FILM_SIREN_NERF: the reference's default depth
+    make_film_kind(8, false),      // MI_FIELD_FILM_SIREN_NERF_NODIR
     // MI_FIELD_TINY_NERF
-    {7, {{256, 60}, {256, 256}, {256, 256}, {256, 256}, {128, 280}, {1, 256}, {3, 128}},
-     false, true, tiny_acts(), tiny_grads(), build_tiny_nerf(), build_tiny_nerf_bwd(), 4, 5},
+    with_nerf_graph({7, {{256, 60}, {256, 256}, {256, 256}, {256, 256}, {128, 280}, {1, 256}, {3, 128}},
+                     false, true, tiny_acts(), tiny_grads(), build_tiny_nerf(), build_tiny_nerf_bwd(), 4, 5, {}}, false),
 };
 
 static_assert(kFieldKinds[MI_FIELD_NERF].macs() == 591488, "NeRF MACs per point");
@@ -138,6 +193,61 @@ static_assert(kFieldKinds[MI_FIELD_NERF].sigma_prefix_ok() && kFieldKinds[MI_FIE
                   kFieldKinds[MI_FIELD_FILM_SIREN_NERF_NODIR].sigma_prefix_ok() && kFieldKinds[MI_FIELD_TINY_NERF].sigma_prefix_ok(),
               "every kind's stream puts the sigma path's weights first");
 
+// ---- the graph's compile-time checks ---------------------------------------------------------------------------------
+// Every layer's inputs tile its weight's columns exactly, every input is a legal range of a region of its class's width,
+// the dA rows are as wide as the layer has outputs, and the kind has no more input-consuming layers than ray_grad.hip's
+// InputGradArgs has slots for (two position consumers, one direction consumer).
+constexpr bool input_ok(const RegionLayout& A, const LayerInput& in) {
+    if (in.region < 0 || in.region >= A.n) return false;
+    const int w = A.width[in.region];
+    switch (in.cls) {
+        case SRC_HIDDEN: return in.c0 == 0 && in.c1 == w && (w == 256 || w == 128);
+        case SRC_XIN: return w == 8 && in.c1 == in.c0 + 3 && (in.c0 == 0 || in.c0 == 3);
+        case SRC_E_POS: return w == 64 && in.c0 == 0 && in.c1 == 60;
+        case SRC_E_DIR: return w == 32 && in.c0 == 0 && in.c1 == 24;
+    }
+    return false;
+}
+constexpr bool graph_ok(const FieldKind& k) {
+    int n_pos = 0, n_dir = 0;
+    for (int i = 0; i < k.n_layers; ++i) {
+        const LayerGraph& g = k.graph[i];
+        if (g.n_in < 1 || g.n_in > 2) return false;
+        int cols = 0;
+        for (int j = 0; j < g.n_in; ++j) {
+            if (!input_ok(k.acts, g.in[j])) return false;
+            cols += g.in[j].width();
+            n_pos += g.in[j].is_pos();
+            n_dir += g.in[j].is_dir();
+        }
+        if (cols != k.dims[i][1]) return false;
+        if (g.da_region < 0 || g.da_region >= k.grads.n) return false;
+        const int w = k.grads.width[g.da_region];
+        if (g.da_c0 < 0 || g.da_c1 > w || g.da_c1 - g.da_c0 != k.dims[i][0]) return false;
+        if (g.head ? (w != 4 || g.da_region != k.grads.n - 1) : (g.da_c0 != 0 || g.da_c1 != w)) return false;
+    }
+    return n_pos >= 1 && n_pos <= 2 && n_dir <= 1;
+}
+constexpr bool film_graphs_ok() {
+    for (int L = kFilmDepthMin; L <= kFilmDepthMax; ++L)
+        if (!graph_ok(make_film_kind(L, true)) || !graph_ok(make_film_kind(L, false))) return false;
+    return true;
+}
+static_assert(graph_ok(kFieldKinds[MI_FIELD_NERF]) && graph_ok(kFieldKinds[MI_FIELD_SIREN_NERF]) &&
+                  graph_ok(kFieldKinds[MI_FIELD_FILM_SIREN_NERF]) && graph_ok(kFieldKinds[MI_FIELD_FILM_SIREN_NERF_NODIR]) &&
+                  graph_ok(kFieldKinds[MI_FIELD_TINY_NERF]) && film_graphs_ok(),
+              "every kind's graph tiles its weights' columns out of regions of the right width");
+// ... and the checks can fail: NeRF with one input moved
+constexpr FieldKind nerf_with_input(int layer, int input, int region, int shift) {
+    FieldKind k = kFieldKinds[MI_FIELD_NERF];
+    LayerInput& in = k.graph[layer].in[input];
+    in.region = region; in.c0 += shift; in.c1 += shift;
+    return k;
+}
+static_assert(graph_ok(nerf_with_input(kSkipLayer, 1, 5, 0)), "the unchanged copy passes");
+static_assert(!graph_ok(nerf_with_input(kSkipLayer, 1, 5, 1)), "skip layer: second input shifted by one column");
+static_assert(!graph_ok(nerf_with_input(9, 1, 11, 0)) && !graph_ok(nerf_with_input(9, 1, 0, 0)), "dir layer: wrong region for E_dir");
+
 // ---- MI_FIELD_FILM_DEPTH kinds -------------------------------------------------------------------------------------
 // A depth kind is no row of kFieldKinds and has no table in constant memory (adam_step.hip keeps one PackTable pair per
 // fixed kind there, about 11 KB each; eighteen more do not fit in 64 KB).  The host reads a depth kind's descriptor from
@@ -173,5 +283,35 @@ inline bool bad_kind(int kind) {
 
 // Descriptor of a VALID kind, fixed or depth (api.hip builds the depth kinds' once, on first use).
 const FieldKind& field_kind(int kind);
+
+
+// ---- the graph's walker (host) -----------------------------------------------------------------------------------------
+// One (layer, input) block of a kind's graph over P points, as pointers and strides: dW[rows][w_ld] at column w_col0 is
+// sum_p dA[p][da_c0 + r] X[p][x_c0 + c].  The bias gradient rides with the layer's hidden input, or with its only input.
+struct GraphBlock {
+    int layer;                                 // parameter pair: weight 2 * layer, bias 2 * layer + 1
+    int cls;                                   // SrcClass of the input
+    bool head, bias;
+    int da_region;                             // FiLM kinds, non-head layers: the layer's FiLM row
+    const float* dA; int da_ld, da_c0, rows;   // [points][da_ld] rows of grads; valid rows of dW
+    const float* X; int x_ld, x_c0, cols;      // [points][x_ld] rows of acts; valid columns of the block
+    int w_ld, w_col0;
+};
+// Visits every block in layer order, inputs in weight-column order.  Rows start at point p0 of the P the buffers hold (a
+// FiLM image's first point).  Null buffers give null-based pointers for plan-only runs: never dereferenced.
+template <class F>
+void for_each_block(const FieldKind& K, const float* acts, const float* grads, int64_t P, int64_t p0, F&& f) {
+    for (int i = 0; i < K.n_layers; ++i) {
+        const LayerGraph& g = K.graph[i];
+        for (int j = 0, wcol = 0; j < g.n_in; wcol += g.in[j++].width()) {
+            const LayerInput& in = g.in[j];
+            const int da_ld = K.grads.width[g.da_region], x_ld = K.acts.width[in.region];
+            f(GraphBlock{i, in.cls, g.head, in.cls == SRC_HIDDEN || g.n_in == 1, g.da_region,
+                         grads + (int64_t)region_offset(K.grads, g.da_region) * P + p0 * da_ld, da_ld, g.da_c0, g.da_c1 - g.da_c0,
+                         acts + (int64_t)region_offset(K.acts, in.region) * P + p0 * x_ld, x_ld, in.c0, in.width(),
+                         K.dims[i][1], wcol});
+        }
+    }
+}
 
 }  // namespace mi

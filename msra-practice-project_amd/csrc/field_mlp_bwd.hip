@@ -990,7 +990,8 @@ int64_t bwd_partial_floats(int64_t P) {
     // pass's real plan against this figure before it launches anything.
     const int64_t slabs256 = (P + 255) / 256 > 0 ? (P + 255) / 256 : 1;          // BwdBatcher::slabs_for never exceeds this
     int64_t most = 8 * (slabs256 < 32 ? slabs256 : 32) * kFilmLayerScratch + 2 * (slabs256 < 512 ? slabs256 : 512) * 1280 + 4096;
-    for (int kind : {MI_FIELD_NERF, MI_FIELD_SIREN_NERF, MI_FIELD_TINY_NERF}) {   // the others: every job of the pass at once
+    for (int kind = 0; kind < MI_FIELD_KINDS; ++kind) {                           // the others: every job of the pass at once
+        if (kFieldKinds[kind].film) continue;
         const int64_t n = batched_partial_floats(kind, P);
         if (n > most) most = n;
     }
@@ -1101,6 +1102,29 @@ struct BwdBatcher {
         thin_red[3 * i + 2] = colsum_dst ? ReduceJob{nullptr, colsum_dst, nullptr, 0, 1024, 4, 256, 256, 0, 4, F, 0, 3}
                                          : ReduceJob{nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     }
+    // The job of one block of a kind's graph (field_kinds.h) into dst[..][ld] at column col0, the bias gradient into
+    // bias_dst (null: none).  Engine and tile follow from the block's shape: a head's 1 or 3 rows are a thin job, the 3 raw
+    // input columns a transposed one (its bias: the record's column sums), everything else the GEMM of its row widths.
+    int add(const GraphBlock& q, float* dst, int ld, int col0, float* bias_dst) {
+        if (q.head) thin_job(q.dA, q.da_ld, q.da_c0, q.rows, q.X, q.x_ld, q.cols, dst, ld, col0, false, bias_dst);
+        else if (q.cls == SRC_XIN) thin_job(q.X, q.x_ld, q.x_c0, q.cols, q.dA, q.da_ld, q.rows, dst, ld, col0, true, nullptr, bias_dst);
+        else if (q.da_ld == 256 && q.x_ld == 256) gemm<4, 2, 2>(g422, q.dA, q.X, dst, ld, col0, q.rows, q.cols, bias_dst);
+        else if (q.da_ld == 256 && q.x_ld == 64) gemm<2, 2, 1>(g221, q.dA, q.X, dst, ld, col0, q.rows, q.cols, bias_dst);
+        else if (q.da_ld == 128 && q.x_ld == 256) gemm<4, 1, 2>(g412, q.dA, q.X, dst, ld, col0, q.rows, q.cols, bias_dst);
+        else if (q.da_ld == 128 && q.x_ld == 32) gemm<1, 1, 1>(g111, q.dA, q.X, dst, ld, col0, q.rows, q.cols, bias_dst);
+        else { set_error("no dW engine for a %d x %d block (layer %d)", q.da_ld, q.x_ld, q.layer); return -1; }
+        return 0;
+    }
+    // every launch of the pass: the four GEMM groups, the thin jobs, the reduction
+    int flush_all() {
+        int rc;
+        if ((rc = flush<4, 2, 2>(g422))) return rc;
+        if ((rc = flush<2, 2, 1>(g221))) return rc;
+        if ((rc = flush<4, 1, 2>(g412))) return rc;
+        if ((rc = flush<1, 1, 1>(g111))) return rc;
+        if ((rc = flush_thin())) return rc;
+        return reduce_all();
+    }
     int flush_thin() {
         if (!n_thin) return 0;
         const int slabs = slabs_for(P, n_thin, 4), slab = slab_pts_for(P, slabs);
@@ -1125,49 +1149,14 @@ struct BwdBatcher {
     }
 };
 
-// The jobs of one backward pass, per kind.  partial == nullptr: plan only (b.used = scratch floats needed).
+// The jobs of one backward pass of a non-FiLM kind: every block of its graph into the gradient tensors.  partial == nullptr:
+// plan only (b.used = scratch floats needed).
 static int batched_backward(int kind, BwdBatcher& b, const float* acts, float* grads, float* const* gp) {
-    const int64_t P = b.P;
-    int rc;
-    const RegionLayout &AL = kFieldKinds[kind].acts, &GL = kFieldKinds[kind].grads;
-    const auto A = [&](int r) { return acts + (int64_t)region_offset(AL, r) * P; };
-    const auto G = [&](int r) { return grads + (int64_t)region_offset(GL, r) * P; };
-    if (kind == MI_FIELD_NERF || kind == MI_FIELD_TINY_NERF) {
-        const bool tiny = kind == MI_FIELD_TINY_NERF;
-        b.gemm<2, 2, 1>(b.g221, G(0), A(0), gp[0], 60, 0, 256, 60, gp[1]);                        // layers_pos.0: dA0 x E_pos
-        if (!tiny) {
-            for (int l = 1; l <= 7; ++l)
-                b.gemm<4, 2, 2>(b.g422, G(l), A(l), gp[2 * l], l == 5 ? 316 : 256, l == 5 ? 60 : 0, 256, 256, gp[2 * l + 1]);
-            b.gemm<2, 2, 1>(b.g221, G(5), A(0), gp[10], 316, 0, 256, 60, nullptr);                // skip layer's E_pos columns
-            b.gemm<4, 2, 2>(b.g422, G(8), A(8), gp[16], 256, 0, 256, 256, gp[17]);                // layers_dir.0 x H8
-            b.gemm<4, 1, 2>(b.g412, G(9), A(9), gp[18], 280, 0, 128, 256, gp[19]);                // layers_dir.1 x [G |
-            b.gemm<1, 1, 1>(b.g111, G(9), A(10), gp[18], 280, 256, 128, 24, nullptr);             //                E_dir]
-            b.thin_job(G(10), 4, 3, 1, A(8), 256, 256, gp[20], 256, 0, false, gp[21]);            // sigma head x H8
-            b.thin_job(G(10), 4, 0, 3, A(11), 128, 128, gp[22], 128, 0, false, gp[23]);           // rgb head x H_d
-        } else {
-            for (int l = 1; l <= 3; ++l) b.gemm<4, 2, 2>(b.g422, G(l), A(l), gp[2 * l], 256, 0, 256, 256, gp[2 * l + 1]);
-            b.gemm<4, 1, 2>(b.g412, G(4), A(4), gp[8], 280, 0, 128, 256, gp[9]);
-            b.gemm<1, 1, 1>(b.g111, G(4), A(5), gp[8], 280, 256, 128, 24, nullptr);
-            b.thin_job(G(5), 4, 3, 1, A(4), 256, 256, gp[10], 256, 0, false, gp[11]);
-            b.thin_job(G(5), 4, 0, 3, A(6), 128, 128, gp[12], 128, 0, false, gp[13]);
-        }
-    } else {                                                                                      // SirenNeRF
-        for (int l = 1; l <= 7; ++l)                                                              // input of layer l: X_l
-            b.gemm<4, 2, 2>(b.g422, G(l), A(l), gp[2 * l], l == 5 ? 259 : 256, l == 5 ? 3 : 0, 256, 256, gp[2 * l + 1]);
-        b.gemm<4, 2, 2>(b.g422, G(8), A(8), gp[16], 256, 0, 256, 256, gp[17]);                    // layers_dir.0 x X8
-        b.gemm<4, 1, 2>(b.g412, G(9), A(9), gp[18], 259, 0, 128, 256, gp[19]);                    // layers_dir.1 x G
-        b.thin_job(A(0), 8, 0, 3, G(0), 256, 256, gp[0], 3, 0, true, nullptr, gp[1]);             // layers_pos.0 (K = 3) + its bias
-        b.thin_job(A(0), 8, 0, 3, G(5), 256, 256, gp[10], 259, 0, true, nullptr);                 // skip layer's xyz columns
-        b.thin_job(A(0), 8, 3, 3, G(9), 128, 128, gp[18], 259, 256, true, nullptr);               // layers_dir.1's dir columns
-        b.thin_job(G(10), 4, 3, 1, A(8), 256, 256, gp[20], 256, 0, false, gp[21]);                // sigma head x X8
-        b.thin_job(G(10), 4, 0, 3, A(10), 128, 128, gp[22], 128, 0, false, gp[23]);               // rgb head x X_d
-    }
-    if ((rc = b.flush<4, 2, 2>(b.g422))) return rc;
-    if ((rc = b.flush<2, 2, 1>(b.g221))) return rc;
-    if ((rc = b.flush<4, 1, 2>(b.g412))) return rc;
-    if ((rc = b.flush<1, 1, 1>(b.g111))) return rc;
-    if ((rc = b.flush_thin())) return rc;
-    return b.reduce_all();
+    int rc = 0;
+    for_each_block(kFieldKinds[kind], acts, grads, b.P, 0, [&](const GraphBlock& q) {
+        if (!rc) rc = b.add(q, gp[2 * q.layer], q.w_ld, q.w_col0, q.bias ? gp[2 * q.layer + 1] : nullptr);
+    });
+    return rc ? rc : b.flush_all();
 }
 
 // A pass's job list is run twice: first as a plan (no scratch, nothing launched) whose scratch need is checked against
@@ -1248,63 +1237,53 @@ int launch_field_backward(int kind_in, const float* packed_bwd, const float* act
     if (!film_kind)
         return plan_then_run(kind, P, P, partial, stream, [&](BwdBatcher& bb) { return batched_backward(kind, bb, acts, grads, gp); });
 
-    const bool use_dir = film_use_dir(kind);
-    const RegionLayout AL = film_acts_depth(L);
+    const FieldKind& K = field_kind(kind);
     const int64_t ppg = points_per_group;
+    const int n_film = L + 1;                            // rows of an image's FiLM table
     // FiLM scratch of the current image: T_l [256][256] + s_l [256] for the L 256-wide FiLM layers (eight at the reference's
     // depth), the K = 3 blocks of layer 0 (xyz) and of layer L (dir) as [256][3] (padded to 4), s_0 [256]
     const auto Tl = [&](int l) { return film_partial + (int64_t)(l - 1) * kFilmLayerScratch; };
-    const auto sl = [&](int l) { return Tl(l) + 256 * 256; };
-    float* T3_0 = film_partial + (int64_t)L * kFilmLayerScratch;
-    float* T3_8 = T3_0 + 256 * 4;
-    float* s0 = T3_8 + 256 * 4;
-    const int ld9 = use_dir ? 259 : 256;
-    const int n_film = L + 1;                            // rows of the FiLM table; parameter pairs: hidden l = pair l,
-    const int p_sigma = L, p_rgbh = L + 1, p_rgb = L + 2;   // then the sigma head, hidden_layer_rgb, the rgb head
-    // Per image g (fixed order, so the sums over images are deterministic): T_g, s_g of every FiLM layer - the eight
+    float* const T3 = film_partial + (int64_t)L * kFilmLayerScratch;
+    float* const s0 = T3 + 2 * 256 * 4;
+    const auto T = [&](const GraphBlock& q) { return q.cls == SRC_XIN ? T3 + (q.da_region ? 256 * 4 : 0) : Tl(q.da_region); };
+    const auto s = [&](const GraphBlock& q) { return q.da_region ? Tl(q.da_region) + 256 * 256 : s0; };
+    // Per image g (fixed order, so the sums over images are deterministic): T_g, s_g of every block of a FiLM layer - the
     // 256 x 256 GEMMs of an image are ONE launch (grid.y = layer, a job needs only 32 slabs to give every CU a
     // workgroup, so 8x fewer partial tiles are written and re-read than with a launch per layer), the K = 3 blocks
-    // one thin launch, one reduction launch for all of them - then per layer
+    // one thin launch, one reduction launch for all of them - then per block (film_finish_kernel)
     // dW += gamma_g (.) T_g, db += gamma_g (.) s_g, d gamma_g = <W, T_g> + b (.) s_g, d beta_g = s_g.
     for (int64_t g = 0; g < n_groups; ++g) {
-        const auto A = [&](int r) { return acts + (int64_t)region_offset(AL, r) * P + g * ppg * AL.width[r]; };
-        const auto G = [&](int l) { return grads + (int64_t)(256 * l) * P + g * ppg * 256; };
         const float* frow = film + (g * n_film) * kFilmRow;
         float* dfrow = grad_film + (g * n_film) * kFilmRow;
         const auto jobs = [&](BwdBatcher& bb) -> int {
-            for (int l = 1; l <= L; ++l)                                  // FiLM layer l: input X_{l-1} = acts region l
-                bb.gemm<4, 2, 2>(bb.g422, G(l), A(l), Tl(l), 256, 0, 256, 256, sl(l));
-            bb.thin_job(A(0), 8, 0, 3, G(0), 256, 256, T3_0, 3, 0, true, nullptr, s0);          // input_layer (K = 3: xyz) + s_0
-            if (use_dir) bb.thin_job(A(0), 8, 3, 3, G(L), 256, 256, T3_8, 3, 0, true, nullptr); // hidden_layer_rgb's dir columns
-            int r;
-            if ((r = bb.flush<4, 2, 2>(bb.g422))) return r;
-            if ((r = bb.flush_thin())) return r;
-            return bb.reduce_all();
+            int r = 0;
+            for_each_block(K, acts, grads, P, g * ppg, [&](const GraphBlock& q) {
+                if (!q.head && !r) r = bb.add(q, T(q), q.cols, 0, q.bias ? s(q) : nullptr);
+            });
+            return r ? r : bb.flush_all();
         };
         if ((rc = plan_then_run(kind, ppg, P, partial, stream, jobs, g == 0))) return rc;   // the plan: first image only
+        // a block without the bias part (hidden_layer_rgb's dir columns) is chained behind its layer's job before it
         FinishBatch fb{};
-        int n_fin = 0, n_heads = 0;
+        int n_fin = 0, n_chains = 0;
         fb.first_group = g == 0;
-        const auto finish = [&](const float* t, int tk, const float* sg, int l, int wp, int w_ld, int col0, int bias_part) {
-            fb.job[n_fin++] = FinishJob{t, sg, params[2 * wp], params[2 * wp + 1], frow + l * kFilmRow, gp[2 * wp], gp[2 * wp + 1],
-                                        dfrow + l * kFilmRow, tk, w_ld, col0, bias_part};
-            n_heads += bias_part;
-        };
-        finish(T3_0, 3, s0, 0, 0, 3, 0, 1);                               // input_layer: FiLM layer 0, parameter pair 0
-        for (int l = 1; l <= L - 1; ++l) finish(Tl(l), 256, sl(l), l, l, 256, 0, 1);  // hidden_layers[l-1]: pair l
-        finish(Tl(L), 256, sl(L), L, p_rgbh, ld9, 0, 1);                  // hidden_layer_rgb: FiLM layer L, pair L+1: [X_{L-1} | dir]
-        if (use_dir) finish(T3_8, 3, sl(L), L, p_rgbh, 259, 256, 0);      // ... its dir columns: chained behind the job above
-        hipLaunchKernelGGL(film_finish_kernel, dim3(256, n_heads), dim3(256), 0, stream, fb);
+        for_each_block(K, acts, grads, P, g * ppg, [&](const GraphBlock& q) {
+            if (q.head) return;
+            fb.job[n_fin++] = FinishJob{T(q), s(q), params[2 * q.layer], params[2 * q.layer + 1], frow + q.da_region * kFilmRow,
+                                        gp[2 * q.layer], gp[2 * q.layer + 1], dfrow + q.da_region * kFilmRow, q.cols, q.w_ld,
+                                        q.w_col0, q.bias};
+            n_chains += q.bias;
+        });
+        hipLaunchKernelGGL(film_finish_kernel, dim3(256, n_chains), dim3(256), 0, stream, fb);
     }
     if ((rc = check_launch("film_finish_kernel"))) return rc;
-    // heads: sigma (param pair L) on X_{L-1}, rgb (pair L+2) on X_L - no FiLM in between, all images at once
-    const auto A = [&](int r) { return acts + (int64_t)region_offset(AL, r) * P; };
-    const float* dpre = grads + (int64_t)(n_film * 256) * P;
+    // heads: no FiLM in between, all images at once
     return plan_then_run(kind, P, P, partial, stream, [&](BwdBatcher& hb) {
-        hb.thin_job(dpre, 4, 3, 1, A(L), 256, 256, gp[2 * p_sigma], 256, 0, false, gp[2 * p_sigma + 1]);   // sigma x X_{L-1}
-        hb.thin_job(dpre, 4, 0, 3, A(L + 1), 256, 256, gp[2 * p_rgb], 256, 0, false, gp[2 * p_rgb + 1]);   // rgb x X_L
-        const int r = hb.flush_thin();
-        return r ? r : hb.reduce_all();
+        int r = 0;
+        for_each_block(K, acts, grads, P, 0, [&](const GraphBlock& q) {
+            if (q.head && !r) r = hb.add(q, gp[2 * q.layer], q.w_ld, q.w_col0, gp[2 * q.layer + 1]);
+        });
+        return r ? r : hb.flush_all();
     });
 }
 
@@ -1313,7 +1292,7 @@ static int64_t batched_partial_floats(int kind, int64_t P) {
     // here: a job's record is TM*TK floats plus TM bias sums when it has a bias destination, and a plan made with null
     // destinations comes out 256 floats per record short of what the real pass writes.
     static float sink;
-    float* gp[24];
+    float* gp[2 * kMaxLayers];
     for (float*& g : gp) g = &sink;
     BwdBatcher bb{P, nullptr, 0, nullptr};
     (void)batched_backward(kind, bb, nullptr, nullptr, gp);

@@ -4,7 +4,9 @@
 //
 // The backward chain (field_mlp_bwd.hip) has already written dL/d(pre-activation) of every linear layer as
 // [point][feature] rows into grads_ws (field_layout.h nerf_grads() .. film_grads_depth()); the gradient of a point's six
-// inputs is one more small contraction of the rows of the INPUT-CONSUMING layers with those layers' input columns:
+// inputs is one more small contraction of the rows of the INPUT-CONSUMING layers with those layers' input columns.  Which
+// layers those are, their dA regions, weight columns and saved encoding rows are read from the kind's layer graph
+// (field_kinds.h: the blocks whose source is the xin row, E_pos or E_dir); per kind that comes to:
 //
 //   NeRF / TinyNeRF   dE_pos = dA(layers_pos.0) W0[:, :60] (+ dA(layers_pos.5) W5[:, :60], the skip, nerf/nerf.py:84)
 //                     dE_dir = dA(dir layer) Wd[:, 256:280]
@@ -16,7 +18,7 @@
 //                     film_bwd_kernel stores dL/du_l = dX_l (.) w_0 cos(w_0 u_l) - the sin derivative is in, gamma is not
 //                     (u = gamma (W x + b) + beta, pi_GAN/modules.py:22-25), so gamma multiplies here.
 //
-// The encoding's sin / cos values are taken from the saved E_pos / E_dir rows (acts regions 0 and 10 / 5): the oracle's
+// The encoding's sin / cos values are taken from the saved E_pos / E_dir rows (the graph's source regions): the oracle's
 // autograd multiplies by cos(2^i x) and sin(2^i x) of the very argument the forward used, the saved rows are the forward's
 // values of exactly those (within the forward's own gate), and the point form has no x to recompute them from - acts holds
 // the encoding, not the raw input.
@@ -290,30 +292,27 @@ static int launch_input_grad(int kind_in, const float* const* params, const floa
     const int64_t ppg = ray_form ? units_pg * n_samples : units_pg;
     const int64_t P = n_groups * ppg;
     if (P == 0) return 0;
-    const auto G = [&](int region) { return grads + (int64_t)region_offset(K.grads, region) * P; };
-    const auto A = [&](int region) { return acts + (int64_t)region_offset(K.acts, region) * P; };
     InputGradArgs a = {};
     a.rays = rays; a.z = z; a.out = out; a.n_samples = n_samples; a.accumulate = accumulate;
     a.points_per_group = ppg;
     a.units_per_group = ray_form ? units_pg : (ppg + kChunk - 1) / kChunk;
     a.units = n_groups * a.units_per_group;
-    a.W0 = params[0]; a.ld0 = K.dims[0][1]; a.dA0 = G(0);
-    bool pe = false;
-    if (kind == MI_FIELD_NERF || kind == MI_FIELD_SIREN_NERF) {
-        // layers_pos.5 = [input | h] (nerf/nerf.py:84,160), layers_dir.1 = [h | dir] (grads regions 5 and 9)
-        a.W5 = params[10]; a.ld5 = K.dims[5][1]; a.dA5 = G(5);
-        a.Wd = params[18]; a.ldd = K.dims[9][1]; a.dAd = G(9); a.col_d = 256; a.dir_rows = 128;
-        pe = kind == MI_FIELD_NERF;
-        if (pe) { a.e_pos = A(0); a.e_dir = A(10); }
-    } else if (kind == MI_FIELD_TINY_NERF) {
-        a.Wd = params[8]; a.ldd = K.dims[4][1]; a.dAd = G(4); a.col_d = 256; a.dir_rows = 128;
-        pe = true;
-        a.e_pos = A(0); a.e_dir = A(5);
-    } else {                                              // FiLM: input_layer, hidden_layer_rgb (layer L + 1, FiLM row L)
-        const int L = film_depth(kind);
-        a.film = film; a.film_rows = L + 1; a.film_dir_row = L;
-        if (K.use_dir) { a.Wd = params[2 * (L + 1)]; a.ldd = K.dims[L + 1][1]; a.dAd = G(L); a.col_d = 256; a.dir_rows = 256; }
-    }
+    if (K.film) { a.film = film; a.film_rows = film_layers(kind); a.film_dir_row = a.film_rows - 1; }   // gamma rows: read even
+    bool pe = false;                                                                    // where no layer reads the direction
+    // the blocks of the kind's graph (field_kinds.h) that read the raw input or its encoding: first and second position
+    // consumer, then the direction consumer (graph_ok: a kind has no more)
+    for_each_block(K, acts, grads, P, 0, [&](const GraphBlock& q) {
+        const float* W = params[2 * q.layer];
+        if (q.cls == SRC_E_POS || (q.cls == SRC_XIN && q.x_c0 == 0)) {
+            if (!a.W0) { a.W0 = W; a.ld0 = q.w_ld; a.dA0 = q.dA; }
+            else { a.W5 = W; a.ld5 = q.w_ld; a.dA5 = q.dA; }
+            if (q.cls == SRC_E_POS) { pe = true; a.e_pos = q.X; }
+        } else if (q.cls != SRC_HIDDEN) {
+            a.Wd = W; a.ldd = q.w_ld; a.dAd = q.dA; a.col_d = q.w_col0; a.dir_rows = q.rows;
+            if (K.film) a.film_dir_row = q.da_region;
+            if (q.cls == SRC_E_DIR) a.e_dir = q.X;
+        }
+    });
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     if (pe) {
