@@ -52,16 +52,15 @@ __global__ __launch_bounds__(256, 1) void nerf_fwd_kernel(MlpArgs a) {
     }
     Ctx c = make_ctx(smem, a, group);
     MI_STAMP(a, 0);
-    issue_first_stage<1, 32, false>(c, 0, 0, 0);   // layer 0: bias + K block 0 (PE features 0..31)
+    issue_first_stage<1, 32, false>(c, 0);   // layer 0: bias + K block 0 (PE features 0..31)
 
     PointIn pt;
     if constexpr (WINDOW) pt = load_window_point(a, tile, live, c.wave * 32 + (c.lane & 31));
     else pt = load_point(a.mode, a.a, a.z, group, a.points_per_group, a.rays_per_group, a.n_samples,
                          tile * 128 + c.wave * 32 + (c.lane & 31));
     f32x16 pe[2], pd[1], X[8], acc[8];
-    float* scr = smem + kLdsChunk0 + kLdsChunk + c.wave * 2048;   // chunk buffer 1 is idle until stage 1
-    posenc_blocks<2>(scr, c.lane, c.h, pt.px, pt.py, pt.pz, 60, pe);
-    posenc_blocks<1>(scr, c.lane, c.h, pt.dx, pt.dy, pt.dz, 24, pd);
+    posenc_blocks<2>(c.h, pt.px, pt.py, pt.pz, 60, pe);
+    posenc_blocks<1>(c.h, pt.dx, pt.dy, pt.dz, 24, pd);
 
     constexpr RegionLayout RL = TINY ? tiny_acts() : nerf_acts();
     const int64_t SP = a.save_points;
@@ -126,10 +125,7 @@ __global__ __launch_bounds__(256, 1) void nerf_fwd_kernel(MlpArgs a) {
         // layers_pos[7] (+ sigma head pieces)
         fwd_layer<8, 8, false, kNextAux, kNextBlock, false, ACT_RELU, SAVE, true, 8>(c, slot, 0, 0, 0.f, 0.f, 0.f, sel_x, acc, X, nullptr,
                                                                       rows(region_offset(RL, 8), 256, SW0 + 7), rows(region_offset(RL, 7), 256));    // H8
-        {
-            const float* aux = smem + kLdsAux0 + slot * kLdsAux;
-            sigma = fmaxf(head_dot<8>(X, aux, 1, c.h) + aux[2 * kPiece], 0.f);
-        }
+        sigma = sigma_head(X, smem + kLdsAux0 + slot * kLdsAux, c.h);
         slot ^= 1;
         MI_STAMP(a, 17);
         if constexpr (!SIGMA_ONLY) {
@@ -149,10 +145,7 @@ __global__ __launch_bounds__(256, 1) void nerf_fwd_kernel(MlpArgs a) {
         slot ^= 1;
         fwd_layer<8, 8, false, kNextAux, kNextBlock, false, ACT_RELU, SAVE, true, 8>(c, slot, 0, 0, 0.f, 0.f, 0.f, sel_x, acc, X, nullptr,
                                                                       rows(region_offset(RL, 4), 256, SW0 + 3), rows(region_offset(RL, 3), 256));
-        {
-            const float* aux = smem + kLdsAux0 + slot * kLdsAux;
-            sigma = fmaxf(head_dot<8>(X, aux, 1, c.h) + aux[2 * kPiece], 0.f);
-        }
+        sigma = sigma_head(X, smem + kLdsAux0 + slot * kLdsAux, c.h);
         slot ^= 1;
     }
     if constexpr (SIGMA_ONLY) {
@@ -191,7 +184,7 @@ __global__ __launch_bounds__(256, 1) void siren_fwd_kernel(MlpArgs a) {
         if (tile * (128 >> a.win_log2) >= live) return;
     }
     Ctx c = make_ctx(smem, a, group);
-    issue_first_stage<4, 0, false>(c, 0, 0, 0);   // layers_pos[0]: bias + 3 weight columns (K = 3, VALU)
+    issue_first_stage<4, 0, false>(c, 0);   // layers_pos[0]: bias + 3 weight columns (K = 3, VALU)
 
     PointIn pt;
     if constexpr (WINDOW) pt = load_window_point(a, tile, live, c.wave * 32 + (c.lane & 31));
@@ -224,7 +217,7 @@ __global__ __launch_bounds__(256, 1) void siren_fwd_kernel(MlpArgs a) {
 
     int slot = 0;
     __syncthreads();
-    issue_first_stage<1, 32, false>(c, 1, 0, 0);
+    issue_first_stage<1, 32, false>(c, 1);
     init_acc<8, true>(smem + kLdsAux0, c.h, 1, pt.px, pt.py, pt.pz, acc);
     sin_act(1); slot ^= 1;
     // sin layers store their own (encoded) rows from the activation hook: nothing is deferred to the next layer
@@ -240,11 +233,7 @@ __global__ __launch_bounds__(256, 1) void siren_fwd_kernel(MlpArgs a) {
     fwd_layer<8, 8, false, 3, 32, false, ACT_SIN30, SAVE, false, 0>(c, slot, 0, 0, 0.f, 0.f, 0.f, sel_x, acc, X, nullptr, sin_rows(7), none);  // [6]
     slot ^= 1;
     fwd_layer<8, 8, false, kNextAux, kNextBlock, false, ACT_SIN30, SAVE, false, 0>(c, slot, 0, 0, 0.f, 0.f, 0.f, sel_x, acc, X, nullptr, sin_rows(8), none);  // [7] + sigma head
-    float sigma;
-    {
-        const float* aux = smem + kLdsAux0 + slot * kLdsAux;
-        sigma = fmaxf(head_dot<8>(X, aux, 1, c.h) + aux[2 * kPiece], 0.f);
-    }
+    const float sigma = sigma_head(X, smem + kLdsAux0 + slot * kLdsAux, c.h);
     if constexpr (SIGMA_ONLY) {
         store_sigma(a, pt, c.h, sigma);
         return;
@@ -284,7 +273,7 @@ __global__ __launch_bounds__(256, 1) void film_fwd_kernel(MlpArgs a) {
                   packed_body_floats(kFieldKinds[USE_DIR ? MI_FIELD_FILM_SIREN_NERF : MI_FIELD_FILM_SIREN_NERF_NODIR].fwd));
     const int kBody = film_body_floats(L, USE_DIR, false);
     c.w0 = a.packed[kBody];
-    issue_first_stage<4, 0, true>(c, 0, 0, 0);   // input_layer: bias + 3 columns, FiLM row 0
+    issue_first_stage<4, 0, true>(c, 0, 0);   // input_layer: bias + 3 columns, FiLM row 0
 
     const PointIn pt = load_point(a.mode, a.a, a.z, group, a.points_per_group, a.rays_per_group, a.n_samples,
                                   tile * 128 + c.wave * 32 + (c.lane & 31));
@@ -314,7 +303,7 @@ __global__ __launch_bounds__(256, 1) void film_fwd_kernel(MlpArgs a) {
 
     int slot = 0;
     __syncthreads();
-    issue_first_stage<1, 32, true>(c, 1, 0, 1);
+    issue_first_stage<1, 32, true>(c, 1, 1);
     init_acc<8, true>(smem + kLdsAux0, c.h, 1, pt.px, pt.py, pt.pz, acc);
     film_act(0, 0); slot ^= 1;
 #pragma unroll 1
@@ -325,11 +314,7 @@ __global__ __launch_bounds__(256, 1) void film_fwd_kernel(MlpArgs a) {
     fwd_layer<8, 8, false, 3, 32, true, ACT_FILM, SAVE, false, 0>(c, slot, L - 1, 0, 0.f, 0.f, 0.f, sel_x, acc, X, film_row(slot), film_rows(L - 2), none);  // hidden_layers[L-3]
     slot ^= 1;
     fwd_layer<8, 8, false, USE_DIR ? 8 : 5, 32, true, ACT_FILM, SAVE, false, 0>(c, slot, L, 0, 0.f, 0.f, 0.f, sel_x, acc, X, film_row(slot), film_rows(L - 1), none);  // hidden_layers[L-2]
-    float sigma;
-    {
-        const float* aux = smem + kLdsAux0 + slot * kLdsAux;
-        sigma = fmaxf(head_dot<8>(X, aux, 1, c.h) + aux[2 * kPiece], 0.f);
-    }
+    const float sigma = sigma_head(X, smem + kLdsAux0 + slot * kLdsAux, c.h);
     slot ^= 1;
     fwd_layer<8, 8, USE_DIR, 0, 0, false, ACT_FILM, SAVE, false, 0>(c, slot, 0, 1, pt.dx, pt.dy, pt.dz, sel_x, acc, X, film_row(slot), film_rows(L), none);   // hidden_layer_rgb
     const float* aux = smem + kLdsAux0 + slot * kLdsAux;

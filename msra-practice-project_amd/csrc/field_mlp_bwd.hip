@@ -75,7 +75,7 @@ __device__ __forceinline__ void load_switches(uint32_t (&mw)[4], const float* __
 // dA = dX (.) relu'(H): the layer's switch bits (`mw`, load_switches) ANDed onto dX; stores dA rows and leaves them in X.
 template <int MB>
 __device__ __forceinline__ void relu_bwd_store(const f32x16 (&dX)[8], f32x16 (&X)[8], const uint32_t (&mw)[4],
-                                               float* __restrict__ dA, int64_t ld, int64_t p, bool valid, int h) {
+                                               float* __restrict__ dA, int64_t ld, int64_t p, int h) {
     f32x4* drow = reinterpret_cast<f32x4*>(dA + p * ld + 4 * h);
     static_for<MB>([&](auto mc) {
         constexpr int m = decltype(mc)::value;
@@ -94,46 +94,42 @@ __device__ __forceinline__ void relu_bwd_store(const f32x16 (&dX)[8], f32x16 (&X
 
 
 // One backward-chain layer with everything but the MFMAs sliced between them (mma_chunk's hooks):
-//   pre(m, part)  : accumulator start (0, or s * aux row `piece`) and the global load of the saved row quarter
-//                   the epilogue of this block needs (H for ReLU, C for sin) - issued a whole layer ahead, so its
-//                   latency sits under ~1000 MFMAs instead of stalling the one resident wave per SIMD;
-//   post(m, part) : dA = dX (.) act'(saved), written to HBM and left in X as the next layer's B operand.
+//   pre(m, part)  : accumulator start, s * aux row `piece` of slot `aux_slot` (SCALED: the sigma head's contribution), else
+//                   nothing: the layer's first MFMAs take srcC = 0;
+//   mid(kb, slot) : the layer's row traffic, spread over its K blocks (below);
+//   post(m, part) : dA = dX (.) act'(saved), left in X as the next layer's B operand.
 // B operands come from bsel; when the last K block reads X[j] with j < MB-1 pass a copy (post overwrites X[j]).
-// Row stores are NOT guarded by `valid`: lanes past the end of a partial tile are clamped to its last point, compute what
-// that point's own lane computes and store the same bytes to the same address; a guard costs a saveexec / branch /
-// restore around every store and stalled the in-order wave for hundreds of cycles each (field_mlp_device.h:fwd_layer).
-enum BwdEpi : int { EPI_LINEAR = 0, EPI_RELU = 1, EPI_SIN = 2, EPI_FILM = 3 };
-
-// EPI_SIN / EPI_FILM: saved = the layer's X rows with the cosine's sign in the lowest mantissa bit; the derivative
-// factor C = 30 cos(30 u) is rebuilt from them (mi_math.h:dsin30_from_saved) one K block after the quarter's load
-// was issued, in the mid slot that issues a later quarter's load.
-// EPI_FILM: writes dL/du = dX (.) C rows and leaves dA = gamma (.) dL/du in X; gamma is
-// this layer's FiLM row in LDS (`film_row`).  FILM layers also DMA the next epilogue's FiLM row (`next_film_layer`)
-// into the other film slot; `issue_slot` is the slot pair index handed to the stage issue (its aux / film
-// target is issue_slot ^ 1), `aux_slot` the slot the SCALED start row is read from.
+// The three epilogues:
+//   EPI_LINEAR : dA = dX; `saved` is not read.
+//   EPI_RELU   : `saved` is the layer's SWITCH region (one bit per unit, MB / 2 dwords per lane: one load in the layer's
+//                first mid slot); dA = dX with the switched-off units cleared.
+//   EPI_SIN    : `saved` = the layer's X rows with the cosine's sign in the lowest mantissa bit; the derivative factor
+//                C = 30 cos(30 u) is rebuilt from them (mi_math.h:dsin30_from_saved_x4) one K block after the quarter's load
+//                was issued, in the mid slot that issues a later quarter's load; dA = dX (.) C.
+// Row stores are NOT guarded: lanes past the end of a partial tile are clamped to its last point, compute what that
+// point's own lane computes and store the same bytes to the same address; a guard costs a saveexec / branch / restore
+// around every store and stalled the in-order wave for hundreds of cycles each (field_mlp_device.h:fwd_layer).
 // Row traffic is spread over the layer instead of bursting in one row (32 x 1 KiB per wave inside 2048 cycles
 // saturates the CU's vector-memory path and stalls the in-order wave): the saved-row quarters are loaded one per mid
-// slot - 8-K-block layers: quarter j in slot 4(j%6) of K block j/6; 4-K-block layers: slot 2(j%8) of K block j/8 - and
-// with DEFER the dA rows this layer produces are not stored by its own epilogue but by the NEXT layer's mid slots
-// (slot 4(j%4)+2 of K block j/4, resp. 2(j%8)+1 of K block j/8; they sit unchanged in X, that layer's B operand, until
-// its last row) - PREV_MB blocks to `prev_dA`.  FiLM layers cannot defer (they store dL/du but carry gamma dL/du).
-template <int KB, int MB, int NEXT_AUX, int NEXT_BLOCK, int EPI, bool SCALED, bool FILM = false, bool DEFER = false,
-          int PREV_MB = 0, class BSel>
+// slot, K blocks ahead of the epilogue that needs them - 8-K-block layers: quarter j in slot 4(j%6) of K block 1 + j/6;
+// 4-K-block layers: slot 2(j%8) of K block j/8 - and with DEFER the dA rows this layer produces are not stored by its own
+// epilogue but by the NEXT layer's mid slots (slot 4(j%4)+2 of K block j/4, resp. 2(j%8)+1 of K block j/8; they sit
+// unchanged in X, that layer's B operand, until its last row) - PREV_MB blocks to `prev_dA`.
+// The FiLM chain has a layer of its own (film_chain_layer): it stores dL/du but carries gamma (.) dL/du.
+enum BwdEpi : int { EPI_LINEAR = 0, EPI_RELU = 1, EPI_SIN = 2 };
+
+template <int KB, int MB, int NEXT_AUX, int NEXT_BLOCK, int EPI, bool SCALED, bool DEFER = false, int PREV_MB = 0, class BSel>
 __device__ __forceinline__ void bwd_layer(Ctx& c, int aux_slot, int piece, float s, BSel bsel, f32x16 (&acc)[8],
-                                          f32x16 (&X)[8], const float* __restrict__ saved, float* __restrict__ dA,
-                                          int64_t ld, int64_t p, bool valid, int issue_slot = -1,
-                                          int next_film_layer = 0, const float* film_row = nullptr,
-                                          float* __restrict__ prev_dA = nullptr, int64_t prev_ld = 0) {
+                                          f32x16 (&X)[8], float* __restrict__ dA, int64_t ld, int64_t p,
+                                          const float* __restrict__ saved = nullptr, float* __restrict__ prev_dA = nullptr,
+                                          int64_t prev_ld = 0) {
     static_assert(KB >= 4, "four K blocks are the fewest whose mid slots carry the 32 row quarters");
     static_assert(KB != 8 || MB == 8, "the 8-K-block slot mapping below counts on 24 mid slots per K block (MB = 8)");
-    static_assert(!(DEFER && EPI == EPI_FILM), "FiLM layers store dL/du, not what they carry on");
     const int h = c.h;
     // only SCALED layers read the start row: lds_base's opaque asm would otherwise keep a dead address alive across a
     // layer loop (the SirenNeRF chain spilled and reloaded exactly that, once per layer, in front of a stage barrier)
     lds4_t pv = nullptr;
     if constexpr (SCALED) pv = lds_base(c.smem + kLdsAux0 + aux_slot * kLdsAux + h * 16);
-    lds4_t pg = nullptr;
-    if constexpr (EPI == EPI_FILM) pg = lds_base(film_row + h * 4);
     // Row addresses as a UNIFORM base (the tile's first point: SGPRs) plus one 32-bit byte offset per lane (the lane's
     // point inside the tile: < 128 rows), so a row instruction is `global_load/store ..., v_off, s[base]` and the three
     // row pointers of a layer cost one VGPR, not three 64-bit pairs: round 4 - the SirenNeRF chain kept its per-lane
@@ -155,32 +151,9 @@ __device__ __forceinline__ void bwd_layer(Ctx& c, int aux_slot, int piece, float
             acc[m][4 * rg + 0] = w.x * s; acc[m][4 * rg + 1] = w.y * s; acc[m][4 * rg + 2] = w.z * s; acc[m][4 * rg + 3] = w.w * s;
         }       // else: nothing to write, the layer's first MFMAs take srcC = 0 (mma_layer_fn ZERO_START)
     };
-    static_assert(!(EPI == EPI_SIN || EPI == EPI_FILM) || KB >= 5, "sin rows are decoded one K block after their load");
+    static_assert(EPI != EPI_SIN || KB >= 5, "sin rows are decoded one K block after their load");
     const auto mid = [&](auto kbc, auto sc) {
         constexpr int kb = decltype(kbc)::value, slot = decltype(sc)::value, j = kb * 8 + slot / 2;
-#if defined(MI_BWD_PHASES) && MI_BWD_PHASES
-        if constexpr (KB == 8) {
-            // EXPERIMENT (round 4): loads and stores in separate phases of the layer instead of interleaved in every K block
-            // (tools/probes/mfma_store_mix.hip: a row instruction costs 17 / 33 cycles among its own kind, 80-110 in a mix):
-            // the previous layer's dA rows go out in K blocks 0..2 (even slots 0..20: 11 per K block), the saved rows come in
-            // during K blocks 3..6 (slots 0, 3, .., 21: 8 per K block) and sin rows are decoded one K block later.
-            if constexpr (kb <= 2 && (slot & 1) == 0 && slot < 22) {
-                constexpr int js = kb * 11 + slot / 2;
-                if constexpr (js < PREV_MB * 4) {
-                    constexpr int m = js / 4, rg = js % 4;
-                    prow[m * 8 + rg * 2] = f32x4{X[m][4 * rg + 0], X[m][4 * rg + 1], X[m][4 * rg + 2], X[m][4 * rg + 3]};
-                }
-            }
-            if constexpr (kb >= 3 && slot % 3 == 0) {
-                constexpr int jl = (kb - 3) * 8 + slot / 3;
-                if constexpr ((EPI == EPI_SIN || EPI == EPI_FILM) && kb >= 4 && jl - 8 >= 0 && jl - 8 < MB * 4) {
-                    sv[jl - 8] = dsin30_from_saved_x4(sv[jl - 8]);
-                }
-                if constexpr ((EPI == EPI_SIN || EPI == EPI_FILM) && kb <= 6 && jl < MB * 4) sv[jl] = srow[(jl / 4) * 8 + (jl % 4) * 2];
-                if constexpr (EPI == EPI_RELU && kb == 3 && slot == 0) load_switches<MB>(mw, saved, p, h);
-            }
-        } else
-#endif
         if constexpr (KB == 8) {
             // 8 K blocks: the row traffic is spread over the whole layer (tools/probes/mfma_store_mix.hip: 8 + 8 quarters
             // per K block run into a mixed read/write ceiling - 80-110 cycles per instruction instead of 17-33 - and
@@ -191,10 +164,10 @@ __device__ __forceinline__ void bwd_layer(Ctx& c, int aux_slot, int piece, float
                 // they arrive later is a K block in which 24 registers stay free while all of X is still live (round 3:
                 // siren_bwd_kernel spilled 6 registers, and each scratch reload drains the wave's row traffic)
                 constexpr int jl = (kb - 1) * 6 + slot / 4;
-                if constexpr ((EPI == EPI_SIN || EPI == EPI_FILM) && kb >= 2 && jl - 6 >= 0 && jl - 6 < MB * 4) {
+                if constexpr (EPI == EPI_SIN && kb >= 2 && jl - 6 >= 0 && jl - 6 < MB * 4) {
                     sv[jl - 6] = dsin30_from_saved_x4(sv[jl - 6]);
                 }
-                if constexpr ((EPI == EPI_SIN || EPI == EPI_FILM) && kb >= 1 && kb < 7 && jl < MB * 4) sv[jl] = srow[(jl / 4) * 8 + (jl % 4) * 2];
+                if constexpr (EPI == EPI_SIN && kb >= 1 && kb < 7 && jl < MB * 4) sv[jl] = srow[(jl / 4) * 8 + (jl % 4) * 2];
                 if constexpr (EPI == EPI_RELU && kb == 1 && slot == 0) load_switches<MB>(mw, saved, p, h);
             } else if constexpr ((slot & 3) == 2 && slot < 16) {
                 constexpr int js = kb * 4 + slot / 4;
@@ -204,12 +177,12 @@ __device__ __forceinline__ void bwd_layer(Ctx& c, int aux_slot, int piece, float
                 }
             }
         } else
-        if constexpr ((EPI == EPI_SIN || EPI == EPI_FILM) && kb >= 1 && kb < 5 && slot < 16 && (slot & 1) == 0 && j - 8 < MB * 4) {
+        if constexpr (EPI == EPI_SIN && kb >= 1 && kb < 5 && slot < 16 && (slot & 1) == 0 && j - 8 < MB * 4) {
             sv[j - 8] = dsin30_from_saved_x4(sv[j - 8]);
         }
         if constexpr (KB != 8 && kb < 4 && slot < 16) {          // 4 K blocks: all 16 mid slots of rows 1-2 are needed
             if constexpr ((slot & 1) == 0) {
-                if constexpr ((EPI == EPI_SIN || EPI == EPI_FILM) && j < MB * 4) sv[j] = srow[(j / 4) * 8 + (j % 4) * 2];
+                if constexpr (EPI == EPI_SIN && j < MB * 4) sv[j] = srow[(j / 4) * 8 + (j % 4) * 2];
                 if constexpr (EPI == EPI_RELU && j == 0) load_switches<MB>(mw, saved, p, h);
             } else if constexpr (j < PREV_MB * 4) {
                 constexpr int m = j / 4, rg = j % 4;
@@ -219,8 +192,7 @@ __device__ __forceinline__ void bwd_layer(Ctx& c, int aux_slot, int piece, float
     };
     const auto post = [&](auto mc, auto pc) {
         constexpr int m = decltype(mc)::value, rg = decltype(pc)::value;
-        f32x4 o, g;
-        if constexpr (EPI == EPI_FILM) g = pg[m * 8 + rg * 2];
+        f32x4 o;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const float d = acc[m][4 * rg + q];
@@ -228,18 +200,16 @@ __device__ __forceinline__ void bwd_layer(Ctx& c, int aux_slot, int piece, float
                 const uint32_t on = q == 0 ? relu_switch_of<m, rg, 0>(mw) : q == 1 ? relu_switch_of<m, rg, 1>(mw)
                                   : q == 2 ? relu_switch_of<m, rg, 2>(mw) : relu_switch_of<m, rg, 3>(mw);
                 o[q] = __uint_as_float(__float_as_uint(d) & on);
-            } else if constexpr (EPI == EPI_SIN || EPI == EPI_FILM) o[q] = sv[m * 4 + rg][q] * d;
+            } else if constexpr (EPI == EPI_SIN) o[q] = sv[m * 4 + rg][q] * d;
             else o[q] = d;
-            if constexpr (EPI == EPI_FILM) X[m][4 * rg + q] = o[q] * g[q];
-            else X[m][4 * rg + q] = o[q];
+            X[m][4 * rg + q] = o[q];
         }
         if constexpr (!DEFER) drow[m * 8 + rg * 2] = o;
     };
     // a layer that stores its own dA rows (the chain's last one: there is no next layer to do it) runs its last K block
     // m-major, so the 32 row stores of the epilogue are spread over 128 MFMAs instead of bursting out of the last 32
     // (stamped profile, round 3: the FiLM chain's last layer took 89.5 k cycles where the others take 76-78 k)
-    mma_layer_fn<KB, MB, 0, NEXT_AUX, NEXT_BLOCK, FILM, true, !SCALED, !DEFER>(c, issue_slot < 0 ? aux_slot : issue_slot, next_film_layer,
-                                                                               NoHook{}, bsel, acc, pre, post, mid);
+    mma_layer_fn<KB, MB, NEXT_AUX, NEXT_BLOCK, false, !SCALED, !DEFER>(c, aux_slot, 0, bsel, acc, pre, post, mid);
 }
 
 // =========================================================================================
@@ -253,7 +223,7 @@ __global__ __launch_bounds__(256, 1) void nerf_bwd_kernel(BwdArgs a) {
     constexpr RegionLayout GL = TINY ? tiny_grads() : nerf_grads();
     constexpr int kHeadAux = TINY ? 4 : 3;                 // rgb rows (+ sigma row for TinyNeRF)
     const int64_t P = a.points;
-    issue_first_stage<kHeadAux, 32, false>(c, 0, 0, 0);
+    issue_first_stage<kHeadAux, 32, false>(c, 0);
 
     const int64_t local = (int64_t)blockIdx.x * 128 + c.wave * 32 + (c.lane & 31);
     const bool valid = local < P;
@@ -291,7 +261,7 @@ __global__ __launch_bounds__(256, 1) void nerf_bwd_kernel(BwdArgs a) {
                 acc[m][4 * rg + 3] = fmaf(w2.w, d2, fmaf(w1.w, d1, w0.w * d0));
             }
     }
-    relu_bwd_store<4>(acc, X, hsw, grads(TINY ? 4 : 9), 128, p, valid, c.h);                    // dA of the dir layer
+    relu_bwd_store<4>(acc, X, hsw, grads(TINY ? 4 : 9), 128, p, c.h);                    // dA of the dir layer
     MI_STAMP(a, 1);
 
     int slot = 0;
@@ -302,33 +272,32 @@ __global__ __launch_bounds__(256, 1) void nerf_bwd_kernel(BwdArgs a) {
 #pragma unroll
         for (int m = 0; m < 4; ++m) Bd[m] = X[m];
         const auto sel_d = [&](auto kb) -> const f32x16& { return Bd[decltype(kb)::value]; };
-        bwd_layer<4, 8, 1, 32, EPI_LINEAR, false, false, true, 0>(c, slot, 0, 0.f, sel_d, acc, X, nullptr, grads(8), 256, p, valid);
+        bwd_layer<4, 8, 1, 32, EPI_LINEAR, false, true, 0>(c, slot, 0, 0.f, sel_d, acc, X, grads(8), 256, p);
         MI_STAMP(a, 2);
         slot ^= 1;
         // layers_dir[0]^T, plus the sigma head's contribution to dH8; dA7 = dH8 (.) [H8>0]
-        bwd_layer<8, 8, 0, 32, EPI_RELU, true, false, true, 8>(c, slot, 0, ds, sel_x, acc, X, sw(8), grads(7), 256, p, valid, -1, 0, nullptr, grads(8), 256);
+        bwd_layer<8, 8, 0, 32, EPI_RELU, true, true, 8>(c, slot, 0, ds, sel_x, acc, X, grads(7), 256, p, sw(8), grads(8), 256);
         MI_STAMP(a, 3);
         slot ^= 1;
 #ifdef MI_PROFILE_STAMPS
         if (a.stamps) c.rowst = a.stamps + (int64_t)blockIdx.x * 128 + 32;                     // rows of L7^T: 32..64
 #endif
-        bwd_layer<8, 8, 0, 32, EPI_RELU, false, false, true, 8>(c, slot, 0, 0.f, sel_x, acc, X, sw(7), grads(6), 256, p, valid, -1, 0, nullptr, grads(7), 256);  // L7^T
+        bwd_layer<8, 8, 0, 32, EPI_RELU, false, true, 8>(c, slot, 0, 0.f, sel_x, acc, X, grads(6), 256, p, sw(7), grads(7), 256);  // L7^T
 #ifdef MI_PROFILE_STAMPS
         if (c.rowst) { MI_ROW_STAMP(c); }
         c.rowst = nullptr;
 #endif
         MI_STAMP(a, 4);
-        bwd_layer<8, 8, 0, 32, EPI_RELU, false, false, true, 8>(c, slot, 0, 0.f, sel_x, acc, X, sw(6), grads(5), 256, p, valid, -1, 0, nullptr, grads(6), 256);  // L6^T
+        bwd_layer<8, 8, 0, 32, EPI_RELU, false, true, 8>(c, slot, 0, 0.f, sel_x, acc, X, grads(5), 256, p, sw(6), grads(6), 256);  // L6^T
         MI_STAMP(a, 5);
-        bwd_layer<8, 8, 0, 32, EPI_RELU, false, false, true, 8>(c, slot, 0, 0.f, sel_x, acc, X, sw(5), grads(4), 256, p, valid, -1, 0, nullptr, grads(5), 256);  // L5^T (h part)
+        bwd_layer<8, 8, 0, 32, EPI_RELU, false, true, 8>(c, slot, 0, 0.f, sel_x, acc, X, grads(4), 256, p, sw(5), grads(5), 256);  // L5^T (h part)
         MI_STAMP(a, 6);
 #pragma unroll 1
         for (int l = 4; l >= 2; --l)                                                           // L4^T .. L2^T
-            bwd_layer<8, 8, 0, 32, EPI_RELU, false, false, true, 8>(c, slot, 0, 0.f, sel_x, acc, X, sw(l),
-                                                                    a.grads + (int64_t)(256 * (l - 1)) * P, 256, p, valid, -1, 0, nullptr,
-                                                                    a.grads + (int64_t)(256 * l) * P, 256);
+            bwd_layer<8, 8, 0, 32, EPI_RELU, false, true, 8>(c, slot, 0, 0.f, sel_x, acc, X, a.grads + (int64_t)(256 * (l - 1)) * P,
+                                                             256, p, sw(l), a.grads + (int64_t)(256 * l) * P, 256);
         MI_STAMP(a, 7);                                                                        // after L4^T .. L2^T
-        bwd_layer<8, 8, 0, 0, EPI_RELU, false, false, false, 8>(c, slot, 0, 0.f, sel_x, acc, X, sw(1), grads(0), 256, p, valid, -1, 0, nullptr, grads(1), 256);   // L1^T
+        bwd_layer<8, 8, 0, 0, EPI_RELU, false, false, 8>(c, slot, 0, 0.f, sel_x, acc, X, grads(0), 256, p, sw(1), grads(1), 256);   // L1^T
         MI_STAMP(a, 8);
     } else {
         // dir layer^T with the sigma head's contribution to dH4 (sigma row is aux piece 3 of slot 0)
@@ -336,17 +305,17 @@ __global__ __launch_bounds__(256, 1) void nerf_bwd_kernel(BwdArgs a) {
 #pragma unroll
         for (int m = 0; m < 4; ++m) Bd[m] = X[m];
         const auto sel_d = [&](auto kb) -> const f32x16& { return Bd[decltype(kb)::value]; };
-        bwd_layer<4, 8, 0, 32, EPI_RELU, true, false, true, 0>(c, 0, 3, ds, sel_d, acc, X, sw(4), grads(3), 256, p, valid);
-        bwd_layer<8, 8, 0, 32, EPI_RELU, false, false, true, 8>(c, slot, 0, 0.f, sel_x, acc, X, sw(3), grads(2), 256, p, valid, -1, 0, nullptr, grads(3), 256);  // L3^T
-        bwd_layer<8, 8, 0, 32, EPI_RELU, false, false, true, 8>(c, slot, 0, 0.f, sel_x, acc, X, sw(2), grads(1), 256, p, valid, -1, 0, nullptr, grads(2), 256);  // L2^T
-        bwd_layer<8, 8, 0, 0, EPI_RELU, false, false, false, 8>(c, slot, 0, 0.f, sel_x, acc, X, sw(1), grads(0), 256, p, valid, -1, 0, nullptr, grads(1), 256);   // L1^T
+        bwd_layer<4, 8, 0, 32, EPI_RELU, true, true, 0>(c, 0, 3, ds, sel_d, acc, X, grads(3), 256, p, sw(4));
+        bwd_layer<8, 8, 0, 32, EPI_RELU, false, true, 8>(c, slot, 0, 0.f, sel_x, acc, X, grads(2), 256, p, sw(3), grads(3), 256);  // L3^T
+        bwd_layer<8, 8, 0, 32, EPI_RELU, false, true, 8>(c, slot, 0, 0.f, sel_x, acc, X, grads(1), 256, p, sw(2), grads(2), 256);  // L2^T
+        bwd_layer<8, 8, 0, 0, EPI_RELU, false, false, 8>(c, slot, 0, 0.f, sel_x, acc, X, grads(0), 256, p, sw(1), grads(1), 256);   // L1^T
     }
 }
 
 // dA = dX (.) C with C = 30 cos(30 A) rebuilt from the saved (sign-encoded) X rows; stores dA rows, leaves them in X.
 template <int MB>
 __device__ __forceinline__ void sin_bwd_store(const f32x16 (&dX)[8], f32x16 (&X)[8], const f32x4 (&xsv)[MB * 4],
-                                              float* __restrict__ dA, int64_t ld, int64_t p, bool valid, int h) {
+                                              float* __restrict__ dA, int64_t ld, int64_t p, int h) {
     f32x4* drow = reinterpret_cast<f32x4*>(dA + p * ld + 4 * h);
 #pragma unroll
     for (int m = 0; m < MB; ++m)
@@ -368,7 +337,7 @@ __global__ __launch_bounds__(256, 1) void siren_bwd_kernel(BwdArgs a) {
     constexpr RegionLayout AL = siren_acts();
     constexpr RegionLayout GL = siren_grads();
     const int64_t P = a.points;
-    issue_first_stage<3, 32, false>(c, 0, 0, 0);
+    issue_first_stage<3, 32, false>(c, 0);
 
     const int64_t local = (int64_t)blockIdx.x * 128 + c.wave * 32 + (c.lane & 31);
     const bool valid = local < P;
@@ -401,24 +370,23 @@ __global__ __launch_bounds__(256, 1) void siren_bwd_kernel(BwdArgs a) {
                 acc[m][4 * rg + 3] = fmaf(w2.w, d2, fmaf(w1.w, d1, w0.w * d0));
             }
     }
-    sin_bwd_store<4>(acc, X, xsv, grads(9), 128, p, valid, c.h);                               // dA layers_dir.1 (X_d rows)
+    sin_bwd_store<4>(acc, X, xsv, grads(9), 128, p, c.h);                               // dA layers_dir.1 (X_d rows)
     int slot = 0;
     {   // layers_dir.1^T (h part); layers_dir.0 is linear: dA = dG.  B operand copied (see nerf_bwd_kernel).
         f32x16 Bd[4];
 #pragma unroll
         for (int m = 0; m < 4; ++m) Bd[m] = X[m];
         const auto sel_d = [&](auto kb) -> const f32x16& { return Bd[decltype(kb)::value]; };
-        bwd_layer<4, 8, 1, 32, EPI_LINEAR, false, false, true, 0>(c, slot, 0, 0.f, sel_d, acc, X, nullptr, grads(8), 256, p, valid);
+        bwd_layer<4, 8, 1, 32, EPI_LINEAR, false, true, 0>(c, slot, 0, 0.f, sel_d, acc, X, grads(8), 256, p);
     }
     slot ^= 1;
     // layers_dir.0^T + sigma head; dA7 = dX8 (.) C8, C_l rebuilt from the saved X_l rows (acts region l)
-    bwd_layer<8, 8, 0, 32, EPI_SIN, true, false, true, 8>(c, slot, 0, ds, sel_x, acc, X, acts(8), grads(7), 256, p, valid, -1, 0, nullptr, grads(8), 256);
+    bwd_layer<8, 8, 0, 32, EPI_SIN, true, true, 8>(c, slot, 0, ds, sel_x, acc, X, grads(7), 256, p, acts(8), grads(8), 256);
 #pragma unroll 1
     for (int l = 7; l >= 2; --l)                                                                // L7^T .. L2^T: dA_{l-1} = dX_l (.) C_l
-        bwd_layer<8, 8, 0, 32, EPI_SIN, false, false, true, 8>(c, slot, 0, 0.f, sel_x, acc, X, a.acts + (int64_t)(8 + 256 * (l - 1)) * P,
-                                                               a.grads + (int64_t)(256 * (l - 1)) * P, 256, p, valid, -1, 0, nullptr,
-                                                               a.grads + (int64_t)(256 * l) * P, 256);
-    bwd_layer<8, 8, 0, 0, EPI_SIN, false, false, false, 8>(c, slot, 0, 0.f, sel_x, acc, X, acts(1), grads(0), 256, p, valid, -1, 0, nullptr, grads(1), 256);   // L1^T: dA0 = dX1 (.) C1
+        bwd_layer<8, 8, 0, 32, EPI_SIN, false, true, 8>(c, slot, 0, 0.f, sel_x, acc, X, a.grads + (int64_t)(256 * (l - 1)) * P, 256, p,
+                                                        a.acts + (int64_t)(8 + 256 * (l - 1)) * P, a.grads + (int64_t)(256 * l) * P, 256);
+    bwd_layer<8, 8, 0, 0, EPI_SIN, false, false, 8>(c, slot, 0, 0.f, sel_x, acc, X, grads(0), 256, p, acts(1), grads(1), 256);   // L1^T: dA0 = dX1 (.) C1
 }
 
 // =========================================================================================
@@ -513,7 +481,7 @@ __device__ __forceinline__ void film_chain_layer(Ctx& c, int piece, float s, f32
         if constexpr (LAST) drow[m * 8 + rg * 2] = o;
     };
     const auto sel_x = [&](auto kb) -> const f32x16& { return X[decltype(kb)::value]; };
-    mma_layer_fn<8, 8, 0, 0, NEXT_BLOCK, FILM_NEXT, true, !SCALED, LAST>(c, issue_slot, next_film_layer, NoHook{}, sel_x, acc, pre, post, mid);
+    mma_layer_fn<8, 8, 0, NEXT_BLOCK, FILM_NEXT, !SCALED, LAST>(c, issue_slot, next_film_layer, sel_x, acc, pre, post, mid);
 }
 
 // RT_DEPTH: hidden_layers = L at run time (BwdArgs::film_depth, wave-uniform) for the MI_FIELD_FILM_DEPTH kinds; kinds 2 / 3
@@ -533,7 +501,7 @@ __global__ __launch_bounds__(256, 1) void film_bwd_kernel(BwdArgs a) {
     c.w0sq = a.packed[kBody + 1];
     const int64_t P = a.points;
     // rgb head rows x3, sigma row; K blocks 0-1 of hidden_layer_rgb^T; FiLM row L -> film slot 0 (row r lives in slot (L - r) & 1)
-    issue_first_stage<4, 32, true>(c, 0, 0, L);
+    issue_first_stage<4, 32, true>(c, 0, L);
 
     const int64_t local = tile * 128 + c.wave * 32 + (c.lane & 31);
     const bool valid = local < a.points_per_group;

@@ -12,7 +12,6 @@
 namespace mi {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define MI_LDS __attribute__((address_space(3)))
 #define MI_GLB __attribute__((address_space(1)))
 typedef const MI_LDS f32x4* lds4_t;
@@ -88,7 +87,7 @@ __device__ __forceinline__ void issue_stage(Ctx& c, int aux_slot, int chunk_buf,
 // First stage of a layer, issued in one go (kernel start, or after a VALU-only first layer): its aux pieces and
 // its first TWO K blocks (every MFMA layer has at least two) into the current stage buffer.
 template <int N_AUX, int BLOCK_PIECES, bool FILM>
-__device__ __forceinline__ void issue_first_stage(Ctx& c, int aux_slot, int /*unused*/, int film_layer) {
+__device__ __forceinline__ void issue_first_stage(Ctx& c, int aux_slot, int film_layer = 0) {
     issue_stage<N_AUX, 2 * BLOCK_PIECES, FILM>(c, aux_slot, c.buf, film_layer);
 }
 
@@ -294,7 +293,7 @@ __device__ __forceinline__ void activate(const f32x16 (&acc)[8], f32x16 (&X)[8],
 }
 
 // Training flavour of the sin activations: besides X = sin(30 u) it stores, as [point][feature] rows, X with the
-// sign of cos(30 u) in its lowest mantissa bit (mi_math.h:hw_sin30_saved) - all the backward needs of the layer.
+// sign of cos(30 u) in its lowest mantissa bit (mi_math.h:hw_sin_w_saved) - all the backward needs of the layer.
 template <int MB, int ACT>
 __device__ __forceinline__ void activate_train(const f32x16 (&acc)[8], f32x16 (&X)[8], const float* film_row, int h,
                                                const float* aux, float* __restrict__ x_rows, int64_t ld, int64_t p,
@@ -329,18 +328,17 @@ __device__ __forceinline__ void activate_train(const f32x16 (&acc)[8], f32x16 (&
 }
 
 // One MFMA layer: KB K blocks; bsel(kb) yields the B-operand register block of K block kb.
-// On entry the layer's first stage (aux + K block 0) has been issued into aux slot
-// `aux_slot` and chunk buffer PAR0.  NEXT_* describe the stage to issue while the last K block
-// computes (the next layer's first stage), 0/0 for none.
+// On entry the layer's first stage (aux + its first two K blocks) has been issued into aux slot `aux_slot` and
+// chunk buffer c.buf.
 // A stage = up to two K blocks behind one barrier (39 barriers per NeRF tile instead of 77).  Stage buffers
 // alternate (c.buf); while stage i computes, stage i+1's pieces (or the next layer's aux pieces + its first
-// two K blocks: NEXT_AUX, NEXT_BLOCK = pieces of one of its K blocks, 0 for none) are DMA'd into the other one.
-// HOOKS: pre(m, part) / post(m, part) are the sliced accumulator start / epilogue of mma_chunk; without them
-// init(acc) runs as one lump before the first MFMA and the caller applies its epilogue after the call.
-template <int KB, int MB, int PAR0_UNUSED, int NEXT_AUX, int NEXT_BLOCK, bool FILM, bool HOOKS = false, bool ZERO_START = false,
-          bool SPREAD_LAST = false, class Init, class BSel, class Pre = NoHook, class Post = NoHook, class Mid = NoHook>
-__device__ __forceinline__ void mma_layer_fn(Ctx& c, int aux_slot, int next_film_layer, Init init, BSel bsel,
-                                             f32x16 (&acc)[8], Pre pre = Pre{}, Post post = Post{}, Mid mid = Mid{}) {
+// two K blocks: NEXT_AUX, NEXT_BLOCK = pieces of one of its K blocks, 0 for none; NEXT_FILM: and FiLM row
+// `next_film_layer`) are DMA'd into the other one.
+// pre(m, part) / post(m, part) / mid(kb, slot) are the sliced accumulator start, epilogue and row traffic of mma_chunk.
+template <int KB, int MB, int NEXT_AUX, int NEXT_BLOCK, bool NEXT_FILM, bool ZERO_START, bool SPREAD_LAST, class BSel,
+          class Pre, class Post, class Mid = NoHook>
+__device__ __forceinline__ void mma_layer_fn(Ctx& c, int aux_slot, int next_film_layer, BSel bsel, f32x16 (&acc)[8],
+                                             Pre pre, Post post, Mid mid = Mid{}) {
     static_assert(KB >= 2, "every MFMA layer has at least two K blocks");
     auto stage = [&](auto ic_) {
         constexpr int i = decltype(ic_)::value;
@@ -350,15 +348,14 @@ __device__ __forceinline__ void mma_layer_fn(Ctx& c, int aux_slot, int next_film
         constexpr int next_blocks = left >= 2 ? 2 : (left > 0 ? left : 0);
         constexpr int zs = ZERO_START ? 8 : 0;         // ORDER bit 3: the layer's first MFMAs take srcC = 0
         constexpr int last = SPREAD_LAST ? 16 : 2;      // the last K block: epilogue in its last row, or spread over all of it
-        constexpr int order0 = HOOKS ? ((kb0 == 0 ? 1 | zs : 0) | (kb0 == KB - 1 ? last : 0)) : 0;
-        constexpr int order1 = HOOKS ? (kb0 + 1 == KB - 1 ? last : 0) : 0;
+        constexpr int order0 = (kb0 == 0 ? 1 | zs : 0) | (kb0 == KB - 1 ? last : 0);
+        constexpr int order1 = kb0 + 1 == KB - 1 ? last : 0;
         __syncthreads();
-        if constexpr (i == 0 && !HOOKS) init(acc);
         const float* buf = c.smem + kLdsChunk0 + c.buf * kLdsChunk;
         mma_chunk<MB, order0, kb0>(c, buf, bsel(ic<kb0>{}), acc, [&](auto sc) {
             constexpr int S = decltype(sc)::value;
             if constexpr (next_blocks > 0) issue_stage_slot<0, next_blocks * MB * 4, false, MB, S>(c, 0, c.buf ^ 1, 0);
-            else issue_stage_slot<NEXT_AUX, 2 * NEXT_BLOCK, FILM, MB, S>(c, aux_slot ^ 1, c.buf ^ 1, next_film_layer);
+            else issue_stage_slot<NEXT_AUX, 2 * NEXT_BLOCK, NEXT_FILM, MB, S>(c, aux_slot ^ 1, c.buf ^ 1, next_film_layer);
         }, pre, post, mid);
         if constexpr (two) mma_chunk<MB, order1, kb0 + 1>(c, buf + MB * 1024, bsel(ic<kb0 + 1>{}), acc, NoHook{}, pre, post, mid);
         c.buf ^= 1;
@@ -400,11 +397,11 @@ __device__ __forceinline__ uint32_t relu_switch_of(const uint32_t (&w)[4]) {
 // consumed).
 // Training stores do not burst either: with DEFER_X this layer's X rows are written by the NEXT layer's mid slots
 // (slot 4(j%4)+1 of K block j/4 for quarter j when that layer has 8 K blocks, else 2(j%PPC)+1 of K block j/PPC; X is
-// that layer's B operand and unchanged until its last row) - that
-// layer receives them as `prev` (PREV_MB blocks).  Sin layers save an ENCODING of X (cosine sign in the lowest bit)
-// that is not what the registers carry on, so their rows are stored by the activation hook itself, one quarter per
-// hook.
-template <int KB, int MB, bool K3, int NEXT_AUX, int NEXT_BLOCK, bool FILM, int ACT, bool SAVE, bool DEFER_X = false,
+// that layer's B operand and unchanged until its last row) - that layer receives them as `prev` (PREV_MB blocks).
+// Sin layers save an ENCODING of X (cosine sign in the lowest bit) that is not what the registers carry on, so their
+// rows are stored by the activation hook itself, one quarter per hook.
+// NEXT_FILM_ROW: the stage issued behind the layer (NEXT_AUX, NEXT_BLOCK) also carries row `next_film_layer` of the FiLM table.
+template <int KB, int MB, bool K3, int NEXT_AUX, int NEXT_BLOCK, bool NEXT_FILM_ROW, int ACT, bool SAVE, bool DEFER_X = false,
           int PREV_MB = 0, class BSel>
 __device__ __forceinline__ void fwd_layer(Ctx& c, int aux_slot, int next_film_layer, int k3_piece, float x, float y,
                                           float z, BSel bsel, f32x16 (&acc)[8], f32x16 (&X)[8], const float* film_row,
@@ -455,7 +452,7 @@ __device__ __forceinline__ void fwd_layer(Ctx& c, int aux_slot, int next_film_la
         }
         const f32x4 bias = bias_q[idx & 1];
         // the whole quarter as ONE four-wide value: every step is two independent packed instructions back to back, so no
-        // dependent packed op waits a state on its predecessor (mi_math.h:hw_turns30_x4)
+        // dependent packed op waits a state on its predecessor (mi_math.h:hw_turns_w_x4)
         f32x4 v = f32x4{acc[m][4 * rg + 0], acc[m][4 * rg + 1], acc[m][4 * rg + 2], acc[m][4 * rg + 3]} + bias;
         f32x4 o, xo;
         if constexpr (ACT == ACT_RELU) {
@@ -506,9 +503,9 @@ __device__ __forceinline__ void fwd_layer(Ctx& c, int aux_slot, int next_film_la
                 prow[m * 8 + rg * 2] = f32x4{X[m][4 * rg + 0], X[m][4 * rg + 1], X[m][4 * rg + 2], X[m][4 * rg + 3]};
             }
         };
-        mma_layer_fn<KB, MB, 0, NEXT_AUX, NEXT_BLOCK, FILM, true, !K3, kSpread>(c, aux_slot, next_film_layer, NoHook{}, bsel, acc, pre, post, mid);
+        mma_layer_fn<KB, MB, NEXT_AUX, NEXT_BLOCK, NEXT_FILM_ROW, !K3, kSpread>(c, aux_slot, next_film_layer, bsel, acc, pre, post, mid);
     } else {
-        mma_layer_fn<KB, MB, 0, NEXT_AUX, NEXT_BLOCK, FILM, true, !K3, kSpread>(c, aux_slot, next_film_layer, NoHook{}, bsel, acc, pre, post);
+        mma_layer_fn<KB, MB, NEXT_AUX, NEXT_BLOCK, NEXT_FILM_ROW, !K3, kSpread>(c, aux_slot, next_film_layer, bsel, acc, pre, post);
     }
     if constexpr (ACT == ACT_RELU && SAVE) {
         // one 16-byte (MB = 8) or 8-byte (MB = 4) store per lane: the wave's 32 points x 2 halves are contiguous
@@ -551,6 +548,11 @@ __device__ __forceinline__ float head_dot(const f32x16 (&X)[8], const float* aux
     return s;
 }
 
+// sigma = relu(w . X + b): the head's weight row is piece 1 and its bias the first float of piece 2 of the aux slot
+__device__ __forceinline__ float sigma_head(const f32x16 (&X)[8], const float* aux, int h) {
+    return fmaxf(head_dot<8>(X, aux, 1, h) + aux[2 * kPiece], 0.f);
+}
+
 __device__ __forceinline__ float sigmoidf(float v) { return 1.f / (1.f + expf(-v)); }
 
 // Positional-encoding blocks, fully unrolled.  Feature f of the encoding of (x,y,z): i = f/6, c = f%6,
@@ -566,8 +568,7 @@ __device__ __forceinline__ float pe_feature(float xv, float scale, float quarter
 }
 
 template <int NBLK>
-__device__ __forceinline__ void posenc_blocks(float* /*scr*/, int /*lane*/, int h, float x, float y, float z, int nfeat,
-                                              f32x16* out) {
+__device__ __forceinline__ void posenc_blocks(int h, float x, float y, float z, int nfeat, f32x16* out) {
     const float xyz[3] = {x, y, z};
     static_for<NBLK * 16>([&](auto sc) {
         constexpr int slot = decltype(sc)::value;
@@ -677,7 +678,6 @@ __device__ __forceinline__ void store_sigma(const MlpArgs& a, const PointIn& pt,
     if (pt.valid && h == 0) a.out[pt.p] = s;
 }
 
-
 // ---- activations <-> HBM in [point][feature] row-major (training: saved layer inputs, gradients) --------
 // Register r of block m on lane (col j, half h) is feature 32m + 8(r>>2) + 4h + (r&3) of point j, so each
 // (m, rg) group of 4 registers is one aligned float4 of the point's row.
@@ -692,6 +692,5 @@ __device__ __forceinline__ void store_rows(float* __restrict__ base, int64_t ld,
         for (int rg = 0; rg < 4; ++rg)
             row[m * 8 + rg * 2] = f32x4{X[m][4 * rg + 0], X[m][4 * rg + 1], X[m][4 * rg + 2], X[m][4 * rg + 3]};
 }
-
 
 }  // namespace mi
