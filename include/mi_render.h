@@ -172,9 +172,17 @@ int mi_sample_pdf(int64_t n, int n_bins, int n_samples, const float* bins, const
  *   of a call with all six outputs.  That coarse pass runs front to back in windows of samples and stops evaluating the
  *   field along a ray once the ray's transmittance has reached zero: every later weight is exactly 0 whatever the field
  *   returns there, so no output bit depends on it - except that a non-finite sigma behind a zero transmittance no longer
- *   reaches the outputs as NaN.  All launches stay asynchronous, with host-known grid sizes (stream capture works). */
+ *   reaches the outputs as NaN.  All launches stay asynchronous, with host-known grid sizes (stream capture works).
+ *   With two different fields, a fine field of a kind that has the kernels (NeRF, TinyNeRF), Nf > 0 and a workspace that
+ *   also holds mi_render_deferred_colour_extra_bytes(n, Nc, Nf) more, the fine pass runs its colour branch only on the
+ *   points with sigma > 0 (in chunks of whole rays: the trunk for every point, then the colour branch over the chunk's
+ *   live points).  A point with sigma == 0 has weight exactly 0, so no output bit depends on its colour - except that a
+ *   non-finite colour at such a point no longer reaches the outputs as NaN.  Without the extra bytes: the whole forward,
+ *   same results. */
 int64_t mi_render_workspace_bytes(int64_t n, int n_coarse, int n_fine);
 int64_t mi_render_shared_field_extra_bytes(int64_t n, int n_coarse, int n_fine);
+int64_t mi_render_deferred_colour_extra_bytes(int64_t n, int n_coarse, int n_fine);    /* 0 with Nf = 0 */
+int mi_field_has_deferred_colour(int kind);    /* 1 if a fine field of this kind can use those bytes, else 0 (needs no GPU) */
 int mi_render_rays(int kind_coarse, const float* packed_coarse, int kind_fine, const float* packed_fine,
                    const float* film, const float* rays, int64_t n_groups, int64_t rays_per_group,
                    float near_, float far_, int n_coarse, int n_fine, const float* z_lin, const float* u_lin,
@@ -407,6 +415,19 @@ int mi_event_elapsed_ms(void* start, void* stop, float* ms);
 /* While set (thread-local; pass NULLs to clear), mi_render_rays records these events on its
  * stream immediately before/after the coarse and the fine field-MLP launch. */
 void mi_render_set_mlp_events(void* start_coarse, void* stop_coarse, void* start_fine, void* stop_fine);
+
+/* ---- test hooks of the deferred colour branch ---------------------------------------- */
+
+/* mi_field_eval_rays with the colour branch deferred to the points with sigma > 0 (NeRF and TinyNeRF, else MI_EINVAL; film
+ * is ignored): raw [n,S,4] has mi_field_eval_rays' bits wherever sigma > 0 and r = g = b = 0 elsewhere (sigma: its bits
+ * everywhere).  extra: a device buffer of mi_render_deferred_colour_extra_bytes(n, Nc, Nf) bytes for any Nc + Nf = n_samples,
+ * Nf > 0; extra_bytes = what the caller really provided. */
+int mi_field_eval_rays_deferred(int kind, const float* packed, const float* film, const float* rays, const float* z,
+                                int64_t n_groups, int64_t rays_per_group, int n_samples, float* raw, void* extra,
+                                int64_t extra_bytes, void* stream);
+/* Points per chunk of the deferred colour branch (process-wide; 0 = the build's constant, 2^22): a debug hook, so that a
+ * test can force several chunks at small sizes.  mi_render_deferred_colour_extra_bytes follows it. */
+void mi_render_set_colour_chunk_rows(int64_t rows);
 
 #ifdef __cplusplus
 }

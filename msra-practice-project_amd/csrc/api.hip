@@ -118,6 +118,42 @@ static int coarse_sigma_windows(int kind, const float* packed, const float* rays
     return MI_OK;
 }
 
+// Points per chunk of the fine pass's deferred colour branch (the row buffer holds that many 1 KiB rows).
+#ifndef MI_COLOUR_CHUNK_ROWS_LOG2
+#define MI_COLOUR_CHUNK_ROWS_LOG2 22
+#endif
+constexpr int64_t kColourChunkRows = (int64_t)1 << MI_COLOUR_CHUNK_ROWS_LOG2;
+static int64_t g_colour_chunk_rows = 0;               // mi_render_set_colour_chunk_rows: 0 = kColourChunkRows
+static int64_t colour_chunk_rows() { return g_colour_chunk_rows > 0 ? g_colour_chunk_rows : kColourChunkRows; }
+
+// kinds with the two kernels, point indices that fit the live list's ints
+static bool can_defer_colour(int kind, int64_t n, int S) { return has_deferred_colour_kernels(kind) && n > 0 && S > 0 && n * S <= 0x7fffffffLL; }
+
+// The field over n rays of S samples with its colour branch deferred to the points with sigma > 0, in chunks of whole rays:
+// per chunk a trunk-and-spill launch ({0, 0, 0, sigma} for every point, H8 rows and indices of the live ones into `extra`)
+// and a colour launch over that list.  A point with sigma == 0 keeps r = g = b = 0: its weight is exactly 0, so 0 * rgb
+// is the +0 that any finite colour gives.  Every chunk has its own count, cleared by one memset node; all launches on `hs`
+// with grids from host values (no read-back: graph-capturable).  `extra`: DeferredColourBuf(n, S, colour_chunk_rows()).
+static int eval_rays_deferred_colour(int kind, const float* packed, const float* rays, const float* z, int64_t n, int S,
+                                     float* raw, void* extra, hipStream_t hs) {
+    const DeferredColourBuf buf(n, S, colour_chunk_rows());
+    const DeferredColourBuf::Regions r = buf.carve(extra);
+    if (hipMemsetAsync(r.counts, 0, sizeof(int) * buf.n_chunks, hs) != hipSuccess) { set_error("deferred colour: hipMemsetAsync failed"); return MI_EHIP; }
+    MlpArgs args = {};
+    args.packed = packed; args.n_samples = S; args.mode = 1;
+    for (int64_t i = 0; i < buf.n_chunks; ++i) {
+        const int64_t r0 = i * buf.chunk_rays, nr = n - r0 < buf.chunk_rays ? n - r0 : buf.chunk_rays;
+        args.a = rays + r0 * 6; args.z = z + r0 * S; args.out = raw + r0 * S * 4;
+        args.rays_per_group = nr; args.points_per_group = nr * S; args.tiles_per_group = (nr * S + 127) / 128;
+        args.save_points = nr * S;
+        const DeferArgs d = {r.rows, r.idx, r.counts + i};
+        int rc;
+        if ((rc = launch_mlp_trunk_spill(kind, args, d, hs))) return rc;
+        if ((rc = launch_mlp_colour(kind, args, d, hs))) return rc;
+    }
+    return MI_OK;
+}
+
 }  // namespace mi
 
 using namespace mi;
@@ -175,6 +211,36 @@ int mi_field_eval_rays(int kind, const float* packed, const float* film, const f
     if (n_samples <= 0) { set_error("n_samples must be positive"); return MI_EINVAL; }
     return eval_common(kind, packed, film, rays, z, n_groups, rays_per_group * n_samples, rays_per_group, n_samples, 1,
                        raw, (hipStream_t)stream);
+}
+
+int64_t mi_render_deferred_colour_extra_bytes(int64_t n, int n_coarse, int n_fine) {
+    if (n <= 0 || n_coarse < 1 || n_fine <= 0) return 0;
+    return DeferredColourBuf(n, (int64_t)n_coarse + n_fine, colour_chunk_rows()).bytes();
+}
+
+int mi_field_has_deferred_colour(int kind) { return bad_kind(kind) ? MI_EINVAL : has_deferred_colour_kernels(kind) ? 1 : 0; }
+
+void mi_render_set_colour_chunk_rows(int64_t rows) { g_colour_chunk_rows = rows > 0 ? rows : 0; }
+
+int mi_field_eval_rays_deferred(int kind, const float* packed, const float* film, const float* rays, const float* z,
+                                int64_t n_groups, int64_t rays_per_group, int n_samples, float* raw, void* extra,
+                                int64_t extra_bytes, void* stream) {
+    (void)film;
+    if (bad_kind(kind)) return MI_EINVAL;
+    if (n_samples <= 0 || n_groups < 0 || rays_per_group < 0) { set_error("mi_field_eval_rays_deferred: bad sizes"); return MI_EINVAL; }
+    const int64_t n = n_groups * rays_per_group;
+    if (n == 0) return MI_OK;
+    if (!packed || !rays || !z || !raw || !extra) { set_error("mi_field_eval_rays_deferred: null pointer argument"); return MI_EINVAL; }
+    if (!can_defer_colour(kind, n, n_samples)) {
+        set_error("mi_field_eval_rays_deferred: kind %d has no deferred colour branch, or n * n_samples exceeds 2^31 - 1", kind);
+        return MI_EINVAL;
+    }
+    const int64_t need = DeferredColourBuf(n, n_samples, colour_chunk_rows()).bytes();
+    if (extra_bytes < need) {
+        set_error("mi_field_eval_rays_deferred: buffer of %lld bytes, needs %lld", (long long)extra_bytes, (long long)need);
+        return MI_EINVAL;
+    }
+    return eval_rays_deferred_colour(kind, packed, rays, z, n, n_samples, raw, extra, (hipStream_t)stream);
 }
 
 int mi_gen_rays(int width, int height, double focal, const float* c2w_host, int64_t ray0, int64_t n, float* rays,
@@ -336,8 +402,15 @@ int mi_render_rays(int kind_coarse, const float* packed_coarse, int kind_fine, c
     }
     if ((rc = mi_sample_fine(n, near_, far_, n_coarse, n_fine, z_lin, u_lin, z_c, w_c, nullptr, z_f, stream))) return rc;
     if (g_mlp_ev[2]) (void)hipEventRecord(g_mlp_ev[2], hs);
-    if ((rc = mi_field_eval_rays(kind_fine, packed_fine, film, rays, z_f, n_groups, rays_per_group, S, raw_f, stream)))
-        return rc;
+    // A fine field of its own, in a workspace that also holds mi_render_deferred_colour_extra_bytes (behind base_bytes, where
+    // the shared path's regions would lie): the colour branch runs on the points with sigma > 0 only.  A caller that did not
+    // provide the extra gets the whole forward (same results).
+    const int64_t defer_bytes = mi_render_deferred_colour_extra_bytes(n, n_coarse, n_fine);
+    if (!shared && defer_bytes > 0 && can_defer_colour(kind_fine, n, S) && workspace_bytes >= base_bytes + defer_bytes)
+        rc = eval_rays_deferred_colour(kind_fine, packed_fine, rays, z_f, n, S, raw_f, (char*)workspace + base_bytes, hs);
+    else
+        rc = mi_field_eval_rays(kind_fine, packed_fine, film, rays, z_f, n_groups, rays_per_group, S, raw_f, stream);
+    if (rc) return rc;
     if (g_mlp_ev[3]) (void)hipEventRecord(g_mlp_ev[3], hs);
     return mi_composite(n, S, raw_f, z_f, rays, rgb_f, depth_f, acc_f, nullptr, stream);
 }

@@ -95,6 +95,8 @@ struct FieldKind {
         const PackItem& k = fwd.item[sigma_items() + branch_aux_pieces()];
         return k.type == ITEM_CHUNK ? k.mb * 1024 / kPiece : 0;
     }
+    // Float offset of that stage in the forward stream: where a kernel that runs the colour branch alone starts reading.
+    constexpr int branch_stream_floats() const { return fwd.dst_off[sigma_items()]; }
 };
 
 // FilmSirenNeRF(hidden_dim = 256, hidden_layers = L, use_dir) (pi_GAN/modules.py:73-94): L + 3 linear layers

@@ -34,10 +34,16 @@ namespace mi {
 // the inference instance's instructions, so sigma has the same bits.
 // WINDOW = the sigma-only instance over one window of samples of the live rays (load_window_point): a block whose tile lies
 // past the live count returns before it issues any LDS DMA.
-template <bool TINY, bool SAVE, bool SIGMA_ONLY, bool WINDOW = false>
-__global__ __launch_bounds__(256, 1) void nerf_fwd_kernel(MlpArgs a) {
+// SPILL = the trunk-and-spill instance of the fine pass's deferred colour branch: the sigma-only instance with another
+// ending.  It writes {0, 0, 0, sigma} to out [M][4] and appends every point with sigma > 0 - its H8 row and its index - to
+// the live list a.defer (spill_live); nerf_colour_kernel below then runs the colour branch over that list alone.  Only this
+// instance's argument block carries the list: every other instance takes MlpArgs as before.
+struct DeferMlpArgs : MlpArgs { DeferArgs defer; };
+template <bool TINY, bool SAVE, bool SIGMA_ONLY, bool WINDOW = false, bool SPILL = false>
+__global__ __launch_bounds__(256, 1) void nerf_fwd_kernel(std::conditional_t<SPILL, DeferMlpArgs, MlpArgs> a) {
     static_assert(!(SAVE && SIGMA_ONLY), "the training forward needs the colour branch");
     static_assert(!WINDOW || SIGMA_ONLY, "windows exist for the sigma-only coarse pass");
+    static_assert(!SPILL || (SIGMA_ONLY && !WINDOW), "the spill is an ending of the sigma-only instance");
     constexpr FieldKind K = kFieldKinds[TINY ? MI_FIELD_TINY_NERF : MI_FIELD_NERF];
     // the stage the last trunk layer issues behind it: the colour branch's first, none if the wave stops at sigma
     constexpr int kNextAux = SIGMA_ONLY ? 0 : K.branch_aux_pieces();
@@ -148,7 +154,11 @@ __global__ __launch_bounds__(256, 1) void nerf_fwd_kernel(MlpArgs a) {
         sigma = sigma_head(X, smem + kLdsAux0 + slot * kLdsAux, c.h);
         slot ^= 1;
     }
-    if constexpr (SIGMA_ONLY) {
+    if constexpr (SPILL) {
+        store_out(a, pt, c.h, 0.f, 0.f, 0.f, sigma);
+        spill_live(a.defer, pt, c.lane, c.h, sigma, X);
+        return;
+    } else if constexpr (SIGMA_ONLY) {
         store_sigma(a, pt, c.h, sigma);
         return;
     }
@@ -163,6 +173,63 @@ __global__ __launch_bounds__(256, 1) void nerf_fwd_kernel(MlpArgs a) {
     const float b = sigmoidf(head_dot<4>(X, aux, 3, c.h) + aux[4 * kPiece + 2]);
     store_out(a, pt, c.h, r, g, b, sigma);
     MI_STAMP(a, 21);
+}
+
+// The colour branch alone, over the live list a trunk-and-spill launch left (same `a`): one tile = 128 list entries, one wave
+// per 32.  A point's H8 comes back from its row (load_rows), its view direction from its ray with load_point's expressions;
+// the packed stream is entered at the colour branch's first stage (field_kinds.h: branch_stream_floats), which this kernel
+// issues itself where the inference instance's last trunk layer issues it.  From there it runs that instance's fwd_layer
+// instantiations and heads, so r, g, b have its bits; they go to out[idx], where sigma already is.  Grid-stride over the
+// tiles below the device count: a frame's worst-case tiles would be several hundred thousand blocks that only read the count.
+template <bool TINY>
+__global__ __launch_bounds__(256, 1) void nerf_colour_kernel(DeferMlpArgs a) {
+    const DeferArgs& d = a.defer;
+    constexpr FieldKind K = kFieldKinds[TINY ? MI_FIELD_TINY_NERF : MI_FIELD_NERF];
+    constexpr int kBranchAux = K.branch_aux_pieces(), kBranchBlock = K.branch_block_pieces();
+    constexpr int kBranchBytes = K.branch_stream_floats() * (int)sizeof(float);
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int64_t count = __builtin_amdgcn_readfirstlane(__hip_atomic_load(d.count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    Ctx c = make_ctx(smem, a, 0);
+    const SaveRows none{nullptr, 0, 0, false};
+    bool again = false;
+    for (int64_t tile = blockIdx.x; tile * 128 < count; tile += gridDim.x) {
+        if (again) __syncthreads();              // every wave has read the last tile's heads: the LDS may be refilled
+        again = true;
+        c.soff = kBranchBytes;
+        c.buf = 0;
+        issue_first_stage<kBranchAux, kBranchBlock, false>(c, 0);
+
+        const int64_t entry = tile * 128 + c.wave * 32 + (c.lane & 31);
+        const bool valid = entry < count;
+        const int64_t ec = valid ? entry : count - 1;            // clamped like load_window_point's entries, masked on the store
+        const int p = d.idx[ec];
+        const float* r6 = a.a + (int64_t)(p / a.n_samples) * 6;
+        const float d0 = r6[3], d1 = r6[4], d2 = r6[5];
+        const float nrm = dir_norm(d0, d1, d2);
+        f32x16 pd[1], X[8], acc[8];
+        posenc_blocks<1>(c.h, d0 / nrm, d1 / nrm, d2 / nrm, 24, pd);
+        load_rows<8>(d.rows, 256, ec, c.h, X);
+
+        const auto sel_x = [&](auto kb) -> const f32x16& { return X[decltype(kb)::value]; };
+        const auto sel_dir = [&](auto kb) -> const f32x16& {
+            constexpr int k = decltype(kb)::value;
+            if constexpr (k < 8) return X[k]; else return pd[0];
+        };
+        int slot = 0;
+        if constexpr (!TINY) {
+            fwd_layer<8, 8, false, 5, 16, false, ACT_LINEAR, false, true, 8>(c, slot, 0, 0, 0.f, 0.f, 0.f, sel_x, acc, X, nullptr, none, none);  // G
+            slot ^= 1;
+        }
+        fwd_layer<9, 4, false, 0, 0, false, ACT_RELU, false, false, 8>(c, slot, 0, 0, 0.f, 0.f, 0.f, sel_dir, acc, X, nullptr, none, none);   // H_d
+        const float* aux = smem + kLdsAux0 + slot * kLdsAux;
+        const float r = sigmoidf(head_dot<4>(X, aux, 1, c.h) + aux[4 * kPiece + 0]);
+        const float g = sigmoidf(head_dot<4>(X, aux, 2, c.h) + aux[4 * kPiece + 1]);
+        const float b = sigmoidf(head_dot<4>(X, aux, 3, c.h) + aux[4 * kPiece + 2]);
+        if (valid && c.h == 0) {
+            float* o = a.out + (int64_t)p * 4;
+            o[0] = r; o[1] = g; o[2] = b;
+        }
+    }
 }
 
 // =========================================================================================
@@ -346,6 +413,13 @@ static const void* const kFilmDepthFwdKernels[2][2] = {
     {(const void*)film_fwd_kernel<false, false, true>, (const void*)film_fwd_kernel<false, true, true>},
     {(const void*)film_fwd_kernel<true, false, true>, (const void*)film_fwd_kernel<true, true, true>}};
 
+// [kind]: the trunk-and-spill instance and the colour-branch kernel of the deferred colour branch (NeRF, TinyNeRF)
+static const void* const kSpillKernels[MI_FIELD_KINDS] = {(const void*)nerf_fwd_kernel<false, false, true, false, true>, nullptr, nullptr,
+                                                          nullptr, (const void*)nerf_fwd_kernel<true, false, true, false, true>};
+static const void* const kColourKernels[MI_FIELD_KINDS] = {(const void*)nerf_colour_kernel<false>, nullptr, nullptr, nullptr,
+                                                           (const void*)nerf_colour_kernel<true>};
+
+bool has_deferred_colour_kernels(int kind) { return kind >= 0 && kind < MI_FIELD_KINDS && kSpillKernels[kind] && kColourKernels[kind]; }
 bool has_sigma_only_kernel(int kind) { return kind >= 0 && kind < MI_FIELD_KINDS && kFwdKernels[kind][FWD_SIGMA]; }
 
 // 148 KiB of dynamic LDS: raise the per-kernel limit once per device (host-side attribute, no device work)
@@ -361,6 +435,12 @@ static int raise_lds_limit(size_t lds) {
         for (const auto& k : kFilmDepthFwdKernels)
             for (const void* f : k) {
                 const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return -2; }
+            }
+        for (const auto* tab : {kSpillKernels, kColourKernels})
+            for (int k = 0; k < MI_FIELD_KINDS; ++k) {
+                if (!tab[k]) continue;
+                const hipError_t e = hipFuncSetAttribute(tab[k], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
                 if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return -2; }
             }
         return 0;
@@ -409,6 +489,53 @@ int launch_mlp_window(int kind_in, const MlpArgs& a, hipStream_t stream) {
     void* args[] = {const_cast<MlpArgs*>(&a)};
     (void)hipLaunchKernel(kFwdKernels[kind][FWD_SIGMA_WINDOW], dim3((unsigned)blocks), dim3(256), args, lds, stream);
     return check_launch("field_mlp_fwd_window");
+}
+
+// compute units of the current device, asked once per device ordinal (0 and the error set if the query fails)
+static int compute_units() {
+    static std::atomic<int> cached[256] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 256) { set_error("hipGetDevice failed"); return 0; }
+    int cus = cached[dev].load(std::memory_order_relaxed);
+    if (cus < 1) {
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) {
+            set_error("field_mlp_colour: no compute-unit count");
+            return 0;
+        }
+        cached[dev].store(cus, std::memory_order_relaxed);
+    }
+    return cus;
+}
+
+// shared checks of the two deferred-colour launches: a mode-1 launch of one group whose point indices fit the list's ints
+static int check_deferred(int kind, const MlpArgs& a, const DeferArgs& d) {
+    if (bad_kind(kind)) return -1;
+    if (!has_deferred_colour_kernels(kind) || a.save || a.film || a.mode != 1 || a.n_samples < 1 || !d.rows || !d.idx || !d.count ||
+        a.points_per_group < 1 || a.points_per_group > 0x7fffffffLL || a.tiles_per_group != (a.points_per_group + 127) / 128) {
+        set_error("kind %d: bad deferred-colour launch", kind);
+        return -1;
+    }
+    return raise_lds_limit(kLdsFloats * sizeof(float));
+}
+
+int launch_mlp_trunk_spill(int kind, const MlpArgs& a, const DeferArgs& d, hipStream_t stream) {
+    if (const int rc = check_deferred(kind, a, d)) return rc;
+    DeferMlpArgs da{a, d};
+    void* args[] = {&da};
+    (void)hipLaunchKernel(kSpillKernels[kind], dim3((unsigned)a.tiles_per_group), dim3(256), args, kLdsFloats * sizeof(float), stream);
+    return check_launch("field_mlp_trunk_spill");
+}
+
+int launch_mlp_colour(int kind, const MlpArgs& a, const DeferArgs& d, hipStream_t stream) {
+    if (const int rc = check_deferred(kind, a, d)) return rc;
+    // one block per CU (148 KiB of LDS each) strides over the tiles below the device count; never more blocks than tiles
+    const int cus = compute_units();
+    if (cus < 1) return -2;
+    const int64_t blocks = a.tiles_per_group < cus ? a.tiles_per_group : cus;
+    DeferMlpArgs da{a, d};
+    void* args[] = {&da};
+    (void)hipLaunchKernel(kColourKernels[kind], dim3((unsigned)blocks), dim3(256), args, kLdsFloats * sizeof(float), stream);
+    return check_launch("field_mlp_colour");
 }
 
 }  // namespace mi

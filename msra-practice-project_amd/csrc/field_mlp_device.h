@@ -590,6 +590,17 @@ struct PointIn {
     bool valid;
 };
 
+// |d| of a ray direction with its roundings stated: the rounded d0 d0, d1 d1 added by one fma, then the rounded d2 d2 added.
+// This is what load_point's / load_window_point's norm compiles to in every instance (the compiler multiplies d0, d2 as a
+// pair and contracts the first sum only); a kernel that must reproduce their view direction from another code shape
+// (nerf_colour_kernel) cannot leave the contraction to the compiler - its own choice there was two fmas, one ulp away on one
+// ray in twenty.  tests/test_gpu_deferred_colour.py holds the two against each other bit for bit.
+__device__ __forceinline__ float dir_norm(float d0, float d1, float d2) {
+#pragma clang fp contract(off)
+    const float s01 = __builtin_fmaf(d1, d1, d0 * d0);
+    return sqrtf(s01 + d2 * d2);
+}
+
 // mode 0: x[M,6] points; mode 1: rays[N,2,3] + z[N,S].
 __device__ __forceinline__ PointIn load_point(int mode, const float* __restrict__ a, const float* __restrict__ zv,
                                                int64_t group, int64_t ppg, int64_t rpg, int S, int64_t local) {
@@ -691,6 +702,38 @@ __device__ __forceinline__ void store_rows(float* __restrict__ base, int64_t ld,
 #pragma unroll
         for (int rg = 0; rg < 4; ++rg)
             row[m * 8 + rg * 2] = f32x4{X[m][4 * rg + 0], X[m][4 * rg + 1], X[m][4 * rg + 2], X[m][4 * rg + 3]};
+}
+
+// ... and back: the inverse of store_rows (row p must exist: callers clamp p)
+template <int MB>
+__device__ __forceinline__ void load_rows(const float* __restrict__ base, int64_t ld, int64_t p, int h, f32x16 (&X)[8]) {
+    const f32x4* row = reinterpret_cast<const f32x4*>(base + p * ld + 4 * h);
+#pragma unroll
+    for (int m = 0; m < MB; ++m)
+#pragma unroll
+        for (int rg = 0; rg < 4; ++rg) {
+            const f32x4 v = row[m * 8 + rg * 2];
+            X[m][4 * rg + 0] = v.x; X[m][4 * rg + 1] = v.y; X[m][4 * rg + 2] = v.z; X[m][4 * rg + 3] = v.w;
+        }
+}
+
+// Trunk-and-spill ending: every valid point with sigma > 0 is appended to the live list d - its H8 row (X, 256 wide) and its
+// point index.  One ballot over the wave's 32 points (the h == 0 lanes: both halves of a column hold the same sigma, the
+// list follows the half that store_out writes), one agent-scope atomic per wave for the slots, a point's slot = the base +
+// the live points on the lanes below it.  Nothing crosses waves, the list order is arbitrary.  The list cannot overflow:
+// it has room for every point of the launch.
+__device__ __forceinline__ void spill_live(const DeferArgs& d, const PointIn& pt, int lane, int h, float sigma,
+                                           const f32x16 (&X)[8]) {
+    const uint64_t live = __ballot(h == 0 && pt.valid && sigma > 0.f);
+    if (!live) return;                                                   // wave-uniform
+    int base = 0;
+    if (lane == 0) base = __hip_atomic_fetch_add(d.count, __popcll(live), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    base = __builtin_amdgcn_readfirstlane(base);
+    const int col = lane & 31;
+    const bool mine = (live >> col) & 1;
+    const int64_t slot = base + __popcll(live & ((1ull << col) - 1));
+    store_rows<8>(d.rows, 256, slot, mine, h, X);
+    if (mine && h == 0) d.idx[slot] = (int)pt.p;
 }
 
 }  // namespace mi

@@ -52,7 +52,8 @@ public:
 constexpr int64_t align64(int64_t x) { return (x + 63) / 64 * 64; }
 
 // The workspace of mi_render_rays / mi_render_rays_train for n rays of Nc + Nf samples: the five regions of
-// mi_render_workspace_bytes, then the three that one field for both passes adds (mi_render_shared_field_extra_bytes).
+// mi_render_workspace_bytes, then the three that one field for both passes adds (mi_render_shared_field_extra_bytes) - or,
+// in their place, what two fields' deferred colour branch adds (DeferredColourBuf below, mi_render_deferred_colour_extra_bytes).
 struct RenderWorkspace {
     struct Regions {
         float *z_c, *raw_c, *w_c, *z_f, *raw_f;       // [n,Nc] [n,Nc,4] [n,Nc] [n,S] [n,S,4]
@@ -80,6 +81,31 @@ struct RenderWorkspace {
     }
 };
 
+// The buffer of the fine pass's deferred colour branch (mi_render_deferred_colour_extra_bytes), for n rays of S samples
+// evaluated in chunks of whole rays of at most chunk_rows points (one ray where S is larger): the H8 rows [cap][256] and the
+// point indices [cap] of one chunk's live list (worst case: every point of the chunk live), and one count per chunk.  In a
+// render workspace it lies behind base_bytes(), where the shared-field regions lie: the two paths exclude each other.
+struct DeferredColourBuf {
+    struct Regions { float* rows; int* idx; int* counts; };
+    int64_t chunk_rays, n_chunks, cap;
+    DeferredColourBuf(int64_t n, int64_t S, int64_t chunk_rows) {
+        chunk_rays = chunk_rows / (S > 0 ? S : 1);
+        if (chunk_rays < 1) chunk_rays = 1;
+        if (chunk_rays > n) chunk_rays = n;
+        n_chunks = chunk_rays > 0 ? (n + chunk_rays - 1) / chunk_rays : 0;
+        // A chunk uses chunk_rays * S rows.  Where that falls short of chunk_rows (S does not divide it) the buffer is still
+        // sized for chunk_rows, so that its size is the documented min(n * S, chunk_rows) rows: slack of less than one ray.
+        cap = chunk_rays * S;
+        if (cap < chunk_rows) cap = chunk_rows < n * S ? chunk_rows : n * S;
+    }
+    int64_t bytes() const { return (align64(cap * 256) + align64(cap) + align64(n_chunks)) * (int64_t)sizeof(float); }
+    Regions carve(void* base) const {
+        float* rows = (float*)base;
+        int* idx = (int*)(rows + align64(cap * 256));
+        return {rows, idx, idx + align64(cap)};
+    }
+};
+
 // arguments of the fused field-MLP kernels (field_mlp.hip)
 struct MlpArgs {
     const float* packed;    // packed weight stream (field_layout.h)
@@ -104,6 +130,14 @@ struct MlpArgs {
     int win_log2;
 };
 
+// The live list of one chunk of the fine pass (DeferredColourBuf): the trunk-and-spill instance appends to it, the colour-branch
+// kernel reads it.  Point indices are relative to the launch's a.out / a.z (the chunk's first point is 0).
+struct DeferArgs {
+    float* rows;            // [entries][256] H8 (the last trunk layer's activation) of the listed points
+    int* idx;               // [entries] point index of each entry
+    int* count;             // entries; cleared before the trunk-and-spill launch
+};
+
 // In-kernel cycle stamps for the diagnostic build (csrc/build.py --profile -> gpurun_tools/libmirender_prof.so);
 // the product build compiles them out.
 #ifdef MI_PROFILE_STAMPS
@@ -122,6 +156,12 @@ bool has_sigma_only_kernel(int kind);
 // the sigma-only instance over a window of samples of the live rays (a.live_rays / a.live_count / a.n_rays / a.win_*;
 // a.a = rays, a.z and a.out [n_rays, n_samples]); the grid covers n_rays, blocks past the live count return at once
 int launch_mlp_window(int kind, const MlpArgs& a, hipStream_t stream);
+// The fine pass with its colour branch deferred to the points with sigma > 0 (NeRF, TinyNeRF: has_deferred_colour_kernels).
+// launch_mlp_trunk_spill: a mode-1 launch of one group that writes {0, 0, 0, sigma} to a.out [points][4] and appends every
+// point with sigma > 0 to the list d; launch_mlp_colour: the colour branch over that list, r, g, b into a.out (same a).
+bool has_deferred_colour_kernels(int kind);
+int launch_mlp_trunk_spill(int kind, const MlpArgs& a, const DeferArgs& d, hipStream_t stream);
+int launch_mlp_colour(int kind, const MlpArgs& a, const DeferArgs& d, hipStream_t stream);
 int64_t bwd_partial_floats(int64_t P);
 int64_t film_partial_floats(int64_t n_groups, int64_t points_per_group);
 int64_t bwd_partial_floats_kind(int kind, int64_t P);                      // ... of any kind (deeper FiLM kinds need more)

@@ -54,6 +54,8 @@ SIGNATURES = {
                             ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp]),
     "mi_render_workspace_bytes": (_i64, [_i64, _int, _int]),
     "mi_render_shared_field_extra_bytes": (_i64, [_i64, _int, _int]),
+    "mi_render_deferred_colour_extra_bytes": (_i64, [_i64, _int, _int]),
+    "mi_field_has_deferred_colour": (_int, [_int]),
     "mi_render_rays": (_int, [_int, _vp, _int, _vp, _vp, _vp, _i64, _i64, _f32, _f32, _int, _int, _vp, _vp, _vp,
                               _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "mi_composite_bwd": (_int, [_i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -90,6 +92,8 @@ SIGNATURES = {
     "mi_event_record": (_int, [_vp, _vp]),
     "mi_event_elapsed_ms": (_int, [_vp, _vp, ctypes.POINTER(_f32)]),
     "mi_render_set_mlp_events": (None, [_vp, _vp, _vp, _vp]),
+    "mi_field_eval_rays_deferred": (_int, [_int, _vp, _vp, _vp, _vp, _i64, _i64, _int, _vp, _vp, _i64, _vp]),
+    "mi_render_set_colour_chunk_rows": (None, [_i64]),
 }
 
 ABI_VERSION = 4      # include/mi_render.h as of this binding (mi_abi_version() of the library must equal it)

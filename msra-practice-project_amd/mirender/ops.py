@@ -253,6 +253,11 @@ def render_rays_fused(pf_c: PackedField, pf_f: PackedField, rays: torch.Tensor, 
         # one field for both passes: with room for z_samples / their raw values / the merge positions the library evaluates
         # the Nf new depths only (mi_render_rays, include/mi_render.h); without it the plain path, same results
         ws_bytes += lib.mi_render_shared_field_extra_bytes(n, n_coarse, n_fine)
+    elif lib.mi_field_has_deferred_colour(pf_f.kind) == 1:
+        # two fields: with room for one chunk's live list the library runs the fine pass's colour branch on the points with
+        # sigma > 0 only (0 bytes with Nf = 0); without it the whole forward, same results.  The list is min(n * S, 2^22)
+        # rows of 1 028 bytes: 4.02 GiB from 21 846 rays of 192 samples on, kept with the workspace between calls
+        ws_bytes += lib.mi_render_deferred_colour_extra_bytes(n, n_coarse, n_fine)
     guard = None
     if os.environ.get("MI_DEBUG_GUARDS") == "1":       # sentinel zone behind the workspace, checked after the call
         ws = torch.empty(int(ws_bytes) + 16384, dtype=torch.uint8, device=dev)

@@ -129,6 +129,15 @@ def checks(s):
          [*r5["value"]["main"], *r5["value"]["branch"], r5["min_gain_pct"]]),
         (r"`roofline.frac` rises from ([\d.]+) to\s+([\d.]+), but only", [r5["frac"]["main"], r5["frac"]["branch"]]),
     ]
+    r6 = deferred_colour_sources()
+    design += [
+        (r"the parent's fine launch takes ([\d.]+) ms; the branch's (\d+) trunk-and-spill launches take ([\d.]+) ms and its (\d+) colour\s+launches ([\d.]+) ms per frame, ([\d.]+) ms together",
+         [r6["fine_parent"], r6["spill_calls"], r6["spill"], r6["colour_calls"], r6["colour"], r6["spill"] + r6["colour"]]),
+        (r"windowed coarse pass, measured for the first time: its (\d+) field launches take ([\d.]+) ms per frame and its (\d+)\s+composite launches ([\d.]+) ms",
+         [r6["window_calls"], r6["window"], r6["wcomp_calls"], r6["wcomp"]]),
+        (r"deferred colour branch alternating on one MI355X\): ([\d ]+) / ([\d ]+) / ([\d ]+) rays/s before against ([\d ]+) / ([\d ]+) / ([\d ]+)\s+after, \+([\d.]+) % at least on every pair; the largest spread among runs of one build is ([\d.]+) %",
+         [*r6["value"]["main"], *r6["value"]["branch"], r6["min_gain_pct"], r6["spread_pct"]]),
+    ]
     return [("DESIGN.md", design), ("README.md", readme)]
 
 
@@ -149,6 +158,34 @@ def sigma_only_sources():
     out["frac"] = {b: sum(v) / len(v) for b, v in out["frac"].items()}
     out["min_gain_pct"] = min(100 * (b / m - 1) for m, b in zip(out["value"]["main"], out["value"]["branch"]))
     out["sigma_tflops"] = 2 * 489728 * 640000 * 64 / (out["coarse"]["branch"] * 1e-3) / 1e12
+    return out
+
+
+def deferred_colour_sources():
+    """The fine pass's deferred colour branch: per-frame kernel totals of the parent's and the branch's kernel
+    statistics (rocprofv3, 4 frames each) and the alternating bench pairs."""
+    frames = 4
+    stats = {}
+    for b in ("parent", "branch"):
+        with open(os.path.join(ROOT, f"profiles/r06_deferred_colour_kernel_stats_{b}.csv")) as f:
+            stats[b] = {r["Name"]: r for r in csv.DictReader(f)}
+
+    def per_frame(b, key):
+        rows = [r for k, r in stats[b].items() if key in k]
+        assert len(rows) == 1, (b, key, len(rows))
+        return int(rows[0]["Calls"]) // frames, float(rows[0]["TotalDurationNs"]) / 1e6 / frames
+
+    out = {"value": {"main": [], "branch": []}}
+    _, out["fine_parent"] = per_frame("parent", "nerf_fwd_kernel<false, false, false, false>")
+    out["spill_calls"], out["spill"] = per_frame("branch", "nerf_fwd_kernel<false, false, true, false, true>")
+    out["colour_calls"], out["colour"] = per_frame("branch", "nerf_colour_kernel<false>")
+    out["window_calls"], out["window"] = per_frame("parent", "nerf_fwd_kernel<false, false, true, true>")
+    out["wcomp_calls"], out["wcomp"] = per_frame("parent", "composite_weights_window_kernel")
+    with open(os.path.join(ROOT, "profiles/r06_deferred_colour_bench_pairs.log")) as f:
+        for r in (json.loads(ln) for ln in f if ln.startswith("{")):
+            out["value"][r["build"]].append(r["line"]["value"])
+    out["min_gain_pct"] = min(100 * (b / m - 1) for m, b in zip(out["value"]["main"], out["value"]["branch"]))
+    out["spread_pct"] = max(100 * (max(v) / min(v) - 1) for v in out["value"].values())
     return out
 
 

@@ -1,13 +1,19 @@
 #!/usr/bin/env python3
 """Build container: compare the gfx950 code of two builds of one translation unit, kernel by kernel.
 
-    python tools/isa_diff.py old/field_mlp.o new/field_mlp.o [kernel-name-filter]
+    python tools/isa_diff.py old/field_mlp.o new/field_mlp.o [kernel-name-filter] [--rename PATTERN REPLACEMENT]
 
 For every kernel in both objects: its disassembly (llvm-objdump -d --no-show-raw-insn --no-leading-addr, `//` comments
 stripped) and its metadata (VGPR / AGPR / SGPR counts, spills, LDS, scratch from llvm-readelf --notes).  The 32-bit
 literals of the address pairs right after s_getpc_b64 (s_add_u32 / s_addc_u32) are masked: they are pc-relative offsets
 of data in the code object and move whenever anything else in the object does.  Prints one line per kernel and exits
-non-zero if any kernel in both builds differs.  The evidence that a host-side refactor left the hot kernels alone."""
+non-zero if any kernel in both builds differs.  The evidence that a host-side refactor left the hot kernels alone.
+
+--rename: kernels are matched by their demangled names after re.sub(PATTERN, REPLACEMENT) on both sides, for a change that
+only renames instances (a template parameter added with a default).  A new parameter `, false` at the end and a parameter
+type that now depends on it:
+
+    --rename '(nerf_fwd_kernel<\w+, \w+, \w+, \w+)(, false)?>\(.*' '\\1>'"""
 import os
 import re
 import subprocess
@@ -54,14 +60,27 @@ def load(obj):
     return {k: (v, meta.get(k, {})) for k, v in kernels.items()}
 
 
+def demangled(kernels, rename):
+    """The same dict keyed by demangled name, after the --rename substitution."""
+    out = {}
+    for k, v in kernels.items():
+        dem = subprocess.run(["c++filt", k], capture_output=True, text=True).stdout.strip()
+        out[re.sub(rename[0], rename[1], dem) if rename else dem] = v
+    return out
+
+
 def main():
-    a, b = load(sys.argv[1]), load(sys.argv[2])
-    flt = sys.argv[3] if len(sys.argv) > 3 else ""
+    argv, rename = sys.argv[1:], None
+    if "--rename" in argv:
+        i = argv.index("--rename")
+        rename, argv = (argv[i + 1], argv[i + 2]), argv[:i] + argv[i + 3:]
+    a, b = demangled(load(argv[0]), rename), demangled(load(argv[1]), rename)
+    flt = argv[2] if len(argv) > 2 else ""
     bad = 0
     for k in sorted(set(a) | set(b)):
         if flt not in k:
             continue
-        dem = subprocess.run(["c++filt", k], capture_output=True, text=True).stdout.strip()[:80]
+        dem = k[:80]
         if k not in a or k not in b:
             print(f"{'only in ' + ('old' if k in a else 'new'):12s} {dem}")
             continue
