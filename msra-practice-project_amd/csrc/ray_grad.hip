@@ -223,7 +223,9 @@ __global__ __launch_bounds__(kPeThreads) void input_grad_pe_kernel(InputGradArgs
     const int mate_p = lane < 60 ? (is_cos ? lane - 3 : lane + 3) : lane;
     const float coef_p = lane < 60 ? (is_cos ? -(float)(1 << fi) : (float)(1 << fi)) : 0.f;
     const int dl = lane & 31;
-    const int mate_d = dl < 24 ? (is_cos ? dl - 3 : dl + 3) : dl;             // lanes < 24: same (i, c) as above
+    // lanes < 24: same (i, c) as above.  The others carry no direction column (coef_d = 0) and read column dl of the point's
+    // OWN row - 0 * NaN is NaN, so a zero coefficient does not excuse a read outside what the forward wrote for this point
+    const int mate_d = lane < 24 ? (is_cos ? lane - 3 : lane + 3) : dl;
     const float coef_d = lane < 24 ? (is_cos ? -(float)(1 << fi) : (float)(1 << fi)) : 0.f;
 
     const int64_t stride = (int64_t)gridDim.x * (kPeThreads / 64);

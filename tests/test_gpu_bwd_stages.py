@@ -85,19 +85,24 @@ def samples_for(ppg):
 CANARY = 0x5CA1AB1E            # the bit pattern of every float of a workspace's tail (run(..., tail=n))
 
 
-def run(kind, ppg, n_img, sharp, seed, pf=None, film=None, kind_queries=False, tail=0):
+def run(kind, ppg, n_img, sharp, seed, pf=None, film=None, kind_queries=False, tail=0, samples=None, fill=None,
+        zero_from=0):
     """Training forward + backward through the C ABI; returns everything the stages read and wrote.
 
     pf / film: another packed field of the kind's network (a FiLM depth kind, a kind id of the same network, a w_0) and
     its FiLM table, instead of the synthetic fixed-kind field.  kind_queries: size the two scratch buffers with the _kind
     queries (the only ones that know a depth kind).  tail: floats of CANARY behind the queried size of acts, grads and both
-    scratch buffers; st["tails"] names the buffers whose tail the two calls changed."""
+    scratch buffers; st["tails"] names the buffers whose tail the two calls changed.  samples: the samples per ray (a divisor
+    of ppg) instead of samples_for's.  fill: a bit pattern every float of acts and grads holds before
+    the two calls (default: whatever the allocator returns).  zero_from: the first of the every-29th rays whose cotangent
+    is zero."""
     from mirender import _lib
     lib = _lib.load()
     if pf is None:
         _m, pf = packed(kind, sharp)
     k = pf.kind
-    S = samples_for(ppg)
+    S = samples_for(ppg) if samples is None else samples
+    assert ppg % S == 0, (ppg, S)
     rpg = ppg // S
     n, P = n_img * rpg, n_img * ppg
     g = torch.Generator(device=dev()).manual_seed(seed)
@@ -113,6 +118,8 @@ def run(kind, ppg, n_img, sharp, seed, pf=None, film=None, kind_queries=False, t
     def buffer(name, floats):
         assert floats > 0, (name, floats, lib.mi_last_error())
         t = torch.empty(floats + tail, device=dev())
+        if fill is not None and name in ("acts", "grads"):
+            t.view(torch.int32).fill_(fill)
         if tail:
             tails[name] = t[floats:].view(torch.int32).fill_(CANARY)
         return t[:floats]
@@ -125,7 +132,7 @@ def run(kind, ppg, n_img, sharp, seed, pf=None, film=None, kind_queries=False, t
                                             _lib.ptr(raw), _lib.ptr(acts), stream), "mi_field_eval_rays_train")
     # dense cotangent: per-ray magnitudes over four decades, every 29th ray exactly zero
     mag = 10.0 ** (4.0 * torch.rand(n, 1, 1, device=dev(), generator=g) - 3.0)
-    mag[::29] = 0.0
+    mag[zero_from::29] = 0.0
     g_raw = (torch.randn(n, S, 4, device=dev(), generator=g) * mag).reshape(P, 4).contiguous()
     gws = buffer("grads", lib.mi_field_train_grads_floats(k) * P)
     part = buffer("partial", lib.mi_field_bwd_partial_floats_kind(k, P) if kind_queries else lib.mi_field_bwd_partial_floats(P))
