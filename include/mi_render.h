@@ -403,6 +403,29 @@ int mi_marching_cubes_emit(const float* volume, int64_t nx, int64_t ny, int64_t 
                            int descent, void* workspace, float* verts, int* faces, float* normals, float* values,
                            void* stream);
 
+/* ---- occupancy grids ------------------------------------------------------------------ */
+
+/* A per-scene occupancy grid is one bit per cell of a dims[0] x dims[1] x dims[2] grid over an axis-aligned box: which cells
+ * can hold density.  Cell (ix, iy, iz) has index (ix * dims[1] + iy) * dims[2] + iz and lives in word index >> 5, bit
+ * index & 31 of a uint32 array of mi_occupancy_words(dims) words.  dims: HOST, 3 ints, each >= 1, product below 2^31 (else
+ * MI_EINVAL; the two size queries need no GPU).  These calls BUILD such a grid from a field; nothing in the library renders
+ * with one yet.
+ * mi_occupancy_cell_points: the supersample^3 (1..8 per axis) regular sub-sample points of cells [head, head + count) in
+ * index order, points [count * supersample^3, 6] with a zero direction (sigma does not depend on it), ready for
+ * mi_field_eval_points; with k = supersample, sub-sample (i, j, l) of the c-th cell of the range is row
+ * c * k^3 + (i * k + j) * k + l and sits at lo + (cell index + (i + 0.5) / k) * cell along each axis, every operation
+ * rounded on its own in fp32 (lo, cell: HOST, 3 floats each - the box's lower corner and a cell's edge lengths).
+ * mi_occupancy_pack: from sigma [cells * supersample^3] in that order, a cell is occupied iff any of its sub-samples has
+ * sigma > threshold (strict; a NaN is not above anything); the result is dilated `dilate` times by the 6-neighbourhood,
+ * clipped at the box, and packed into bits (spare bits of the last word 0).  workspace:
+ * mi_occupancy_pack_workspace_bytes(dims, dilate) device bytes; workspace_bytes = what the caller really provided. */
+int64_t mi_occupancy_words(const int* dims);
+int64_t mi_occupancy_pack_workspace_bytes(const int* dims, int dilate);
+int mi_occupancy_cell_points(const int* dims, const float* lo, const float* cell, int supersample, int64_t head, int64_t count,
+                             float* points, void* stream);
+int mi_occupancy_pack(const float* sigma, const int* dims, int supersample, float threshold, int dilate, uint32_t* bits,
+                      void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- measurement hooks (bench.py) ---------------------------------------------------- */
 
 /* HIP events owned by the library's HIP runtime (the one the kernels launch on), so a host

@@ -154,6 +154,18 @@ static int eval_rays_deferred_colour(int kind, const float* packed, const float*
     return MI_OK;
 }
 
+// dims >= 1 with a product below 2^31 (a cell's bit index is an int); the product, or 0 with the error set
+static int64_t occupancy_cells(const char* fn, const int* dims) {
+    if (!dims) { set_error("%s: null grid dims", fn); return 0; }
+    int64_t cells = 1;
+    for (int c = 0; c < 3; ++c) {
+        if (dims[c] < 1) { set_error("%s: grid dims %d x %d x %d (each must be at least 1)", fn, dims[0], dims[1], dims[2]); return 0; }
+        cells *= dims[c];                                  // < 2^31 * 2^31 before the check below
+        if (cells >= (int64_t)1 << 31) { set_error("%s: grid dims %d x %d x %d (2^31 cells or more)", fn, dims[0], dims[1], dims[2]); return 0; }
+    }
+    return cells;
+}
+
 }  // namespace mi
 
 using namespace mi;
@@ -241,6 +253,45 @@ int mi_field_eval_rays_deferred(int kind, const float* packed, const float* film
         return MI_EINVAL;
     }
     return eval_rays_deferred_colour(kind, packed, rays, z, n, n_samples, raw, extra, (hipStream_t)stream);
+}
+
+int64_t mi_occupancy_words(const int* dims) {
+    const int64_t cells = occupancy_cells("mi_occupancy_words", dims);
+    return cells ? (cells + 31) / 32 : MI_EINVAL;
+}
+
+int64_t mi_occupancy_pack_workspace_bytes(const int* dims, int dilate) {
+    const int64_t cells = occupancy_cells("mi_occupancy_pack_workspace_bytes", dims);
+    if (!cells) return MI_EINVAL;
+    if (dilate < 0) { set_error("mi_occupancy_pack_workspace_bytes: dilate = %d", dilate); return MI_EINVAL; }
+    return occupancy_pack_workspace_bytes(cells, dilate);
+}
+
+int mi_occupancy_cell_points(const int* dims, const float* lo, const float* cell, int supersample, int64_t head, int64_t count,
+                             float* points, void* stream) {
+    const int64_t cells = occupancy_cells("mi_occupancy_cell_points", dims);
+    if (!cells) return MI_EINVAL;
+    if (!lo || !cell || supersample < 1 || supersample > 8 || head < 0 || count < 0 || head + count > cells || (count > 0 && !points)) {
+        set_error("mi_occupancy_cell_points: bad arguments (need 1 <= supersample <= 8, 0 <= head, head + count <= cells)");
+        return MI_EINVAL;
+    }
+    return launch_occupancy_cell_points(dims, lo, cell, supersample, head, count, points, (hipStream_t)stream);
+}
+
+int mi_occupancy_pack(const float* sigma, const int* dims, int supersample, float threshold, int dilate, uint32_t* bits,
+                      void* workspace, int64_t workspace_bytes, void* stream) {
+    const int64_t cells = occupancy_cells("mi_occupancy_pack", dims);
+    if (!cells) return MI_EINVAL;
+    if (!sigma || !bits || !workspace || supersample < 1 || supersample > 8 || dilate < 0) {
+        set_error("mi_occupancy_pack: bad arguments (non-null sigma, bits, workspace; 1 <= supersample <= 8; dilate >= 0)");
+        return MI_EINVAL;
+    }
+    const int64_t need = occupancy_pack_workspace_bytes(cells, dilate);
+    if (workspace_bytes < need) {
+        set_error("mi_occupancy_pack: workspace of %lld bytes, needs %lld", (long long)workspace_bytes, (long long)need);
+        return MI_EINVAL;
+    }
+    return launch_occupancy_pack(sigma, dims, supersample, threshold, dilate, bits, workspace, (hipStream_t)stream);
 }
 
 int mi_gen_rays(int width, int height, double focal, const float* c2w_host, int64_t ray0, int64_t n, float* rays,

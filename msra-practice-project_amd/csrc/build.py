@@ -23,6 +23,7 @@ SOURCES = {
     # un-fused mul/add like the torch / NumPy ops these kernels restate
     "render_stages.hip": ["-ffp-contract=off"],
     "eval_stages.hip": ["-ffp-contract=off"],
+    "occupancy.hip": ["-ffp-contract=off"],
     "adam_step.hip": [],
     "mesh_stages.hip": [],
     "train_path.hip": [],

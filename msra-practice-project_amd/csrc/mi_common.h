@@ -162,6 +162,12 @@ int launch_mlp_window(int kind, const MlpArgs& a, hipStream_t stream);
 bool has_deferred_colour_kernels(int kind);
 int launch_mlp_trunk_spill(int kind, const MlpArgs& a, const DeferArgs& d, hipStream_t stream);
 int launch_mlp_colour(int kind, const MlpArgs& a, const DeferArgs& d, hipStream_t stream);
+// occupancy.hip: construction of a per-scene occupancy bit grid (include/mi_render.h)
+int launch_occupancy_cell_points(const int* dims, const float* lo, const float* cell, int k, int64_t head, int64_t count,
+                                 float* points, hipStream_t stream);
+int64_t occupancy_pack_workspace_bytes(int64_t cells, int dilate);
+int launch_occupancy_pack(const float* sigma, const int* dims, int k, float threshold, int dilate, uint32_t* bits,
+                          void* workspace, hipStream_t stream);
 int64_t bwd_partial_floats(int64_t P);
 int64_t film_partial_floats(int64_t n_groups, int64_t points_per_group);
 int64_t bwd_partial_floats_kind(int kind, int64_t P);                      // ... of any kind (deeper FiLM kinds need more)

@@ -1,0 +1,111 @@
+// occupancy.hip - construction of a per-scene occupancy bit grid (gfx950): one bit per cell of a Gx x Gy x Gz grid over an
+// axis-aligned box, cell (ix, iy, iz) at bit (ix Gy + iy) Gz + iz (include/mi_render.h).
+//
+//   occupancy_cell_points_kernel  k^3 regular sub-sample points per cell, [count k^3, 6] rows for mi_field_eval_points
+//   occupancy_threshold / dilate / pack kernels   sigma at those points -> one byte per cell, dilated, packed into words
+//
+// Small kernels next to the field evaluations between them (cells k^3 MLP points).  Compiled with -ffp-contract=off: a
+// sub-sample point is a chain of separately rounded operations, which a test restates in torch.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "mi_common.h"
+
+namespace mi {
+
+struct CellPointsArgs { int dims[3]; float lo[3], cell[3]; int k; };
+
+// Row i of the output: sub-sample i % k^3 of cell head + i / k^3; sub-sample (si, sj, sk) = ((s / k) / k, (s / k) % k, s % k)
+// sits at lo_c + (i_c + (s_c + 0.5) / k) * cell_c, every operation rounded on its own; direction 0 (sigma does not depend on it).
+__global__ __launch_bounds__(256) void occupancy_cell_points_kernel(CellPointsArgs a, int64_t head, int64_t rows,
+                                                                    float* __restrict__ pts) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= rows) return;
+    const int k3 = a.k * a.k * a.k;
+    const int64_t cell = head + i / k3;
+    const int s = (int)(i % k3);
+    const int c[3] = {(int)(cell / ((int64_t)a.dims[1] * a.dims[2])), (int)((cell / a.dims[2]) % a.dims[1]), (int)(cell % a.dims[2])};
+    const int sub[3] = {s / (a.k * a.k), (s / a.k) % a.k, s % a.k};
+    float* o = pts + i * 6;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        const float f = __fdiv_rn(__fadd_rn((float)sub[d], 0.5f), (float)a.k);
+        o[d] = __fadd_rn(a.lo[d], __fmul_rn(__fadd_rn((float)c[d], f), a.cell[d]));
+        o[3 + d] = 0.f;
+    }
+}
+
+int launch_occupancy_cell_points(const int* dims, const float* lo, const float* cell, int k, int64_t head, int64_t count,
+                                 float* points, hipStream_t stream) {
+    const int64_t rows = count * k * k * k;
+    if (rows <= 0) return 0;
+    if ((rows + 255) / 256 > 0x7fffffffLL) { set_error("occupancy cell points: too many rows (%lld)", (long long)rows); return -1; }
+    CellPointsArgs a;
+    for (int d = 0; d < 3; ++d) { a.dims[d] = dims[d]; a.lo[d] = lo[d]; a.cell[d] = cell[d]; }
+    a.k = k;
+    hipLaunchKernelGGL(occupancy_cell_points_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, a, head, rows, points);
+    return check_launch("occupancy_cell_points");
+}
+
+// a cell is occupied iff any of its k^3 sub-samples has sigma > threshold (strict; a NaN sigma is not above anything)
+__global__ __launch_bounds__(256) void occupancy_threshold_kernel(const float* __restrict__ sigma, int cells, int k3,
+                                                                  float threshold, uint8_t* __restrict__ occ) {
+    const int64_t cell = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (cell >= cells) return;
+    const float* s = sigma + cell * k3;
+    bool any = false;
+    for (int i = 0; i < k3; ++i) any = any || s[i] > threshold;
+    occ[cell] = any ? 1 : 0;
+}
+
+// one step of 6-neighbourhood dilation, clipped at the box
+__global__ __launch_bounds__(256) void occupancy_dilate_kernel(const uint8_t* __restrict__ in, int g0, int g1, int g2,
+                                                               uint8_t* __restrict__ out) {
+    const int64_t at = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (at >= (int64_t)g0 * g1 * g2) return;
+    const int cell = (int)at;
+    const int iz = cell % g2, iy = (cell / g2) % g1, ix = cell / (g1 * g2);
+    uint8_t v = in[cell];
+    if (ix > 0) v |= in[cell - g1 * g2];
+    if (ix + 1 < g0) v |= in[cell + g1 * g2];
+    if (iy > 0) v |= in[cell - g2];
+    if (iy + 1 < g1) v |= in[cell + g2];
+    if (iz > 0) v |= in[cell - 1];
+    if (iz + 1 < g2) v |= in[cell + 1];
+    out[cell] = v;
+}
+
+// 32 cells per thread into one word (cell index i: word i >> 5, bit i & 31); the last word's spare bits are 0
+__global__ __launch_bounds__(256) void occupancy_pack_kernel(const uint8_t* __restrict__ occ, int cells, int words,
+                                                             uint32_t* __restrict__ bits) {
+    const int w = blockIdx.x * 256 + threadIdx.x;
+    if (w >= words) return;
+    uint32_t v = 0;
+    for (int b = 0; b < 32; ++b) {
+        const int64_t cell = (int64_t)w * 32 + b;
+        if (cell < cells && occ[cell]) v |= 1u << b;
+    }
+    bits[w] = v;
+}
+
+// one byte per cell, a second copy for the dilation's ping-pong; each region a whole number of 256-byte blocks
+static int64_t occ_region_bytes(int64_t cells) { return (cells + 255) / 256 * 256; }
+int64_t occupancy_pack_workspace_bytes(int64_t cells, int dilate) { return occ_region_bytes(cells) * (dilate > 0 ? 2 : 1); }
+
+int launch_occupancy_pack(const float* sigma, const int* dims, int k, float threshold, int dilate, uint32_t* bits,
+                          void* workspace, hipStream_t stream) {
+    const int cells = dims[0] * dims[1] * dims[2], words = (int)(((int64_t)cells + 31) / 32);
+    uint8_t* buf[2] = {(uint8_t*)workspace, (uint8_t*)workspace + occ_region_bytes(cells)};
+    const dim3 grid((unsigned)(((int64_t)cells + 255) / 256));
+    hipLaunchKernelGGL(occupancy_threshold_kernel, grid, dim3(256), 0, stream, sigma, cells, k * k * k, threshold, buf[0]);
+    if (const int rc = check_launch("occupancy_threshold")) return rc;
+    int cur = 0;
+    for (int i = 0; i < dilate; ++i, cur ^= 1) {
+        hipLaunchKernelGGL(occupancy_dilate_kernel, grid, dim3(256), 0, stream, buf[cur], dims[0], dims[1], dims[2], buf[cur ^ 1]);
+        if (const int rc = check_launch("occupancy_dilate")) return rc;
+    }
+    hipLaunchKernelGGL(occupancy_pack_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, stream, buf[cur], cells, words, bits);
+    return check_launch("occupancy_pack");
+}
+
+}  // namespace mi

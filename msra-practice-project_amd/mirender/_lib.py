@@ -94,6 +94,11 @@ SIGNATURES = {
     "mi_render_set_mlp_events": (None, [_vp, _vp, _vp, _vp]),
     "mi_field_eval_rays_deferred": (_int, [_int, _vp, _vp, _vp, _vp, _i64, _i64, _int, _vp, _vp, _i64, _vp]),
     "mi_render_set_colour_chunk_rows": (None, [_i64]),
+    "mi_occupancy_words": (_i64, [ctypes.POINTER(_int)]),
+    "mi_occupancy_pack_workspace_bytes": (_i64, [ctypes.POINTER(_int), _int]),
+    "mi_occupancy_cell_points": (_int, [ctypes.POINTER(_int), ctypes.POINTER(_f32), ctypes.POINTER(_f32), _int, _i64, _i64,
+                                        _vp, _vp]),
+    "mi_occupancy_pack": (_int, [_vp, ctypes.POINTER(_int), _int, _f32, _int, _vp, _vp, _i64, _vp]),
 }
 
 ABI_VERSION = 4      # include/mi_render.h as of this binding (mi_abi_version() of the library must equal it)

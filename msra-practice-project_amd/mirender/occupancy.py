@@ -1,0 +1,132 @@
+"""Per-scene occupancy grids: one bit per cell of a box, saying which cells can hold density.
+
+    grid = OccupancyGrid.from_field(fine_model, lo=(-1.5,) * 3, hi=(1.5,) * 3, resolution=128)
+    grid.occupied_fraction(); grid.to_dense()
+
+`from_field` builds the grid on the device from a field's sigma (mi_occupancy_cell_points, the fused field kernel,
+mi_occupancy_pack; include/mi_render.h), `from_dense` / `to_dense` go through bool [Gx,Gy,Gz] arrays in numpy.
+For the kinds without FiLM (NeRF, SirenNeRF, TinyNeRF).  This module builds and holds grids; the renderer does not use them yet.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib, fields
+
+
+def _i3(v):
+    a = np.ascontiguousarray(np.asarray(v, dtype=np.int32).reshape(3))
+    return a, a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+
+
+def _f3(v):
+    a = np.ascontiguousarray(np.asarray(v, dtype=np.float32).reshape(3))
+    return a, a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+
+
+def pack_dense(dense) -> np.ndarray:
+    """bool [Gx,Gy,Gz] -> uint32 words: cell (ix, iy, iz) is bit (ix * Gy + iy) * Gz + iz, in word index >> 5, bit index & 31."""
+    flat = np.asarray(dense, dtype=bool).reshape(-1)
+    padded = np.zeros((flat.size + 31) // 32 * 32, dtype=np.uint8)
+    padded[:flat.size] = flat
+    return np.packbits(padded.reshape(-1, 32), axis=1, bitorder="little").view("<u4").reshape(-1).copy()
+
+
+def unpack_dense(words, dims) -> np.ndarray:
+    """The inverse of pack_dense: bool [Gx,Gy,Gz]."""
+    dims = tuple(int(d) for d in dims)
+    cells = dims[0] * dims[1] * dims[2]
+    w = np.ascontiguousarray(np.asarray(words).astype("<u4")).view(np.uint8).reshape(-1, 4)
+    return np.unpackbits(w, axis=1, bitorder="little").reshape(-1)[:cells].astype(bool).reshape(dims)
+
+
+class OccupancyGrid:
+    """One bit per cell of a dims[0] x dims[1] x dims[2] grid over the box [lo, hi).  `bits`: an int32 device tensor of
+    mi_occupancy_words(dims) words (the uint32 words' bits).  inv_cell, the cells per unit length that places a point in its cell
+    (t = (p - lo) * inv_cell, cell = floor(t)), is computed once on the host as np.float32(dims) / (np.float32(hi) - np.float32(lo))."""
+
+    def __init__(self, bits: torch.Tensor, lo, hi, dims):
+        self.dims = tuple(int(d) for d in np.asarray(dims).reshape(3))
+        self.lo = np.asarray(lo, dtype=np.float32).reshape(3).copy()
+        self.hi = np.asarray(hi, dtype=np.float32).reshape(3).copy()
+        if min(self.dims) < 1 or self.dims[0] * self.dims[1] * self.dims[2] >= 2 ** 31:
+            raise _lib.MiRenderError(f"occupancy grid dims {self.dims}: each at least 1, fewer than 2^31 cells")
+        if not bool(np.all(self.hi > self.lo)):
+            raise _lib.MiRenderError("occupancy grid: hi must be above lo on every axis")
+        self.inv_cell = np.float32(self.dims) / (self.hi - self.lo)
+        if not (isinstance(bits, torch.Tensor) and bits.is_cuda and bits.dtype == torch.int32 and bits.is_contiguous()
+                and bits.numel() == self.words):
+            raise _lib.MiRenderError(f"occupancy grid bits: a contiguous int32 device tensor of {self.words} words")
+        self.bits = bits
+
+    @property
+    def cells(self) -> int:
+        return self.dims[0] * self.dims[1] * self.dims[2]
+
+    @property
+    def words(self) -> int:
+        return (self.cells + 31) // 32
+
+    @property
+    def device(self):
+        return self.bits.device
+
+    def to_dense(self) -> np.ndarray:
+        return unpack_dense(self.bits.cpu().numpy().view(np.uint32), self.dims)
+
+    @classmethod
+    def from_dense(cls, dense, lo, hi, device=None) -> "OccupancyGrid":
+        """From bool [Gx,Gy,Gz]; the packing is done in numpy."""
+        dense = np.asarray(dense, dtype=bool)
+        if dense.ndim != 3:
+            raise _lib.MiRenderError("from_dense: expected bool [Gx,Gy,Gz]")
+        device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+        bits = torch.from_numpy(pack_dense(dense).view(np.int32)).to(device)
+        return cls(bits, lo, hi, dense.shape)
+
+    def occupied_fraction(self) -> float:
+        return float(self.to_dense().mean())
+
+    @classmethod
+    def from_field(cls, model, lo, hi, resolution=128, threshold=0.0, supersample=2, dilate=1,
+                   max_batch=64 ** 3) -> "OccupancyGrid":
+        """A cell is occupied iff sigma of `model` exceeds `threshold` at any of its supersample^3 regular sub-sample points
+        (at (i + 0.5) / supersample of the cell); the bits are then dilated `dilate` times by the 6-neighbourhood.  Points are
+        generated on the device (mi_occupancy_cell_points), evaluated by the fused kernel in batches of `max_batch` points
+        with a zero direction (sigma does not depend on it, as in grid.py) and packed by mi_occupancy_pack."""
+        pf = fields.as_packed_field(model)
+        if pf is None or fields.is_film(pf.kind):
+            raise _lib.MiRenderError("OccupancyGrid.from_field: needs a NeRF, SirenNeRF or TinyNeRF field (a FiLM field's "
+                                     "table is per image, a per-scene grid has no meaning there)")
+        lib = _lib.load()
+        dev = pf.device
+        dims = (int(resolution),) * 3 if np.ndim(resolution) == 0 else tuple(int(r) for r in resolution)
+        k = int(supersample)
+        lo32, hi32 = np.asarray(lo, dtype=np.float32).reshape(3), np.asarray(hi, dtype=np.float32).reshape(3)
+        _, pdims = _i3(dims)
+        _, plo = _f3(lo32)
+        _, pcell = _f3((hi32 - lo32) / np.float32(dims))
+        words = lib.mi_occupancy_words(pdims)
+        if words < 0:
+            _lib.check(int(words), "mi_occupancy_words")
+        cells, k3 = dims[0] * dims[1] * dims[2], k ** 3
+        per = max(1, int(max_batch) // k3)
+        sigma = torch.empty(cells * k3, dtype=torch.float32, device=dev)
+        with torch.no_grad(), torch.cuda.device(dev):
+            for head in range(0, cells, per):
+                count = min(per, cells - head)
+                pts = torch.empty((count * k3, 6), dtype=torch.float32, device=dev)
+                _lib.check(lib.mi_occupancy_cell_points(pdims, plo, pcell, k, head, count, _lib.ptr(pts), _lib.stream_ptr(dev)),
+                           "mi_occupancy_cell_points")
+                sigma[head * k3:(head + count) * k3] = fields.eval_points(pf, pts)[:, 3]
+            bits = torch.empty(words, dtype=torch.int32, device=dev)
+            ws_bytes = lib.mi_occupancy_pack_workspace_bytes(pdims, int(dilate))
+            if ws_bytes < 0:
+                _lib.check(int(ws_bytes), "mi_occupancy_pack_workspace_bytes")
+            ws = torch.empty(int(ws_bytes), dtype=torch.uint8, device=dev)
+            _lib.check(lib.mi_occupancy_pack(_lib.ptr(sigma), pdims, k, float(threshold), int(dilate), _lib.ptr(bits),
+                                             _lib.ptr(ws), int(ws_bytes), _lib.stream_ptr(dev)), "mi_occupancy_pack")
+        return cls(bits, lo32, hi32, dims)
