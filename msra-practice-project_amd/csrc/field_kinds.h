@@ -4,7 +4,9 @@
 // weight columns every linear layer multiplies, and where its dA rows live) is read from here.  The graph is stated once,
 // by two builders (with_nerf_graph, make_film_kind), checked at compile time (graph_ok) and read by one host-side walker
 // (for_each_block): the weight-gradient jobs of field_mlp_bwd.hip and the input gradients of ray_grad.hip are derived
-// from it.  Host only: the kernels get pointers and strides, and constant memory holds the PackTables alone.
+// from it.  The packed streams are held against the graph segment by segment (segments_ok), and the fused MLP kernels read
+// their stage shapes from the same segments (field_layout.h).  Host only but for those compile-time reads: the kernels get
+// pointers and strides, and constant memory holds the PackTables alone.
 #pragma once
 #include <stdint.h>
 
@@ -71,32 +73,30 @@ struct FieldKind {
             if (in_sigma_path(l)) s += (int64_t)dims[l][0] * dims[l][1];
         return s;
     }
-    // The sigma prefix of the forward stream: items [0, sigma_items()) hold every weight sigma needs, item sigma_items()
-    // starts the colour branch.  A sigma-only forward consumes exactly this prefix of the same packed buffer.
-    constexpr int sigma_items() const {
+    constexpr int rgb_head() const { return n_layers - 1; }      // the rgb head's layer: every kind's last
+    // The sigma prefix of the forward stream, in segments (field_layout.h): segments [0, sigma_segments()) are the trunk's
+    // and hold every weight sigma needs - a sigma-only forward consumes exactly this prefix of the same packed buffer.
+    // Segment sigma_segments() is the colour branch's first: the last trunk layer issues its aux pieces and first K blocks
+    // while its own last K blocks compute (a sigma-only forward issues neither), and a kernel that runs the colour
+    // branch alone enters the stream at its float offset.
+    constexpr int sigma_segments() const {
+        const Segments S = segments(fwd);
         int i = 0;
-        while (i < fwd.n_items && in_sigma_path(fwd.item[i].param / 2)) ++i;
+        while (i < S.n && S.seg[i].layer < trunk) ++i;
         return i;
     }
-    // true if no item of the colour branch sits inside the prefix and no sigma item behind it
+    // true if no piece of the colour branch sits inside the prefix and no sigma piece behind it
     constexpr bool sigma_prefix_ok() const {
-        for (int i = 0; i < fwd.n_items; ++i)
-            if (in_sigma_path(fwd.item[i].param / 2) != (i < sigma_items())) return false;
-        return sigma_items() < fwd.n_items;
+        const Segments S = segments(fwd);
+        const int n = sigma_segments();
+        for (int i = 0; i < S.n; ++i) {
+            const Segment& s = S.seg[i];
+            if (in_sigma_path(s.layer) != (i < n)) return false;
+            for (int j = 0; j < s.aux && j < kMaxAuxPieces; ++j)
+                if (in_sigma_path(s.item[j].layer) != (i < n)) return false;
+        }
+        return n < S.n;
     }
-    // The first stage of the colour branch, which the last trunk layer issues while its last K blocks compute: its aux
-    // (VEC / PLAIN) pieces, and the DMA pieces of one of its K blocks.  A sigma-only forward issues neither.
-    constexpr int branch_aux_pieces() const {
-        int n = 0;
-        for (int i = sigma_items(); i < fwd.n_items && fwd.item[i].type != ITEM_CHUNK; ++i) ++n;
-        return n;
-    }
-    constexpr int branch_block_pieces() const {
-        const PackItem& k = fwd.item[sigma_items() + branch_aux_pieces()];
-        return k.type == ITEM_CHUNK ? k.mb * 1024 / kPiece : 0;
-    }
-    // Float offset of that stage in the forward stream: where a kernel that runs the colour branch alone starts reading.
-    constexpr int branch_stream_floats() const { return fwd.dst_off[sigma_items()]; }
 };
 
 // FilmSirenNeRF(hidden_dim = 256, hidden_layers = L, use_dir) (pi_GAN/modules.py:73-94): L + 3 linear layers
@@ -249,6 +249,104 @@ constexpr FieldKind nerf_with_input(int layer, int input, int region, int shift)
 static_assert(graph_ok(nerf_with_input(kSkipLayer, 1, 5, 0)), "the unchanged copy passes");
 static_assert(!graph_ok(nerf_with_input(kSkipLayer, 1, 5, 1)), "skip layer: second input shifted by one column");
 static_assert(!graph_ok(nerf_with_input(9, 1, 11, 0)) && !graph_ok(nerf_with_input(9, 1, 0, 0)), "dir layer: wrong region for E_dir");
+
+// ---- the packed streams against the graph ----------------------------------------------------------------------------
+// Forward: one segment (field_layout.h) per non-head layer, in layer order: the layer's bias first, then the three weight
+// columns of each K = 3 (xin) input, then whole heads (a head's rows in order, then its scalars); its K blocks are the
+// layer's other inputs in 32-wide blocks, each as many row blocks high as the layer has outputs.
+constexpr bool fwd_segments_ok(const FieldKind& k) {
+    const Segments S = segments(k.fwd);
+    if (S.covered != k.fwd.n_items) return false;
+    int layer = -1;
+    for (int i = 0; i < S.n; ++i) {
+        const Segment& s = S.seg[i];
+        if (s.layer <= layer || s.layer >= k.n_layers || k.graph[s.layer].head || s.aux > kMaxAuxPieces) return false;
+        layer = s.layer;
+        const LayerGraph& g = k.graph[layer];
+        if (s.piece(AUX_BIAS, layer) != 0) return false;
+        int a = 1, kb = 0;
+        for (int j = 0, wcol = 0; j < g.n_in; wcol += g.in[j++].width()) {
+            if (g.in[j].cls != SRC_XIN) { kb += (g.in[j].width() + 31) / 32; continue; }
+            for (int c = 0; c < 3; ++c)
+                if (s.piece(AUX_WCOL, layer, wcol + c) != a++) return false;
+        }
+        if (s.blocks != kb || (kb && s.mb * 32 != k.dims[layer][0])) return false;
+        while (a < s.aux) {
+            const int hl = s.item[a].layer;
+            if (hl >= k.n_layers || !k.graph[hl].head) return false;
+            for (int r = 0; r < k.dims[hl][0]; ++r)
+                if (s.piece(AUX_WROW, hl, r) != a++) return false;
+            if (s.piece(AUX_SCALARS, hl) != a++) return false;
+        }
+        if (a != s.aux) return false;
+    }
+    return S.n == k.n_layers - 2;
+}
+// Backward chain: one segment per non-head layer but the first, in reverse layer order: head rows only in front of the K
+// blocks, which are the layer's outputs in 32-wide blocks for the 256 rows of its hidden input; every head row once.
+constexpr bool bwd_segments_ok(const FieldKind& k) {
+    const Segments S = segments(k.bwd);
+    if (S.covered != k.bwd.n_items) return false;
+    int layer = k.n_layers, rows = 0;
+    for (int i = 0; i < S.n; ++i) {
+        const Segment& s = S.seg[i];
+        if (s.layer >= layer || s.layer < 1 || k.graph[s.layer].head || s.aux > kMaxAuxPieces) return false;
+        layer = s.layer;
+        if (s.blocks * 32 != k.dims[layer][0] || s.mb * 32 != kHidden) return false;
+        for (int a = 0; a < s.aux; ++a) {
+            const AuxItem& it = s.item[a];
+            if (it.kind != AUX_WROW || !k.graph[it.layer].head || it.index >= k.dims[it.layer][0] || s.piece(AUX_WROW, it.layer, it.index) != a)
+                return false;
+            ++rows;
+        }
+    }
+    return S.n == k.n_layers - 3 && rows == k.dims[k.sigma_head][0] + k.dims[k.rgb_head()][0];
+}
+constexpr bool segments_ok(const FieldKind& k) { return fwd_segments_ok(k) && bwd_segments_ok(k); }
+// The run-time-depth FiLM kernels take their shapes from depth 8: at every depth the segments at the same distance from
+// either end of the stream (forward: two from the front, three from the back; backward: one and one) have depth 8's
+// shapes, and every segment between has the shape of depth 8's.
+constexpr bool film_depth_like_8(int L, bool use_dir, bool bwd) {
+    const FieldKind k = make_film_kind(L, use_dir), k8 = make_film_kind(8, use_dir);
+    const Segments S = segments(bwd ? k.bwd : k.fwd), D = segments(bwd ? k8.bwd : k8.fwd);
+    const int front = bwd ? 1 : 2, back = bwd ? 1 : 3;
+    if (S.n != (bwd ? L : L + 1) || D.n != (bwd ? 8 : 9) || k.sigma_segments() != L) return false;
+    for (int i = 0; i < S.n; ++i) {
+        const Segment& d = i < front ? D.seg[i] : S.n - i <= back ? D.seg[D.n - (S.n - i)] : D.seg[front];
+        if (!S.seg[i].same_shape(d)) return false;
+    }
+    return D.uniform(1, D.n - (bwd ? 2 : 4));       // the kernels' hidden-layer loops at depth 8
+}
+constexpr bool film_segments_ok(bool use_dir) {
+    for (int L = kFilmDepthMin; L <= kFilmDepthMax; ++L)
+        if (!segments_ok(make_film_kind(L, use_dir)) || !film_depth_like_8(L, use_dir, false) || !film_depth_like_8(L, use_dir, true))
+            return false;
+    return true;
+}
+static_assert(segments_ok(kFieldKinds[MI_FIELD_NERF]) && segments_ok(kFieldKinds[MI_FIELD_SIREN_NERF]) &&
+                  segments_ok(kFieldKinds[MI_FIELD_FILM_SIREN_NERF]) && segments_ok(kFieldKinds[MI_FIELD_FILM_SIREN_NERF_NODIR]) &&
+                  segments_ok(kFieldKinds[MI_FIELD_TINY_NERF]) && film_segments_ok(true) && film_segments_ok(false),
+              "every kind's streams carry, segment by segment, what its graph's layers consume");
+// ... and the checks can fail: NeRF's forward stream with the sigma head's row in front of layers_pos.7's bias, and with
+// layers_pos.3 one K block short
+constexpr FieldKind nerf_fwd_with(int segment, int at, bool swap) {
+    FieldKind k = kFieldKinds[MI_FIELD_NERF];
+    const int i = segments(k.fwd).seg[segment].first + at;
+    if (swap) {                               // items i and i + 1 trade places (both are one piece: the offsets stay)
+        const PackItem t = k.fwd.item[i];
+        k.fwd.item[i] = k.fwd.item[i + 1];
+        k.fwd.item[i + 1] = t;
+    } else if (at >= 0) {                     // item i leaves
+        for (int j = i; j + 1 < k.fwd.n_items; ++j) { k.fwd.item[j] = k.fwd.item[j + 1]; k.fwd.dst_off[j] = k.fwd.dst_off[j + 1]; }
+        --k.fwd.n_items;
+    }
+    return k;
+}
+static_assert(segments_ok(nerf_fwd_with(7, -1, false)), "the unchanged copy passes");
+static_assert(!segments_ok(nerf_fwd_with(7, 0, true)), "a head row in front of its layer's bias");
+static_assert(!segments_ok(nerf_fwd_with(3, 1, false)), "a layer's K blocks one short");
+static_assert(nerf_acts().relu_switch0() == 12 && tiny_acts().relu_switch0() == 7 && siren_acts().relu_switch0() < 0,
+              "the ReLU kinds' switch regions follow their layer inputs");
 
 // ---- MI_FIELD_FILM_DEPTH kinds -------------------------------------------------------------------------------------
 // A depth kind is no row of kFieldKinds and has no table in constant memory (adam_step.hip keeps one PackTable pair per

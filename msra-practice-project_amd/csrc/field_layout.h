@@ -58,12 +58,102 @@ __host__ __device__ inline int vec_slot(int f) {
     return (m * 2 + h) * 16 + rg * 4 + q;
 }
 
+// ---- the stream as SEGMENTS: what one layer step of a fused kernel consumes -----------------------------------------
+// A segment is a run of aux items (VEC / PLAIN) followed by the K blocks (CHUNK items) of ONE weight.  Aux items
+// accumulate; a bias opens a new segment when the current one has aux items and no K blocks (the K = 3 first layer of the
+// sin kinds has no K blocks at all); a run of CHUNKs of one parameter ends the segment.  The kernels of field_mlp.hip /
+// field_mlp_bwd.hip take every piece count, K-block count, row-block count and aux-piece index from this view of the table
+// the pack kernel fills the stream from, and static_assert the structure the view cannot express (which segments one loop
+// body serves, that the segments they issue are the whole table) next to its use; segments_ok (field_kinds.h) holds
+// every table against its kind's layer graph.
+enum AuxKind : int { AUX_BIAS = 0, AUX_WROW, AUX_WCOL, AUX_SCALARS };
+struct AuxItem { int kind, layer, index; };     // index: the row of a WROW, the weight column of a WCOL, else 0
+constexpr AuxItem aux_item(const PackItem& it) {
+    if (it.type == ITEM_PLAIN) return {AUX_SCALARS, it.param / 2, 0};
+    if (it.param & 1) return {AUX_BIAS, it.param / 2, 0};
+    return it.stride == 1 ? AuxItem{AUX_WROW, it.param / 2, it.row0} : AuxItem{AUX_WCOL, it.param / 2, it.col0};
+}
+
+struct Segment {
+    int first, off;                  // its first item, and that item's float offset in the stream
+    int aux, blocks, mb;             // aux pieces; K blocks and the MFMA row blocks of each (0, 0: a VALU-only layer)
+    int layer;                       // the linear layer whose step consumes it: its K blocks', else its first item's
+    AuxItem item[kMaxAuxPieces];     // what each aux piece is
+    constexpr int block_pieces() const { return mb * 1024 / kPiece; }      // DMA pieces of one K block
+    // aux-piece index, inside the segment, of an item: a head's weight row, a head's scalars, a bias; -1 if it has none
+    constexpr int piece(int kind, int of_layer, int index = 0) const {
+        for (int i = 0; i < aux && i < kMaxAuxPieces; ++i)
+            if (item[i].kind == kind && item[i].layer == of_layer && item[i].index == index) return i;
+        return -1;
+    }
+    // ... of the first of the three K = 3 input columns
+    constexpr int k3_piece() const {
+        for (int i = 0; i < aux && i < kMaxAuxPieces; ++i)
+            if (item[i].kind == AUX_WCOL) return i;
+        return -1;
+    }
+    // same counts and the same kind of item at every aux piece (whose layer it is may differ)
+    constexpr bool same_shape(const Segment& o) const {
+        if (aux != o.aux || blocks != o.blocks || mb != o.mb) return false;
+        for (int i = 0; i < aux && i < kMaxAuxPieces; ++i)
+            if (item[i].kind != o.item[i].kind || item[i].index != o.item[i].index) return false;
+        return true;
+    }
+};
+
+constexpr int kMaxSegments = 16;      // the depth-12 FiLM forward table has 13
+struct Segments {
+    int n, covered;                   // segments; items they cover (== the table's n_items unless it has too many)
+    Segment seg[kMaxSegments];
+    // Shapes by index, reading as "nothing" behind the last segment: what a kernel's last layer issues behind itself.
+    constexpr int aux(int i) const { return i < n ? seg[i].aux : 0; }
+    constexpr int blocks(int i) const { return i < n ? seg[i].blocks : 0; }
+    constexpr int mb(int i) const { return i < n ? seg[i].mb : 0; }
+    constexpr int block_pieces(int i) const { return i < n ? seg[i].block_pieces() : 0; }
+    // One instantiation may serve segments first..last (a layer loop): they have one shape, and the segments behind them,
+    // first + 1..last + 1, ask the same of the layer in front - it issues their aux pieces and their first K blocks.
+    constexpr bool uniform(int first, int last) const {
+        if (first < 0 || first > last || last + 1 >= n) return false;
+        for (int i = first; i <= last; ++i)
+            if (!seg[i].same_shape(seg[first]) || seg[i + 1].aux != seg[first + 1].aux ||
+                seg[i + 1].block_pieces() != seg[first + 1].block_pieces())
+                return false;
+        return true;
+    }
+};
+constexpr Segments segments(const PackTable& t) {
+    Segments S{};
+    int i = 0;
+    while (i < t.n_items && S.n < kMaxSegments) {
+        Segment& s = S.seg[S.n++];
+        s.first = i;
+        s.off = t.dst_off[i];
+        s.layer = t.item[i].param / 2;
+        while (i < t.n_items && t.item[i].type != ITEM_CHUNK && !(s.aux > 0 && aux_item(t.item[i]).kind == AUX_BIAS)) {
+            if (s.aux < kMaxAuxPieces) s.item[s.aux] = aux_item(t.item[i]);
+            ++s.aux;
+            ++i;
+        }
+        if (i < t.n_items && t.item[i].type == ITEM_CHUNK) {
+            const int param = t.item[i].param;
+            s.layer = param / 2;
+            s.mb = t.item[i].mb;
+            for (; i < t.n_items && t.item[i].type == ITEM_CHUNK && t.item[i].param == param; ++i) ++s.blocks;
+        }
+    }
+    S.covered = i;
+    return S;
+}
+
 }  // namespace mi
 
 // ---------------------------------------------------------------------------------------
 // Per-kind recipes.  params[2*i] / params[2*i+1] = weight / bias of linear layer i in the
 // state-dict order listed per kind below (same order as oracle/fields.py SPECS).
-// The fused kernels in field_mlp.hip consume the stream in exactly this order.
+// The fused kernels consume the stream in exactly this order, and that is enforced at compile time: every stage shape
+// and aux-piece index in field_mlp.hip / field_mlp_bwd.hip is read from the segment view (segments(), above) of the table
+// built here, each kernel static_asserts that the segments it issues are the whole table (the sigma-only instances: the
+// sigma prefix), and segments_ok (field_kinds.h) holds every table against its kind's layer graph.
 // ---------------------------------------------------------------------------------------
 namespace mi {
 
@@ -256,7 +346,18 @@ constexpr PickedItem film_item(int L, bool use_dir, bool bwd, int i) {
 // ---- training buffers: per-point row-major regions [points][width], region r at offset_r * points ------
 // acts  = layer inputs saved by the forward (what dW = dA X^T and the activation derivatives need)
 // grads = dA of every linear layer written by the backward chain (+ 4 head pre-activation grads)
-struct RegionLayout { int n; int width[40]; };
+struct RegionLayout {
+    int n;
+    int width[40];
+    // ReLU kinds' acts: the switch region of H1 (H_l: relu_switch0() + l - 1; the dir layer's is the last region) - the
+    // first 8-dword region behind region 0 (an input: E_pos, or the sin kinds' xin row); -1 for none.  This reads widths, so
+    // it relies on no saved layer input behind region 0 being 8 wide; field_kinds.h pins the result for the ReLU kinds.
+    constexpr int relu_switch0() const {
+        for (int i = 1; i < n; ++i)
+            if (width[i] == 8) return i;
+        return -1;
+    }
+};
 constexpr int region_offset(const RegionLayout& L, int idx) {
     int o = 0;
     for (int i = 0; i < idx; ++i) o += L.width[i];

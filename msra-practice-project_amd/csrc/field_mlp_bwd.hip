@@ -92,6 +92,16 @@ __device__ __forceinline__ void relu_bwd_store(const f32x16 (&dX)[8], f32x16 (&X
     });
 }
 
+// Head gradients of point p (rgb = sigmoid(pre), sigma = relu(pre)): dL/d(pre) from the forward outputs and their gradients.
+// The caller stores them to its kind's heads region ([points][4]: rgb 0..2, sigma 3).
+struct HeadGrads { float d0, d1, d2, ds; };
+__device__ __forceinline__ HeadGrads head_grads(const BwdArgs& a, int64_t p) {
+    const f32x4 g = reinterpret_cast<const f32x4*>(a.g_raw)[p];
+    const f32x4 o = reinterpret_cast<const f32x4*>(a.raw)[p];
+    const float d0 = g.x * o.x * (1.f - o.x), d1 = g.y * o.y * (1.f - o.y), d2 = g.z * o.z * (1.f - o.z);
+    const float ds = o.w > 0.f ? g.w : 0.f;
+    return {d0, d1, d2, ds};
+}
 
 // One backward-chain layer with everything but the MFMAs sliced between them (mma_chunk's hooks):
 //   pre(m, part)  : accumulator start, s * aux row `piece` of slot `aux_slot` (SCALED: the sigma head's contribution), else
@@ -117,6 +127,7 @@ __device__ __forceinline__ void relu_bwd_store(const f32x16 (&dX)[8], f32x16 (&X
 // unchanged in X, that layer's B operand, until its last row) - PREV_MB blocks to `prev_dA`.
 // The FiLM chain has a layer of its own (film_chain_layer): it stores dL/du but carries gamma (.) dL/du.
 enum BwdEpi : int { EPI_LINEAR = 0, EPI_RELU = 1, EPI_SIN = 2 };
+constexpr int kNoStart = 0;      // `piece` of a layer that is not SCALED: never read
 
 template <int KB, int MB, int NEXT_AUX, int NEXT_BLOCK, int EPI, bool SCALED, bool DEFER = false, int PREV_MB = 0, class BSel>
 __device__ __forceinline__ void bwd_layer(Ctx& c, int aux_slot, int piece, float s, BSel bsel, f32x16 (&acc)[8],
@@ -221,94 +232,110 @@ __global__ __launch_bounds__(256, 1) void nerf_bwd_kernel(BwdArgs a) {
     Ctx c = make_ctx_raw(smem, a.packed, nullptr);
     constexpr RegionLayout AL = TINY ? tiny_acts() : nerf_acts();
     constexpr RegionLayout GL = TINY ? tiny_grads() : nerf_grads();
-    constexpr int kHeadAux = TINY ? 4 : 3;                 // rgb rows (+ sigma row for TinyNeRF)
+    // Backward segment 0 is the dir layer's (the rgb head's rows in front of it; TinyNeRF: and the sigma head's), segment i
+    // the layer's i layers further back: S the one whose start takes the sigma head's row, N - 1 the chain's last (layers_pos.1).
+    constexpr FieldKind K = kFieldKinds[TINY ? MI_FIELD_TINY_NERF : MI_FIELD_NERF];
+    constexpr Segments B = segments(K.bwd);
+    constexpr int N = B.n, S = TINY ? 0 : 1;
+    constexpr int kRgbRow = B.seg[0].piece(AUX_WROW, K.rgb_head()), kSigmaRow = B.seg[S].piece(AUX_WROW, K.sigma_head);
+    static_assert(kRgbRow >= 0 && kSigmaRow >= 0, "the heads' rows ride in front of the layers whose input gradient they start");
+    static_assert(B.seg[0].piece(AUX_WROW, K.rgb_head(), 1) == kRgbRow + 1 && B.seg[0].piece(AUX_WROW, K.rgb_head(), 2) == kRgbRow + 2,
+                  "the rgb head's three rows are consecutive pieces: the W_rgb^T loop below reads kRgbRow + 0..2");
+    constexpr int kDirBlocks = 4, kXBlocks = 8;             // K blocks the B-operand selectors below serve
+    static_assert(N == (TINY ? 4 : 9) && B.blocks(0) == kDirBlocks && B.blocks(1) == kXBlocks && B.uniform(TINY ? 1 : 2, N - 2) &&
+                      B.blocks(N - 2) == kXBlocks && B.blocks(N - 1) == kXBlocks,
+                  "the layers this kernel spells out are the whole chain; the plain ones have one shape, and K blocks for all of X");
     const int64_t P = a.points;
-    issue_first_stage<kHeadAux, 32, false>(c, 0);
+    issue_first_stage<B.aux(0), B.block_pieces(0), false>(c, 0);
 
     const int64_t local = (int64_t)blockIdx.x * 128 + c.wave * 32 + (c.lane & 31);
     const bool valid = local < P;
     const int64_t p = valid ? local : P - 1;
-    const f32x4 g = reinterpret_cast<const f32x4*>(a.g_raw)[p];
-    const f32x4 o = reinterpret_cast<const f32x4*>(a.raw)[p];
-    // heads: rgb = sigmoid(pre), sigma = relu(pre)
-    const float d0 = g.x * o.x * (1.f - o.x), d1 = g.y * o.y * (1.f - o.y), d2 = g.z * o.z * (1.f - o.z);
-    const float ds = o.w > 0.f ? g.w : 0.f;
-    if (valid && c.h == 0)
-        reinterpret_cast<f32x4*>(a.grads + (int64_t)region_offset(GL, GL.n - 1) * P)[p] = f32x4{d0, d1, d2, ds};
+    const HeadGrads hg = head_grads(a, p);
+    const float ds = hg.ds;
+    if (valid && c.h == 0) reinterpret_cast<f32x4*>(a.grads + (int64_t)region_offset(GL, GL.n - 1) * P)[p] = f32x4{hg.d0, hg.d1, hg.d2, ds};
 
-    f32x16 X[8], acc[8];
+    f32x16 X[kXBlocks], acc[8];
     const auto sel_x = [&](auto kb) -> const f32x16& { return X[decltype(kb)::value]; };
     const auto acts = [&](int region) { return a.acts + (int64_t)region_offset(AL, region) * P; };
     const auto grads = [&](int region) { return a.grads + (int64_t)region_offset(GL, region) * P; };
     // ReLU switches (one bit per unit) of layer H_l: region SW0 + l - 1, of the dir layer H_d: the last region
-    constexpr int SW0 = TINY ? 7 : 12;
+    constexpr int SW0 = AL.relu_switch0();
     const auto sw = [&](int l) { return a.acts + ((int64_t)region_offset(AL, SW0) + 8 * (l - 1)) * P; };
     uint32_t hsw[4];
     load_switches<4>(hsw, acts(AL.n - 1), p, c.h);
     MI_STAMP(a, 0);
 
     __syncthreads();                                        // head rows (and K block 0) have landed
-    {   // dH_d = W_rgb^T d_pre_rgb   (128 features)
+    {   // dH_d = W_rgb^T d_pre_rgb (128 features); the head's three rows are consecutive aux pieces of slot 0
         const lds4_t pw = lds_base(smem + kLdsAux0 + c.h * 16);
 #pragma unroll
-        for (int m = 0; m < 4; ++m)
+        for (int m = 0; m < kDirBlocks; ++m)
 #pragma unroll
             for (int rg = 0; rg < 4; ++rg) {
-                const f32x4 w0 = pw[0 * 64 + m * 8 + rg], w1 = pw[1 * 64 + m * 8 + rg], w2 = pw[2 * 64 + m * 8 + rg];
-                acc[m][4 * rg + 0] = fmaf(w2.x, d2, fmaf(w1.x, d1, w0.x * d0));
-                acc[m][4 * rg + 1] = fmaf(w2.y, d2, fmaf(w1.y, d1, w0.y * d0));
-                acc[m][4 * rg + 2] = fmaf(w2.z, d2, fmaf(w1.z, d1, w0.z * d0));
-                acc[m][4 * rg + 3] = fmaf(w2.w, d2, fmaf(w1.w, d1, w0.w * d0));
+                const f32x4 w0 = pw[(kRgbRow + 0) * 64 + m * 8 + rg], w1 = pw[(kRgbRow + 1) * 64 + m * 8 + rg], w2 = pw[(kRgbRow + 2) * 64 + m * 8 + rg];
+                acc[m][4 * rg + 0] = fmaf(w2.x, hg.d2, fmaf(w1.x, hg.d1, w0.x * hg.d0));
+                acc[m][4 * rg + 1] = fmaf(w2.y, hg.d2, fmaf(w1.y, hg.d1, w0.y * hg.d0));
+                acc[m][4 * rg + 2] = fmaf(w2.z, hg.d2, fmaf(w1.z, hg.d1, w0.z * hg.d0));
+                acc[m][4 * rg + 3] = fmaf(w2.w, hg.d2, fmaf(w1.w, hg.d1, w0.w * hg.d0));
             }
     }
-    relu_bwd_store<4>(acc, X, hsw, grads(TINY ? 4 : 9), 128, p, c.h);                    // dA of the dir layer
+    relu_bwd_store<kDirBlocks>(acc, X, hsw, grads(TINY ? 4 : 9), 128, p, c.h);            // dA of the dir layer
     MI_STAMP(a, 1);
 
     int slot = 0;
     if constexpr (!TINY) {
         // layers_dir[1]^T: dG = W[:, :256]^T dA (K = 128); layers_dir[0] is linear: dA = dG.  The B operand is a
         // copy: the epilogue rewrites X[0..3] while the last K block still reads X[3].
-        f32x16 Bd[4];
+        f32x16 Bd[kDirBlocks];
 #pragma unroll
-        for (int m = 0; m < 4; ++m) Bd[m] = X[m];
+        for (int m = 0; m < kDirBlocks; ++m) Bd[m] = X[m];
         const auto sel_d = [&](auto kb) -> const f32x16& { return Bd[decltype(kb)::value]; };
-        bwd_layer<4, 8, 1, 32, EPI_LINEAR, false, true, 0>(c, slot, 0, 0.f, sel_d, acc, X, grads(8), 256, p);
+        bwd_layer<B.blocks(0), B.mb(0), B.aux(1), B.block_pieces(1), EPI_LINEAR, false, true, 0>(c, slot, kNoStart, 0.f, sel_d, acc, X, grads(8), 256, p);
         MI_STAMP(a, 2);
         slot ^= 1;
         // layers_dir[0]^T, plus the sigma head's contribution to dH8; dA7 = dH8 (.) [H8>0]
-        bwd_layer<8, 8, 0, 32, EPI_RELU, true, true, 8>(c, slot, 0, ds, sel_x, acc, X, grads(7), 256, p, sw(8), grads(8), 256);
+        bwd_layer<B.blocks(1), B.mb(1), B.aux(2), B.block_pieces(2), EPI_RELU, true, true, B.mb(0)>(c, slot, kSigmaRow, ds, sel_x, acc, X, grads(7), 256, p,
+                                                                                                    sw(8), grads(8), 256);
         MI_STAMP(a, 3);
         slot ^= 1;
 #ifdef MI_PROFILE_STAMPS
         if (a.stamps) c.rowst = a.stamps + (int64_t)blockIdx.x * 128 + 32;                     // rows of L7^T: 32..64
 #endif
-        bwd_layer<8, 8, 0, 32, EPI_RELU, false, true, 8>(c, slot, 0, 0.f, sel_x, acc, X, grads(6), 256, p, sw(7), grads(7), 256);  // L7^T
+        bwd_layer<B.blocks(2), B.mb(2), B.aux(3), B.block_pieces(3), EPI_RELU, false, true, B.mb(1)>(c, slot, kNoStart, 0.f, sel_x, acc, X, grads(6), 256, p,
+                                                                                                     sw(7), grads(7), 256);  // L7^T
 #ifdef MI_PROFILE_STAMPS
         if (c.rowst) { MI_ROW_STAMP(c); }
         c.rowst = nullptr;
 #endif
         MI_STAMP(a, 4);
-        bwd_layer<8, 8, 0, 32, EPI_RELU, false, true, 8>(c, slot, 0, 0.f, sel_x, acc, X, grads(5), 256, p, sw(6), grads(6), 256);  // L6^T
+        bwd_layer<B.blocks(2), B.mb(2), B.aux(3), B.block_pieces(3), EPI_RELU, false, true, B.mb(1)>(c, slot, kNoStart, 0.f, sel_x, acc, X, grads(5), 256, p,
+                                                                                                     sw(6), grads(6), 256);  // L6^T
         MI_STAMP(a, 5);
-        bwd_layer<8, 8, 0, 32, EPI_RELU, false, true, 8>(c, slot, 0, 0.f, sel_x, acc, X, grads(4), 256, p, sw(5), grads(5), 256);  // L5^T (h part)
+        bwd_layer<B.blocks(2), B.mb(2), B.aux(3), B.block_pieces(3), EPI_RELU, false, true, B.mb(1)>(c, slot, kNoStart, 0.f, sel_x, acc, X, grads(4), 256, p,
+                                                                                                     sw(5), grads(5), 256);  // L5^T (h part)
         MI_STAMP(a, 6);
 #pragma unroll 1
         for (int l = 4; l >= 2; --l)                                                           // L4^T .. L2^T
-            bwd_layer<8, 8, 0, 32, EPI_RELU, false, true, 8>(c, slot, 0, 0.f, sel_x, acc, X, a.grads + (int64_t)(256 * (l - 1)) * P,
-                                                             256, p, sw(l), a.grads + (int64_t)(256 * l) * P, 256);
+            bwd_layer<B.blocks(2), B.mb(2), B.aux(3), B.block_pieces(3), EPI_RELU, false, true, B.mb(1)>(
+                c, slot, kNoStart, 0.f, sel_x, acc, X, a.grads + (int64_t)(256 * (l - 1)) * P, 256, p, sw(l), a.grads + (int64_t)(256 * l) * P, 256);
         MI_STAMP(a, 7);                                                                        // after L4^T .. L2^T
-        bwd_layer<8, 8, 0, 0, EPI_RELU, false, false, 8>(c, slot, 0, 0.f, sel_x, acc, X, grads(0), 256, p, sw(1), grads(1), 256);   // L1^T
+        bwd_layer<B.blocks(N - 1), B.mb(N - 1), B.aux(N), B.block_pieces(N), EPI_RELU, false, false, B.mb(N - 2)>(c, slot, kNoStart, 0.f, sel_x, acc, X,
+                                                                                                              grads(0), 256, p, sw(1), grads(1), 256);   // L1^T
         MI_STAMP(a, 8);
     } else {
-        // dir layer^T with the sigma head's contribution to dH4 (sigma row is aux piece 3 of slot 0)
-        f32x16 Bd[4];
+        // dir layer^T with the sigma head's contribution to dH4 (the sigma row rides behind the rgb rows in aux slot 0)
+        f32x16 Bd[kDirBlocks];
 #pragma unroll
-        for (int m = 0; m < 4; ++m) Bd[m] = X[m];
+        for (int m = 0; m < kDirBlocks; ++m) Bd[m] = X[m];
         const auto sel_d = [&](auto kb) -> const f32x16& { return Bd[decltype(kb)::value]; };
-        bwd_layer<4, 8, 0, 32, EPI_RELU, true, true, 0>(c, 0, 3, ds, sel_d, acc, X, grads(3), 256, p, sw(4));
-        bwd_layer<8, 8, 0, 32, EPI_RELU, false, true, 8>(c, slot, 0, 0.f, sel_x, acc, X, grads(2), 256, p, sw(3), grads(3), 256);  // L3^T
-        bwd_layer<8, 8, 0, 32, EPI_RELU, false, true, 8>(c, slot, 0, 0.f, sel_x, acc, X, grads(1), 256, p, sw(2), grads(2), 256);  // L2^T
-        bwd_layer<8, 8, 0, 0, EPI_RELU, false, false, 8>(c, slot, 0, 0.f, sel_x, acc, X, grads(0), 256, p, sw(1), grads(1), 256);   // L1^T
+        bwd_layer<B.blocks(0), B.mb(0), B.aux(1), B.block_pieces(1), EPI_RELU, true, true, 0>(c, 0, kSigmaRow, ds, sel_d, acc, X, grads(3), 256, p, sw(4));
+        bwd_layer<B.blocks(1), B.mb(1), B.aux(2), B.block_pieces(2), EPI_RELU, false, true, B.mb(0)>(c, slot, kNoStart, 0.f, sel_x, acc, X, grads(2), 256, p,
+                                                                                                     sw(3), grads(3), 256);  // L3^T
+        bwd_layer<B.blocks(2), B.mb(2), B.aux(3), B.block_pieces(3), EPI_RELU, false, true, B.mb(1)>(c, slot, kNoStart, 0.f, sel_x, acc, X, grads(1), 256, p,
+                                                                                                     sw(2), grads(2), 256);  // L2^T
+        bwd_layer<B.blocks(N - 1), B.mb(N - 1), B.aux(N), B.block_pieces(N), EPI_RELU, false, false, B.mb(N - 2)>(c, slot, kNoStart, 0.f, sel_x, acc, X,
+                                                                                                              grads(0), 256, p, sw(1), grads(1), 256);   // L1^T
     }
 }
 
@@ -336,57 +363,69 @@ __global__ __launch_bounds__(256, 1) void siren_bwd_kernel(BwdArgs a) {
     Ctx c = make_ctx_raw(smem, a.packed, nullptr);
     constexpr RegionLayout AL = siren_acts();
     constexpr RegionLayout GL = siren_grads();
+    // backward segments as in nerf_bwd_kernel: 0 layers_dir.1's (rgb rows in front), 1 layers_dir.0's (sigma row), N - 1 the last
+    constexpr FieldKind K = kFieldKinds[MI_FIELD_SIREN_NERF];
+    constexpr Segments B = segments(K.bwd);
+    constexpr int N = B.n;
+    constexpr int kRgbRow = B.seg[0].piece(AUX_WROW, K.rgb_head()), kSigmaRow = B.seg[1].piece(AUX_WROW, K.sigma_head);
+    static_assert(kRgbRow >= 0 && kSigmaRow >= 0, "the heads' rows ride in front of the layers whose input gradient they start");
+    static_assert(B.seg[0].piece(AUX_WROW, K.rgb_head(), 1) == kRgbRow + 1 && B.seg[0].piece(AUX_WROW, K.rgb_head(), 2) == kRgbRow + 2,
+                  "the rgb head's three rows are consecutive pieces: the W_rgb^T loop below reads kRgbRow + 0..2");
+    constexpr int kDirBlocks = 4, kXBlocks = 8;             // K blocks the B-operand selectors below serve
+    static_assert(N == 9 && B.blocks(0) == kDirBlocks && B.blocks(1) == kXBlocks && B.uniform(2, N - 2) && B.blocks(2) == kXBlocks &&
+                      B.blocks(N - 1) == kXBlocks,
+                  "layers_dir.1, .0, the loop's six and layers_pos.1 are the whole chain; the loop's have one shape, and K blocks for all of X");
     const int64_t P = a.points;
-    issue_first_stage<3, 32, false>(c, 0);
+    issue_first_stage<B.aux(0), B.block_pieces(0), false>(c, 0);
 
     const int64_t local = (int64_t)blockIdx.x * 128 + c.wave * 32 + (c.lane & 31);
     const bool valid = local < P;
     const int64_t p = valid ? local : P - 1;
-    const f32x4 g = reinterpret_cast<const f32x4*>(a.g_raw)[p];
-    const f32x4 o = reinterpret_cast<const f32x4*>(a.raw)[p];
-    const float d0 = g.x * o.x * (1.f - o.x), d1 = g.y * o.y * (1.f - o.y), d2 = g.z * o.z * (1.f - o.z);
-    const float ds = o.w > 0.f ? g.w : 0.f;
-    if (valid && c.h == 0)
-        reinterpret_cast<f32x4*>(a.grads + (int64_t)region_offset(GL, GL.n - 1) * P)[p] = f32x4{d0, d1, d2, ds};
+    const HeadGrads hg = head_grads(a, p);
+    const float ds = hg.ds;
+    if (valid && c.h == 0) reinterpret_cast<f32x4*>(a.grads + (int64_t)region_offset(GL, GL.n - 1) * P)[p] = f32x4{hg.d0, hg.d1, hg.d2, ds};
 
-    f32x16 X[8], acc[8];
+    f32x16 X[kXBlocks], acc[8];
     const auto sel_x = [&](auto kb) -> const f32x16& { return X[decltype(kb)::value]; };
     const auto acts = [&](int region) { return a.acts + (int64_t)region_offset(AL, region) * P; };
     const auto grads = [&](int region) { return a.grads + (int64_t)region_offset(GL, region) * P; };
-    f32x4 xsv[16];
-    load_saved_row<4>(xsv, acts(10), 128, p, c.h);
+    f32x4 xsv[kDirBlocks * 4];
+    load_saved_row<kDirBlocks>(xsv, acts(10), 128, p, c.h);
 
     __syncthreads();
-    {   // dX_d = W_rgb^T d_pre_rgb (128 features)
+    {   // dH_d = W_rgb^T d_pre_rgb (128 features); the head's three rows are consecutive aux pieces of slot 0
         const lds4_t pw = lds_base(smem + kLdsAux0 + c.h * 16);
 #pragma unroll
-        for (int m = 0; m < 4; ++m)
+        for (int m = 0; m < kDirBlocks; ++m)
 #pragma unroll
             for (int rg = 0; rg < 4; ++rg) {
-                const f32x4 w0 = pw[0 * 64 + m * 8 + rg], w1 = pw[1 * 64 + m * 8 + rg], w2 = pw[2 * 64 + m * 8 + rg];
-                acc[m][4 * rg + 0] = fmaf(w2.x, d2, fmaf(w1.x, d1, w0.x * d0));
-                acc[m][4 * rg + 1] = fmaf(w2.y, d2, fmaf(w1.y, d1, w0.y * d0));
-                acc[m][4 * rg + 2] = fmaf(w2.z, d2, fmaf(w1.z, d1, w0.z * d0));
-                acc[m][4 * rg + 3] = fmaf(w2.w, d2, fmaf(w1.w, d1, w0.w * d0));
+                const f32x4 w0 = pw[(kRgbRow + 0) * 64 + m * 8 + rg], w1 = pw[(kRgbRow + 1) * 64 + m * 8 + rg], w2 = pw[(kRgbRow + 2) * 64 + m * 8 + rg];
+                acc[m][4 * rg + 0] = fmaf(w2.x, hg.d2, fmaf(w1.x, hg.d1, w0.x * hg.d0));
+                acc[m][4 * rg + 1] = fmaf(w2.y, hg.d2, fmaf(w1.y, hg.d1, w0.y * hg.d0));
+                acc[m][4 * rg + 2] = fmaf(w2.z, hg.d2, fmaf(w1.z, hg.d1, w0.z * hg.d0));
+                acc[m][4 * rg + 3] = fmaf(w2.w, hg.d2, fmaf(w1.w, hg.d1, w0.w * hg.d0));
             }
     }
-    sin_bwd_store<4>(acc, X, xsv, grads(9), 128, p, c.h);                               // dA layers_dir.1 (X_d rows)
+    sin_bwd_store<kDirBlocks>(acc, X, xsv, grads(9), 128, p, c.h);                       // dA layers_dir.1 (X_d rows)
     int slot = 0;
     {   // layers_dir.1^T (h part); layers_dir.0 is linear: dA = dG.  B operand copied (see nerf_bwd_kernel).
-        f32x16 Bd[4];
+        f32x16 Bd[kDirBlocks];
 #pragma unroll
-        for (int m = 0; m < 4; ++m) Bd[m] = X[m];
+        for (int m = 0; m < kDirBlocks; ++m) Bd[m] = X[m];
         const auto sel_d = [&](auto kb) -> const f32x16& { return Bd[decltype(kb)::value]; };
-        bwd_layer<4, 8, 1, 32, EPI_LINEAR, false, true, 0>(c, slot, 0, 0.f, sel_d, acc, X, grads(8), 256, p);
+        bwd_layer<B.blocks(0), B.mb(0), B.aux(1), B.block_pieces(1), EPI_LINEAR, false, true, 0>(c, slot, kNoStart, 0.f, sel_d, acc, X, grads(8), 256, p);
     }
     slot ^= 1;
     // layers_dir.0^T + sigma head; dA7 = dX8 (.) C8, C_l rebuilt from the saved X_l rows (acts region l)
-    bwd_layer<8, 8, 0, 32, EPI_SIN, true, true, 8>(c, slot, 0, ds, sel_x, acc, X, grads(7), 256, p, acts(8), grads(8), 256);
+    bwd_layer<B.blocks(1), B.mb(1), B.aux(2), B.block_pieces(2), EPI_SIN, true, true, B.mb(0)>(c, slot, kSigmaRow, ds, sel_x, acc, X, grads(7), 256, p, acts(8),
+                                                                                               grads(8), 256);
 #pragma unroll 1
     for (int l = 7; l >= 2; --l)                                                                // L7^T .. L2^T: dA_{l-1} = dX_l (.) C_l
-        bwd_layer<8, 8, 0, 32, EPI_SIN, false, true, 8>(c, slot, 0, 0.f, sel_x, acc, X, a.grads + (int64_t)(256 * (l - 1)) * P, 256, p,
-                                                        a.acts + (int64_t)(8 + 256 * (l - 1)) * P, a.grads + (int64_t)(256 * l) * P, 256);
-    bwd_layer<8, 8, 0, 0, EPI_SIN, false, false, 8>(c, slot, 0, 0.f, sel_x, acc, X, grads(0), 256, p, acts(1), grads(1), 256);   // L1^T: dA0 = dX1 (.) C1
+        bwd_layer<B.blocks(2), B.mb(2), B.aux(3), B.block_pieces(3), EPI_SIN, false, true, B.mb(1)>(
+            c, slot, kNoStart, 0.f, sel_x, acc, X, a.grads + (int64_t)(256 * (l - 1)) * P, 256, p, a.acts + (int64_t)(8 + 256 * (l - 1)) * P,
+            a.grads + (int64_t)(256 * l) * P, 256);
+    bwd_layer<B.blocks(N - 1), B.mb(N - 1), B.aux(N), B.block_pieces(N), EPI_SIN, false, false, B.mb(N - 2)>(c, slot, kNoStart, 0.f, sel_x, acc, X, grads(0),
+                                                                                                             256, p, acts(1), grads(1), 256);   // L1^T: dA0 = dX1 (.) C1
 }
 
 // =========================================================================================
@@ -495,24 +534,36 @@ __global__ __launch_bounds__(256, 1) void film_bwd_kernel(BwdArgs a) {
     Ctx c = make_ctx_raw(smem, a.packed, a.film + group * ((L + 1) * kFilmRow));
     // fl(w_0^2) of the module's w_0 (pi_GAN/modules.py:11,73) from the backward stream's trailer: the rebuilt derivative
     // factor is +-sqrt(w_0^2 (1 - X^2)); a uniform (scalar) load
-    static_assert(film_body_floats(8, USE_DIR, true) ==
-                  packed_body_floats(kFieldKinds[USE_DIR ? MI_FIELD_FILM_SIREN_NERF : MI_FIELD_FILM_SIREN_NERF_NODIR].bwd));
+    constexpr FieldKind K = kFieldKinds[USE_DIR ? MI_FIELD_FILM_SIREN_NERF : MI_FIELD_FILM_SIREN_NERF_NODIR];
+    static_assert(film_body_floats(8, USE_DIR, true) == packed_body_floats(K.bwd));
     const int kBody = film_body_floats(L, USE_DIR, true);
     c.w0sq = a.packed[kBody + 1];
+    // The shapes are depth 8's (kinds 2 / 3): segment 0 is hidden_layer_rgb^T's with both heads' rows in front of it, every
+    // other one a plain hidden layer's, the last followed by nothing.  Any other depth's stream has the same (field_kinds.h:
+    // film_depth_like_8).  film_chain_layer runs 8 K blocks of 8 row blocks: all of X.
+    constexpr Segments B = segments(K.bwd);
+    constexpr int N = B.n;
+    constexpr int kRgbRow = B.seg[0].piece(AUX_WROW, K.rgb_head()), kSigmaRow = B.seg[0].piece(AUX_WROW, K.sigma_head);
+    static_assert(kRgbRow >= 0 && kSigmaRow >= 0, "the heads' rows ride in front of the chain's first layer");
+    static_assert(B.seg[0].piece(AUX_WROW, K.rgb_head(), 1) == kRgbRow + 1 && B.seg[0].piece(AUX_WROW, K.rgb_head(), 2) == kRgbRow + 2,
+                  "the rgb head's three rows are consecutive pieces: the W_rgb^T loop below reads kRgbRow + 0..2");
+    constexpr int kXBlocks = 8;
+    static_assert(N == 8 && B.uniform(1, N - 2) && B.aux(1) == 0 && B.blocks(0) == kXBlocks && B.mb(0) == kXBlocks && B.blocks(1) == kXBlocks &&
+                      B.mb(1) == kXBlocks && B.seg[N - 1].same_shape(B.seg[1]),
+                  "one chain layer per segment, each film_chain_layer's 8 x 8 blocks with no aux pieces issued behind it");
+    static_assert(!RT_DEPTH || film_segments_ok(USE_DIR), "every depth's stream has depth 8's shapes at depth 8's distances from its ends");
     const int64_t P = a.points;
     // rgb head rows x3, sigma row; K blocks 0-1 of hidden_layer_rgb^T; FiLM row L -> film slot 0 (row r lives in slot (L - r) & 1)
-    issue_first_stage<4, 32, true>(c, 0, L);
+    issue_first_stage<B.aux(0), B.block_pieces(0), true>(c, 0, L);
 
     const int64_t local = tile * 128 + c.wave * 32 + (c.lane & 31);
     const bool valid = local < a.points_per_group;
     const int64_t p = group * a.points_per_group + (valid ? local : a.points_per_group - 1);
-    const f32x4 g = reinterpret_cast<const f32x4*>(a.g_raw)[p];
-    const f32x4 o = reinterpret_cast<const f32x4*>(a.raw)[p];
-    const float d0 = g.x * o.x * (1.f - o.x), d1 = g.y * o.y * (1.f - o.y), d2 = g.z * o.z * (1.f - o.z);
-    const float ds = o.w > 0.f ? g.w : 0.f;
-    if (valid && c.h == 0) reinterpret_cast<f32x4*>(a.grads + (int64_t)((L + 1) * 256) * P)[p] = f32x4{d0, d1, d2, ds};
+    const HeadGrads hg = head_grads(a, p);
+    const float ds = hg.ds;
+    if (valid && c.h == 0) reinterpret_cast<f32x4*>(a.grads + (int64_t)((L + 1) * 256) * P)[p] = f32x4{hg.d0, hg.d1, hg.d2, ds};
 
-    f32x16 X[8], acc[8];
+    f32x16 X[kXBlocks], acc[8];
     const auto film_row = [&](int r) { return smem + kLdsFilm0 + ((L - r) & 1) * kFilmRow; };       // FiLM row r's LDS slot
     const auto C = [&](int l) { return a.acts + (int64_t)(8 + 256 * l) * P; };    // saved X_l rows: C_l is rebuilt from them
     const auto dU = [&](int l) { return a.grads + (int64_t)(256 * l) * P; };
@@ -524,28 +575,28 @@ __global__ __launch_bounds__(256, 1) void film_bwd_kernel(BwdArgs a) {
     }
 
     __syncthreads();
-    {   // dX_8 = W_rgb^T d_pre_rgb (256 features)
+    {   // dX_L = W_rgb^T d_pre_rgb (256 features)
         const lds4_t pw = lds_base(smem + kLdsAux0 + c.h * 16);
 #pragma unroll
-        for (int m = 0; m < 8; ++m)
+        for (int m = 0; m < kXBlocks; ++m)
 #pragma unroll
             for (int rg = 0; rg < 4; ++rg) {
-                const f32x4 w0 = pw[0 * 64 + m * 8 + rg], w1 = pw[1 * 64 + m * 8 + rg], w2 = pw[2 * 64 + m * 8 + rg];
-                acc[m][4 * rg + 0] = fmaf(w2.x, d2, fmaf(w1.x, d1, w0.x * d0));
-                acc[m][4 * rg + 1] = fmaf(w2.y, d2, fmaf(w1.y, d1, w0.y * d0));
-                acc[m][4 * rg + 2] = fmaf(w2.z, d2, fmaf(w1.z, d1, w0.z * d0));
-                acc[m][4 * rg + 3] = fmaf(w2.w, d2, fmaf(w1.w, d1, w0.w * d0));
+                const f32x4 w0 = pw[(kRgbRow + 0) * 64 + m * 8 + rg], w1 = pw[(kRgbRow + 1) * 64 + m * 8 + rg], w2 = pw[(kRgbRow + 2) * 64 + m * 8 + rg];
+                acc[m][4 * rg + 0] = fmaf(w2.x, hg.d2, fmaf(w1.x, hg.d1, w0.x * hg.d0));
+                acc[m][4 * rg + 1] = fmaf(w2.y, hg.d2, fmaf(w1.y, hg.d1, w0.y * hg.d0));
+                acc[m][4 * rg + 2] = fmaf(w2.z, hg.d2, fmaf(w1.z, hg.d1, w0.z * hg.d0));
+                acc[m][4 * rg + 3] = fmaf(w2.w, hg.d2, fmaf(w1.w, hg.d1, w0.w * hg.d0));
             }
     }
     MI_STAMP(a, 0);
-    film_bwd_first<8>(acc, X, ring, c.w0sq);                                                             // hidden_layer_rgb: X = dU_8
+    film_bwd_first<kXBlocks>(acc, X, ring, c.w0sq);                                                      // hidden_layer_rgb: X = dU_L
     MI_STAMP(a, 1);
     // Chain layer j multiplies by FiLM row j + 1 (slot (L - 1 - j) & 1) and DMAs row j - what layer j - 1 multiplies by -
-    // into the other slot.  j = L - 1 starts from the sigma head's row (aux slot 0, piece 3).
+    // into the other slot.  j = L - 1 starts from the sigma head's row (aux slot 0, behind the rgb head's).
 #if defined(MI_PROFILE_STAMPS) && defined(MI_STAMP_LAYER) && MI_STAMP_LAYER == 7
     if (a.stamps) c.rowst = a.stamps + (int64_t)blockIdx.x * 128 + 32;                          // rows of layer 7: 32..64
 #endif
-    film_chain_layer<32, true, true, false>(c, 3, ds, acc, X, ring, C(L - 1), dU(L - 1), dU(L), p, 0, L - 1, film_row(L));
+    film_chain_layer<B.block_pieces(1), true, true, false>(c, kSigmaRow, ds, acc, X, ring, C(L - 1), dU(L - 1), dU(L), p, 0, L - 1, film_row(L));
 #if defined(MI_PROFILE_STAMPS) && defined(MI_STAMP_LAYER) && MI_STAMP_LAYER == 7
     if (c.rowst) { MI_ROW_STAMP(c); }
     c.rowst = nullptr;
@@ -558,14 +609,14 @@ __global__ __launch_bounds__(256, 1) void film_bwd_kernel(BwdArgs a) {
         if (j == 4 && a.stamps) c.rowst = a.stamps + (int64_t)blockIdx.x * 128 + 32;            // rows of layer j = 4: 32..64
 #endif
 #endif
-        film_chain_layer<32, false, true, false>(c, 0, 0.f, acc, X, ring, C(j), dU(j), dU(j + 1), p, (L - 1 - j) & 1, j, film_row(j + 1));
+        film_chain_layer<B.block_pieces(2), false, true, false>(c, kNoStart, 0.f, acc, X, ring, C(j), dU(j), dU(j + 1), p, (L - 1 - j) & 1, j, film_row(j + 1));
 #ifdef MI_PROFILE_STAMPS
         if (c.rowst) { MI_ROW_STAMP(c); }
         c.rowst = nullptr;
         if (threadIdx.x == 0 && a.stamps) a.stamps[(int64_t)blockIdx.x * 128 + 3 + (L - 2 - j)] = __builtin_amdgcn_s_memtime();   // 3..L
 #endif
     }
-    film_chain_layer<0, false, false, true>(c, 0, 0.f, acc, X, ring, C(0), dU(0), dU(1), p, (L - 1) & 1, 0, film_row(1));   // input_layer
+    film_chain_layer<B.block_pieces(N), false, false, true>(c, kNoStart, 0.f, acc, X, ring, C(0), dU(0), dU(1), p, (L - 1) & 1, 0, film_row(1));   // input_layer
     MI_STAMP(a, 9);
 }
 

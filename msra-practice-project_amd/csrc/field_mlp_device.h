@@ -548,12 +548,23 @@ __device__ __forceinline__ float head_dot(const f32x16 (&X)[8], const float* aux
     return s;
 }
 
-// sigma = relu(w . X + b): the head's weight row is piece 1 and its bias the first float of piece 2 of the aux slot
-__device__ __forceinline__ float sigma_head(const f32x16 (&X)[8], const float* aux, int h) {
-    return fmaxf(head_dot<8>(X, aux, 1, h) + aux[2 * kPiece], 0.f);
+// sigma = relu(w . X + b): the head's weight row is aux piece `row` and its bias the first float of aux piece `scalars`
+// of the slot (Segment::piece, field_layout.h)
+__device__ __forceinline__ float sigma_head(const f32x16 (&X)[8], const float* aux, int row, int scalars, int h) {
+    return fmaxf(head_dot<8>(X, aux, row, h) + aux[scalars * kPiece], 0.f);
 }
 
 __device__ __forceinline__ float sigmoidf(float v) { return 1.f / (1.f + expf(-v)); }
+
+// r, g, b = sigmoid(W X + b) over MB blocks of X: the head's three weight rows are aux pieces row0 .. row0 + 2 and its
+// biases the first three floats of aux piece `scalars`
+template <int MB>
+__device__ __forceinline__ void rgb_heads(const f32x16 (&X)[8], const float* aux, int row0, int scalars, int h, float& r,
+                                          float& g, float& b) {
+    r = sigmoidf(head_dot<MB>(X, aux, row0 + 0, h) + aux[scalars * kPiece + 0]);
+    g = sigmoidf(head_dot<MB>(X, aux, row0 + 1, h) + aux[scalars * kPiece + 1]);
+    b = sigmoidf(head_dot<MB>(X, aux, row0 + 2, h) + aux[scalars * kPiece + 2]);
+}
 
 // Positional-encoding blocks, fully unrolled.  Feature f of the encoding of (x,y,z): i = f/6, c = f%6,
 // c < 3 -> sin(2^i x_c), else cos(2^i x_{c-3}) (nerf/nerf.py:44-49).  Register r of block blk holds feature
@@ -687,6 +698,16 @@ __device__ __forceinline__ void store_out(const MlpArgs& a, const PointIn& pt, i
 // sigma-only forward: out is a compact sigma buffer [points] (one float per point, not [points][4])
 __device__ __forceinline__ void store_sigma(const MlpArgs& a, const PointIn& pt, int h, float s) {
     if (pt.valid && h == 0) a.out[pt.p] = s;
+}
+
+// training forward of the sin kinds: the point's xin row (xyz, dir, 0, 0), region 0 of siren_acts() / film_acts(), stored by
+// the lane that owns the point (`mine`: valid, lower half)
+__device__ __forceinline__ void store_xin(float* save, const PointIn& pt, bool mine) {
+    if (mine) {
+        f32x4* xin = reinterpret_cast<f32x4*>(save + pt.p * 8);
+        xin[0] = f32x4{pt.px, pt.py, pt.pz, pt.dx};
+        xin[1] = f32x4{pt.dy, pt.dz, 0.f, 0.f};
+    }
 }
 
 // ---- activations <-> HBM in [point][feature] row-major (training: saved layer inputs, gradients) --------
