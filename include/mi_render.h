@@ -173,6 +173,13 @@ int mi_sample_pdf(int64_t n, int n_bins, int n_samples, const float* bins, const
  *   field along a ray once the ray's transmittance has reached zero: every later weight is exactly 0 whatever the field
  *   returns there, so no output bit depends on it - except that a non-finite sigma behind a zero transmittance no longer
  *   reaches the outputs as NaN.  All launches stay asynchronous, with host-known grid sizes (stream capture works).
+ *   When depth_c and acc_c are NULL as well, the coarse weights have one reader left, the fine sampler, which uses a
+ *   weight only as w + 1e-5f: that pass then stops along a ray as soon as the transmittance in front of a window is
+ *   <= 2^-42.  No later weight can exceed the transmittance in front of it (alpha <= 1, and the running product only
+ *   falls), and a weight below 2^-41, half an ulp of 1e-5f, leaves that sum unchanged: the fine depths and the fine
+ *   outputs are still the same bits (64 + 128 samples, 800x800, one MI355X: the coarse launches take 42.8 instead of
+ *   111.6 ms per frame, the frame 897.5 instead of 965.1 ms).  The caveat above then holds from that earlier point on:
+ *   a non-finite sigma behind it no longer reaches the pixel.
  *   With two different fields, a fine field of a kind that has the kernels (NeRF, TinyNeRF), Nf > 0 and a workspace that
  *   also holds mi_render_deferred_colour_extra_bytes(n, Nc, Nf) more, the fine pass runs its colour branch only on the
  *   points with sigma > 0 (in chunks of whole rays: the trunk for every point, then the colour branch over the chunk's

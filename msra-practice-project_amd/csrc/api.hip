@@ -91,14 +91,17 @@ static_assert(kCoarseWindow >= 1 && 128 % kCoarseWindow == 0, "a tile is 128 / k
 // The sigma-only coarse pass, front to back in windows of kCoarseWindow samples: window r evaluates the field at its
 // samples of the rays that are still live, then the resumable weights composite (render_stages.hip) writes the window's
 // weights and drops every ray whose transmittance has reached zero - all its later weights are exactly 0 whatever the
-// field says there, so the field is not asked.  Same weights / depth_c / acc_c bits as one whole pass.  Everything is
-// launched with worst-case grids from host values only (no read-back: graph-capturable); `scratch` is the part of raw_c's
-// region behind the compact sigma buffer: two live lists [n] and one count per window.
+// field says there, so the field is not asked.  Same weights / depth_c / acc_c bits as one whole pass.  A caller that
+// asks for neither depth_c nor acc_c leaves sample_fine as the weights' only reader, and a ray is dropped as soon as no
+// later weight can change w + kPdfEps there (kStopBelowPdfEps, mi_common.h): same z_fine bits, far fewer points.
+// Everything is launched with worst-case grids from host values only (no read-back: graph-capturable); `scratch` is the
+// part of raw_c's region behind the compact sigma buffer: two live lists [n] and one count per window.
 static int coarse_sigma_windows(int kind, const float* packed, const float* rays, const float* z_c, int64_t n, int n_coarse,
                                 float* sigma, int* scratch, float* depth_c, float* acc_c, float* w_c, hipStream_t hs) {
     const int rounds = (n_coarse + kCoarseWindow - 1) / kCoarseWindow;
     int* list[2] = {scratch, scratch + n};
     int* counts = scratch + 2 * n;
+    const double stop = depth_c || acc_c ? kStopZeroWeight : kStopBelowPdfEps;
     if (hipMemsetAsync(counts, 0, sizeof(int) * rounds, hs) != hipSuccess) { set_error("mi_render_rays: hipMemsetAsync failed"); return MI_EHIP; }
     MlpArgs args = {};
     args.packed = packed; args.a = rays; args.z = z_c; args.out = sigma;
@@ -113,7 +116,7 @@ static int coarse_sigma_windows(int kind, const float* packed, const float* rays
         if ((rc = launch_mlp_window(kind, args, hs))) return rc;
         if ((rc = launch_composite_weights_window(n, n_coarse, sigma, z_c, rays, depth_c, acc_c, w_c, args.live_rays,
                                                   args.live_count, last ? nullptr : list[(r + 1) & 1],
-                                                  last ? nullptr : counts + r + 1, k0, k1, hs))) return rc;
+                                                  last ? nullptr : counts + r + 1, k0, k1, stop, hs))) return rc;
     }
     return MI_OK;
 }

@@ -184,12 +184,41 @@ int launch_composite(int64_t n, int S, const float* raw, const float* z, const f
                      float* acc, float* weights, hipStream_t stream);
 int launch_composite_weights(int64_t n, int S, const float* sigma, int sigma_stride, const float* z, const float* rays,
                              float* depth, float* acc, float* weights, hipStream_t stream);
+// The epsilon sample_pdf adds to every weight before it normalises them (render.py:31); normalise_pdf (render_stages.hip)
+// is its one user.
+constexpr float kPdfEps = 1e-5f;
+// ulp of a positive normal float: 2^-23 times the power of two at or below it
+constexpr double float_ulp(float x) {
+    double p = 1.0;
+    while (p > (double)x) p *= 0.5;
+    while (p * 2.0 <= (double)x) p *= 2.0;
+    return p * 0x1p-23;
+}
+// Where the resumable weights composite stops a ray: at a window boundary whose fp64 running product D is <= the threshold.
+//   * kStopZeroWeight, 2^-151: every later weight is exactly 0.0f (composite_weights_window_kernel's comment), so every
+//     consumer of the weights, the sums depth_c / acc_c included, keeps its bits.
+//   * kStopBelowPdfEps, 2^-42, for a coarse pass whose only product is the weights that sample_fine reads.  normalise_pdf
+//     uses a weight only as w + kPdfEps, in the sum and in the quotient, un-fused (-ffp-contract=off).  kPdfEps lies in
+//     [2^-17, 2^-16), so its ulp is 2^-40 and every 0 <= w < 2^-41, half an ulp, gives fl(w + kPdfEps) == kPdfEps whichever
+//     way a tie would round: such a weight is indistinguishable from 0.  A later sample's weight is
+//     alpha * (float)(T * excl) with alpha in [0, 1] and the factors f = (1-alpha)+1e-10f <= 1 (sigma >= 0, ascending
+//     depths), so the exact product can only fall: no later weight exceeds the transmittance in front of it, whatever its
+//     sigma is.  The scans' products differ from the exact ones by a relative 2^-45 at most, and rounding to float adds
+//     2^-24: far inside the factor 2 between the threshold, a quarter ulp, and the half ulp - the margin 2^-151 keeps under
+//     2^-150.  Zero weights behind the stop therefore give the same pdf, cdf, z_samples and z_fine bits, and the fine
+//     outputs keep theirs.  depth_c and acc_c add every weight, however small: a call that asks for either keeps 2^-151.
+constexpr double kStopZeroWeight = 0x1p-151;
+constexpr double kStopBelowPdfEps = 0x1p-42;
+static_assert(kStopBelowPdfEps <= 0.25 * float_ulp(kPdfEps),
+              "a weight below half an ulp of kPdfEps vanishes in w + kPdfEps; the stop keeps a factor 2 under that");
+static_assert(kStopZeroWeight <= kStopBelowPdfEps, "the early stop never waits longer than the exact one");
+
 // composite_weights over samples [0, k1) of the live rays, k1 > k0 the end of the window just evaluated: writes the weights
 // of [k0, k1), appends the rays that can still contribute behind k1 to live_out, finishes the others (zero weights behind
-// k1, depth / acc); live_out null = the last window, every ray is finished
+// k1, depth / acc); live_out null = the last window, every ray is finished.  stop: kStopZeroWeight or kStopBelowPdfEps
 int launch_composite_weights_window(int64_t n, int S, const float* sigma, const float* z, const float* rays, float* depth,
                                     float* acc, float* weights, const int* live_in, const int* count_in, int* live_out,
-                                    int* count_out, int k0, int k1, hipStream_t stream);
+                                    int* count_out, int k0, int k1, double stop, hipStream_t stream);
 int launch_composite_bwd(int64_t n, int S, const float* raw, const float* z, const float* rays, const float* g_rgb,
                          const float* g_depth, const float* g_acc, const float* g_w, float* g_raw, hipStream_t stream);
 int launch_composite_bwd_rays(int64_t n, int S, const float* raw, const float* z, const float* rays, const float* g_rgb,

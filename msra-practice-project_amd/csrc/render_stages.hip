@@ -209,7 +209,9 @@ __global__ __launch_bounds__(256) void composite_weights_kernel(int64_t n, int S
 
 // The weights form made resumable, for a coarse pass evaluated front to back in windows of samples (mi_render_rays): the
 // call behind the window [k0, k1) runs the passes over samples [0, k1) of every live ray under dispatch_G's G for S, a
-// sample >= k1 standing in as w = 0, and writes the weights of [k0, k1).  Then it decides the ray:
+// sample >= k1 standing in as w = 0, and writes the weights of [k0, k1).  Then it decides the ray against `stop`, the
+// caller's threshold (mi_common.h: kStopZeroWeight = 2^-151, or kStopBelowPdfEps = 2^-42 when sample_fine is the weights'
+// only reader - the argument why it then sees the same bits stands there).  With 2^-151:
 //   * D, the fp64 running product in front of sample k1, is <= 2^-151: every later sample's (float)(T * excl) is 0.0f
 //     whatever its sigma is.  The factors f = (1-alpha)+1e-10f are <= 1 (sigma >= 0, ascending depths), so the exact
 //     product can only fall; the scans' products of <= 2G factors differ from the exact ones by a relative 2^-45 at most,
@@ -227,7 +229,8 @@ template <int G>
 __global__ __launch_bounds__(256) void composite_weights_window_kernel(
     int64_t n, int S, const float* __restrict__ sigma, const float* __restrict__ z, const float* __restrict__ rays,
     float* __restrict__ depth, float* __restrict__ acc, float* __restrict__ weights, const int* __restrict__ live_in,
-    const int* __restrict__ count_in, int* __restrict__ live_out, int* __restrict__ count_out, int k0, int k1) {
+    const int* __restrict__ count_in, int* __restrict__ live_out, int* __restrict__ count_out, int k0, int k1,
+    double stop) {
     constexpr int kPerBlock = 256 / G * kWindowIter;
     __shared__ int s_keep[kPerBlock];
     __shared__ int s_n, s_base;
@@ -259,7 +262,7 @@ __global__ __launch_bounds__(256) void composite_weights_window_kernel(
                 if (live && k >= k0) weights[rc * S + k] = o.w;
             }
         }
-        const bool done = !live_out || D <= 0x1p-151;
+        const bool done = !live_out || D <= stop;
         if (live && !done && sub == 0) s_keep[atomicAdd(&s_n, 1)] = (int)rc;
         if (live && done)
             for (int k = k1 + sub; k < S; k += G) weights[rc * S + k] = 0.f;
@@ -492,14 +495,15 @@ __device__ __forceinline__ uint64_t sort_key(float v, int i) {
 
 // ---------------------------------------------------------------------------------------
 // The inverse-CDF draw of sample_pdf (render.py:27-56), one wave per ray, in two parts around cdf_like_cumsum.
-// pdf[j] = (w[j] + 1e-5) / sum_j (w[j] + 1e-5), j < nw: strided partial sums, xor reduction, one division per entry.
+// pdf[j] = (w[j] + kPdfEps) / sum_j (w[j] + kPdfEps), j < nw, kPdfEps = 1e-5 (mi_common.h): strided partial sums, xor
+// reduction, one division per entry.
 // ---------------------------------------------------------------------------------------
 __device__ __forceinline__ void normalise_pdf(const float* __restrict__ w, int nw, int lane, float* pdf) {
     float part = 0.f;
-    for (int j = lane; j < nw; j += 64) part += w[j] + 1e-5f;
+    for (int j = lane; j < nw; j += 64) part += w[j] + kPdfEps;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
-    for (int j = lane; j < nw; j += 64) pdf[j] = (w[j] + 1e-5f) / part;
+    for (int j = lane; j < nw; j += 64) pdf[j] = (w[j] + kPdfEps) / part;
 }
 
 // the sample at u: idx = #(cdf <= u) (searchsorted right=True on the ascending cdf [nb]), both neighbours clamped into
@@ -710,12 +714,13 @@ int launch_composite_weights(int64_t n, int S, const float* sigma, int sigma_str
 
 int launch_composite_weights_window(int64_t n, int S, const float* sigma, const float* z, const float* rays, float* depth,
                                     float* acc, float* weights, const int* live_in, const int* count_in, int* live_out,
-                                    int* count_out, int k0, int k1, hipStream_t stream) {
+                                    int* count_out, int k0, int k1, double stop, hipStream_t stream) {
     if (n <= 0) return 0;
     dispatch_G(S, [&](auto g) {                          // grid: the worst case, every ray live
         constexpr int G = decltype(g)::value;
         hipLaunchKernelGGL(composite_weights_window_kernel<G>, ray_grid<G>(n, kWindowIter), dim3(256), 0, stream, n, S,
-                           sigma, z, rays, depth, acc, weights, live_in, count_in, live_out, count_out, k0, k1);
+                           sigma, z, rays, depth, acc, weights, live_in, count_in, live_out, count_out, k0, k1,
+                           stop);
     });
     return check_launch("composite_weights_window");
 }

@@ -138,6 +138,16 @@ def checks(s):
         (r"deferred colour branch alternating on one MI355X\): ([\d ]+) / ([\d ]+) / ([\d ]+) rays/s before against ([\d ]+) / ([\d ]+) / ([\d ]+)\s+after, \+([\d.]+) % at least on every pair; the largest spread among runs of one build is ([\d.]+) %",
          [*r6["value"]["main"], *r6["value"]["branch"], r6["min_gain_pct"], r6["spread_pct"]]),
     ]
+    st = sampler_stop_sources()
+    design += [
+        (r"the (\d+) coarse field launches take ([\d.]+) ms against ([\d.]+) ms before and the (\d+) window composites ([\d.]+) ms against ([\d.]+) ms;\s+the fine pass is unchanged, (\d+) trunk-and-spill launches ([\d.]+) ms against ([\d.]+) ms and (\d+) colour launches ([\d.]+) ms against ([\d.]+) ms",
+         [st["window_calls"], st["window"]["branch"], st["window"]["parent"], st["wcomp_calls"], st["wcomp"]["branch"], st["wcomp"]["parent"],
+          st["spill_calls"], st["spill"]["branch"], st["spill"]["parent"], st["colour_calls"], st["colour"]["branch"], st["colour"]["parent"]]),
+        (r"its parent on one MI355X\): ([\d ]+) / ([\d ]+) / ([\d ]+) rays/s before against ([\d ]+) / ([\d ]+) / ([\d ]+)\s+after, \+([\d.]+) % at least on every pair; the largest spread among runs of one build is ([\d.]+) %",
+         [*st["value"]["main"], *st["value"]["branch"], st["min_gain_pct"], st["spread_pct"]]),
+        (r"windows of 4 give\s+([\d ]+) / ([\d ]+) / ([\d ]+) rays/s against ([\d ]+) / ([\d ]+) / ([\d ]+) with windows of 8",
+         [*st["value"]["w4"], *st["value"]["w8"]]),
+    ]
     return [("DESIGN.md", design), ("README.md", readme)]
 
 
@@ -186,6 +196,31 @@ def deferred_colour_sources():
             out["value"][r["build"]].append(r["line"]["value"])
     out["min_gain_pct"] = min(100 * (b / m - 1) for m, b in zip(out["value"]["main"], out["value"]["branch"]))
     out["spread_pct"] = max(100 * (max(v) / min(v) - 1) for v in out["value"].values())
+    return out
+
+
+def sampler_stop_sources():
+    """The 2^-42 stop of the windowed coarse pass: per-frame kernel totals of the parent's and the branch's
+    kernel statistics (rocprofv3, 4 frames each), the alternating bench pairs, and the window-4 against window-8 pairs."""
+    frames = 4
+    keys = {"window": "nerf_fwd_kernel<false, false, true, true, false>", "wcomp": "composite_weights_window_kernel",
+            "spill": "nerf_fwd_kernel<false, false, true, false, true>", "colour": "nerf_colour_kernel<false>"}
+    out = {k: {} for k in keys}
+    out["value"] = {"main": [], "branch": [], "w4": [], "w8": []}
+    for b in ("parent", "branch"):
+        with open(os.path.join(ROOT, f"profiles/sampler_stop_kernel_stats_{b}.csv")) as f:
+            stats = {r["Name"]: r for r in csv.DictReader(f)}
+        for name, key in keys.items():
+            rows = [r for k, r in stats.items() if key in k]
+            assert len(rows) == 1, (b, key, len(rows))
+            out[name + "_calls"] = int(rows[0]["Calls"]) // frames
+            out[name][b] = float(rows[0]["TotalDurationNs"]) / 1e6 / frames
+    for log in ("bench_pairs", "window_pairs"):
+        with open(os.path.join(ROOT, f"profiles/sampler_stop_{log}.log")) as f:
+            for r in (json.loads(ln) for ln in f if ln.startswith("{")):
+                out["value"][r["build"]].append(r["line"]["value"])
+    out["min_gain_pct"] = min(100 * (b / m - 1) for m, b in zip(out["value"]["main"], out["value"]["branch"]))
+    out["spread_pct"] = max(100 * (max(out["value"][b]) / min(out["value"][b]) - 1) for b in ("main", "branch"))
     return out
 
 
