@@ -415,8 +415,8 @@ int mi_marching_cubes_emit(const float* volume, int64_t nx, int64_t ny, int64_t 
 /* A per-scene occupancy grid is one bit per cell of a dims[0] x dims[1] x dims[2] grid over an axis-aligned box: which cells
  * can hold density.  Cell (ix, iy, iz) has index (ix * dims[1] + iy) * dims[2] + iz and lives in word index >> 5, bit
  * index & 31 of a uint32 array of mi_occupancy_words(dims) words.  dims: HOST, 3 ints, each >= 1, product below 2^31 (else
- * MI_EINVAL; the two size queries need no GPU).  These calls BUILD such a grid from a field; nothing in the library renders
- * with one yet.
+ * MI_EINVAL; the two size queries need no GPU).  These calls BUILD such a grid from a field; "rendering with a grid" below
+ * reads one.
  * mi_occupancy_cell_points: the supersample^3 (1..8 per axis) regular sub-sample points of cells [head, head + count) in
  * index order, points [count * supersample^3, 6] with a zero direction (sigma does not depend on it), ready for
  * mi_field_eval_points; with k = supersample, sub-sample (i, j, l) of the c-th cell of the range is row
@@ -432,6 +432,42 @@ int mi_occupancy_cell_points(const int* dims, const float* lo, const float* cell
                              float* points, void* stream);
 int mi_occupancy_pack(const float* sigma, const int* dims, int supersample, float threshold, int dilate, uint32_t* bits,
                       void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- rendering with a grid (inference; NeRF, SirenNeRF, TinyNeRF) ------------------------
+ *
+ * The one rule: with a grid, a sample whose point lies in an unoccupied cell, or outside the box [lo, hi), has
+ * raw = {0, 0, 0, 0} instead of the field's value; everything else is mi_render_rays.  The point is the fused forward's
+ * p = o + d * z, for this rule with a rounded multiply, then a rounded add; it is placed by t = (p - lo) * inv_cell (a
+ * rounded subtract, then a rounded multiply; lo, inv_cell: HOST, 3 floats each, inv_cell = cells per unit length), is inside
+ * iff 0 <= t < dims on every axis (a NaN is not inside), and its cell is floor(t).
+ *
+ * mi_occupancy_mark_rays: the samples of rays [n,2,3] at depths z [n,S] that are occupied, as point indices ray * S + k
+ * appended in any order to list [n*S] (device ints) and counted in the device int *count, which the call clears first.
+ * raw [n,S,4], when not NULL, gets the rows of the unoccupied samples zeroed; occupied rows are not touched.  n * S must
+ * fit an int (else MI_EINVAL, before any launch).
+ *
+ * mi_field_eval_rays_list: the field at the listed points alone - raw[list[e]] for e < *count has mi_field_eval_rays' bits,
+ * no other row is written.  list entries are point indices in [0, n*S); FiLM kinds: MI_EINVAL.  The launch is sized for
+ * n * S points from host values (no read-back; stream capture works).
+ *
+ * mi_render_rays_occupancy: mi_render_rays (one group, no film) under the rule above: sample_coarse, mark, list forward,
+ * composite, sample_fine, mark, list forward, composite.  The coarse outputs are optional as there.  evaluated: optional
+ * device int[2], the number of samples the coarse and the fine pass evaluated.  workspace: mi_render_workspace_bytes(n, Nc,
+ * Nf) + mi_render_occupancy_extra_bytes(n, Nc, Nf) bytes (one list of n * (Nc + Nf) ints, used by both passes, and the
+ * two counts); n * (Nc + Nf) must fit an int.  Both passes evaluate whole forwards of their listed points: the windowed
+ * sigma-only coarse pass, the deferred colour branch and the shared-field merge of mi_render_rays are not combined with a
+ * grid. */
+int mi_occupancy_mark_rays(const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell, const float* rays,
+                           const float* z, int64_t n, int n_samples, int* list, int* count, float* raw, void* stream);
+int mi_field_eval_rays_list(int kind, const float* packed, const float* rays, const float* z, int64_t n, int n_samples,
+                            const int* list, const int* count, float* raw, void* stream);
+int64_t mi_render_occupancy_extra_bytes(int64_t n, int n_coarse, int n_fine);
+int mi_render_rays_occupancy(int kind_coarse, const float* packed_coarse, int kind_fine, const float* packed_fine,
+                             const float* rays, int64_t n, float near_, float far_, int n_coarse, int n_fine,
+                             const float* z_lin, const float* u_lin, const float* t_rand, uint64_t seed, uint64_t ray0,
+                             const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell, float* rgb_c,
+                             float* depth_c, float* acc_c, float* rgb_f, float* depth_f, float* acc_f, int* evaluated,
+                             void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---- measurement hooks (bench.py) ---------------------------------------------------- */
 

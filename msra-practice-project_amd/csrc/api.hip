@@ -297,6 +297,103 @@ int mi_occupancy_pack(const float* sigma, const int* dims, int supersample, floa
     return launch_occupancy_pack(sigma, dims, supersample, threshold, dilate, bits, workspace, (hipStream_t)stream);
 }
 
+int mi_occupancy_mark_rays(const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell, const float* rays,
+                           const float* z, int64_t n, int n_samples, int* list, int* count, float* raw, void* stream) {
+    if (!occupancy_cells("mi_occupancy_mark_rays", dims)) return MI_EINVAL;
+    if (!bits || !lo || !inv_cell || !rays || !z || !list || !count) { set_error("mi_occupancy_mark_rays: null pointer argument"); return MI_EINVAL; }
+    if (n < 0 || n_samples < 1) { set_error("mi_occupancy_mark_rays: bad sizes (n >= 0, n_samples >= 1)"); return MI_EINVAL; }
+    if (n > 0x7fffffffLL / n_samples) {
+        set_error("mi_occupancy_mark_rays: n * n_samples = %lld * %d exceeds 2^31 - 1 (the list holds int point indices)", (long long)n, n_samples);
+        return MI_EINVAL;
+    }
+    return launch_occupancy_mark_rays(bits, dims, lo, inv_cell, rays, z, n, n_samples, list, count, raw, (hipStream_t)stream);
+}
+
+// the field at the points of a device-counted list: a mode-1 launch of one group of n rays x S samples
+static int eval_rays_list(int kind, const float* packed, const float* rays, const float* z, int64_t n, int S, const int* list,
+                          const int* count, float* raw, hipStream_t hs) {
+    MlpArgs args = {};
+    args.packed = packed; args.a = rays; args.z = z; args.out = raw;
+    args.points_per_group = n * S; args.rays_per_group = n; args.tiles_per_group = (n * S + 127) / 128;
+    args.n_samples = S; args.mode = 1; args.save_points = n * S; args.n_rays = n;
+    return launch_mlp_list(kind, args, list, count, hs);
+}
+
+int mi_field_eval_rays_list(int kind, const float* packed, const float* rays, const float* z, int64_t n, int n_samples,
+                            const int* list, const int* count, float* raw, void* stream) {
+    if (bad_kind(kind)) return MI_EINVAL;
+    if (!has_list_kernel(kind)) { set_error("mi_field_eval_rays_list: kind %d has no list-driven forward (NeRF, SirenNeRF, TinyNeRF have)", kind); return MI_EINVAL; }
+    if (!packed || !rays || !z || !list || !count || !raw) { set_error("mi_field_eval_rays_list: null pointer argument"); return MI_EINVAL; }
+    if (n < 0 || n_samples < 1) { set_error("mi_field_eval_rays_list: bad sizes (n >= 0, n_samples >= 1)"); return MI_EINVAL; }
+    if (n > 0x7fffffffLL / n_samples) {
+        set_error("mi_field_eval_rays_list: n * n_samples = %lld * %d exceeds 2^31 - 1 (the list holds int point indices)", (long long)n, n_samples);
+        return MI_EINVAL;
+    }
+    if (n == 0) return MI_OK;
+    return eval_rays_list(kind, packed, rays, z, n, n_samples, list, count, raw, (hipStream_t)stream);
+}
+
+// the region behind mi_render_workspace_bytes that rendering with a grid adds: one list [n * S] of ints, then the two counts
+static int64_t occupancy_list_floats(int64_t n, int S) { return align64(n * S); }
+int64_t mi_render_occupancy_extra_bytes(int64_t n, int n_coarse, int n_fine) {
+    if (n <= 0 || n_coarse < 1 || n_fine < 0) return 0;
+    return (occupancy_list_floats(n, n_coarse + n_fine) + align64(2)) * (int64_t)sizeof(float);
+}
+
+int mi_render_rays_occupancy(int kind_coarse, const float* packed_coarse, int kind_fine, const float* packed_fine,
+                             const float* rays, int64_t n, float near_, float far_, int n_coarse, int n_fine,
+                             const float* z_lin, const float* u_lin, const float* t_rand, uint64_t seed, uint64_t ray0,
+                             const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell, float* rgb_c,
+                             float* depth_c, float* acc_c, float* rgb_f, float* depth_f, float* acc_f, int* evaluated,
+                             void* workspace, int64_t workspace_bytes, void* stream) {
+    const char* fn = "mi_render_rays_occupancy";
+    if (n < 0 || n_coarse < 3 || n_fine < 0) { set_error("%s: bad sizes (n >= 0, Nc >= 3, Nf >= 0)", fn); return MI_EINVAL; }
+    if (bad_kind(kind_coarse) || bad_kind(kind_fine)) return MI_EINVAL;
+    if (!has_list_kernel(kind_coarse) || !has_list_kernel(kind_fine)) {
+        set_error("%s: kinds %d / %d: rendering with a grid is built for NeRF, SirenNeRF and TinyNeRF, not for FiLM kinds", fn, kind_coarse, kind_fine);
+        return MI_EINVAL;
+    }
+    if (!occupancy_cells(fn, dims)) return MI_EINVAL;
+    if (!packed_coarse || !packed_fine || !rays || !bits || !lo || !inv_cell || !workspace || (rgb_c && (!depth_c || !acc_c)) ||
+        !rgb_f || !depth_f || !acc_f) {
+        set_error("%s: null pointer argument", fn);
+        return MI_EINVAL;
+    }
+    const int S = n_coarse + n_fine;
+    if (n > 0x7fffffffLL / S) {
+        set_error("%s: n * (Nc + Nf) = %lld * %d exceeds 2^31 - 1 (the list holds int point indices)", fn, (long long)n, S);
+        return MI_EINVAL;
+    }
+    if (n == 0) return MI_OK;                                  // no rays: nothing to launch, no buffer is touched
+    const RenderWorkspace layout(n, n_coarse, n_fine);
+    const int64_t base_bytes = layout.base_bytes(), need = base_bytes + mi_render_occupancy_extra_bytes(n, n_coarse, n_fine);
+    if (workspace_bytes < need) {
+        set_error("%s: workspace of %lld bytes, mi_render_workspace_bytes + mi_render_occupancy_extra_bytes say %lld", fn,
+                  (long long)workspace_bytes, (long long)need);
+        return MI_EINVAL;
+    }
+    const RenderWorkspace::Regions ws = layout.carve(workspace);
+    int* list = (int*)((char*)workspace + base_bytes);
+    int* counts = list + occupancy_list_floats(n, S);
+    hipStream_t hs = (hipStream_t)stream;
+    int rc;
+    if ((rc = mi_sample_coarse(n, near_, far_, n_coarse, z_lin, t_rand, seed, ray0, ws.z_c, stream))) return rc;
+    if ((rc = launch_occupancy_mark_rays(bits, dims, lo, inv_cell, rays, ws.z_c, n, n_coarse, list, counts, ws.raw_c, hs))) return rc;
+    if ((rc = eval_rays_list(kind_coarse, packed_coarse, rays, ws.z_c, n, n_coarse, list, counts, ws.raw_c, hs))) return rc;
+    if (rgb_c) rc = mi_composite(n, n_coarse, ws.raw_c, ws.z_c, rays, rgb_c, depth_c, acc_c, ws.w_c, stream);
+    else rc = launch_composite_weights(n, n_coarse, ws.raw_c + 3, 4, ws.z_c, rays, depth_c, acc_c, ws.w_c, hs);   // raw's sigma channel
+    if (rc) return rc;
+    if ((rc = mi_sample_fine(n, near_, far_, n_coarse, n_fine, z_lin, u_lin, ws.z_c, ws.w_c, nullptr, ws.z_f, stream))) return rc;
+    if ((rc = launch_occupancy_mark_rays(bits, dims, lo, inv_cell, rays, ws.z_f, n, S, list, counts + 1, ws.raw_f, hs))) return rc;
+    if ((rc = eval_rays_list(kind_fine, packed_fine, rays, ws.z_f, n, S, list, counts + 1, ws.raw_f, hs))) return rc;
+    if ((rc = mi_composite(n, S, ws.raw_f, ws.z_f, rays, rgb_f, depth_f, acc_f, nullptr, stream))) return rc;
+    if (evaluated && hipMemcpyAsync(evaluated, counts, 2 * sizeof(int), hipMemcpyDeviceToDevice, hs) != hipSuccess) {
+        set_error("%s: copy of the evaluated counts failed", fn);
+        return MI_EHIP;
+    }
+    return MI_OK;
+}
+
 int mi_gen_rays(int width, int height, double focal, const float* c2w_host, int64_t ray0, int64_t n, float* rays,
                 int compute_f64, void* stream) {
     if (width <= 0 || height <= 0 || !c2w_host || !rays || ray0 < 0 || n < 0 || ray0 + n > (int64_t)width * height) {

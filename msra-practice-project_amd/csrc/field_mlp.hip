@@ -38,12 +38,15 @@ namespace mi {
 // ending.  It writes {0, 0, 0, sigma} to out [M][4] and appends every point with sigma > 0 - its H8 row and its index - to
 // the live list a.defer (spill_live); nerf_colour_kernel below then runs the colour branch over that list alone.  Only this
 // instance's argument block carries the list: every other instance takes MlpArgs as before.
+// LIST = the inference instance over a device-counted list of points (load_list_point: rendering with an occupancy grid): a
+// block whose tile lies past the count returns before it issues any LDS DMA; behind the loader it is the inference instance.
 struct DeferMlpArgs : MlpArgs { DeferArgs defer; };
-template <bool TINY, bool SAVE, bool SIGMA_ONLY, bool WINDOW = false, bool SPILL = false>
+template <bool TINY, bool SAVE, bool SIGMA_ONLY, bool WINDOW = false, bool SPILL = false, bool LIST = false>
 __global__ __launch_bounds__(256, 1) void nerf_fwd_kernel(std::conditional_t<SPILL, DeferMlpArgs, MlpArgs> a) {
     static_assert(!(SAVE && SIGMA_ONLY), "the training forward needs the colour branch");
     static_assert(!WINDOW || SIGMA_ONLY, "windows exist for the sigma-only coarse pass");
     static_assert(!SPILL || (SIGMA_ONLY && !WINDOW), "the spill is an ending of the sigma-only instance");
+    static_assert(!LIST || (!SAVE && !SIGMA_ONLY && !WINDOW && !SPILL), "the list drives the inference instance");
     constexpr FieldKind K = kFieldKinds[TINY ? MI_FIELD_TINY_NERF : MI_FIELD_NERF];
     // Forward segment i is layer i's (field_layout.h): T - 1 the trunk's last, with the sigma head's pieces; D the dir layer,
     // with the rgb head's.  A layer issues, behind its own K blocks, the aux pieces and first K blocks of the segment after it.
@@ -57,12 +60,16 @@ __global__ __launch_bounds__(256, 1) void nerf_fwd_kernel(std::conditional_t<SPI
     constexpr int kRgbRow = F.seg[D].piece(AUX_WROW, K.rgb_head()), kRgbBias = F.seg[D].piece(AUX_SCALARS, K.rgb_head());
     static_assert(kSigmaRow >= 0 && kSigmaBias >= 0 && kRgbRow >= 0 && kRgbBias >= 0, "the heads' pieces ride with the layers in front of them");
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int64_t group = WINDOW ? 0 : blockIdx.x / a.tiles_per_group;
-    const int64_t tile = WINDOW ? blockIdx.x : blockIdx.x % a.tiles_per_group;
+    const int64_t group = WINDOW || LIST ? 0 : blockIdx.x / a.tiles_per_group;
+    const int64_t tile = WINDOW || LIST ? blockIdx.x : blockIdx.x % a.tiles_per_group;
     int64_t live = 0;
     if constexpr (WINDOW) {
         live = window_live_count(a);
         if (tile * (128 >> a.win_log2) >= live) return;
+    }
+    if constexpr (LIST) {
+        live = window_live_count(a);
+        if (tile * 128 >= live) return;
     }
     Ctx c = make_ctx(smem, a, group);
     MI_STAMP(a, 0);
@@ -70,6 +77,7 @@ __global__ __launch_bounds__(256, 1) void nerf_fwd_kernel(std::conditional_t<SPI
 
     PointIn pt;
     if constexpr (WINDOW) pt = load_window_point(a, tile, live, c.wave * 32 + (c.lane & 31));
+    else if constexpr (LIST) pt = load_list_point(a, tile, live, c.wave * 32 + (c.lane & 31));
     else pt = load_point(a.mode, a.a, a.z, group, a.points_per_group, a.rays_per_group, a.n_samples,
                          tile * 128 + c.wave * 32 + (c.lane & 31));
     constexpr int kPeBlocks = 2, kDirBlocks = 1, kXBlocks = 8;      // K blocks the B-operand selectors below serve
@@ -255,10 +263,11 @@ __global__ __launch_bounds__(256, 1) void nerf_colour_kernel(DeferMlpArgs a) {
 // =========================================================================================
 // SirenNeRF (nerf/nerf.py:153-170): sin(30 * linear) layers on raw xyz / dir
 // =========================================================================================
-template <bool SAVE, bool SIGMA_ONLY, bool WINDOW = false>
+template <bool SAVE, bool SIGMA_ONLY, bool WINDOW = false, bool LIST = false>
 __global__ __launch_bounds__(256, 1) void siren_fwd_kernel(MlpArgs a) {
     static_assert(!(SAVE && SIGMA_ONLY), "the training forward needs the colour branch");
     static_assert(!WINDOW || SIGMA_ONLY, "windows exist for the sigma-only coarse pass");
+    static_assert(!LIST || (!SAVE && !SIGMA_ONLY && !WINDOW), "the list drives the inference instance");
     constexpr FieldKind K = kFieldKinds[MI_FIELD_SIREN_NERF];
     // forward segment i is layer i's, as in nerf_fwd_kernel; layer 0 is K = 3 (VALU): its segment has no K blocks
     constexpr Segments F = segments(K.fwd);
@@ -276,18 +285,23 @@ __global__ __launch_bounds__(256, 1) void siren_fwd_kernel(MlpArgs a) {
                       F.blocks(6) == kXBlocks && F.blocks(7) == kXBlocks && F.blocks(8) == kXBlocks && F.blocks(9) == kXBlocks,
                   "the loop's segments have one shape, and every MFMA layer's K blocks are X's");
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int64_t group = WINDOW ? 0 : blockIdx.x / a.tiles_per_group;
-    const int64_t tile = WINDOW ? blockIdx.x : blockIdx.x % a.tiles_per_group;
+    const int64_t group = WINDOW || LIST ? 0 : blockIdx.x / a.tiles_per_group;
+    const int64_t tile = WINDOW || LIST ? blockIdx.x : blockIdx.x % a.tiles_per_group;
     int64_t live = 0;
     if constexpr (WINDOW) {                        // as in nerf_fwd_kernel
         live = window_live_count(a);
         if (tile * (128 >> a.win_log2) >= live) return;
+    }
+    if constexpr (LIST) {
+        live = window_live_count(a);
+        if (tile * 128 >= live) return;
     }
     Ctx c = make_ctx(smem, a, group);
     issue_first_stage<F.aux(0), F.block_pieces(0), false>(c, 0);   // layers_pos[0]: bias + 3 weight columns (K = 3, VALU)
 
     PointIn pt;
     if constexpr (WINDOW) pt = load_window_point(a, tile, live, c.wave * 32 + (c.lane & 31));
+    else if constexpr (LIST) pt = load_list_point(a, tile, live, c.wave * 32 + (c.lane & 31));
     else pt = load_point(a.mode, a.a, a.z, group, a.points_per_group, a.rays_per_group, a.n_samples,
                          tile * 128 + c.wave * 32 + (c.lane & 31));
     f32x16 X[kXBlocks], acc[8];
@@ -438,30 +452,34 @@ __global__ __launch_bounds__(256, 1) void film_fwd_kernel(MlpArgs a) {
 // One table of instances, [row][variant].  Rows: the fixed kinds, then the run-time-depth FiLM instances without / with the
 // direction (MI_FIELD_FILM_DEPTH kinds other than depth 8, which IS kinds 2 / 3).  Variants: the inference, the training
 // (layer inputs saved), the sigma-only and the windowed sigma-only instance of the kind's kernel, then the two kernels of the
-// deferred colour branch (NeRF, TinyNeRF): the trunk-and-spill instance and the colour-branch kernel.
+// deferred colour branch (NeRF, TinyNeRF): the trunk-and-spill instance and the colour-branch kernel, then the list-driven
+// inference instance (NeRF, SirenNeRF, TinyNeRF: the kinds an occupancy grid exists for).
 // The FiLM kinds have no sigma-only instance (their caller, pi_GAN, renders both passes with one field and needs the
 // coarse colours for the merge): has_sigma_only_kernel() is false for them.
-enum FwdVariant : int { FWD_INFER = 0, FWD_SAVE, FWD_SIGMA, FWD_SIGMA_WINDOW, FWD_SPILL, FWD_COLOUR, FWD_VARIANTS };
+enum FwdVariant : int { FWD_INFER = 0, FWD_SAVE, FWD_SIGMA, FWD_SIGMA_WINDOW, FWD_SPILL, FWD_COLOUR, FWD_LIST, FWD_VARIANTS };
 constexpr int kFilmDepthRow = MI_FIELD_KINDS;      // + use_dir
 static const void* const kKernels[MI_FIELD_KINDS + 2][FWD_VARIANTS] = {
     // MI_FIELD_NERF
     {(const void*)nerf_fwd_kernel<false, false, false>, (const void*)nerf_fwd_kernel<false, true, false>,
      (const void*)nerf_fwd_kernel<false, false, true>, (const void*)nerf_fwd_kernel<false, false, true, true>,
-     (const void*)nerf_fwd_kernel<false, false, true, false, true>, (const void*)nerf_colour_kernel<false>},
+     (const void*)nerf_fwd_kernel<false, false, true, false, true>, (const void*)nerf_colour_kernel<false>,
+     (const void*)nerf_fwd_kernel<false, false, false, false, false, true>},
     // MI_FIELD_SIREN_NERF
     {(const void*)siren_fwd_kernel<false, false>, (const void*)siren_fwd_kernel<true, false>, (const void*)siren_fwd_kernel<false, true>,
-     (const void*)siren_fwd_kernel<false, true, true>},
+     (const void*)siren_fwd_kernel<false, true, true>, nullptr, nullptr, (const void*)siren_fwd_kernel<false, false, false, true>},
     {(const void*)film_fwd_kernel<true, false>, (const void*)film_fwd_kernel<true, true>},                // MI_FIELD_FILM_SIREN_NERF
     {(const void*)film_fwd_kernel<false, false>, (const void*)film_fwd_kernel<false, true>},              // ..._NODIR
     // MI_FIELD_TINY_NERF
     {(const void*)nerf_fwd_kernel<true, false, false>, (const void*)nerf_fwd_kernel<true, true, false>,
      (const void*)nerf_fwd_kernel<true, false, true>, (const void*)nerf_fwd_kernel<true, false, true, true>,
-     (const void*)nerf_fwd_kernel<true, false, true, false, true>, (const void*)nerf_colour_kernel<true>},
+     (const void*)nerf_fwd_kernel<true, false, true, false, true>, (const void*)nerf_colour_kernel<true>,
+     (const void*)nerf_fwd_kernel<true, false, false, false, false, true>},
     {(const void*)film_fwd_kernel<false, false, true>, (const void*)film_fwd_kernel<false, true, true>},  // any depth, no dir
     {(const void*)film_fwd_kernel<true, false, true>, (const void*)film_fwd_kernel<true, true, true>}};   // any depth, dir
 
 bool has_deferred_colour_kernels(int kind) { return kind >= 0 && kind < MI_FIELD_KINDS && kKernels[kind][FWD_SPILL] && kKernels[kind][FWD_COLOUR]; }
 bool has_sigma_only_kernel(int kind) { return kind >= 0 && kind < MI_FIELD_KINDS && kKernels[kind][FWD_SIGMA]; }
+bool has_list_kernel(int kind) { return kind >= 0 && kind < MI_FIELD_KINDS && kKernels[kind][FWD_LIST]; }
 
 // Every instance runs 256 threads on 148 KiB of dynamic LDS: the per-kernel limit is raised once per device (host-side
 // attribute, no device work).
@@ -515,6 +533,21 @@ int launch_mlp_window(int kind_in, const MlpArgs& a, hipStream_t stream) {
     if (blocks <= 0) return 0;
     if (blocks > 0x7fffffffLL) { set_error("too many point tiles (%lld)", (long long)blocks); return -1; }
     return launch_instance(kKernels[kind][FWD_SIGMA_WINDOW], blocks, const_cast<MlpArgs*>(&a), stream, "field_mlp_fwd_window");
+}
+
+int launch_mlp_list(int kind_in, const MlpArgs& a_in, const int* list, const int* count, hipStream_t stream) {
+    const int kind = canon_kind(kind_in);
+    if (bad_kind(kind)) return -1;
+    if (!has_list_kernel(kind) || a_in.save || a_in.film || a_in.mode != 1 || a_in.n_samples < 1 || !list || !count ||
+        a_in.points_per_group < 1 || a_in.points_per_group > 0x7fffffffLL ||
+        a_in.points_per_group != a_in.rays_per_group * a_in.n_samples) {
+        set_error("kind %d: bad list-driven launch", kind);
+        return -1;
+    }
+    MlpArgs a = a_in;
+    a.live_rays = list; a.live_count = count;
+    const int64_t blocks = (a.points_per_group + 127) / 128;           // worst case: every point listed
+    return launch_instance(kKernels[kind][FWD_LIST], blocks, &a, stream, "field_mlp_fwd_list");
 }
 
 // compute units of the current device, asked once per device ordinal (0 and the error set if the query fails)

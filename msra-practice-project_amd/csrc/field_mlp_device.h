@@ -666,6 +666,26 @@ __device__ __forceinline__ int64_t window_live_count(const MlpArgs& a) {
     return __builtin_amdgcn_readfirstlane(__hip_atomic_load(a.live_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
 }
 
+// List-driven point source of the inference forward (launch_mlp_list): entry e = tile * 128 + i of the device-counted list
+// a.live_rays names point p = list[e] of a mode-1 launch of one group; its row stays p, its ray p / S.  The point and the view
+// direction come from load_point itself, called with the launch's run-time a.mode (1) as the inference instance calls it, so
+// the list cannot change a point's bits - except that the norm's contraction is not left to the compiler: behind this loader
+// its own choice was two fmas, dir_norm's one ulp on one ray in twenty, and the rows lost mi_field_eval_rays' bits.  The view
+// direction is therefore formed again with dir_norm, as nerf_colour_kernel forms it (tests/test_gpu_occupancy_render.py
+// holds the rows equal bit for bit).  Entries at and past `count` (uniform, > the tile's first entry) are clamped like
+// load_window_point's and masked on the store.
+__device__ __forceinline__ PointIn load_list_point(const MlpArgs& a, int64_t tile, int64_t count, int i) {
+    const int64_t entry = tile * 128 + i;
+    const int64_t ec = entry < count ? entry : count - 1;
+    PointIn o = load_point(a.mode, a.a, a.z, 0, a.points_per_group, a.rays_per_group, a.n_samples, (int64_t)a.live_rays[ec]);
+    const float* r = a.a + (o.p / a.n_samples) * 6;
+    const float d0 = r[3], d1 = r[4], d2 = r[5];
+    const float nrm = dir_norm(d0, d1, d2);
+    o.dx = d0 / nrm; o.dy = d1 / nrm; o.dz = d2 / nrm;
+    o.valid = o.valid && entry < count;
+    return o;
+}
+
 __device__ __forceinline__ Ctx make_ctx_raw(float* smem, const float* packed, const float* film_group) {
     Ctx c;
     c.smem = smem;

@@ -123,6 +123,7 @@ struct MlpArgs {
     unsigned long long* stamps;   // diagnostic build (-DMI_PROFILE_STAMPS) only: [block][128] s_memtime values
     int film_depth;         // FiLM kinds: hidden_layers (wave-uniform; the run-time-depth instances read it), else 0
     // windowed sigma-only forward (launch_mlp_window): samples [win_k0, win_k0 + 2^win_log2) of the rays in a live list
+    // (the list-driven forward, launch_mlp_list, keeps its list of POINT indices and that list's count in the same two fields)
     const int* live_rays;   // [live count] ray indices, any order; null = rays 0..n_rays-1
     const int* live_count;  // device count of live_rays; null = n_rays
     int64_t n_rays;         // rays of the call (the worst-case live count the grid is sized for)
@@ -168,6 +169,17 @@ int launch_occupancy_cell_points(const int* dims, const float* lo, const float* 
 int64_t occupancy_pack_workspace_bytes(int64_t cells, int dilate);
 int launch_occupancy_pack(const float* sigma, const int* dims, int k, float threshold, int dilate, uint32_t* bits,
                           void* workspace, hipStream_t stream);
+// ... and reading one: the samples of n rays x S depths that lie in occupied cells, appended to `list` (point indices ray * S + k,
+// any order) and counted in the device int `count`, which the call clears; the raw rows [n*S][4] of the others are zeroed
+// (raw may be null).  n * S fits an int (the caller checks).
+int launch_occupancy_mark_rays(const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell, const float* rays,
+                               const float* z, int64_t n, int S, int* list, int* count, float* raw, hipStream_t stream);
+// The inference forward over a device-counted list of point indices (NeRF, SirenNeRF, TinyNeRF: has_list_kernel): a mode-1
+// launch of one group (a.a = rays, a.z and a.out [rays_per_group * n_samples]) that evaluates point list[e] for every e below
+// *count and writes its row a.out[list[e]] alone.  The grid covers every point of the launch (host values, no read-back);
+// blocks past the count return at once.
+bool has_list_kernel(int kind);
+int launch_mlp_list(int kind, const MlpArgs& a, const int* list, const int* count, hipStream_t stream);
 int64_t bwd_partial_floats(int64_t P);
 int64_t film_partial_floats(int64_t n_groups, int64_t points_per_group);
 int64_t bwd_partial_floats_kind(int kind, int64_t P);                      // ... of any kind (deeper FiLM kinds need more)

@@ -3,6 +3,7 @@
 //
 //   occupancy_cell_points_kernel  k^3 regular sub-sample points per cell, [count k^3, 6] rows for mi_field_eval_points
 //   occupancy_threshold / dilate / pack kernels   sigma at those points -> one byte per cell, dilated, packed into words
+//   occupancy_mark_rays_kernel    reading a grid: the samples of a render pass that lie in occupied cells, as a device-counted list
 //
 // Small kernels next to the field evaluations between them (cells k^3 MLP points).  Compiled with -ffp-contract=off: a
 // sub-sample point is a chain of separately rounded operations, which a test restates in torch.
@@ -106,6 +107,84 @@ int launch_occupancy_pack(const float* sigma, const int* dims, int k, float thre
     }
     hipLaunchKernelGGL(occupancy_pack_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, stream, buf[cur], cells, words, bits);
     return check_launch("occupancy_pack");
+}
+
+// ---- reading a grid: which samples of a pass are evaluated (mi_occupancy_mark_rays) ---------------------------------------------
+struct MarkArgs { int dims[3]; float lo[3], inv_cell[3]; };
+
+// The rule every layer of rendering with a grid is tested against.  The point is the one the fused forward evaluates
+// (field_mlp_device.h: load_point, p = o + d z, a multiply and an add), placed by t = (p - lo) * inv_cell (a subtract and a
+// multiply); inside iff 0 <= t < G on every axis, so a NaN is not inside; its cell is floor(t).
+__device__ __forceinline__ bool point_occupied(const MarkArgs& g, const uint32_t* __restrict__ bits, const float* __restrict__ rays,
+                                               const float* __restrict__ z, int64_t p, int S) {
+    const float* r = rays + (p / S) * 6;
+    const float zz = z[p];
+    float t[3];
+    bool inside = true;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        const float x = __fadd_rn(r[d], __fmul_rn(r[3 + d], zz));
+        t[d] = __fmul_rn(__fsub_rn(x, g.lo[d]), g.inv_cell[d]);
+        inside = inside && t[d] >= 0.f && t[d] < (float)g.dims[d];
+    }
+    if (!inside) return false;
+    const int bit = ((int)floorf(t[0]) * g.dims[1] + (int)floorf(t[1])) * g.dims[2] + (int)floorf(t[2]);
+    return (bits[bit >> 5] >> (bit & 31)) & 1u;
+}
+
+// One thread per point, kMarkPerThread rounds of 256 points per workgroup.  A frame's 10^8 points must not queue on the one
+// counter wave by wave, so a workgroup compacts its 4096 points itself: every round's ballot gives a per-wave count in LDS,
+// one thread turns the 64 counts into exclusive offsets and takes ONE atomic for the workgroup's slots, and a point's slot is
+// the workgroup's base + its (round, wave) offset + the occupied lanes below it.  Unoccupied points get their raw row zeroed
+// (a vector store); occupied rows are not touched.  The list has room for every point, so it cannot overflow.
+constexpr int kMarkPerThread = 16;
+constexpr int kMarkBlock = 256 * kMarkPerThread;
+
+__global__ __launch_bounds__(256) void occupancy_mark_rays_kernel(MarkArgs g, const uint32_t* __restrict__ bits,
+                                                                  const float* __restrict__ rays, const float* __restrict__ z,
+                                                                  int64_t total, int S, int* __restrict__ list, int* count,
+                                                                  float* __restrict__ raw) {
+    __shared__ int offs[kMarkPerThread * 4];
+    __shared__ int base_s;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t p0 = (int64_t)blockIdx.x * kMarkBlock + threadIdx.x;
+    uint32_t mine = 0;                                          // bit `it`: this thread's point of round `it` is occupied
+    for (int it = 0; it < kMarkPerThread; ++it) {
+        const int64_t p = p0 + it * 256;
+        bool occ = false;
+        if (p < total) {
+            occ = point_occupied(g, bits, rays, z, p, S);
+            if (!occ && raw) reinterpret_cast<float4*>(raw)[p] = float4{0.f, 0.f, 0.f, 0.f};
+        }
+        const uint64_t b = __ballot(occ);
+        if (lane == 0) offs[it * 4 + wave] = __popcll(b);
+        mine |= (uint32_t)occ << it;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int sum = 0;
+        for (int i = 0; i < kMarkPerThread * 4; ++i) { const int c = offs[i]; offs[i] = sum; sum += c; }
+        base_s = sum ? __hip_atomic_fetch_add(count, sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+    }
+    __syncthreads();
+    const int base = base_s;
+    for (int it = 0; it < kMarkPerThread; ++it) {
+        const bool occ = (mine >> it) & 1u;
+        const uint64_t b = __ballot(occ);
+        if (occ) list[base + offs[it * 4 + wave] + __popcll(b & ((1ull << lane) - 1))] = (int)(p0 + it * 256);
+    }
+}
+
+int launch_occupancy_mark_rays(const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell, const float* rays,
+                               const float* z, int64_t n, int S, int* list, int* count, float* raw, hipStream_t stream) {
+    if (hipMemsetAsync(count, 0, sizeof(int), stream) != hipSuccess) { set_error("occupancy mark: hipMemsetAsync failed"); return -2; }
+    const int64_t total = n * S;
+    if (total <= 0) return 0;
+    MarkArgs g;
+    for (int d = 0; d < 3; ++d) { g.dims[d] = dims[d]; g.lo[d] = lo[d]; g.inv_cell[d] = inv_cell[d]; }
+    hipLaunchKernelGGL(occupancy_mark_rays_kernel, dim3((unsigned)((total + kMarkBlock - 1) / kMarkBlock)), dim3(256), 0, stream, g,
+                       bits, rays, z, total, S, list, count, raw);
+    return check_launch("occupancy_mark_rays");
 }
 
 }  // namespace mi

@@ -99,6 +99,13 @@ SIGNATURES = {
     "mi_occupancy_cell_points": (_int, [ctypes.POINTER(_int), ctypes.POINTER(_f32), ctypes.POINTER(_f32), _int, _i64, _i64,
                                         _vp, _vp]),
     "mi_occupancy_pack": (_int, [_vp, ctypes.POINTER(_int), _int, _f32, _int, _vp, _vp, _i64, _vp]),
+    "mi_occupancy_mark_rays": (_int, [_vp, ctypes.POINTER(_int), ctypes.POINTER(_f32), ctypes.POINTER(_f32), _vp, _vp, _i64,
+                                      _int, _vp, _vp, _vp, _vp]),
+    "mi_field_eval_rays_list": (_int, [_int, _vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp]),
+    "mi_render_occupancy_extra_bytes": (_i64, [_i64, _int, _int]),
+    "mi_render_rays_occupancy": (_int, [_int, _vp, _int, _vp, _vp, _i64, _f32, _f32, _int, _int, _vp, _vp, _vp, _u64, _u64,
+                                        _vp, ctypes.POINTER(_int), ctypes.POINTER(_f32), ctypes.POINTER(_f32), _vp, _vp, _vp,
+                                        _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
 }
 
 ABI_VERSION = 4      # include/mi_render.h as of this binding (mi_abi_version() of the library must equal it)

@@ -2,10 +2,15 @@
 
     grid = OccupancyGrid.from_field(fine_model, lo=(-1.5,) * 3, hi=(1.5,) * 3, resolution=128)
     grid.occupied_fraction(); grid.to_dense()
+    rgb, depth, acc = render_image(W, H, focal, pose, near, far, coarse_model, fine_model, 64, 128, grid=grid)
 
 `from_field` builds the grid on the device from a field's sigma (mi_occupancy_cell_points, the fused field kernel,
 mi_occupancy_pack; include/mi_render.h), `from_dense` / `to_dense` go through bool [Gx,Gy,Gz] arrays in numpy.
-For the kinds without FiLM (NeRF, SirenNeRF, TinyNeRF).  This module builds and holds grids; the renderer does not use them yet.
+For the kinds without FiLM (NeRF, SirenNeRF, TinyNeRF).  This module builds and holds grids; the renderer reads them through the
+keyword `grid=` of render_rays / render_image / render_image_tensor / render_video (inference only): a sample whose point
+o + d * z lies in an unoccupied cell, or outside [lo, hi), counts as raw = 0 and is not evaluated (ops.render_rays_occupancy,
+mi_render_rays_occupancy).  A grid that misses cells where the field has density therefore changes the picture: build it with
+a threshold, supersampling and dilation that suit the field.
 """
 from __future__ import annotations
 

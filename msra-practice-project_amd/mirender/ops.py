@@ -276,3 +276,47 @@ def render_rays_fused(pf_c: PackedField, pf_f: PackedField, rays: torch.Tensor, 
     if guard is not None and not bool((guard == 0xA5).all()):
         raise _lib.MiRenderError("mi_render_rays wrote past mi_render_workspace_bytes")
     return tuple(outs)
+
+
+def render_rays_occupancy(pf_c: PackedField, pf_f: PackedField, rays: torch.Tensor, near: float, far: float,
+                          n_coarse: int, n_fine: int, grid, t_rand=None, seed: int = 0, ray0: int = 0,
+                          coarse_outputs: bool = True):
+    """render_rays with an occupancy grid (mi_render_rays_occupancy): a sample whose point lies in an unoccupied cell of
+    `grid` (mirender.occupancy.OccupancyGrid), or outside its box, counts as raw = 0 and is not evaluated; everything else is
+    render_rays_fused.  Returns (the 6-tuple, counts): counts is a device int32 [2], the samples the coarse and the fine pass
+    evaluated.  coarse_outputs=False: the coarse slots come back as None."""
+    from .occupancy import _f3, _i3
+    lib = _lib.load()
+    dev = pf_c.device
+    if is_film(pf_c.kind) or is_film(pf_f.kind):
+        raise _lib.MiRenderError("rendering with an occupancy grid is not built for FiLM fields")
+    rays = _f32c(rays, dev).reshape(-1, 2, 3)
+    n = rays.shape[0]
+    if t_rand is not None:
+        t_rand = _f32c(t_rand, dev)
+        if tuple(t_rand.shape) != (n, n_coarse):
+            raise _lib.MiRenderError(f"t_rand must be [{n},{n_coarse}]")
+    outs = [torch.empty(s, dtype=torch.float32, device=dev) if coarse_outputs or k >= 3 else None
+            for k, s in enumerate(((n, 3), (n,), (n,), (n, 3), (n,), (n,)))]
+    counts = torch.zeros(2, dtype=torch.int32, device=dev)
+    ws_bytes = lib.mi_render_workspace_bytes(n, n_coarse, n_fine) + lib.mi_render_occupancy_extra_bytes(n, n_coarse, n_fine)
+    guard = None
+    if os.environ.get("MI_DEBUG_GUARDS") == "1":       # sentinel zone behind the workspace, checked after the call
+        ws = torch.empty(int(ws_bytes) + 16384, dtype=torch.uint8, device=dev)
+        ws[int(ws_bytes):] = 0xA5
+        guard = ws[int(ws_bytes):]
+    else:
+        ws = _Workspace.get(dev, ws_bytes)
+    zl = linspace_table(near, far, n_coarse, dev)
+    ul = linspace_table(0.0, 1.0, n_fine, dev)
+    (_, pdims), (_, plo), (_, pinv) = _i3(grid.dims), _f3(grid.lo), _f3(grid.inv_cell)
+    with torch.cuda.device(dev):
+        _lib.check(lib.mi_render_rays_occupancy(pf_c.kind, _lib.ptr(pf_c.refresh()), pf_f.kind, _lib.ptr(pf_f.refresh()),
+                                                _lib.ptr(rays), n, float(near), float(far), n_coarse, n_fine, _lib.ptr(zl),
+                                                _lib.ptr(ul), _lib.ptr(t_rand), int(seed) & (2 ** 64 - 1), int(ray0),
+                                                _lib.ptr(grid.bits), pdims, plo, pinv, *[_lib.ptr(o) for o in outs],
+                                                _lib.ptr(counts), _lib.ptr(ws), int(ws_bytes), _lib.stream_ptr(dev)),
+                   "mi_render_rays_occupancy")
+    if guard is not None and not bool((guard == 0xA5).all()):
+        raise _lib.MiRenderError("mi_render_rays_occupancy wrote past its workspace")
+    return tuple(outs), counts

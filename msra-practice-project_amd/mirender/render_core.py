@@ -105,19 +105,36 @@ def _eval_pass(model, pf, rays, z, film):
     return autograd.field_eval_rays(pf, rays, z, film if fields.is_film(pf.kind) else None)
 
 
+def _check_grid(grid, pf_c, pf_f, film):
+    """What rendering with an occupancy grid is not built for, said by name."""
+    if pf_c is None or pf_f is None:
+        raise _lib.MiRenderError("rendering with an occupancy grid is not built for callables with no known layout "
+                                 "(the generic path): both models must be NeRF, SirenNeRF or TinyNeRF fields")
+    if fields.is_film(pf_c.kind) or fields.is_film(pf_f.kind):
+        raise _lib.MiRenderError("rendering with an occupancy grid is not built for FiLM fields (a FiLM field's table is per "
+                                 "image, a per-scene grid has no meaning there)")
+    if torch.is_grad_enabled() and any(p.requires_grad for p in pf_c.params + pf_f.params):
+        raise _lib.MiRenderError("rendering with an occupancy grid is not built for calls that need gradients (training): "
+                                 "call it under torch.no_grad()")
+    if torch.device(grid.device) != torch.device(pf_c.device):
+        raise _lib.MiRenderError(f"the occupancy grid is on {grid.device}, the fields are on {pf_c.device}")
+
+
 def render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, fine_sample_num, *,
-                t_rand=None, seed=None, film=None, ray0=0):
+                t_rand=None, seed=None, film=None, ray0=0, grid=None):
     """nerf/render.py:106-147.  rays [N,2,3] -> (rgb_c, depth_c, acc_c, rgb_f, depth_f, acc_f).
     `ray0`: index of rays[0] in the caller's full ray list; the seeded jitter is keyed by (seed, ray0 + k, sample),
     so a frame rendered in pieces (chunks, GPUs) gets the jitter it would get in one call.
     `film` [b,rows,512] (FiLM fields only; rows = hidden_layers + 1, 9 for the default depth) renders b images in one call: rays are b equal consecutive groups and
-    group g uses film[g]; by default the model's own film_params (one image) are used like the reference."""
+    group g uses film[g]; by default the model's own film_params (one image) are used like the reference.
+    `grid` (mirender.occupancy.OccupancyGrid; inference with NeRF, SirenNeRF or TinyNeRF fields): a sample in an unoccupied
+    cell, or outside the grid's box, counts as raw = 0 and is not evaluated (ops.render_rays_occupancy)."""
     return _render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, fine_sample_num, t_rand=t_rand,
-                        seed=seed, film=film, ray0=ray0)
+                        seed=seed, film=film, ray0=ray0, grid=grid)
 
 
 def _render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, fine_sample_num, *,
-                 t_rand=None, seed=None, film=None, ray0=0, coarse_outputs=True):
+                 t_rand=None, seed=None, film=None, ray0=0, coarse_outputs=True, grid=None):
     """render_rays; coarse_outputs=False lets the fused inference path skip what only the coarse outputs need
     (ops.render_rays_fused), which may then return None in their slots.  The fine outputs are the same bits."""
     dev = _device_of(coarse_model, fine_model, rays=rays)
@@ -126,6 +143,11 @@ def _render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, f
     if seed is None and t_rand is None:
         seed = _fresh_seed()
     pf_c, pf_f = fields.as_packed_field(coarse_model), fields.as_packed_field(fine_model)
+    if grid is not None:
+        _check_grid(grid, pf_c, pf_f, film)
+        if rays.shape[0]:
+            return ops.render_rays_occupancy(pf_c, pf_f, rays, near, far, nc, nf, grid, t_rand, seed or 0, ray0=ray0,
+                                             coarse_outputs=coarse_outputs)[0]
     if rays.shape[0] == 0:
         # no rays (an empty batch, a rank of a group larger than the frame): six empty outputs; under autograd they hang
         # off the parameters with zero gradients, so a loss over an empty shard still backpropagates
@@ -172,7 +194,7 @@ def _render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, f
 
 
 def _render_image_device(width, height, focal, pose, near, far, coarse_model, fine_model, nc, nf, chunk,
-                         t_rand=None, seed=None, ray0=0, n_rays=None):
+                         t_rand=None, seed=None, ray0=0, n_rays=None, grid=None):
     """Rays [ray0, ray0+n) of the image -> device tensors (rgb[n,3], depth[n], acc[n]) of the FINE pass."""
     dev = _device_of(coarse_model, fine_model)
     total = width * height
@@ -187,7 +209,7 @@ def _render_image_device(width, height, focal, pose, near, far, coarse_model, fi
         rays = ops.gen_rays(width, height, focal, pose, dev, i, m)
         tr = None if t_rand is None else t_rand[i - ray0:i - ray0 + m]   # row k of t_rand <-> ray ray0 + k
         out = _render_rays(rays, near, far, coarse_model, fine_model, nc, nf, t_rand=tr, seed=seed, ray0=i,
-                           coarse_outputs=False)
+                           coarse_outputs=False, grid=grid)
         parts.append(out[3:6])
     if not parts:                                          # an empty ray range (a rank of a group larger than the frame)
         return (torch.empty((0, 3), dtype=torch.float32, device=dev), torch.empty(0, dtype=torch.float32, device=dev),
@@ -198,11 +220,11 @@ def _render_image_device(width, height, focal, pose, near, far, coarse_model, fi
 
 
 def render_image(width, height, focal, pose, near, far, coarse_model, fine_model, coarse_sample_num,
-                 fine_sample_num, chunk=1024 * 16, *, t_rand=None, seed=None):
+                 fine_sample_num, chunk=1024 * 16, *, t_rand=None, seed=None, grid=None):
     """nerf/render.py:150-167: NumPy rgb[H,W,3], depth[H,W,1], acc[H,W,1] of the fine pass."""
     with torch.no_grad():
         rgb, depth, acc = _render_image_device(width, height, focal, pose, near, far, coarse_model, fine_model,
-                                               int(coarse_sample_num), int(fine_sample_num), None, t_rand, seed)
+                                               int(coarse_sample_num), int(fine_sample_num), None, t_rand, seed, grid=grid)
     return (rgb.cpu().numpy().reshape(height, width, 3), depth.cpu().numpy().reshape(height, width, 1),
             acc.cpu().numpy().reshape(height, width, 1))
 
@@ -211,15 +233,15 @@ render_image_np = render_image   # pi_GAN/render.py:209-226 is the same function
 
 
 def render_image_tensor(width, height, focal, pose, near, far, coarse_model, fine_model, coarse_sample_num,
-                        fine_sample_num, chunk=1024 * 16, *, t_rand=None, seed=None):
+                        fine_sample_num, chunk=1024 * 16, *, t_rand=None, seed=None, grid=None):
     """pi_GAN/render.py:195-206: rgb of the fine pass as a device tensor [H,W,3] carrying the autograd graph."""
     rgb, _, _ = _render_image_device(width, height, focal, pose, near, far, coarse_model, fine_model,
-                                     int(coarse_sample_num), int(fine_sample_num), None, t_rand, seed)
+                                     int(coarse_sample_num), int(fine_sample_num), None, t_rand, seed, grid=grid)
     return rgb.reshape(height, width, 3)
 
 
 def render_video(width, height, focal, poses, near, far, coarse_model, fine_model, coarse_sample_num,
-                 fine_sample_num, chunk=1024 * 16, *, t_rand=None, seed=None):
+                 fine_sample_num, chunk=1024 * 16, *, t_rand=None, seed=None, grid=None):
     """nerf/render.py:170-182 (and the evident intent of pi_GAN/render.py:229-241, whose body unpacks
     three values from the tensor-returning render_image): stacked NumPy frames rgb[F,H,W,3], depth[F,H,W,1],
     acc[F,H,W,1].  Keyword-only extras: `t_rand` [F, H*W, Nc] injects each frame's jitter, `seed` seeds frame i with
@@ -241,7 +263,7 @@ def render_video(width, height, focal, poses, near, far, coarse_model, fine_mode
         with torch.no_grad():
             outs = _render_image_device(width, height, focal, p, near, far, coarse_model, fine_model,
                                         int(coarse_sample_num), int(fine_sample_num), None,
-                                        None if t_rand is None else t_rand[i], None if seed is None else seed + i)
+                                        None if t_rand is None else t_rand[i], None if seed is None else seed + i, grid=grid)
         dev = outs[0].device
         if copy_stream is None:
             copy_stream = torch.cuda.Stream(dev)
