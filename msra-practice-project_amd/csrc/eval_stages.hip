@@ -114,6 +114,12 @@ __global__ __launch_bounds__(256) void image_metrics_reduce_kernel(const float* 
     }
 }
 
+// dynamic LDS of image_metrics_kernel: the two halos [span][span] and the five row-filtered planes [span][kTile]
+constexpr size_t metrics_lds_bytes(int window_size) {
+    const int span = kTile + 2 * (window_size / 2);
+    return (size_t)(2 * span * span + 5 * span * kTile) * sizeof(float);
+}
+
 int64_t image_metrics_workspace_floats(int images, int channels, int H, int W) {
     const int64_t bx = (W + kTile - 1) / kTile, by = (H + kTile - 1) / kTile;
     return (int64_t)images * channels * bx * by * 2;
@@ -121,12 +127,26 @@ int64_t image_metrics_workspace_floats(int images, int channels, int H, int W) {
 
 int launch_image_metrics(const float* img1, const float* img2, int images, int channels, int H, int W,
                          const float* window, int window_size, float* workspace, float* out, hipStream_t stream) {
+    // -1 is MI_EINVAL: mi_image_metrics refuses the same sizes before it gets here
+    if (window_size < 1 || window_size > kMaxWindow || window_size % 2 == 0) {
+        set_error("image_metrics: window %d is not odd and <= %d", window_size, kMaxWindow); return -1;
+    }
     Window win{};
     win.size = window_size;
     for (int i = 0; i < window_size; ++i) win.g[i] = window[i];
-    const int span = kTile + 2 * (window_size / 2);
-    const size_t lds = (size_t)(2 * span * span + 5 * span * kTile) * sizeof(float);
-    if (lds > 64 * 1024) { set_error("image_metrics: window %d needs %zu B of LDS", window_size, lds); return -1; }
+    const size_t lds = metrics_lds_bytes(window_size);
+    // windows 29 and 31 need 67 200 and 70 432 B, past the 64 KiB a kernel gets by default: raise the limit to what the
+    // largest window the header promises needs (a CU of gfx950 has 160 KiB)
+    static_assert(metrics_lds_bytes(kMaxWindow) <= 160 * 1024, "image_metrics_kernel: kMaxWindow needs more LDS than a CU has");
+    static PerDeviceOnce attr_once;
+    const int arc = attr_once.run([&]() {
+        if (hipFuncSetAttribute((const void*)image_metrics_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)metrics_lds_bytes(kMaxWindow)) != hipSuccess) {
+            set_error("hipFuncSetAttribute(image_metrics) failed"); return -2;
+        }
+        return 0;
+    });
+    if (arc) return arc;
     const unsigned bx = (W + kTile - 1) / kTile, by = (H + kTile - 1) / kTile;
     const int64_t planes = (int64_t)images * channels;
     if (planes > 65535) { set_error("image_metrics: too many planes (%lld)", (long long)planes); return -1; }
