@@ -469,6 +469,66 @@ int mi_render_rays_occupancy(int kind_coarse, const float* packed_coarse, int ki
                              float* depth_c, float* acc_c, float* rgb_f, float* depth_f, float* acc_f, int* evaluated,
                              void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- training with a grid (NeRF, SirenNeRF, TinyNeRF) -------------------------------------
+ *
+ * The rule above, differentiated: a listed sample contributes to the parameter gradients exactly what it contributes without
+ * a grid, an unlisted sample (raw = 0, a constant) contributes nothing; the composite's backward runs on the full [n,S,4]
+ * raw, zeros included.  A cell that is empty in the grid therefore gets no gradient and cannot fill up until the caller
+ * rebuilds the grid: warm-up steps without a grid, dilation and the rebuild period are the caller's policy.
+ *
+ * mi_occupancy_mark_rays_ordered: mi_occupancy_mark_rays with the list in ASCENDING order of the point index, written without
+ * atomics (a count per workgroup, a scan, a scatter), so that the list - the row order of the weight-gradient sums - is the
+ * same in every run.  Same zeroing of raw, same count.  list needs room for mi_occupancy_ordered_list_ints(n, S) ints: the
+ * n * S entries, then one scan slot per workgroup of 4096 points.
+ *
+ * mi_field_eval_rays_list_train: mi_field_eval_rays_list that keeps the layer inputs.  raw[list[e]] has
+ * mi_field_eval_rays_train's bits; the saved rows of entry e are written at ROW e of every region of acts
+ * (mi_field_train_acts_floats(kind) * n * S floats: compact rows, regions at the stride of the capacity n * S), with the
+ * bits of that call's row list[e].  Rows at and past *count are not written.
+ *
+ * mi_field_backward_list: mi_field_backward over those compact rows: rows [0, *count) of acts, raw and g_raw [capacity,4]
+ * read at rows list[e], dA rows e in grads_ws (mi_field_train_grads_floats(kind) * capacity floats), partial_ws of
+ * mi_field_bwd_partial_floats_kind(kind, capacity) floats.  Every launch is sized from the capacity; the row count is read
+ * on the device.  The weight-gradient kernels plan their number of slabs from the capacity, as mi_field_backward does for
+ * that many points, and cut the rows they have into that many equal slabs: slab length = ceil(count / slabs) rounded up to
+ * a multiple of 32.  grad_params are overwritten; with *count == 0 they are exactly 0.
+ *
+ * mi_render_rays_occupancy_train / _backward: mi_render_rays_occupancy keeping layer inputs, and the gradients of every
+ * parameter from the six output cotangents (NULL = zero; a pass without any cotangent is skipped).  One range per pass,
+ * nothing recomputed: workspace = mi_render_workspace_bytes + mi_render_occupancy_train_extra_bytes (each pass keeps its
+ * list), saved = mi_render_occupancy_train_saved_bytes (both passes' compact rows at worst-case capacity), bwd_workspace =
+ * mi_render_occupancy_backward_workspace_bytes; a caller with more rays than its memory allows cuts the rays into calls.
+ * shared != 0: one field for both passes (packed_bwd_fine and grad_params_fine are not read); both passes run as passes of
+ * that field over all their listed points and the two gradient sums are added into grad_params_coarse.  fields_written:
+ * MI_WROTE_COARSE | MI_WROTE_FINE.  FiLM kinds, n * (Nc + Nf) past an int, short buffers and (forward) grid
+ * bits that the runtime knows as memory of another device than the current one: MI_EINVAL before any launch. */
+int64_t mi_occupancy_ordered_list_ints(int64_t n, int n_samples);
+int mi_occupancy_mark_rays_ordered(const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell,
+                                   const float* rays, const float* z, int64_t n, int n_samples, int* list, int* count,
+                                   float* raw, void* stream);
+int mi_field_eval_rays_list_train(int kind, const float* packed, const float* rays, const float* z, int64_t n, int n_samples,
+                                  const int* list, const int* count, float* raw, float* acts, void* stream);
+int mi_field_backward_list(int kind, const float* packed_bwd, const float* acts, float* grads_ws, const float* raw,
+                           const float* g_raw, const int* list, const int* count, int64_t capacity, float* partial_ws,
+                           float* const* grad_params, void* stream);
+int64_t mi_render_occupancy_train_extra_bytes(int64_t n, int n_coarse, int n_fine);
+int64_t mi_render_occupancy_train_saved_bytes(int kind_coarse, int kind_fine, int64_t n, int n_coarse, int n_fine);
+int64_t mi_render_occupancy_backward_workspace_bytes(int kind_coarse, int kind_fine, int shared, int64_t n, int n_coarse,
+                                                     int n_fine);
+int mi_render_rays_occupancy_train(int kind_coarse, const float* packed_coarse, int kind_fine, const float* packed_fine,
+                                   const float* rays, int64_t n, float near_, float far_, int n_coarse, int n_fine,
+                                   const float* z_lin, const float* u_lin, const float* t_rand, uint64_t seed, uint64_t ray0,
+                                   const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell, float* rgb_c,
+                                   float* depth_c, float* acc_c, float* rgb_f, float* depth_f, float* acc_f, int* evaluated,
+                                   void* workspace, int64_t workspace_bytes, void* saved, int64_t saved_bytes, void* stream);
+int mi_render_rays_occupancy_backward(int kind_coarse, const float* packed_bwd_coarse, int kind_fine,
+                                      const float* packed_bwd_fine, int shared, const float* rays, int64_t n, int n_coarse,
+                                      int n_fine, const void* workspace, int64_t workspace_bytes, const void* saved,
+                                      int64_t saved_bytes, const float* g_rgb_c, const float* g_depth_c, const float* g_acc_c,
+                                      const float* g_rgb_f, const float* g_depth_f, const float* g_acc_f,
+                                      float* const* grad_params_coarse, float* const* grad_params_fine, void* bwd_workspace,
+                                      int64_t bwd_workspace_bytes, int* fields_written, void* stream);
+
 /* ---- measurement hooks (bench.py) ---------------------------------------------------- */
 
 /* HIP events owned by the library's HIP runtime (the one the kernels launch on), so a host

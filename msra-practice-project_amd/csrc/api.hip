@@ -333,6 +333,62 @@ int mi_field_eval_rays_list(int kind, const float* packed, const float* rays, co
     return eval_rays_list(kind, packed, rays, z, n, n_samples, list, count, raw, (hipStream_t)stream);
 }
 
+// ---- training with a grid: the stages (train_path.hip holds the call pair) ---------------------------------------------------------
+static int check_list_sizes(const char* fn, int64_t n, int n_samples) {
+    if (n < 0 || n_samples < 1) { set_error("%s: bad sizes (n >= 0, n_samples >= 1)", fn); return MI_EINVAL; }
+    if (n > 0x7fffffffLL / n_samples) {
+        set_error("%s: n * n_samples = %lld * %d exceeds 2^31 - 1 (the list holds int point indices)", fn, (long long)n, n_samples);
+        return MI_EINVAL;
+    }
+    return MI_OK;
+}
+
+int64_t mi_occupancy_ordered_list_ints(int64_t n, int n_samples) {
+    if (check_list_sizes("mi_occupancy_ordered_list_ints", n, n_samples)) return MI_EINVAL;
+    return occupancy_ordered_list_ints(n * n_samples);
+}
+
+int mi_occupancy_mark_rays_ordered(const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell, const float* rays,
+                                   const float* z, int64_t n, int n_samples, int* list, int* count, float* raw, void* stream) {
+    const char* fn = "mi_occupancy_mark_rays_ordered";
+    if (!occupancy_cells(fn, dims)) return MI_EINVAL;
+    if (!bits || !lo || !inv_cell || !rays || !z || !list || !count) { set_error("%s: null pointer argument", fn); return MI_EINVAL; }
+    if (int rc = check_list_sizes(fn, n, n_samples)) return rc;
+    return launch_occupancy_mark_rays_ordered(bits, dims, lo, inv_cell, rays, z, n, n_samples, list, count, raw, (hipStream_t)stream);
+}
+
+int mi_field_eval_rays_list_train(int kind, const float* packed, const float* rays, const float* z, int64_t n, int n_samples,
+                                  const int* list, const int* count, float* raw, float* acts, void* stream) {
+    const char* fn = "mi_field_eval_rays_list_train";
+    if (bad_kind(kind)) return MI_EINVAL;
+    if (!has_list_kernel(kind)) { set_error("%s: kind %d has no list-driven forward (NeRF, SirenNeRF, TinyNeRF have)", fn, kind); return MI_EINVAL; }
+    if (!packed || !rays || !z || !list || !count || !raw || !acts) { set_error("%s: null pointer argument", fn); return MI_EINVAL; }
+    if (int rc = check_list_sizes(fn, n, n_samples)) return rc;
+    if (n == 0) return MI_OK;
+    MlpArgs args = {};
+    args.packed = packed; args.a = rays; args.z = z; args.out = raw;
+    args.points_per_group = n * n_samples; args.rays_per_group = n; args.tiles_per_group = (n * n_samples + 127) / 128;
+    args.n_samples = n_samples; args.mode = 1; args.save = acts; args.save_points = n * n_samples; args.n_rays = n;
+    return launch_mlp_list(kind, args, list, count, (hipStream_t)stream);
+}
+
+int mi_field_backward_list(int kind, const float* packed_bwd, const float* acts, float* grads_ws, const float* raw,
+                           const float* g_raw, const int* list, const int* count, int64_t capacity, float* partial_ws,
+                           float* const* grad_params, void* stream) {
+    const char* fn = "mi_field_backward_list";
+    if (bad_kind(kind)) return MI_EINVAL;
+    if (!has_list_kernel(kind)) { set_error("%s: kind %d has no counted backward (NeRF, SirenNeRF, TinyNeRF have)", fn, kind); return MI_EINVAL; }
+    if (!packed_bwd || !acts || !grads_ws || !raw || !g_raw || !list || !count || !partial_ws || !grad_params) {
+        set_error("%s: null pointer argument", fn);
+        return MI_EINVAL;
+    }
+    if (capacity < 0 || capacity > 0x7fffffffLL) { set_error("%s: capacity %lld does not fit the list's int indices", fn, (long long)capacity); return MI_EINVAL; }
+    for (int i = 0; i < 2 * field_kind(kind).n_layers; ++i)
+        if (!grad_params[i]) { set_error("%s: gradient pointer %d is null", fn, i); return MI_EINVAL; }
+    return launch_field_backward_list(kind, packed_bwd, acts, grads_ws, raw, g_raw, list, count, capacity, partial_ws, grad_params,
+                                      (hipStream_t)stream);
+}
+
 // the region behind mi_render_workspace_bytes that rendering with a grid adds: one list [n * S] of ints, then the two counts
 static int64_t occupancy_list_floats(int64_t n, int S) { return align64(n * S); }
 int64_t mi_render_occupancy_extra_bytes(int64_t n, int n_coarse, int n_fine) {

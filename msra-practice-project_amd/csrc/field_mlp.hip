@@ -40,13 +40,15 @@ namespace mi {
 // instance's argument block carries the list: every other instance takes MlpArgs as before.
 // LIST = the inference instance over a device-counted list of points (load_list_point: rendering with an occupancy grid): a
 // block whose tile lies past the count returns before it issues any LDS DMA; behind the loader it is the inference instance.
+// LIST + SAVE = the training instance over such a list: entry e evaluates point p = list[e], its raw row goes to out[p] and its
+// saved rows (SaveRows, store_xin, the switch words) to row e of every region - compact, in list order (list_save_row).
 struct DeferMlpArgs : MlpArgs { DeferArgs defer; };
 template <bool TINY, bool SAVE, bool SIGMA_ONLY, bool WINDOW = false, bool SPILL = false, bool LIST = false>
 __global__ __launch_bounds__(256, 1) void nerf_fwd_kernel(std::conditional_t<SPILL, DeferMlpArgs, MlpArgs> a) {
     static_assert(!(SAVE && SIGMA_ONLY), "the training forward needs the colour branch");
     static_assert(!WINDOW || SIGMA_ONLY, "windows exist for the sigma-only coarse pass");
     static_assert(!SPILL || (SIGMA_ONLY && !WINDOW), "the spill is an ending of the sigma-only instance");
-    static_assert(!LIST || (!SAVE && !SIGMA_ONLY && !WINDOW && !SPILL), "the list drives the inference instance");
+    static_assert(!LIST || (!SIGMA_ONLY && !WINDOW && !SPILL), "the list drives the inference and the training instance");
     constexpr FieldKind K = kFieldKinds[TINY ? MI_FIELD_TINY_NERF : MI_FIELD_NERF];
     // Forward segment i is layer i's (field_layout.h): T - 1 the trunk's last, with the sigma head's pieces; D the dir layer,
     // with the rgb head's.  A layer issues, behind its own K blocks, the aux pieces and first K blocks of the segment after it.
@@ -87,18 +89,19 @@ __global__ __launch_bounds__(256, 1) void nerf_fwd_kernel(std::conditional_t<SPI
 
     constexpr RegionLayout RL = TINY ? tiny_acts() : nerf_acts();
     const int64_t SP = a.save_points;
+    const int64_t srow = list_save_row<LIST && SAVE>(pt, tile, live, c.wave * 32 + (c.lane & 31));   // row of the saved regions
     // `sw`: the region of the layer's ReLU switch bits (nerf_acts() 12.. / tiny_acts() 7..), -1 for none
     const auto rows = [&](int off_floats_per_point, int width, int sw = -1) {
-        return SaveRows{SAVE ? a.save + (int64_t)off_floats_per_point * SP : nullptr, width, pt.p, pt.valid,
+        return SaveRows{SAVE ? a.save + (int64_t)off_floats_per_point * SP : nullptr, width, srow, pt.valid,
                         SAVE && sw >= 0 ? a.save + (int64_t)region_offset(RL, sw) * SP : nullptr};
     };
     constexpr int SW0 = RL.relu_switch0();                 // switch region of H1; H_l: SW0 + l - 1; H_d: the last region
     if constexpr (SAVE) {
         f32x16 tmp[8];
         tmp[0] = pe[0]; tmp[1] = pe[1];
-        store_rows<2>(a.save, 64, pt.p, pt.valid, c.h, tmp);
+        store_rows<2>(a.save, 64, srow, pt.valid, c.h, tmp);
         tmp[0] = pd[0];
-        store_rows<1>(a.save + (int64_t)region_offset(RL, TINY ? 5 : 10) * SP, 32, pt.p, pt.valid, c.h, tmp);
+        store_rows<1>(a.save + (int64_t)region_offset(RL, TINY ? 5 : 10) * SP, 32, srow, pt.valid, c.h, tmp);
     }
 
     const auto sel_pe = [&](auto kb) -> const f32x16& { return pe[decltype(kb)::value]; };
@@ -267,7 +270,7 @@ template <bool SAVE, bool SIGMA_ONLY, bool WINDOW = false, bool LIST = false>
 __global__ __launch_bounds__(256, 1) void siren_fwd_kernel(MlpArgs a) {
     static_assert(!(SAVE && SIGMA_ONLY), "the training forward needs the colour branch");
     static_assert(!WINDOW || SIGMA_ONLY, "windows exist for the sigma-only coarse pass");
-    static_assert(!LIST || (!SAVE && !SIGMA_ONLY && !WINDOW), "the list drives the inference instance");
+    static_assert(!LIST || (!SIGMA_ONLY && !WINDOW), "the list drives the inference and the training instance");
     constexpr FieldKind K = kFieldKinds[MI_FIELD_SIREN_NERF];
     // forward segment i is layer i's, as in nerf_fwd_kernel; layer 0 is K = 3 (VALU): its segment has no K blocks
     constexpr Segments F = segments(K.fwd);
@@ -308,20 +311,25 @@ __global__ __launch_bounds__(256, 1) void siren_fwd_kernel(MlpArgs a) {
     const auto sel_x = [&](auto kb) -> const f32x16& { return X[decltype(kb)::value]; };
     constexpr RegionLayout RL = siren_acts();
     const int64_t SP = a.save_points;
+    const int64_t srow = list_save_row<LIST && SAVE>(pt, tile, live, c.wave * 32 + (c.lane & 31));   // row of the saved regions
     const auto region = [&](int idx) { return a.save + (int64_t)region_offset(RL, idx) * SP; };
     // sin layer l (1..8): X_l (cosine sign in the lowest bit) -> region l
     const auto sin_rows = [&](int l) {
-        return SaveRows{SAVE ? a.save + (int64_t)(8 + 256 * (l - 1)) * SP : nullptr, 256, pt.p, pt.valid};
+        return SaveRows{SAVE ? a.save + (int64_t)(8 + 256 * (l - 1)) * SP : nullptr, 256, srow, pt.valid};
     };
     const SaveRows none{nullptr, 0, 0, false};
     const auto sin_act = [&](int l) {
         if constexpr (SAVE)
             activate_train<8, ACT_SIN30>(acc, X, nullptr, c.h, smem + kLdsAux0, a.save + (int64_t)(8 + 256 * (l - 1)) * SP, 256,
-                                         pt.p, pt.valid);
+                                         srow, pt.valid);
         else
             activate<8, ACT_SIN30>(acc, X, nullptr, c.h, smem + kLdsAux0);
     };
-    if constexpr (SAVE) store_xin(a.save, pt, pt.valid && c.h == 0);
+    if constexpr (SAVE && LIST) {
+        PointIn at = pt;
+        at.p = srow;
+        store_xin(a.save, at, pt.valid && c.h == 0);
+    } else if constexpr (SAVE) store_xin(a.save, pt, pt.valid && c.h == 0);
 
     int slot = 0;
     __syncthreads();
@@ -352,12 +360,12 @@ __global__ __launch_bounds__(256, 1) void siren_fwd_kernel(MlpArgs a) {
         return;
     }
     slot ^= 1;
-    const SaveRows g_rows{SAVE ? region(9) : nullptr, 256, pt.p, pt.valid};
+    const SaveRows g_rows{SAVE ? region(9) : nullptr, 256, srow, pt.valid};
     fwd_layer<F.blocks(8), F.mb(8), false, F.aux(9), F.block_pieces(9), false, ACT_LINEAR, SAVE, true, 0>(
         c, slot, 0, 0, 0.f, 0.f, 0.f, sel_x, acc, X, nullptr, g_rows, none);  // layers_dir[0] linear: G (stored by the next layer)
     slot ^= 1;
     fwd_layer<F.blocks(D), F.mb(D), true, F.aux(D + 1), F.block_pieces(D + 1), false, ACT_SIN30, SAVE, false, F.mb(8)>(
-        c, slot, 0, kDirCols, pt.dx, pt.dy, pt.dz, sel_x, acc, X, nullptr, SaveRows{SAVE ? region(10) : nullptr, 128, pt.p, pt.valid},
+        c, slot, 0, kDirCols, pt.dx, pt.dy, pt.dz, sel_x, acc, X, nullptr, SaveRows{SAVE ? region(10) : nullptr, 128, srow, pt.valid},
         g_rows);  // layers_dir[1]: [h | dir]; G from X
     float r, g, b;
     rgb_heads<F.mb(D)>(X, smem + kLdsAux0 + slot * kLdsAux, kRgbRow, kRgbBias, c.h, r, g, b);
@@ -453,33 +461,36 @@ __global__ __launch_bounds__(256, 1) void film_fwd_kernel(MlpArgs a) {
 // direction (MI_FIELD_FILM_DEPTH kinds other than depth 8, which IS kinds 2 / 3).  Variants: the inference, the training
 // (layer inputs saved), the sigma-only and the windowed sigma-only instance of the kind's kernel, then the two kernels of the
 // deferred colour branch (NeRF, TinyNeRF): the trunk-and-spill instance and the colour-branch kernel, then the list-driven
-// inference instance (NeRF, SirenNeRF, TinyNeRF: the kinds an occupancy grid exists for).
+// inference instance and the list-driven training instance (NeRF, SirenNeRF, TinyNeRF: the kinds an occupancy grid exists for).
 // The FiLM kinds have no sigma-only instance (their caller, pi_GAN, renders both passes with one field and needs the
 // coarse colours for the merge): has_sigma_only_kernel() is false for them.
-enum FwdVariant : int { FWD_INFER = 0, FWD_SAVE, FWD_SIGMA, FWD_SIGMA_WINDOW, FWD_SPILL, FWD_COLOUR, FWD_LIST, FWD_VARIANTS };
+enum FwdVariant : int { FWD_INFER = 0, FWD_SAVE, FWD_SIGMA, FWD_SIGMA_WINDOW, FWD_SPILL, FWD_COLOUR, FWD_LIST, FWD_LIST_SAVE, FWD_VARIANTS };
 constexpr int kFilmDepthRow = MI_FIELD_KINDS;      // + use_dir
 static const void* const kKernels[MI_FIELD_KINDS + 2][FWD_VARIANTS] = {
     // MI_FIELD_NERF
     {(const void*)nerf_fwd_kernel<false, false, false>, (const void*)nerf_fwd_kernel<false, true, false>,
      (const void*)nerf_fwd_kernel<false, false, true>, (const void*)nerf_fwd_kernel<false, false, true, true>,
      (const void*)nerf_fwd_kernel<false, false, true, false, true>, (const void*)nerf_colour_kernel<false>,
-     (const void*)nerf_fwd_kernel<false, false, false, false, false, true>},
+     (const void*)nerf_fwd_kernel<false, false, false, false, false, true>,
+     (const void*)nerf_fwd_kernel<false, true, false, false, false, true>},
     // MI_FIELD_SIREN_NERF
     {(const void*)siren_fwd_kernel<false, false>, (const void*)siren_fwd_kernel<true, false>, (const void*)siren_fwd_kernel<false, true>,
-     (const void*)siren_fwd_kernel<false, true, true>, nullptr, nullptr, (const void*)siren_fwd_kernel<false, false, false, true>},
+     (const void*)siren_fwd_kernel<false, true, true>, nullptr, nullptr, (const void*)siren_fwd_kernel<false, false, false, true>,
+     (const void*)siren_fwd_kernel<true, false, false, true>},
     {(const void*)film_fwd_kernel<true, false>, (const void*)film_fwd_kernel<true, true>},                // MI_FIELD_FILM_SIREN_NERF
     {(const void*)film_fwd_kernel<false, false>, (const void*)film_fwd_kernel<false, true>},              // ..._NODIR
     // MI_FIELD_TINY_NERF
     {(const void*)nerf_fwd_kernel<true, false, false>, (const void*)nerf_fwd_kernel<true, true, false>,
      (const void*)nerf_fwd_kernel<true, false, true>, (const void*)nerf_fwd_kernel<true, false, true, true>,
      (const void*)nerf_fwd_kernel<true, false, true, false, true>, (const void*)nerf_colour_kernel<true>,
-     (const void*)nerf_fwd_kernel<true, false, false, false, false, true>},
+     (const void*)nerf_fwd_kernel<true, false, false, false, false, true>,
+     (const void*)nerf_fwd_kernel<true, true, false, false, false, true>},
     {(const void*)film_fwd_kernel<false, false, true>, (const void*)film_fwd_kernel<false, true, true>},  // any depth, no dir
     {(const void*)film_fwd_kernel<true, false, true>, (const void*)film_fwd_kernel<true, true, true>}};   // any depth, dir
 
 bool has_deferred_colour_kernels(int kind) { return kind >= 0 && kind < MI_FIELD_KINDS && kKernels[kind][FWD_SPILL] && kKernels[kind][FWD_COLOUR]; }
 bool has_sigma_only_kernel(int kind) { return kind >= 0 && kind < MI_FIELD_KINDS && kKernels[kind][FWD_SIGMA]; }
-bool has_list_kernel(int kind) { return kind >= 0 && kind < MI_FIELD_KINDS && kKernels[kind][FWD_LIST]; }
+bool has_list_kernel(int kind) { return kind >= 0 && kind < MI_FIELD_KINDS && kKernels[kind][FWD_LIST] && kKernels[kind][FWD_LIST_SAVE]; }
 
 // Every instance runs 256 threads on 148 KiB of dynamic LDS: the per-kernel limit is raised once per device (host-side
 // attribute, no device work).
@@ -538,7 +549,7 @@ int launch_mlp_window(int kind_in, const MlpArgs& a, hipStream_t stream) {
 int launch_mlp_list(int kind_in, const MlpArgs& a_in, const int* list, const int* count, hipStream_t stream) {
     const int kind = canon_kind(kind_in);
     if (bad_kind(kind)) return -1;
-    if (!has_list_kernel(kind) || a_in.save || a_in.film || a_in.mode != 1 || a_in.n_samples < 1 || !list || !count ||
+    if (!has_list_kernel(kind) || (a_in.save && a_in.save_points < a_in.points_per_group) || a_in.film || a_in.mode != 1 || a_in.n_samples < 1 || !list || !count ||
         a_in.points_per_group < 1 || a_in.points_per_group > 0x7fffffffLL ||
         a_in.points_per_group != a_in.rays_per_group * a_in.n_samples) {
         set_error("kind %d: bad list-driven launch", kind);
@@ -547,7 +558,7 @@ int launch_mlp_list(int kind_in, const MlpArgs& a_in, const int* list, const int
     MlpArgs a = a_in;
     a.live_rays = list; a.live_count = count;
     const int64_t blocks = (a.points_per_group + 127) / 128;           // worst case: every point listed
-    return launch_instance(kKernels[kind][FWD_LIST], blocks, &a, stream, "field_mlp_fwd_list");
+    return launch_instance(kKernels[kind][a.save ? FWD_LIST_SAVE : FWD_LIST], blocks, &a, stream, "field_mlp_fwd_list");
 }
 
 // compute units of the current device, asked once per device ordinal (0 and the error set if the query fails)

@@ -39,6 +39,29 @@ struct BwdArgs {
     int film_depth;          // FiLM kinds: hidden_layers (the run-time-depth chain reads it), else 0
 };
 
+// The COUNTED instances (training with an occupancy grid): the rows are the first *count entries of a device-counted list of
+// point indices.  acts / grads hold COMPACT rows (row e belongs to point list[e]; a.points = the capacity, the regions'
+// stride), raw / g_raw stay [all points of the pass][4] and are read at row list[e].
+struct CountedBwdArgs : BwdArgs {
+    const int* list;
+    const int* count;
+};
+// rows of a counted launch (block-uniform), never more than the capacity the buffers were sized for
+__device__ __forceinline__ int64_t counted_rows(const int* count, int64_t capacity) {
+    const int64_t n = __builtin_amdgcn_readfirstlane(__hip_atomic_load(count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    return n < 0 ? 0 : n < capacity ? n : capacity;
+}
+// The slab length of the counted weight-gradient kernels: the host plans n_slabs from the CAPACITY (BwdBatcher::slabs_for /
+// slab_pts_for, as for a plain pass) and sizes the partial records for it; the device cuts the rows it really has into that
+// many equal slabs of whole 32-point stages, slab_len = ceil32(ceil(count / n_slabs)).  With count == capacity this is the
+// host planner's slab length (n_slabs = ceil(P / slab) gives (n_slabs - 1) slab < P <= n_slabs slab, so ceil(P / n_slabs) <=
+// slab, and n_slabs <= the planned slabs gives >=); n_slabs * slab_len >= count always; a slab past the rows is empty and
+// writes a zero record.
+__host__ __device__ constexpr int counted_slab_pts(int64_t count, int n_slabs) {
+    return (int)(((count + n_slabs - 1) / n_slabs + 31) / 32 * 32);
+}
+struct CountedRows { const int* count; int64_t capacity; int n_slabs; };
+
 #ifdef MI_PROFILE_STAMPS
 unsigned long long* g_bwd_stamps = nullptr;       // set by mi_debug_set_stamps (api.hip), diagnostic build only
 #endif
@@ -95,6 +118,7 @@ __device__ __forceinline__ void relu_bwd_store(const f32x16 (&dX)[8], f32x16 (&X
 // Head gradients of point p (rgb = sigmoid(pre), sigma = relu(pre)): dL/d(pre) from the forward outputs and their gradients.
 // The caller stores them to its kind's heads region ([points][4]: rgb 0..2, sigma 3).
 struct HeadGrads { float d0, d1, d2, ds; };
+// (p: the row of raw / g_raw - the point's own, or list[e] of a counted launch)
 __device__ __forceinline__ HeadGrads head_grads(const BwdArgs& a, int64_t p) {
     const f32x4 g = reinterpret_cast<const f32x4*>(a.g_raw)[p];
     const f32x4 o = reinterpret_cast<const f32x4*>(a.raw)[p];
@@ -226,9 +250,14 @@ __device__ __forceinline__ void bwd_layer(Ctx& c, int aux_slot, int piece, float
 // =========================================================================================
 // NeRF / TinyNeRF backward chain (reverse of nerf/nerf.py:75-94)
 // =========================================================================================
-template <bool TINY>
-__global__ __launch_bounds__(256, 1) void nerf_bwd_kernel(BwdArgs a) {
+template <bool TINY, bool COUNTED = false>
+__global__ __launch_bounds__(256, 1) void nerf_bwd_kernel(std::conditional_t<COUNTED, CountedBwdArgs, BwdArgs> a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
+    int64_t rows = a.points;                     // rows of the launch; P below stays the regions' stride
+    if constexpr (COUNTED) {
+        rows = counted_rows(a.count, a.points);
+        if ((int64_t)blockIdx.x * 128 >= rows) return;      // before any LDS DMA
+    }
     Ctx c = make_ctx_raw(smem, a.packed, nullptr);
     constexpr RegionLayout AL = TINY ? tiny_acts() : nerf_acts();
     constexpr RegionLayout GL = TINY ? tiny_grads() : nerf_grads();
@@ -249,9 +278,11 @@ __global__ __launch_bounds__(256, 1) void nerf_bwd_kernel(BwdArgs a) {
     issue_first_stage<B.aux(0), B.block_pieces(0), false>(c, 0);
 
     const int64_t local = (int64_t)blockIdx.x * 128 + c.wave * 32 + (c.lane & 31);
-    const bool valid = local < P;
-    const int64_t p = valid ? local : P - 1;
-    const HeadGrads hg = head_grads(a, p);
+    const bool valid = local < rows;
+    const int64_t p = valid ? local : rows - 1;
+    int64_t q = p;                               // row of raw / g_raw
+    if constexpr (COUNTED) q = a.list[p];
+    const HeadGrads hg = head_grads(a, q);
     const float ds = hg.ds;
     if (valid && c.h == 0) reinterpret_cast<f32x4*>(a.grads + (int64_t)region_offset(GL, GL.n - 1) * P)[p] = f32x4{hg.d0, hg.d1, hg.d2, ds};
 
@@ -358,8 +389,14 @@ __device__ __forceinline__ void sin_bwd_store(const f32x16 (&dX)[8], f32x16 (&X)
 // =========================================================================================
 // SirenNeRF backward chain (reverse of nerf/nerf.py:153-170); same shape as NeRF's, sin derivatives
 // =========================================================================================
-__global__ __launch_bounds__(256, 1) void siren_bwd_kernel(BwdArgs a) {
+template <bool COUNTED = false>
+__global__ __launch_bounds__(256, 1) void siren_bwd_kernel(std::conditional_t<COUNTED, CountedBwdArgs, BwdArgs> a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
+    int64_t rows = a.points;                     // as in nerf_bwd_kernel
+    if constexpr (COUNTED) {
+        rows = counted_rows(a.count, a.points);
+        if ((int64_t)blockIdx.x * 128 >= rows) return;
+    }
     Ctx c = make_ctx_raw(smem, a.packed, nullptr);
     constexpr RegionLayout AL = siren_acts();
     constexpr RegionLayout GL = siren_grads();
@@ -379,9 +416,11 @@ __global__ __launch_bounds__(256, 1) void siren_bwd_kernel(BwdArgs a) {
     issue_first_stage<B.aux(0), B.block_pieces(0), false>(c, 0);
 
     const int64_t local = (int64_t)blockIdx.x * 128 + c.wave * 32 + (c.lane & 31);
-    const bool valid = local < P;
-    const int64_t p = valid ? local : P - 1;
-    const HeadGrads hg = head_grads(a, p);
+    const bool valid = local < rows;
+    const int64_t p = valid ? local : rows - 1;
+    int64_t q = p;                               // row of raw / g_raw
+    if constexpr (COUNTED) q = a.list[p];
+    const HeadGrads hg = head_grads(a, q);
     const float ds = hg.ds;
     if (valid && c.h == 0) reinterpret_cast<f32x4*>(a.grads + (int64_t)region_offset(GL, GL.n - 1) * P)[p] = f32x4{hg.d0, hg.d1, hg.d2, ds};
 
@@ -721,8 +760,20 @@ constexpr size_t gemm_lds_bytes() {
     return stage > merge ? stage : merge;
 }
 
-template <int CB, int WM, int WK>
-__global__ __launch_bounds__(256, 1) void dw_gemm_kernel(GemmBatch jobs, int64_t P, int slab_pts) {
+// COUNTED: the rows and the slab length come from the device count (counted_slab_pts); a slab past the rows contracts nothing
+// (its descriptors bound zero records, its ring reads zeros) and writes a zero record.
+template <int CB, int WM, int WK, bool COUNTED = false>
+__global__ __launch_bounds__(256, 1) void dw_gemm_kernel(GemmBatch jobs, std::conditional_t<COUNTED, CountedRows, int64_t> rows_in,
+                                                         int slab_in) {
+    int64_t P;
+    int slab_pts;
+    if constexpr (COUNTED) {
+        P = counted_rows(rows_in.count, rows_in.capacity);
+        slab_pts = counted_slab_pts(P, rows_in.n_slabs);
+    } else {
+        P = rows_in;
+        slab_pts = slab_in;
+    }
     const float* __restrict__ dA = jobs.dA[blockIdx.y];
     const float* __restrict__ X = jobs.X[blockIdx.y];
     float* __restrict__ partial = jobs.partial[blockIdx.y];
@@ -740,7 +791,8 @@ __global__ __launch_bounds__(256, 1) void dw_gemm_kernel(GemmBatch jobs, int64_t
     const int tile = wave % TILES, ks = wave / TILES;
     const int wm = tile / WK, wk = tile % WK;
     const int64_t p0 = (int64_t)blockIdx.x * slab_pts;
-    const int64_t p1 = p0 + slab_pts < P ? p0 + slab_pts : P;
+    int64_t p1 = p0 + slab_pts < P ? p0 + slab_pts : P;
+    if constexpr (COUNTED) p1 = p1 < p0 ? p0 : p1;                   // an empty slab: zero records, zero stages
     const int n_stages = (int)((p1 - p0 + T - 1) / T);
     const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void*)(dA + p0 * TM), 0, (int)((p1 - p0) * TM * 4), 0x00020000);
     const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void*)(X + p0 * TK), 0, (int)((p1 - p0) * TK * 4), 0x00020000);
@@ -882,7 +934,17 @@ struct ThinBatch {
     float* partial[kMaxThinJobs]; float* bias_partial[kMaxThinJobs];
     int lds_[kMaxThinJobs], c0[kMaxThinJobs], nc[kMaxThinJobs], ldh[kMaxThinJobs], F[kMaxThinJobs];
 };
-__global__ __launch_bounds__(256) void thin_grad_kernel(ThinBatch tb, int64_t P, int slab_pts) {
+template <bool COUNTED = false>
+__global__ __launch_bounds__(256) void thin_grad_kernel(ThinBatch tb, std::conditional_t<COUNTED, CountedRows, int64_t> rows_in, int slab_in) {
+    int64_t P;
+    int slab_pts;
+    if constexpr (COUNTED) {                    // as in dw_gemm_kernel; an empty slab's loops do not run: a zero record
+        P = counted_rows(rows_in.count, rows_in.capacity);
+        slab_pts = counted_slab_pts(P, rows_in.n_slabs);
+    } else {
+        P = rows_in;
+        slab_pts = slab_in;
+    }
     const int job = blockIdx.y;
     const float* __restrict__ S = tb.S[job];
     const float* __restrict__ H = tb.H[job];
@@ -1044,6 +1106,7 @@ struct BwdBatcher {
     float* partial;            // scratch base (null: plan only - used to size the scratch)
     int64_t used = 0;          // floats of scratch handed out
     hipStream_t stream;
+    const int* count = nullptr;   // a counted pass: rows [0, *count) of P (the capacity the plan is made from)
     struct Group { GemmBatch b{}; int n = 0; ReduceJob red[kMaxGemmJobs]; } g422, g221, g412, g111;
     ThinBatch thin{};
     int n_thin = 0;
@@ -1098,12 +1161,18 @@ struct BwdBatcher {
         static_assert(lds <= 160 * 1024, "dw_gemm_kernel: this tile shape needs more LDS than a CU has");
         static PerDeviceOnce attr_once;                                               // one per template instance
         const int arc = attr_once.run([&]() {
-            if (hipFuncSetAttribute((const void*)dw_gemm_kernel<CB, WM, WK>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)lds) != hipSuccess) { set_error("hipFuncSetAttribute(dw_gemm) failed"); return -2; }
+            for (const void* f : {(const void*)dw_gemm_kernel<CB, WM, WK>, (const void*)dw_gemm_kernel<CB, WM, WK, true>})
+                if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+                    set_error("hipFuncSetAttribute(dw_gemm) failed"); return -2;
+                }
             return 0;
         });
         if (arc) return arc;
-        hipLaunchKernelGGL((dw_gemm_kernel<CB, WM, WK>), dim3(n_slabs, g.n), dim3(256), lds, stream, g.b, P, slab);
+        if (count)
+            hipLaunchKernelGGL((dw_gemm_kernel<CB, WM, WK, true>), dim3(n_slabs, g.n), dim3(256), lds, stream, g.b,
+                               CountedRows{count, P, n_slabs}, 0);
+        else
+            hipLaunchKernelGGL((dw_gemm_kernel<CB, WM, WK>), dim3(n_slabs, g.n), dim3(256), lds, stream, g.b, P, slab);
         return check_launch("dw_gemm (batched)");
     }
     // out[c][f] = sum_p S[p][c0+c] H[p][f]: heads (dst [nc][F], bias gb[nc]) or K = 3 weight columns (transposed into
@@ -1158,7 +1227,10 @@ struct BwdBatcher {
             if (c.dst) { c.n = n_slabs; c.src = thin.partial[i]; add_reduce(c); }
         }
         if (!partial) return 0;
-        hipLaunchKernelGGL(thin_grad_kernel, dim3(n_slabs, n_thin), dim3(256), 0, stream, thin, P, slab);
+        if (count)
+            hipLaunchKernelGGL(thin_grad_kernel<true>, dim3(n_slabs, n_thin), dim3(256), 0, stream, thin, CountedRows{count, P, n_slabs}, 0);
+        else
+            hipLaunchKernelGGL(thin_grad_kernel<false>, dim3(n_slabs, n_thin), dim3(256), 0, stream, thin, P, slab);
         return check_launch("thin_grad (batched)");
     }
     int reduce_all() {
@@ -1183,7 +1255,8 @@ static int batched_backward(int kind, BwdBatcher& b, const float* acts, float* g
 // out-of-bounds write by the GEMMs - then for real over `pts` points.  check = false skips the plan (a pass already
 // checked for the same shape).
 template <class Jobs>
-static int plan_then_run(int kind, int64_t pts, int64_t P, float* partial, hipStream_t stream, const Jobs& jobs, bool check = true) {
+static int plan_then_run(int kind, int64_t pts, int64_t P, float* partial, hipStream_t stream, const Jobs& jobs, bool check = true,
+                         const int* count = nullptr) {
     if (check) {
         BwdBatcher plan{pts, nullptr, 0, stream};
         (void)jobs(plan);
@@ -1194,17 +1267,20 @@ static int plan_then_run(int kind, int64_t pts, int64_t P, float* partial, hipSt
             return -1;
         }
     }
-    BwdBatcher run{pts, partial, 0, stream};
+    BwdBatcher run{pts, partial, 0, stream, count};
     return jobs(run);
 }
 
 // [kind]: the backward chain kernel of each kind
 static const void* const kBwdKernels[MI_FIELD_KINDS] = {
     (const void*)nerf_bwd_kernel<false>,      // MI_FIELD_NERF
-    (const void*)siren_bwd_kernel,            // MI_FIELD_SIREN_NERF
+    (const void*)siren_bwd_kernel<false>,     // MI_FIELD_SIREN_NERF
     (const void*)film_bwd_kernel<true>,       // MI_FIELD_FILM_SIREN_NERF
     (const void*)film_bwd_kernel<false>,      // MI_FIELD_FILM_SIREN_NERF_NODIR
     (const void*)nerf_bwd_kernel<true>};      // MI_FIELD_TINY_NERF
+// ... and its counted instance (the kinds an occupancy grid exists for)
+static const void* const kCountedBwdKernels[MI_FIELD_KINDS] = {
+    (const void*)nerf_bwd_kernel<false, true>, (const void*)siren_bwd_kernel<true>, nullptr, nullptr, (const void*)nerf_bwd_kernel<true, true>};
 static_assert(kFilmDepthMax <= kMaxGemmJobs && kFilmDepthMax + 6 <= kMaxReduceJobs,
               "an image's FiLM layers are one GEMM batch and, with the thin jobs, one reduction batch");
 // [use_dir]: the run-time-depth FiLM chain (MI_FIELD_FILM_DEPTH kinds other than depth 8)
@@ -1304,6 +1380,39 @@ int launch_field_backward(int kind_in, const float* packed_bwd, const float* act
         });
         return r ? r : hb.flush_all();
     });
+}
+
+// Backward of a non-FiLM field over the first *count rows of compact acts (the list-driven training forward left them): the
+// counted chain, then the pass's weight-gradient jobs planned from the capacity P and run over the device count.  Every grid
+// is sized from P; nothing is read back.
+int launch_field_backward_list(int kind_in, const float* packed_bwd, const float* acts, float* grads, const float* raw,
+                               const float* g_raw, const int* list, const int* count, int64_t P, float* partial,
+                               float* const* gp, hipStream_t stream) {
+    if (P <= 0) return 0;
+    if (bad_kind(kind_in)) return -1;
+    const int kind = canon_kind(kind_in);
+    if (kind < 0 || kind >= MI_FIELD_KINDS || !kCountedBwdKernels[kind]) { set_error("kind %d has no counted backward", kind); return -1; }
+    const size_t lds = kLdsFloats * sizeof(float);
+    static PerDeviceOnce attr_once;
+    const int arc = attr_once.run([&]() {
+        for (const void* f : kCountedBwdKernels)
+            if (f && hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+                set_error("hipFuncSetAttribute failed"); return -2;
+            }
+        return 0;
+    });
+    if (arc) return arc;
+#ifdef MI_PROFILE_STAMPS
+    unsigned long long* stamps = g_bwd_stamps;
+#else
+    unsigned long long* stamps = nullptr;
+#endif
+    CountedBwdArgs a{{packed_bwd, acts, grads, raw, g_raw, P, nullptr, nullptr, P, (P + 127) / 128, (P + 127) / 128, stamps, 0}, list, count};
+    void* args[] = {&a};
+    (void)hipLaunchKernel(kCountedBwdKernels[kind], dim3((unsigned)((P + 127) / 128)), dim3(256), args, lds, stream);
+    if (const int rc = check_launch("backward chain (counted)")) return rc;
+    return plan_then_run(kind, P, P, partial, stream, [&](BwdBatcher& bb) { return batched_backward(kind, bb, acts, grads, gp); }, true,
+                         count);
 }
 
 static int64_t batched_partial_floats(int kind, int64_t P) {

@@ -686,6 +686,19 @@ __device__ __forceinline__ PointIn load_list_point(const MlpArgs& a, int64_t til
     return o;
 }
 
+// Row of the saved regions a point's layer inputs go to: its own row p, or - the list-driven training instance - its list
+// entry, clamped like the point itself so that every address formed from it lies inside the regions.  Lanes past the count
+// have pt.valid false (load_list_point) and every saving store is masked by it: they store nothing.
+template <bool BY_ENTRY>
+__device__ __forceinline__ int64_t list_save_row(const PointIn& pt, int64_t tile, int64_t count, int i) {
+    if constexpr (BY_ENTRY) {
+        const int64_t entry = tile * 128 + i;
+        return entry < count ? entry : count - 1;
+    } else {
+        return pt.p;
+    }
+}
+
 __device__ __forceinline__ Ctx make_ctx_raw(float* smem, const float* packed, const float* film_group) {
     Ctx c;
     c.smem = smem;

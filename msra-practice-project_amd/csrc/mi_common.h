@@ -174,12 +174,27 @@ int launch_occupancy_pack(const float* sigma, const int* dims, int k, float thre
 // (raw may be null).  n * S fits an int (the caller checks).
 int launch_occupancy_mark_rays(const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell, const float* rays,
                                const float* z, int64_t n, int S, int* list, int* count, float* raw, hipStream_t stream);
+// ... and the same list in ASCENDING order, written without atomics (a count per workgroup, a scan, a scatter): the order a
+// training step needs, whose weight-gradient sums run over the list's rows.  `list` has room for
+// occupancy_ordered_list_ints(n * S) ints: the entries, then one scan slot per workgroup.
+int64_t occupancy_ordered_list_ints(int64_t points);
+int launch_occupancy_mark_rays_ordered(const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell,
+                                       const float* rays, const float* z, int64_t n, int S, int* list, int* count, float* raw,
+                                       hipStream_t stream);
 // The inference forward over a device-counted list of point indices (NeRF, SirenNeRF, TinyNeRF: has_list_kernel): a mode-1
 // launch of one group (a.a = rays, a.z and a.out [rays_per_group * n_samples]) that evaluates point list[e] for every e below
 // *count and writes its row a.out[list[e]] alone.  The grid covers every point of the launch (host values, no read-back);
-// blocks past the count return at once.
+// blocks past the count return at once.  With a.save set it is the training forward over the list (the FWD_LIST_SAVE
+// instances): the saved rows of entry e are written at row e of every region (compact; a.save_points = the capacity, the
+// regions' stride), rows at and past the count are not written.
 bool has_list_kernel(int kind);
 int launch_mlp_list(int kind, const MlpArgs& a, const int* list, const int* count, hipStream_t stream);
+// Backward of a field over the first *count rows of compact acts (launch_mlp_list with a.save): the chain reads raw / g_raw at
+// rows list[e], writes dA rows e; the weight-gradient kernels contract rows [0, *count) in n_slabs slabs planned from the
+// capacity, each counted_slab_pts(*count, n_slabs) long.  Non-FiLM kinds.  No host read-back.
+int launch_field_backward_list(int kind, const float* packed_bwd, const float* acts, float* grads, const float* raw,
+                               const float* g_raw, const int* list, const int* count, int64_t capacity, float* partial,
+                               float* const* gp, hipStream_t stream);
 int64_t bwd_partial_floats(int64_t P);
 int64_t film_partial_floats(int64_t n_groups, int64_t points_per_group);
 int64_t bwd_partial_floats_kind(int kind, int64_t P);                      // ... of any kind (deeper FiLM kinds need more)

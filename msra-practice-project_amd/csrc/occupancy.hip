@@ -4,6 +4,7 @@
 //   occupancy_cell_points_kernel  k^3 regular sub-sample points per cell, [count k^3, 6] rows for mi_field_eval_points
 //   occupancy_threshold / dilate / pack kernels   sigma at those points -> one byte per cell, dilated, packed into words
 //   occupancy_mark_rays_kernel    reading a grid: the samples of a render pass that lie in occupied cells, as a device-counted list
+//   occupancy_mark_ordered_kernel / occupancy_scan_blocks_kernel   the same list in ascending order, without atomics (training)
 //
 // Small kernels next to the field evaluations between them (cells k^3 MLP points).  Compiled with -ffp-contract=off: a
 // sub-sample point is a chain of separately rounded operations, which a test restates in torch.
@@ -185,6 +186,94 @@ int launch_occupancy_mark_rays(const uint32_t* bits, const int* dims, const floa
     hipLaunchKernelGGL(occupancy_mark_rays_kernel, dim3((unsigned)((total + kMarkBlock - 1) / kMarkBlock)), dim3(256), 0, stream, g,
                        bits, rays, z, total, S, list, count, raw);
     return check_launch("occupancy_mark_rays");
+}
+
+// ---- the same list in ascending order, without atomics (mi_occupancy_mark_rays_ordered: training with a grid) --------------------
+// The list order is the row order of the weight-gradient sums, so it must not depend on which workgroup's atomic lands first.
+// Inside a workgroup the kernel above already writes ascending indices ((round, wave, lane) order IS point order); only the
+// workgroups' bases are timing-dependent.  Three launches replace the atomic:
+//   count   : the occupancy test, the zeroing of unlisted raw rows, one count per workgroup into blk[workgroup];
+//   scan    : one workgroup turns blk[] into exclusive offsets and writes their total to the device count;
+//   scatter : the occupancy test again (a few loads per point: cheaper than keeping 4096 bits per workgroup in memory), slots
+//             from blk[workgroup] + the (round, wave) offset + the occupied lanes below.
+// blk lies behind the list's n * S entries: one int per workgroup of kMarkBlock points (occupancy_ordered_list_ints).
+template <bool SCATTER>
+__global__ __launch_bounds__(256) void occupancy_mark_ordered_kernel(MarkArgs g, const uint32_t* __restrict__ bits,
+                                                                     const float* __restrict__ rays, const float* __restrict__ z,
+                                                                     int64_t total, int S, int* __restrict__ list, int* __restrict__ blk,
+                                                                     float* __restrict__ raw) {
+    __shared__ int offs[kMarkPerThread * 4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t p0 = (int64_t)blockIdx.x * kMarkBlock + threadIdx.x;
+    uint32_t mine = 0;                                          // bit `it`: this thread's point of round `it` is occupied
+    for (int it = 0; it < kMarkPerThread; ++it) {
+        const int64_t p = p0 + it * 256;
+        bool occ = false;
+        if (p < total) {
+            occ = point_occupied(g, bits, rays, z, p, S);
+            if (!SCATTER && !occ && raw) reinterpret_cast<float4*>(raw)[p] = float4{0.f, 0.f, 0.f, 0.f};
+        }
+        const uint64_t b = __ballot(occ);
+        if (lane == 0) offs[it * 4 + wave] = __popcll(b);
+        mine |= (uint32_t)occ << it;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int sum = 0;
+        for (int i = 0; i < kMarkPerThread * 4; ++i) { const int c = offs[i]; offs[i] = sum; sum += c; }
+        if (!SCATTER) blk[blockIdx.x] = sum;
+    }
+    if (!SCATTER) return;
+    __syncthreads();
+    const int base = blk[blockIdx.x];
+    for (int it = 0; it < kMarkPerThread; ++it) {
+        const bool occ = (mine >> it) & 1u;
+        const uint64_t b = __ballot(occ);
+        if (occ) list[base + offs[it * 4 + wave] + __popcll(b & ((1ull << lane) - 1))] = (int)(p0 + it * 256);
+    }
+}
+
+// blk[0 .. n_blocks) -> its exclusive prefix sums, their total -> *count.  One workgroup: thread t sums a run of consecutive
+// entries, thread 0 scans the 256 run sums, every thread rewrites its run (a frame's 30 000 entries are 118 per thread).
+__global__ __launch_bounds__(256) void occupancy_scan_blocks_kernel(int* __restrict__ blk, int n_blocks, int* __restrict__ count) {
+    __shared__ int part[256];
+    const int per = (n_blocks + 255) / 256, t = threadIdx.x;
+    const int lo = t * per < n_blocks ? t * per : n_blocks, hi = lo + per < n_blocks ? lo + per : n_blocks;
+    int s = 0;
+    for (int i = lo; i < hi; ++i) s += blk[i];
+    part[t] = s;
+    __syncthreads();
+    if (t == 0) {
+        int sum = 0;
+        for (int i = 0; i < 256; ++i) { const int c = part[i]; part[i] = sum; sum += c; }
+        *count = sum;
+    }
+    __syncthreads();
+    int run = part[t];
+    for (int i = lo; i < hi; ++i) { const int c = blk[i]; blk[i] = run; run += c; }
+}
+
+int64_t occupancy_ordered_list_ints(int64_t points) { return points + (points + kMarkBlock - 1) / kMarkBlock; }
+
+int launch_occupancy_mark_rays_ordered(const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell, const float* rays,
+                                       const float* z, int64_t n, int S, int* list, int* count, float* raw, hipStream_t stream) {
+    const int64_t total = n * S;
+    if (total <= 0) {
+        if (hipMemsetAsync(count, 0, sizeof(int), stream) != hipSuccess) { set_error("occupancy mark: hipMemsetAsync failed"); return -2; }
+        return 0;
+    }
+    MarkArgs g;
+    for (int d = 0; d < 3; ++d) { g.dims[d] = dims[d]; g.lo[d] = lo[d]; g.inv_cell[d] = inv_cell[d]; }
+    const int n_blocks = (int)((total + kMarkBlock - 1) / kMarkBlock);
+    int* blk = list + total;
+    hipLaunchKernelGGL(occupancy_mark_ordered_kernel<false>, dim3((unsigned)n_blocks), dim3(256), 0, stream, g, bits, rays, z, total, S,
+                       list, blk, raw);
+    if (const int rc = check_launch("occupancy_mark_ordered (count)")) return rc;
+    hipLaunchKernelGGL(occupancy_scan_blocks_kernel, dim3(1), dim3(256), 0, stream, blk, n_blocks, count);
+    if (const int rc = check_launch("occupancy_scan_blocks")) return rc;
+    hipLaunchKernelGGL(occupancy_mark_ordered_kernel<true>, dim3((unsigned)n_blocks), dim3(256), 0, stream, g, bits, rays, z, total, S,
+                       list, blk, raw);
+    return check_launch("occupancy_mark_ordered (scatter)");
 }
 
 }  // namespace mi

@@ -106,6 +106,20 @@ SIGNATURES = {
     "mi_render_rays_occupancy": (_int, [_int, _vp, _int, _vp, _vp, _i64, _f32, _f32, _int, _int, _vp, _vp, _vp, _u64, _u64,
                                         _vp, ctypes.POINTER(_int), ctypes.POINTER(_f32), ctypes.POINTER(_f32), _vp, _vp, _vp,
                                         _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "mi_occupancy_ordered_list_ints": (_i64, [_i64, _int]),
+    "mi_occupancy_mark_rays_ordered": (_int, [_vp, ctypes.POINTER(_int), ctypes.POINTER(_f32), ctypes.POINTER(_f32), _vp, _vp,
+                                              _i64, _int, _vp, _vp, _vp, _vp]),
+    "mi_field_eval_rays_list_train": (_int, [_int, _vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp]),
+    "mi_field_backward_list": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, ctypes.POINTER(_vp), _vp]),
+    "mi_render_occupancy_train_extra_bytes": (_i64, [_i64, _int, _int]),
+    "mi_render_occupancy_train_saved_bytes": (_i64, [_int, _int, _i64, _int, _int]),
+    "mi_render_occupancy_backward_workspace_bytes": (_i64, [_int, _int, _int, _i64, _int, _int]),
+    "mi_render_rays_occupancy_train": (_int, [_int, _vp, _int, _vp, _vp, _i64, _f32, _f32, _int, _int, _vp, _vp, _vp, _u64,
+                                              _u64, _vp, ctypes.POINTER(_int), ctypes.POINTER(_f32), ctypes.POINTER(_f32),
+                                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
+    "mi_render_rays_occupancy_backward": (_int, [_int, _vp, _int, _vp, _int, _vp, _i64, _int, _int, _vp, _i64, _vp, _i64,
+                                                 _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                                                 _vp, _i64, ctypes.POINTER(_int), _vp]),
 }
 
 ABI_VERSION = 4      # include/mi_render.h as of this binding (mi_abi_version() of the library must equal it)

@@ -10,7 +10,8 @@ For the kinds without FiLM (NeRF, SirenNeRF, TinyNeRF).  This module builds and 
 keyword `grid=` of render_rays / render_image / render_image_tensor / render_video (inference only): a sample whose point
 o + d * z lies in an unoccupied cell, or outside [lo, hi), counts as raw = 0 and is not evaluated (ops.render_rays_occupancy,
 mi_render_rays_occupancy).  A grid that misses cells where the field has density therefore changes the picture: build it with
-a threshold, supersampling and dilation that suit the field.
+a threshold, supersampling and dilation that suit the field.  Training with a grid is the opt-in module
+mirender.occupancy_train (render_rays(..., grid=) with a graph to the fields' parameters).
 """
 from __future__ import annotations
 

@@ -1,0 +1,164 @@
+"""Training with an occupancy grid: render_rays(..., grid=) with a graph to the two fields' parameters.
+
+    from mirender import occupancy_train
+    outs = occupancy_train.render_rays(rays, near, far, coarse, fine, 64, 128, grid=grid, seed=step)
+    loss(outs).backward()
+
+An opt-in surface, as mirender.pose is for ray gradients: render_core.render_rays(..., grid=) keeps refusing calls that need
+gradients.  The rule is the inference rule (mirender.occupancy): a sample whose point lies in an unoccupied
+cell, or outside the grid's box, has raw = 0 and is not evaluated - forward or backward.  A listed sample contributes to the
+parameter gradients exactly what it contributes without a grid, an unlisted one nothing.
+
+What that means for a training loop: A CELL THAT IS EMPTY IN THE GRID GETS NO GRADIENT AND CANNOT FILL UP UNTIL THE GRID IS
+REBUILT.  Warm-up steps without a grid, the grid's `dilate` and the rebuild period are the caller's policy
+(examples/train_nerf_occupancy.py shows one).
+
+From C: mi_render_rays_occupancy_train / mi_render_rays_occupancy_backward (include/mi_render.h).  NeRF, SirenNeRF and
+TinyNeRF fields; not built: FiLM kinds, generic callables, gradients to the rays (mirender.pose), render_image_dist.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import _lib, fields, ops, render_core
+from .occupancy import _f3, _i3
+
+
+def _grid_args(grid):
+    (_, pdims), (_, plo), (_, pinv) = _i3(grid.dims), _f3(grid.lo), _f3(grid.inv_cell)
+    return pdims, plo, pinv
+
+
+class _OccupancyRenderFn(torch.autograd.Function):
+    """One call of the pair over n rays: forward keeps the workspace (z, raw, weights, the two lists and counts) and the
+    compact saved rows; backward hands the six cotangents to mi_render_rays_occupancy_backward."""
+
+    @staticmethod
+    def forward(ctx, pf_c, pf_f, rays, near, far, nc, nf, grid, t_rand, seed, ray0, *params):
+        lib = _lib.load()
+        dev = pf_c.device
+        n = rays.shape[0]
+        shared = pf_c is pf_f
+        outs = [torch.empty(s, dtype=torch.float32, device=dev) for s in ((n, 3), (n,), (n,), (n, 3), (n,), (n,))]
+        counts = torch.zeros(2, dtype=torch.int32, device=dev)
+        ws_bytes = int(lib.mi_render_workspace_bytes(n, nc, nf) + lib.mi_render_occupancy_train_extra_bytes(n, nc, nf))
+        sv_bytes = int(lib.mi_render_occupancy_train_saved_bytes(pf_c.kind, pf_f.kind, n, nc, nf))
+        if sv_bytes < 0:
+            _lib.check(sv_bytes, "mi_render_occupancy_train_saved_bytes")
+        # owned by this call (not the shared inference workspace): the backward reads both
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        saved = torch.empty(sv_bytes, dtype=torch.uint8, device=dev)
+        zl = ops.linspace_table(near, far, nc, dev)
+        ul = ops.linspace_table(0.0, 1.0, nf, dev)
+        pdims, plo, pinv = _grid_args(grid)
+        with torch.cuda.device(dev):
+            _lib.check(lib.mi_render_rays_occupancy_train(
+                pf_c.kind, _lib.ptr(pf_c.refresh()), pf_f.kind, _lib.ptr(pf_f.refresh()), _lib.ptr(rays), n, float(near),
+                float(far), nc, nf, _lib.ptr(zl), _lib.ptr(ul), _lib.ptr(t_rand), int(seed) & (2 ** 64 - 1), int(ray0),
+                _lib.ptr(grid.bits), pdims, plo, pinv, *[_lib.ptr(o) for o in outs], _lib.ptr(counts), _lib.ptr(ws), ws_bytes,
+                _lib.ptr(saved), sv_bytes, _lib.stream_ptr(dev)), "mi_render_rays_occupancy_train")
+        ctx.pf_c, ctx.pf_f, ctx.shared, ctx.n, ctx.nc, ctx.nf = pf_c, pf_f, shared, n, nc, nf
+        ctx.rays, ctx.ws, ctx.saved, ctx.counts = rays, ws, saved, counts
+        ctx.mark_non_differentiable(counts)
+        return (*outs, counts)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_rgb_c, g_depth_c, g_acc_c, g_rgb_f, g_depth_f, g_acc_f, _g_counts=None):
+        lib = _lib.load()
+        pf_c, pf_f, n, nc, nf = ctx.pf_c, ctx.pf_f, ctx.n, ctx.nc, ctx.nf
+        dev = pf_c.device
+        gs = [None if g is None else g.to(device=dev, dtype=torch.float32).contiguous()
+              for g in (g_rgb_c, g_depth_c, g_acc_c, g_rgb_f, g_depth_f, g_acc_f)]
+        grads_c = [torch.empty_like(p) for p in pf_c.params]
+        grads_f = None if ctx.shared else [torch.empty_like(p) for p in pf_f.params]
+        arr_c = (ctypes.c_void_p * len(grads_c))(*[g.data_ptr() for g in grads_c])
+        arr_f = None if grads_f is None else (ctypes.c_void_p * len(grads_f))(*[g.data_ptr() for g in grads_f])
+        bws_bytes = int(lib.mi_render_occupancy_backward_workspace_bytes(pf_c.kind, pf_f.kind, int(ctx.shared), n, nc, nf))
+        bws = torch.empty(bws_bytes, dtype=torch.uint8, device=dev)
+        written = ctypes.c_int(0)
+        with torch.cuda.device(dev):
+            _lib.check(lib.mi_render_rays_occupancy_backward(
+                pf_c.kind, _lib.ptr(pf_c.refresh_bwd()), pf_f.kind, None if ctx.shared else _lib.ptr(pf_f.refresh_bwd()),
+                int(ctx.shared), _lib.ptr(ctx.rays), n, nc, nf, _lib.ptr(ctx.ws), ctx.ws.numel(), _lib.ptr(ctx.saved),
+                ctx.saved.numel(), *[_lib.ptr(g) for g in gs], arr_c, arr_f, _lib.ptr(bws), bws_bytes, ctypes.byref(written),
+                _lib.stream_ptr(dev)), "mi_render_rays_occupancy_backward")
+        gc = tuple(grads_c) if written.value & 1 else (None,) * len(grads_c)
+        gf = () if ctx.shared else (tuple(grads_f) if written.value & 2 else (None,) * len(grads_f))
+        return (None,) * 11 + gc + gf
+
+
+def _check(grid, coarse_model, fine_model, pf_c, pf_f, rays):
+    """What training with an occupancy grid is not built for, said by name."""
+    if pf_c is None or pf_f is None:
+        raise _lib.MiRenderError("training with an occupancy grid is not built for generic callables (models with no known "
+                                 "layout): both models must be NeRF, SirenNeRF or TinyNeRF fields")
+    if fields.is_film(pf_c.kind) or fields.is_film(pf_f.kind):
+        raise _lib.MiRenderError("training with an occupancy grid is not built for FiLM kinds (a FiLM field's table is per "
+                                 "image, a per-scene grid has no meaning there)")
+    if isinstance(rays, torch.Tensor) and rays.requires_grad and torch.is_grad_enabled():
+        raise _lib.MiRenderError("training with an occupancy grid is not built for gradients to the rays (mirender.pose "
+                                 "renders without a grid)")
+    if grid is None:
+        raise _lib.MiRenderError("occupancy_train.render_rays needs grid= (without one, call render_core.render_rays)")
+    if torch.device(grid.device) != torch.device(pf_c.device):
+        raise _lib.MiRenderError(f"the occupancy grid is on {grid.device}, the fields are on {pf_c.device}")
+
+
+def render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, fine_sample_num, *, grid, t_rand=None,
+                seed=None, ray0=0, max_points=None, return_counts=False):
+    """render_core.render_rays(..., grid=) with a graph to the two fields' parameters: (rgb_c, depth_c, acc_c, rgb_f, depth_f,
+    acc_f); with return_counts=True (not part of render_core's signature: the example and the benchmark report it) also an
+    int32 device tensor [calls, 2] of the samples each pass evaluated, under no_grad too.
+
+    max_points: the rays are cut into consecutive calls of at most max_points // (2 Nc + Nf) rays (the samples a call
+    evaluates at worst; its saved rows and workspaces are sized for them) and autograd sums the calls' gradients.  `ray0`
+    keeps the seeded jitter keyed by the absolute ray index, so the cut does not change a sample.
+    Under torch.no_grad() (or with no parameter that requires a gradient) this is render_core.render_rays(grid=).
+    A cell that is empty in `grid` gets no gradient and cannot fill up until the caller rebuilds the grid.
+    Not built: FiLM kinds, generic callables, gradients to the rays (mirender.pose), render_image_dist."""
+    pf_c, pf_f = fields.as_packed_field(coarse_model), fields.as_packed_field(fine_model)
+    _check(grid, coarse_model, fine_model, pf_c, pf_f, rays)
+    dev = pf_c.device
+    nc, nf = int(coarse_sample_num), int(fine_sample_num)
+    needs_grad = torch.is_grad_enabled() and any(p.requires_grad for p in pf_c.params + pf_f.params)
+    if not needs_grad:
+        with torch.no_grad():
+            if not return_counts:
+                return render_core.render_rays(rays, near, far, coarse_model, fine_model, nc, nf, t_rand=t_rand, seed=seed,
+                                               ray0=ray0, grid=grid)
+            # the call render_core.render_rays(grid=) makes, keeping the counts it drops: one call, so counts is [1, 2]
+            r = torch.as_tensor(rays).to(device=dev, dtype=torch.float32).reshape(-1, 2, 3).contiguous()
+            if seed is None and t_rand is None:
+                seed = render_core._fresh_seed()
+            if r.shape[0] == 0:
+                return (render_core.render_rays(r, near, far, coarse_model, fine_model, nc, nf, t_rand=t_rand, seed=seed),
+                        torch.zeros((0, 2), dtype=torch.int32, device=dev))
+            outs, counts = ops.render_rays_occupancy(pf_c, pf_f, r, near, far, nc, nf, grid, t_rand, seed or 0, ray0=ray0)
+            return outs, counts[None]
+    rays = torch.as_tensor(rays).detach().to(device=dev, dtype=torch.float32).reshape(-1, 2, 3).contiguous()
+    n = rays.shape[0]
+    if seed is None and t_rand is None:
+        seed = render_core._fresh_seed()
+    if t_rand is not None:
+        t_rand = torch.as_tensor(t_rand).detach().to(device=dev, dtype=torch.float32).contiguous()
+        if tuple(t_rand.shape) != (n, nc):
+            raise _lib.MiRenderError(f"t_rand must be [{n},{nc}]")
+    params = list(pf_c.params) if pf_c is pf_f else list(pf_c.params) + list(pf_f.params)
+    step = n if not max_points else max(1, int(max_points) // (2 * nc + nf))
+    if n == 0:                                      # no rays: render_core's empty outputs, hanging off the parameters
+        outs = render_core.render_rays(rays, near, far, coarse_model, fine_model, nc, nf, t_rand=t_rand, seed=seed, ray0=ray0)
+        return (outs, torch.zeros((0, 2), dtype=torch.int32, device=dev)) if return_counts else outs
+    pieces, counts = [], []
+    for r0 in range(0, n, max(step, 1)):
+        r1 = min(n, r0 + step)
+        res = _OccupancyRenderFn.apply(pf_c, pf_f, rays[r0:r1].contiguous(), float(near), float(far), nc, nf, grid,
+                                       None if t_rand is None else t_rand[r0:r1].contiguous(), int(seed or 0),
+                                       int(ray0) + r0, *params)
+        pieces.append(res[:6])
+        counts.append(res[6])
+    outs = pieces[0] if len(pieces) == 1 else tuple(torch.cat([p[k] for p in pieces]) for k in range(6))
+    return (outs, torch.stack(counts)) if return_counts else outs
