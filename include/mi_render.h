@@ -493,10 +493,12 @@ int mi_render_rays_occupancy(int kind_coarse, const float* packed_coarse, int ki
  * that many points, and cut the rows they have into that many equal slabs: slab length = ceil(count / slabs) rounded up to
  * a multiple of 32.  grad_params are overwritten; with *count == 0 they are exactly 0.
  *
- * mi_render_rays_occupancy_train / _backward: mi_render_rays_occupancy keeping layer inputs, and the gradients of every
- * parameter from the six output cotangents (NULL = zero; a pass without any cotangent is skipped).  One range per pass,
- * nothing recomputed: workspace = mi_render_workspace_bytes + mi_render_occupancy_train_extra_bytes (each pass keeps its
- * list), saved = mi_render_occupancy_train_saved_bytes (both passes' compact rows at worst-case capacity), bwd_workspace =
+ * mi_render_rays_occupancy_train / _backward: mi_render_rays_occupancy's sequence with the ordered mark and the list forward
+ * that keeps layer inputs, and the gradients of every parameter from the six output cotangents (NULL = zero; a pass without
+ * any cotangent is skipped).  All six outputs are required.  One range per pass, nothing recomputed: workspace =
+ * mi_render_workspace_bytes + mi_render_occupancy_train_extra_bytes (the same region behind the workspace as at inference,
+ * but with an ordered list per pass, scan slots included, where inference has one list for both: the backward reads both
+ * lists), saved = mi_render_occupancy_train_saved_bytes (both passes' compact rows at worst-case capacity), bwd_workspace =
  * mi_render_occupancy_backward_workspace_bytes; a caller with more rays than its memory allows cuts the rays into calls.
  * shared != 0: one field for both passes (packed_bwd_fine and grad_params_fine are not read); both passes run as passes of
  * that field over all their listed points and the two gradient sums are added into grad_params_coarse.  fields_written:

@@ -169,6 +169,27 @@ static int64_t occupancy_cells(const char* fn, const int* dims) {
     return cells;
 }
 
+// the one place a grid is checked: its dims first, then its three pointers
+int occupancy_grid_args(const char* fn, const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell,
+                        OccupancyGridArgs* grid) {
+    if (!occupancy_cells(fn, dims)) return MI_EINVAL;
+    if (!bits || !lo || !inv_cell) { set_error("%s: null pointer argument", fn); return MI_EINVAL; }
+    for (int d = 0; d < 3; ++d) { grid->cells.dims[d] = dims[d]; grid->cells.lo[d] = lo[d]; grid->cells.inv_cell[d] = inv_cell[d]; }
+    grid->bits = bits;
+    return MI_OK;
+}
+
+// the field at the points of a device-counted list: a mode-1 launch of one group of n rays x S samples; acts: the listed
+// points' layer inputs are kept there (training), null = inference
+int eval_rays_list(int kind, const float* packed, const float* rays, const float* z, int64_t n, int S, const int* list,
+                   const int* count, float* raw, float* acts, hipStream_t hs) {
+    MlpArgs args = {};
+    args.packed = packed; args.a = rays; args.z = z; args.out = raw;
+    args.points_per_group = n * S; args.rays_per_group = n; args.tiles_per_group = (n * S + 127) / 128;
+    args.n_samples = S; args.mode = 1; args.save = acts; args.save_points = n * S; args.n_rays = n;
+    return launch_mlp_list(kind, args, list, count, hs);
+}
+
 }  // namespace mi
 
 using namespace mi;
@@ -297,43 +318,7 @@ int mi_occupancy_pack(const float* sigma, const int* dims, int supersample, floa
     return launch_occupancy_pack(sigma, dims, supersample, threshold, dilate, bits, workspace, (hipStream_t)stream);
 }
 
-int mi_occupancy_mark_rays(const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell, const float* rays,
-                           const float* z, int64_t n, int n_samples, int* list, int* count, float* raw, void* stream) {
-    if (!occupancy_cells("mi_occupancy_mark_rays", dims)) return MI_EINVAL;
-    if (!bits || !lo || !inv_cell || !rays || !z || !list || !count) { set_error("mi_occupancy_mark_rays: null pointer argument"); return MI_EINVAL; }
-    if (n < 0 || n_samples < 1) { set_error("mi_occupancy_mark_rays: bad sizes (n >= 0, n_samples >= 1)"); return MI_EINVAL; }
-    if (n > 0x7fffffffLL / n_samples) {
-        set_error("mi_occupancy_mark_rays: n * n_samples = %lld * %d exceeds 2^31 - 1 (the list holds int point indices)", (long long)n, n_samples);
-        return MI_EINVAL;
-    }
-    return launch_occupancy_mark_rays(bits, dims, lo, inv_cell, rays, z, n, n_samples, list, count, raw, (hipStream_t)stream);
-}
-
-// the field at the points of a device-counted list: a mode-1 launch of one group of n rays x S samples
-static int eval_rays_list(int kind, const float* packed, const float* rays, const float* z, int64_t n, int S, const int* list,
-                          const int* count, float* raw, hipStream_t hs) {
-    MlpArgs args = {};
-    args.packed = packed; args.a = rays; args.z = z; args.out = raw;
-    args.points_per_group = n * S; args.rays_per_group = n; args.tiles_per_group = (n * S + 127) / 128;
-    args.n_samples = S; args.mode = 1; args.save_points = n * S; args.n_rays = n;
-    return launch_mlp_list(kind, args, list, count, hs);
-}
-
-int mi_field_eval_rays_list(int kind, const float* packed, const float* rays, const float* z, int64_t n, int n_samples,
-                            const int* list, const int* count, float* raw, void* stream) {
-    if (bad_kind(kind)) return MI_EINVAL;
-    if (!has_list_kernel(kind)) { set_error("mi_field_eval_rays_list: kind %d has no list-driven forward (NeRF, SirenNeRF, TinyNeRF have)", kind); return MI_EINVAL; }
-    if (!packed || !rays || !z || !list || !count || !raw) { set_error("mi_field_eval_rays_list: null pointer argument"); return MI_EINVAL; }
-    if (n < 0 || n_samples < 1) { set_error("mi_field_eval_rays_list: bad sizes (n >= 0, n_samples >= 1)"); return MI_EINVAL; }
-    if (n > 0x7fffffffLL / n_samples) {
-        set_error("mi_field_eval_rays_list: n * n_samples = %lld * %d exceeds 2^31 - 1 (the list holds int point indices)", (long long)n, n_samples);
-        return MI_EINVAL;
-    }
-    if (n == 0) return MI_OK;
-    return eval_rays_list(kind, packed, rays, z, n, n_samples, list, count, raw, (hipStream_t)stream);
-}
-
-// ---- training with a grid: the stages (train_path.hip holds the call pair) ---------------------------------------------------------
+// n * n_samples points whose indices fit the list's ints
 static int check_list_sizes(const char* fn, int64_t n, int n_samples) {
     if (n < 0 || n_samples < 1) { set_error("%s: bad sizes (n >= 0, n_samples >= 1)", fn); return MI_EINVAL; }
     if (n > 0x7fffffffLL / n_samples) {
@@ -343,6 +328,22 @@ static int check_list_sizes(const char* fn, int64_t n, int n_samples) {
     return MI_OK;
 }
 
+// the two marks: the atomic one (any order) and the ordered one (ascending, what training needs)
+static int mark_rays(const char* fn, bool ordered, const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell,
+                     const float* rays, const float* z, int64_t n, int n_samples, int* list, int* count, float* raw, void* stream) {
+    OccupancyGridArgs grid;
+    if (int rc = occupancy_grid_args(fn, bits, dims, lo, inv_cell, &grid)) return rc;
+    if (!rays || !z || !list || !count) { set_error("%s: null pointer argument", fn); return MI_EINVAL; }
+    if (int rc = check_list_sizes(fn, n, n_samples)) return rc;
+    return (ordered ? launch_occupancy_mark_rays_ordered : launch_occupancy_mark_rays)(grid, rays, z, n, n_samples, list, count, raw,
+                                                                                      (hipStream_t)stream);
+}
+
+int mi_occupancy_mark_rays(const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell, const float* rays,
+                           const float* z, int64_t n, int n_samples, int* list, int* count, float* raw, void* stream) {
+    return mark_rays("mi_occupancy_mark_rays", false, bits, dims, lo, inv_cell, rays, z, n, n_samples, list, count, raw, stream);
+}
+
 int64_t mi_occupancy_ordered_list_ints(int64_t n, int n_samples) {
     if (check_list_sizes("mi_occupancy_ordered_list_ints", n, n_samples)) return MI_EINVAL;
     return occupancy_ordered_list_ints(n * n_samples);
@@ -350,26 +351,28 @@ int64_t mi_occupancy_ordered_list_ints(int64_t n, int n_samples) {
 
 int mi_occupancy_mark_rays_ordered(const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell, const float* rays,
                                    const float* z, int64_t n, int n_samples, int* list, int* count, float* raw, void* stream) {
-    const char* fn = "mi_occupancy_mark_rays_ordered";
-    if (!occupancy_cells(fn, dims)) return MI_EINVAL;
-    if (!bits || !lo || !inv_cell || !rays || !z || !list || !count) { set_error("%s: null pointer argument", fn); return MI_EINVAL; }
+    return mark_rays("mi_occupancy_mark_rays_ordered", true, bits, dims, lo, inv_cell, rays, z, n, n_samples, list, count, raw, stream);
+}
+
+// the two list-driven forwards: inference (acts null) and the one that keeps the listed points' layer inputs
+static int eval_rays_list_checked(const char* fn, bool train, int kind, const float* packed, const float* rays, const float* z,
+                                  int64_t n, int n_samples, const int* list, const int* count, float* raw, float* acts, void* stream) {
+    if (bad_kind(kind)) return MI_EINVAL;
+    if (!has_list_kernel(kind)) { set_error("%s: kind %d has no list-driven forward (NeRF, SirenNeRF, TinyNeRF have)", fn, kind); return MI_EINVAL; }
+    if (!packed || !rays || !z || !list || !count || !raw || (train && !acts)) { set_error("%s: null pointer argument", fn); return MI_EINVAL; }
     if (int rc = check_list_sizes(fn, n, n_samples)) return rc;
-    return launch_occupancy_mark_rays_ordered(bits, dims, lo, inv_cell, rays, z, n, n_samples, list, count, raw, (hipStream_t)stream);
+    if (n == 0) return MI_OK;
+    return eval_rays_list(kind, packed, rays, z, n, n_samples, list, count, raw, acts, (hipStream_t)stream);
+}
+
+int mi_field_eval_rays_list(int kind, const float* packed, const float* rays, const float* z, int64_t n, int n_samples,
+                            const int* list, const int* count, float* raw, void* stream) {
+    return eval_rays_list_checked("mi_field_eval_rays_list", false, kind, packed, rays, z, n, n_samples, list, count, raw, nullptr, stream);
 }
 
 int mi_field_eval_rays_list_train(int kind, const float* packed, const float* rays, const float* z, int64_t n, int n_samples,
                                   const int* list, const int* count, float* raw, float* acts, void* stream) {
-    const char* fn = "mi_field_eval_rays_list_train";
-    if (bad_kind(kind)) return MI_EINVAL;
-    if (!has_list_kernel(kind)) { set_error("%s: kind %d has no list-driven forward (NeRF, SirenNeRF, TinyNeRF have)", fn, kind); return MI_EINVAL; }
-    if (!packed || !rays || !z || !list || !count || !raw || !acts) { set_error("%s: null pointer argument", fn); return MI_EINVAL; }
-    if (int rc = check_list_sizes(fn, n, n_samples)) return rc;
-    if (n == 0) return MI_OK;
-    MlpArgs args = {};
-    args.packed = packed; args.a = rays; args.z = z; args.out = raw;
-    args.points_per_group = n * n_samples; args.rays_per_group = n; args.tiles_per_group = (n * n_samples + 127) / 128;
-    args.n_samples = n_samples; args.mode = 1; args.save = acts; args.save_points = n * n_samples; args.n_rays = n;
-    return launch_mlp_list(kind, args, list, count, (hipStream_t)stream);
+    return eval_rays_list_checked("mi_field_eval_rays_list_train", true, kind, packed, rays, z, n, n_samples, list, count, raw, acts, stream);
 }
 
 int mi_field_backward_list(int kind, const float* packed_bwd, const float* acts, float* grads_ws, const float* raw,
@@ -387,67 +390,6 @@ int mi_field_backward_list(int kind, const float* packed_bwd, const float* acts,
         if (!grad_params[i]) { set_error("%s: gradient pointer %d is null", fn, i); return MI_EINVAL; }
     return launch_field_backward_list(kind, packed_bwd, acts, grads_ws, raw, g_raw, list, count, capacity, partial_ws, grad_params,
                                       (hipStream_t)stream);
-}
-
-// the region behind mi_render_workspace_bytes that rendering with a grid adds: one list [n * S] of ints, then the two counts
-static int64_t occupancy_list_floats(int64_t n, int S) { return align64(n * S); }
-int64_t mi_render_occupancy_extra_bytes(int64_t n, int n_coarse, int n_fine) {
-    if (n <= 0 || n_coarse < 1 || n_fine < 0) return 0;
-    return (occupancy_list_floats(n, n_coarse + n_fine) + align64(2)) * (int64_t)sizeof(float);
-}
-
-int mi_render_rays_occupancy(int kind_coarse, const float* packed_coarse, int kind_fine, const float* packed_fine,
-                             const float* rays, int64_t n, float near_, float far_, int n_coarse, int n_fine,
-                             const float* z_lin, const float* u_lin, const float* t_rand, uint64_t seed, uint64_t ray0,
-                             const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell, float* rgb_c,
-                             float* depth_c, float* acc_c, float* rgb_f, float* depth_f, float* acc_f, int* evaluated,
-                             void* workspace, int64_t workspace_bytes, void* stream) {
-    const char* fn = "mi_render_rays_occupancy";
-    if (n < 0 || n_coarse < 3 || n_fine < 0) { set_error("%s: bad sizes (n >= 0, Nc >= 3, Nf >= 0)", fn); return MI_EINVAL; }
-    if (bad_kind(kind_coarse) || bad_kind(kind_fine)) return MI_EINVAL;
-    if (!has_list_kernel(kind_coarse) || !has_list_kernel(kind_fine)) {
-        set_error("%s: kinds %d / %d: rendering with a grid is built for NeRF, SirenNeRF and TinyNeRF, not for FiLM kinds", fn, kind_coarse, kind_fine);
-        return MI_EINVAL;
-    }
-    if (!occupancy_cells(fn, dims)) return MI_EINVAL;
-    if (!packed_coarse || !packed_fine || !rays || !bits || !lo || !inv_cell || !workspace || (rgb_c && (!depth_c || !acc_c)) ||
-        !rgb_f || !depth_f || !acc_f) {
-        set_error("%s: null pointer argument", fn);
-        return MI_EINVAL;
-    }
-    const int S = n_coarse + n_fine;
-    if (n > 0x7fffffffLL / S) {
-        set_error("%s: n * (Nc + Nf) = %lld * %d exceeds 2^31 - 1 (the list holds int point indices)", fn, (long long)n, S);
-        return MI_EINVAL;
-    }
-    if (n == 0) return MI_OK;                                  // no rays: nothing to launch, no buffer is touched
-    const RenderWorkspace layout(n, n_coarse, n_fine);
-    const int64_t base_bytes = layout.base_bytes(), need = base_bytes + mi_render_occupancy_extra_bytes(n, n_coarse, n_fine);
-    if (workspace_bytes < need) {
-        set_error("%s: workspace of %lld bytes, mi_render_workspace_bytes + mi_render_occupancy_extra_bytes say %lld", fn,
-                  (long long)workspace_bytes, (long long)need);
-        return MI_EINVAL;
-    }
-    const RenderWorkspace::Regions ws = layout.carve(workspace);
-    int* list = (int*)((char*)workspace + base_bytes);
-    int* counts = list + occupancy_list_floats(n, S);
-    hipStream_t hs = (hipStream_t)stream;
-    int rc;
-    if ((rc = mi_sample_coarse(n, near_, far_, n_coarse, z_lin, t_rand, seed, ray0, ws.z_c, stream))) return rc;
-    if ((rc = launch_occupancy_mark_rays(bits, dims, lo, inv_cell, rays, ws.z_c, n, n_coarse, list, counts, ws.raw_c, hs))) return rc;
-    if ((rc = eval_rays_list(kind_coarse, packed_coarse, rays, ws.z_c, n, n_coarse, list, counts, ws.raw_c, hs))) return rc;
-    if (rgb_c) rc = mi_composite(n, n_coarse, ws.raw_c, ws.z_c, rays, rgb_c, depth_c, acc_c, ws.w_c, stream);
-    else rc = launch_composite_weights(n, n_coarse, ws.raw_c + 3, 4, ws.z_c, rays, depth_c, acc_c, ws.w_c, hs);   // raw's sigma channel
-    if (rc) return rc;
-    if ((rc = mi_sample_fine(n, near_, far_, n_coarse, n_fine, z_lin, u_lin, ws.z_c, ws.w_c, nullptr, ws.z_f, stream))) return rc;
-    if ((rc = launch_occupancy_mark_rays(bits, dims, lo, inv_cell, rays, ws.z_f, n, S, list, counts + 1, ws.raw_f, hs))) return rc;
-    if ((rc = eval_rays_list(kind_fine, packed_fine, rays, ws.z_f, n, S, list, counts + 1, ws.raw_f, hs))) return rc;
-    if ((rc = mi_composite(n, S, ws.raw_f, ws.z_f, rays, rgb_f, depth_f, acc_f, nullptr, stream))) return rc;
-    if (evaluated && hipMemcpyAsync(evaluated, counts, 2 * sizeof(int), hipMemcpyDeviceToDevice, hs) != hipSuccess) {
-        set_error("%s: copy of the evaluated counts failed", fn);
-        return MI_EHIP;
-    }
-    return MI_OK;
 }
 
 int mi_gen_rays(int width, int height, double focal, const float* c2w_host, int64_t ray0, int64_t n, float* rays,

@@ -27,6 +27,7 @@ SOURCES = {
     "adam_step.hip": [],
     "mesh_stages.hip": [],
     "train_path.hip": [],
+    "occupancy_path.hip": [],
     "api.hip": [],
 }
 HEADERS = ["field_layout.h", "field_kinds.h", "mi_common.h", "mesh_cube.h", "mi_math.h", "field_mlp_device.h", os.path.join("..", "..", "include", "mi_render.h")]

@@ -1286,6 +1286,31 @@ static_assert(kFilmDepthMax <= kMaxGemmJobs && kFilmDepthMax + 6 <= kMaxReduceJo
 // [use_dir]: the run-time-depth FiLM chain (MI_FIELD_FILM_DEPTH kinds other than depth 8)
 static const void* const kFilmDepthBwdKernels[2] = {(const void*)film_bwd_kernel<false, true>, (const void*)film_bwd_kernel<true, true>};
 
+// Launches one chain kernel over `blocks` tiles.  The dynamic-LDS attribute of every chain instance is set the first time a
+// device is seen; the stamps pointer is the diagnostic build's.  `a` is the kernel's whole argument block: a BwdArgs, or the
+// CountedBwdArgs it is the base (and so the first bytes) of.
+static int launch_chain(const void* kernel, BwdArgs& a, unsigned blocks, const char* what, hipStream_t stream) {
+    const size_t lds = kLdsFloats * sizeof(float);
+    static PerDeviceOnce attr_once;
+    const int arc = attr_once.run([&]() {
+        const struct { const void* const* kernels; int n; } tables[] = {
+            {kBwdKernels, MI_FIELD_KINDS}, {kCountedBwdKernels, MI_FIELD_KINDS}, {kFilmDepthBwdKernels, 2}};
+        for (const auto& t : tables)
+            for (int i = 0; i < t.n; ++i)                // null: a kind without a counted instance
+                if (t.kernels[i] && hipFuncSetAttribute(t.kernels[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+                    set_error("hipFuncSetAttribute failed"); return -2;
+                }
+        return 0;
+    });
+    if (arc) return arc;
+#ifdef MI_PROFILE_STAMPS
+    a.stamps = g_bwd_stamps;
+#endif
+    void* args[] = {&a};
+    (void)hipLaunchKernel(kernel, dim3(blocks), dim3(256), args, lds, stream);
+    return check_launch(what);
+}
+
 // Backward of a field over P points.  grad_params[2i], [2i+1]: device pointers to the weight /
 // bias gradient tensors (torch layout), overwritten.
 int launch_field_backward(int kind_in, const float* packed_bwd, const float* acts, float* grads, const float* raw,
@@ -1296,39 +1321,18 @@ int launch_field_backward(int kind_in, const float* packed_bwd, const float* act
     if (P <= 0) return 0;
     if (bad_kind(kind_in)) return -1;
     const int kind = canon_kind(kind_in);
-    const size_t lds = kLdsFloats * sizeof(float);
-    static PerDeviceOnce attr_once;
-    const int arc = attr_once.run([&]() {
-        for (const void* f : kBwdKernels)
-            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-                set_error("hipFuncSetAttribute failed"); return -2;
-            }
-        for (const void* f : kFilmDepthBwdKernels)
-            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-                set_error("hipFuncSetAttribute failed"); return -2;
-            }
-        return 0;
-    });
-    if (arc) return arc;
     const bool film_kind = is_film(kind);
     if (film_kind && (!film || !film_partial || !grad_film || !params)) {
         set_error("FiLM backward needs film, the FiLM scratch, grad_film and the parameter pointers");
         return -1;
     }
     const int64_t tpg = (points_per_group + 127) / 128;
-#ifdef MI_PROFILE_STAMPS
-    unsigned long long* stamps = g_bwd_stamps;
-#else
-    unsigned long long* stamps = nullptr;
-#endif
     const int L = film_depth(kind);                      // hidden_layers of a FiLM kind: FiLM layers 0..L
-    BwdArgs a{packed_bwd, acts, grads, raw, g_raw, P, film, film_partial, points_per_group, tpg, n_groups * tpg, stamps, L};
+    BwdArgs a{packed_bwd, acts, grads, raw, g_raw, P, film, film_partial, points_per_group, tpg, n_groups * tpg, nullptr, L};
     const unsigned blocks = (unsigned)(film_kind ? n_groups * tpg : (P + 127) / 128);
-    void* args[] = {&a};
-    (void)hipLaunchKernel(is_depth_kind(kind) ? kFilmDepthBwdKernels[film_use_dir(kind)] : kBwdKernels[kind], dim3(blocks),
-                          dim3(256), args, lds, stream);
     int rc;
-    if ((rc = check_launch("backward chain"))) return rc;
+    if ((rc = launch_chain(is_depth_kind(kind) ? kFilmDepthBwdKernels[film_use_dir(kind)] : kBwdKernels[kind], a, blocks,
+                           "backward chain", stream))) return rc;
     if (!film_kind)
         return plan_then_run(kind, P, P, partial, stream, [&](BwdBatcher& bb) { return batched_backward(kind, bb, acts, grads, gp); });
 
@@ -1392,25 +1396,8 @@ int launch_field_backward_list(int kind_in, const float* packed_bwd, const float
     if (bad_kind(kind_in)) return -1;
     const int kind = canon_kind(kind_in);
     if (kind < 0 || kind >= MI_FIELD_KINDS || !kCountedBwdKernels[kind]) { set_error("kind %d has no counted backward", kind); return -1; }
-    const size_t lds = kLdsFloats * sizeof(float);
-    static PerDeviceOnce attr_once;
-    const int arc = attr_once.run([&]() {
-        for (const void* f : kCountedBwdKernels)
-            if (f && hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-                set_error("hipFuncSetAttribute failed"); return -2;
-            }
-        return 0;
-    });
-    if (arc) return arc;
-#ifdef MI_PROFILE_STAMPS
-    unsigned long long* stamps = g_bwd_stamps;
-#else
-    unsigned long long* stamps = nullptr;
-#endif
-    CountedBwdArgs a{{packed_bwd, acts, grads, raw, g_raw, P, nullptr, nullptr, P, (P + 127) / 128, (P + 127) / 128, stamps, 0}, list, count};
-    void* args[] = {&a};
-    (void)hipLaunchKernel(kCountedBwdKernels[kind], dim3((unsigned)((P + 127) / 128)), dim3(256), args, lds, stream);
-    if (const int rc = check_launch("backward chain (counted)")) return rc;
+    CountedBwdArgs a{{packed_bwd, acts, grads, raw, g_raw, P, nullptr, nullptr, P, (P + 127) / 128, (P + 127) / 128, nullptr, 0}, list, count};
+    if (const int rc = launch_chain(kCountedBwdKernels[kind], a, (unsigned)((P + 127) / 128), "backward chain (counted)", stream)) return rc;
     return plan_then_run(kind, P, P, partial, stream, [&](BwdBatcher& bb) { return batched_backward(kind, bb, acts, grads, gp); }, true,
                          count);
 }

@@ -169,18 +169,23 @@ int launch_occupancy_cell_points(const int* dims, const float* lo, const float* 
 int64_t occupancy_pack_workspace_bytes(int64_t cells, int dilate);
 int launch_occupancy_pack(const float* sigma, const int* dims, int k, float threshold, int dilate, uint32_t* bits,
                           void* workspace, hipStream_t stream);
-// ... and reading one: the samples of n rays x S depths that lie in occupied cells, appended to `list` (point indices ray * S + k,
+// ... and reading one.  A grid as the kernels take it: box and cells by value (MarkArgs, a kernel argument) and the device words.
+// occupancy_grid_args (api.hip) is the one place a caller's grid is checked (dims first, then the pointers) and copied into one.
+struct MarkArgs { int dims[3]; float lo[3], inv_cell[3]; };
+struct OccupancyGridArgs { MarkArgs cells; const uint32_t* bits; };
+int occupancy_grid_args(const char* fn, const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell,
+                        OccupancyGridArgs* grid);
+// The samples of n rays x S depths that lie in occupied cells, appended to `list` (point indices ray * S + k,
 // any order) and counted in the device int `count`, which the call clears; the raw rows [n*S][4] of the others are zeroed
 // (raw may be null).  n * S fits an int (the caller checks).
-int launch_occupancy_mark_rays(const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell, const float* rays,
-                               const float* z, int64_t n, int S, int* list, int* count, float* raw, hipStream_t stream);
+int launch_occupancy_mark_rays(const OccupancyGridArgs& grid, const float* rays, const float* z, int64_t n, int S, int* list,
+                               int* count, float* raw, hipStream_t stream);
 // ... and the same list in ASCENDING order, written without atomics (a count per workgroup, a scan, a scatter): the order a
 // training step needs, whose weight-gradient sums run over the list's rows.  `list` has room for
 // occupancy_ordered_list_ints(n * S) ints: the entries, then one scan slot per workgroup.
 int64_t occupancy_ordered_list_ints(int64_t points);
-int launch_occupancy_mark_rays_ordered(const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell,
-                                       const float* rays, const float* z, int64_t n, int S, int* list, int* count, float* raw,
-                                       hipStream_t stream);
+int launch_occupancy_mark_rays_ordered(const OccupancyGridArgs& grid, const float* rays, const float* z, int64_t n, int S, int* list,
+                                       int* count, float* raw, hipStream_t stream);
 // The inference forward over a device-counted list of point indices (NeRF, SirenNeRF, TinyNeRF: has_list_kernel): a mode-1
 // launch of one group (a.a = rays, a.z and a.out [rays_per_group * n_samples]) that evaluates point list[e] for every e below
 // *count and writes its row a.out[list[e]] alone.  The grid covers every point of the launch (host values, no read-back);
@@ -189,12 +194,19 @@ int launch_occupancy_mark_rays_ordered(const uint32_t* bits, const int* dims, co
 // regions' stride), rows at and past the count are not written.
 bool has_list_kernel(int kind);
 int launch_mlp_list(int kind, const MlpArgs& a, const int* list, const int* count, hipStream_t stream);
+// api.hip: launch_mlp_list over one group of n rays x S samples; acts null = inference, else the saved rows' destination
+int eval_rays_list(int kind, const float* packed, const float* rays, const float* z, int64_t n, int S, const int* list,
+                   const int* count, float* raw, float* acts, hipStream_t stream);
 // Backward of a field over the first *count rows of compact acts (launch_mlp_list with a.save): the chain reads raw / g_raw at
 // rows list[e], writes dA rows e; the weight-gradient kernels contract rows [0, *count) in n_slabs slabs planned from the
 // capacity, each counted_slab_pts(*count, n_slabs) long.  Non-FiLM kinds.  No host read-back.
 int launch_field_backward_list(int kind, const float* packed_bwd, const float* acts, float* grads, const float* raw,
                                const float* g_raw, const int* list, const int* count, int64_t capacity, float* partial,
                                float* const* gp, hipStream_t stream);
+// train_path.hip: a scratch copy of a kind's parameter gradients (its floats; its tensors, out[2 * n_layers]); dst[i] += src[i]
+int64_t param_floats(int kind);
+void scratch_params(int kind, float* base, float** out);
+int add_param_grads(int kind, float* const* dst, float* const* src, hipStream_t stream);
 int64_t bwd_partial_floats(int64_t P);
 int64_t film_partial_floats(int64_t n_groups, int64_t points_per_group);
 int64_t bwd_partial_floats_kind(int kind, int64_t P);                      // ... of any kind (deeper FiLM kinds need more)

@@ -110,9 +110,7 @@ int launch_occupancy_pack(const float* sigma, const int* dims, int k, float thre
     return check_launch("occupancy_pack");
 }
 
-// ---- reading a grid: which samples of a pass are evaluated (mi_occupancy_mark_rays) ---------------------------------------------
-struct MarkArgs { int dims[3]; float lo[3], inv_cell[3]; };
-
+// ---- reading a grid: which samples of a pass are evaluated (mi_occupancy_mark_rays; MarkArgs: mi_common.h) ----------------------
 // The rule every layer of rendering with a grid is tested against.  The point is the one the fused forward evaluates
 // (field_mlp_device.h: load_point, p = o + d z, a multiply and an add), placed by t = (p - lo) * inv_cell (a subtract and a
 // multiply); inside iff 0 <= t < G on every axis, so a NaN is not inside; its cell is floor(t).
@@ -176,15 +174,13 @@ __global__ __launch_bounds__(256) void occupancy_mark_rays_kernel(MarkArgs g, co
     }
 }
 
-int launch_occupancy_mark_rays(const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell, const float* rays,
-                               const float* z, int64_t n, int S, int* list, int* count, float* raw, hipStream_t stream) {
+int launch_occupancy_mark_rays(const OccupancyGridArgs& grid, const float* rays, const float* z, int64_t n, int S, int* list,
+                               int* count, float* raw, hipStream_t stream) {
     if (hipMemsetAsync(count, 0, sizeof(int), stream) != hipSuccess) { set_error("occupancy mark: hipMemsetAsync failed"); return -2; }
     const int64_t total = n * S;
     if (total <= 0) return 0;
-    MarkArgs g;
-    for (int d = 0; d < 3; ++d) { g.dims[d] = dims[d]; g.lo[d] = lo[d]; g.inv_cell[d] = inv_cell[d]; }
-    hipLaunchKernelGGL(occupancy_mark_rays_kernel, dim3((unsigned)((total + kMarkBlock - 1) / kMarkBlock)), dim3(256), 0, stream, g,
-                       bits, rays, z, total, S, list, count, raw);
+    hipLaunchKernelGGL(occupancy_mark_rays_kernel, dim3((unsigned)((total + kMarkBlock - 1) / kMarkBlock)), dim3(256), 0, stream,
+                       grid.cells, grid.bits, rays, z, total, S, list, count, raw);
     return check_launch("occupancy_mark_rays");
 }
 
@@ -255,24 +251,22 @@ __global__ __launch_bounds__(256) void occupancy_scan_blocks_kernel(int* __restr
 
 int64_t occupancy_ordered_list_ints(int64_t points) { return points + (points + kMarkBlock - 1) / kMarkBlock; }
 
-int launch_occupancy_mark_rays_ordered(const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell, const float* rays,
-                                       const float* z, int64_t n, int S, int* list, int* count, float* raw, hipStream_t stream) {
+int launch_occupancy_mark_rays_ordered(const OccupancyGridArgs& grid, const float* rays, const float* z, int64_t n, int S, int* list,
+                                       int* count, float* raw, hipStream_t stream) {
     const int64_t total = n * S;
     if (total <= 0) {
         if (hipMemsetAsync(count, 0, sizeof(int), stream) != hipSuccess) { set_error("occupancy mark: hipMemsetAsync failed"); return -2; }
         return 0;
     }
-    MarkArgs g;
-    for (int d = 0; d < 3; ++d) { g.dims[d] = dims[d]; g.lo[d] = lo[d]; g.inv_cell[d] = inv_cell[d]; }
     const int n_blocks = (int)((total + kMarkBlock - 1) / kMarkBlock);
     int* blk = list + total;
-    hipLaunchKernelGGL(occupancy_mark_ordered_kernel<false>, dim3((unsigned)n_blocks), dim3(256), 0, stream, g, bits, rays, z, total, S,
-                       list, blk, raw);
+    hipLaunchKernelGGL(occupancy_mark_ordered_kernel<false>, dim3((unsigned)n_blocks), dim3(256), 0, stream, grid.cells, grid.bits, rays, z,
+                       total, S, list, blk, raw);
     if (const int rc = check_launch("occupancy_mark_ordered (count)")) return rc;
     hipLaunchKernelGGL(occupancy_scan_blocks_kernel, dim3(1), dim3(256), 0, stream, blk, n_blocks, count);
     if (const int rc = check_launch("occupancy_scan_blocks")) return rc;
-    hipLaunchKernelGGL(occupancy_mark_ordered_kernel<true>, dim3((unsigned)n_blocks), dim3(256), 0, stream, g, bits, rays, z, total, S,
-                       list, blk, raw);
+    hipLaunchKernelGGL(occupancy_mark_ordered_kernel<true>, dim3((unsigned)n_blocks), dim3(256), 0, stream, grid.cells, grid.bits, rays, z,
+                       total, S, list, blk, raw);
     return check_launch("occupancy_mark_ordered (scatter)");
 }
 

@@ -1,0 +1,287 @@
+// occupancy_path.hip - rendering and training with an occupancy grid through the C ABI (include/mi_render.h):
+// mi_render_rays_occupancy, mi_render_rays_occupancy_train, mi_render_rays_occupancy_backward and their size queries.
+// One sequence (run_passes) serves both forwards: per pass, mark the samples in occupied cells into a device-counted list,
+// evaluate the field at the listed points alone, composite.  Training differs in three values: the ordered mark, a field that
+// keeps the listed points' layer inputs, and a list per pass (OccLists), which the backward reads.  It is deliberately small:
+// one range per pass, nothing recomputed, one group, no FiLM; one field for both passes runs as two passes of that field over
+// all their listed points (no merge, as at inference) and its two gradient sums are added.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/mi_render.h"
+#include "field_kinds.h"
+#include "mi_common.h"
+
+namespace mi {
+
+// The region behind RenderWorkspace::base_bytes(), in ints, each part on a 64-int block.  Inference: one list of n (Nc + Nf)
+// ints that the passes fill in turn.  Training: an ascending list per pass, each with its scan slots
+// (occupancy_ordered_list_ints).  Then the two counts.
+struct OccLists {
+    struct Regions { int* list[2]; int* counts; };
+    int64_t ints[2];                                     // ints[1] == 0: the fine pass reuses the coarse pass's list
+    OccLists(bool training, int64_t n, int nc, int nf) {
+        const int64_t pc = n * nc, pf = n * ((int64_t)nc + nf);
+        ints[0] = align64(training ? occupancy_ordered_list_ints(pc) : pf);
+        ints[1] = training ? align64(occupancy_ordered_list_ints(pf)) : 0;
+    }
+    int64_t bytes() const { return (ints[0] + ints[1] + align64(2)) * (int64_t)sizeof(int); }
+    Regions carve(const void* workspace, int64_t base_bytes) const {
+        int* first = (int*)((char*)const_cast<void*>(workspace) + base_bytes);
+        return {{first, ints[1] ? first + ints[0] : first}, first + ints[0] + ints[1]};
+    }
+};
+
+// the backward workspace, in floats: dL/d(raw) of both composites, one pass's dA rows and dW scratch, one field: the fine
+// pass's parameter gradients
+struct OccBwdLayout {
+    int64_t g_raw_c, g_raw_f, grads, partial, fine_total, total;
+    OccBwdLayout(int kind_c, int kind_f, bool shared, int64_t n, int nc, int nf) {
+        const int64_t pc = n * nc, pf = n * ((int64_t)nc + nf);
+        int64_t f = 0;
+        auto take = [&](int64_t x) { const int64_t o = f; f += align64(x); return o; };
+        const int64_t gc = pc * region_total(field_kind(kind_c).grads), gf = pf * region_total(field_kind(kind_f).grads);
+        const int64_t bc = bwd_partial_floats_kind(kind_c, pc), bf = bwd_partial_floats_kind(kind_f, pf);
+        g_raw_c = take(pc * 4);
+        g_raw_f = take(pf * 4);
+        grads = take(gc > gf ? gc : gf);
+        partial = take(bc > bf ? bc : bf);
+        fine_total = take(shared ? param_floats(kind_c) : 0);
+        total = f;
+    }
+    int64_t bytes() const { return total * (int64_t)sizeof(float); }
+};
+
+// the compact saved rows of the coarse pass; the fine pass's follow them
+static int64_t saved_floats_coarse(int kind_c, int64_t n, int nc) { return region_total(field_kind(kind_c).acts) * n * nc; }
+static int64_t saved_bytes_of(int kind_c, int kind_f, int64_t n, int nc, int nf) {
+    return 4 * (saved_floats_coarse(kind_c, n, nc) + region_total(field_kind(kind_f).acts) * n * ((int64_t)nc + nf));
+}
+
+// Sizes, kinds, the list kernels, the int bound on a pass's points and - where the call reads one (grid non-null) - the grid.
+// doing: "rendering" / "training", the word in which the two calls' FiLM messages differ.
+static int check_call(const char* fn, const char* doing, int kind_c, int kind_f, int64_t n, int nc, int nf, const uint32_t* bits = nullptr,
+                      const int* dims = nullptr, const float* lo = nullptr, const float* inv_cell = nullptr, OccupancyGridArgs* grid = nullptr) {
+    if (n < 0 || nc < 3 || nf < 0) { set_error("%s: bad sizes (n >= 0, Nc >= 3, Nf >= 0)", fn); return MI_EINVAL; }
+    if (bad_kind(kind_c) || bad_kind(kind_f)) return MI_EINVAL;
+    if (!has_list_kernel(kind_c) || !has_list_kernel(kind_f)) {
+        set_error("%s: kinds %d / %d: %s with a grid is built for NeRF, SirenNeRF and TinyNeRF, not for FiLM kinds", fn, kind_c, kind_f, doing);
+        return MI_EINVAL;
+    }
+    if (n > 0x7fffffffLL / (nc + nf)) {
+        set_error("%s: n * (Nc + Nf) = %lld * %d exceeds 2^31 - 1 (the list holds int point indices)", fn, (long long)n, nc + nf);
+        return MI_EINVAL;
+    }
+    return grid ? occupancy_grid_args(fn, bits, dims, lo, inv_cell, grid) : MI_OK;
+}
+
+// The caller's buffers against the size queries: the workspace always, the saved rows from the training forward on, the
+// backward workspace in the backward.
+enum OccCall { OCC_RENDER, OCC_TRAIN, OCC_BACKWARD };
+static int check_buffers(const char* fn, OccCall call, int kind_c, int kind_f, bool shared, int64_t n, int nc, int nf,
+                         const void* workspace, int64_t workspace_bytes, const void* saved = nullptr, int64_t saved_bytes = 0,
+                         const void* bwd_workspace = nullptr, int64_t bwd_workspace_bytes = 0) {
+    const auto refused = [&](const char* what, const void* p, int64_t have, int64_t need, const char* query) {
+        if (p && have >= need) return false;
+        set_error("%s: %s of %lld bytes, %s %lld", fn, what, (long long)have, query, (long long)need);
+        return true;
+    };
+    const bool train = call != OCC_RENDER;
+    if (refused("workspace", workspace, workspace_bytes, RenderWorkspace(n, nc, nf).base_bytes() + OccLists(train, n, nc, nf).bytes(),
+                train ? "mi_render_workspace_bytes + mi_render_occupancy_train_extra_bytes say"
+                      : "mi_render_workspace_bytes + mi_render_occupancy_extra_bytes say") ||
+        (train && refused("saved buffer", saved, saved_bytes, saved_bytes_of(kind_c, kind_f, n, nc, nf),
+                          "mi_render_occupancy_train_saved_bytes says")) ||
+        (call == OCC_BACKWARD && refused("backward workspace", bwd_workspace, bwd_workspace_bytes,
+                                         OccBwdLayout(kind_c, kind_f, shared, n, nc, nf).bytes(),
+                                         "mi_render_occupancy_backward_workspace_bytes says")))
+        return MI_EINVAL;
+    return MI_OK;
+}
+
+// Refuses grid words that the runtime knows as memory of ANOTHER device; what it cannot classify is left to the launch.
+static int check_grid_device(const char* fn, const uint32_t* bits) {
+    hipPointerAttribute_t attr;
+    int dev = 0;
+    if (hipPointerGetAttributes(&attr, bits) != hipSuccess || hipGetDevice(&dev) != hipSuccess) {
+        (void)hipGetLastError();
+        return MI_OK;
+    }
+    if (attr.type == hipMemoryTypeDevice && attr.device != dev) {
+        set_error("%s: the occupancy grid is on device %d, the call runs on device %d", fn, attr.device, dev);
+        return MI_EINVAL;
+    }
+    return MI_OK;
+}
+
+// one pass of the sequence: its field, where its list and count go, and where the listed points' layer inputs go (null: inference)
+struct OccPass { int kind; const float* packed; int* list; int* count; float* acts; };
+
+// The grid-driven sequence: sample coarse, mark, list-driven field, composite, sample fine, mark, list-driven field, composite,
+// copy the counts.  Everything is already checked; launches only, grids from host values (no read-back).  out: rgb_c, depth_c,
+// acc_c, rgb_f, depth_f, acc_f; without rgb_c the coarse composite gives the weights alone (depth_c / acc_c where asked for).
+static int run_passes(const char* fn, const OccPass pass[2], bool ordered, const OccupancyGridArgs& grid, const float* rays,
+                      int64_t n, float near_, float far_, int nc, int nf, const float* z_lin, const float* u_lin,
+                      const float* t_rand, uint64_t seed, uint64_t ray0, float* const out[6], int* evaluated,
+                      const RenderWorkspace::Regions& ws, hipStream_t hs) {
+    const int S = nc + nf;
+    const auto field = [&](const OccPass& p, const float* z, int samples, float* raw) -> int {
+        const auto mark = ordered ? launch_occupancy_mark_rays_ordered : launch_occupancy_mark_rays;
+        if (int rc = mark(grid, rays, z, n, samples, p.list, p.count, raw, hs)) return rc;
+        return eval_rays_list(p.kind, p.packed, rays, z, n, samples, p.list, p.count, raw, p.acts, hs);
+    };
+    int rc;
+    if ((rc = launch_sample_coarse(n, near_, far_, nc, z_lin, t_rand, seed, ray0, ws.z_c, hs))) return rc;
+    if ((rc = field(pass[0], ws.z_c, nc, ws.raw_c))) return rc;
+    if (out[0]) rc = launch_composite(n, nc, ws.raw_c, ws.z_c, rays, out[0], out[1], out[2], ws.w_c, hs);
+    else rc = launch_composite_weights(n, nc, ws.raw_c + 3, 4, ws.z_c, rays, out[1], out[2], ws.w_c, hs);   // raw's sigma channel
+    if (rc) return rc;
+    if ((rc = launch_sample_fine(n, near_, far_, nc, nf, z_lin, u_lin, ws.z_c, ws.w_c, nullptr, ws.z_f, nullptr, hs))) return rc;
+    if ((rc = field(pass[1], ws.z_f, S, ws.raw_f))) return rc;
+    if ((rc = launch_composite(n, S, ws.raw_f, ws.z_f, rays, out[3], out[4], out[5], nullptr, hs))) return rc;
+    // the two counts are neighbours in the workspace (OccLists)
+    if (evaluated && hipMemcpyAsync(evaluated, pass[0].count, 2 * sizeof(int), hipMemcpyDeviceToDevice, hs) != hipSuccess) {
+        set_error("%s: copy of the evaluated counts failed", fn);
+        return MI_EHIP;
+    }
+    return MI_OK;
+}
+
+}  // namespace mi
+
+using namespace mi;
+
+extern "C" {
+
+int64_t mi_render_occupancy_extra_bytes(int64_t n, int n_coarse, int n_fine) {
+    if (n <= 0 || n_coarse < 1 || n_fine < 0) return 0;
+    return OccLists(false, n, n_coarse, n_fine).bytes();
+}
+
+int64_t mi_render_occupancy_train_extra_bytes(int64_t n, int n_coarse, int n_fine) {
+    if (n <= 0 || n_coarse < 1 || n_fine < 0 || n > 0x7fffffffLL / ((int64_t)n_coarse + n_fine)) return 0;
+    return OccLists(true, n, n_coarse, n_fine).bytes();
+}
+
+int64_t mi_render_occupancy_train_saved_bytes(int kind_coarse, int kind_fine, int64_t n, int n_coarse, int n_fine) {
+    if (int rc = check_call("mi_render_occupancy_train_saved_bytes", "training", kind_coarse, kind_fine, n, n_coarse, n_fine)) return rc;
+    return saved_bytes_of(kind_coarse, kind_fine, n, n_coarse, n_fine);
+}
+
+int64_t mi_render_occupancy_backward_workspace_bytes(int kind_coarse, int kind_fine, int shared, int64_t n, int n_coarse, int n_fine) {
+    if (int rc = check_call("mi_render_occupancy_backward_workspace_bytes", "training", kind_coarse, kind_fine, n, n_coarse, n_fine)) return rc;
+    if (n == 0) return 0;
+    return OccBwdLayout(kind_coarse, kind_fine, shared != 0, n, n_coarse, n_fine).bytes();
+}
+
+int mi_render_rays_occupancy(int kind_coarse, const float* packed_coarse, int kind_fine, const float* packed_fine,
+                             const float* rays, int64_t n, float near_, float far_, int n_coarse, int n_fine,
+                             const float* z_lin, const float* u_lin, const float* t_rand, uint64_t seed, uint64_t ray0,
+                             const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell, float* rgb_c,
+                             float* depth_c, float* acc_c, float* rgb_f, float* depth_f, float* acc_f, int* evaluated,
+                             void* workspace, int64_t workspace_bytes, void* stream) {
+    const char* fn = "mi_render_rays_occupancy";
+    OccupancyGridArgs grid;
+    if (int rc = check_call(fn, "rendering", kind_coarse, kind_fine, n, n_coarse, n_fine, bits, dims, lo, inv_cell, &grid)) return rc;
+    // the coarse outputs are optional, as in mi_render_rays: without rgb_c, depth_c / acc_c each may be null too
+    if (!packed_coarse || !packed_fine || !rays || !workspace || (rgb_c && (!depth_c || !acc_c)) || !rgb_f || !depth_f || !acc_f) {
+        set_error("%s: null pointer argument", fn);
+        return MI_EINVAL;
+    }
+    if (n == 0) return MI_OK;                                  // no rays: nothing to launch, no buffer is touched
+    if (int rc = check_buffers(fn, OCC_RENDER, kind_coarse, kind_fine, false, n, n_coarse, n_fine, workspace, workspace_bytes)) return rc;
+    const RenderWorkspace layout(n, n_coarse, n_fine);
+    const OccLists::Regions r = OccLists(false, n, n_coarse, n_fine).carve(workspace, layout.base_bytes());
+    const OccPass pass[2] = {{kind_coarse, packed_coarse, r.list[0], r.counts, nullptr}, {kind_fine, packed_fine, r.list[1], r.counts + 1, nullptr}};
+    float* const out[6] = {rgb_c, depth_c, acc_c, rgb_f, depth_f, acc_f};
+    return run_passes(fn, pass, false, grid, rays, n, near_, far_, n_coarse, n_fine, z_lin, u_lin, t_rand, seed, ray0, out, evaluated,
+                      layout.carve(workspace), (hipStream_t)stream);
+}
+
+int mi_render_rays_occupancy_train(int kind_coarse, const float* packed_coarse, int kind_fine, const float* packed_fine,
+                                   const float* rays, int64_t n, float near_, float far_, int n_coarse, int n_fine,
+                                   const float* z_lin, const float* u_lin, const float* t_rand, uint64_t seed, uint64_t ray0,
+                                   const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell, float* rgb_c,
+                                   float* depth_c, float* acc_c, float* rgb_f, float* depth_f, float* acc_f, int* evaluated,
+                                   void* workspace, int64_t workspace_bytes, void* saved, int64_t saved_bytes, void* stream) {
+    const char* fn = "mi_render_rays_occupancy_train";
+    OccupancyGridArgs grid;
+    if (int rc = check_call(fn, "training", kind_coarse, kind_fine, n, n_coarse, n_fine, bits, dims, lo, inv_cell, &grid)) return rc;
+    if (!packed_coarse || !packed_fine || !rays || !rgb_c || !depth_c || !acc_c || !rgb_f || !depth_f || !acc_f) {
+        set_error("%s: null pointer argument", fn);
+        return MI_EINVAL;
+    }
+    if (n == 0) return MI_OK;
+    if (int rc = check_buffers(fn, OCC_TRAIN, kind_coarse, kind_fine, false, n, n_coarse, n_fine, workspace, workspace_bytes, saved,
+                               saved_bytes)) return rc;
+    // Training only: a step is one call, so one host query per step.  Inference renders a frame in many chunks and would pay
+    // the query per chunk; nobody has measured that, so mi_render_rays_occupancy leaves a grid on another device to the launch.
+    if (int rc = check_grid_device(fn, bits)) return rc;
+    const RenderWorkspace layout(n, n_coarse, n_fine);
+    const OccLists::Regions r = OccLists(true, n, n_coarse, n_fine).carve(workspace, layout.base_bytes());
+    float* acts = (float*)saved;
+    const OccPass pass[2] = {{kind_coarse, packed_coarse, r.list[0], r.counts, acts},
+                             {kind_fine, packed_fine, r.list[1], r.counts + 1, acts + saved_floats_coarse(kind_coarse, n, n_coarse)}};
+    float* const out[6] = {rgb_c, depth_c, acc_c, rgb_f, depth_f, acc_f};
+    return run_passes(fn, pass, true, grid, rays, n, near_, far_, n_coarse, n_fine, z_lin, u_lin, t_rand, seed, ray0, out, evaluated,
+                      layout.carve(workspace), (hipStream_t)stream);
+}
+
+int mi_render_rays_occupancy_backward(int kind_coarse, const float* packed_bwd_coarse, int kind_fine,
+                                      const float* packed_bwd_fine, int shared, const float* rays, int64_t n, int n_coarse,
+                                      int n_fine, const void* workspace, int64_t workspace_bytes, const void* saved,
+                                      int64_t saved_bytes, const float* g_rgb_c, const float* g_depth_c, const float* g_acc_c,
+                                      const float* g_rgb_f, const float* g_depth_f, const float* g_acc_f,
+                                      float* const* grad_params_coarse, float* const* grad_params_fine, void* bwd_workspace,
+                                      int64_t bwd_workspace_bytes, int* fields_written, void* stream) {
+    const char* fn = "mi_render_rays_occupancy_backward";
+    if (fields_written) *fields_written = 0;
+    if (int rc = check_call(fn, "training", kind_coarse, kind_fine, n, n_coarse, n_fine)) return rc;
+    if (shared && kind_coarse != kind_fine) { set_error("%s: one field for both passes has one kind (%d and %d)", fn, kind_coarse, kind_fine); return MI_EINVAL; }
+    if (n == 0) return MI_OK;
+    const bool want_c = g_rgb_c || g_depth_c || g_acc_c, want_f = g_rgb_f || g_depth_f || g_acc_f;
+    if (!rays) { set_error("%s: null pointer argument", fn); return MI_EINVAL; }
+    const int kinds[2] = {kind_coarse, kind_fine};
+    const float* packed_bwd[2] = {packed_bwd_coarse, shared ? packed_bwd_coarse : packed_bwd_fine};
+    float* const* grads[2] = {grad_params_coarse, shared ? grad_params_coarse : grad_params_fine};
+    const bool wants[2] = {want_c, want_f};
+    for (int f = 0; f < 2; ++f) {
+        if (!wants[f]) continue;
+        const char* which = f && !shared ? "fine" : "coarse";
+        if (!packed_bwd[f]) { set_error("%s: the %s field has no transposed stream", fn, which); return MI_EINVAL; }
+        if (!grads[f]) { set_error("%s: the %s field gets a cotangent but has no gradient array", fn, which); return MI_EINVAL; }
+        for (int i = 0; i < 2 * field_kind(kinds[f]).n_layers; ++i)
+            if (!grads[f][i]) { set_error("%s: %s gradient pointer %d is null", fn, which, i); return MI_EINVAL; }
+    }
+    if (int rc = check_buffers(fn, OCC_BACKWARD, kind_coarse, kind_fine, shared != 0, n, n_coarse, n_fine, workspace, workspace_bytes,
+                               saved, saved_bytes, bwd_workspace, bwd_workspace_bytes)) return rc;
+    if (!want_c && !want_f) return MI_OK;
+    const OccBwdLayout L(kind_coarse, kind_fine, shared != 0, n, n_coarse, n_fine);
+    const RenderWorkspace layout(n, n_coarse, n_fine);
+    const RenderWorkspace::Regions ws = layout.carve(const_cast<void*>(workspace));
+    const OccLists::Regions r = OccLists(true, n, n_coarse, n_fine).carve(workspace, layout.base_bytes());
+    const float* acts_c = (const float*)saved;
+    const float* acts_f = acts_c + saved_floats_coarse(kind_coarse, n, n_coarse);
+    const int S = n_coarse + n_fine;
+    float* bws = (float*)bwd_workspace;
+    hipStream_t hs = (hipStream_t)stream;
+    int rc;
+    if (want_c) {
+        if ((rc = launch_composite_bwd(n, n_coarse, ws.raw_c, ws.z_c, rays, g_rgb_c, g_depth_c, g_acc_c, nullptr, bws + L.g_raw_c, hs))) return rc;
+        if ((rc = launch_field_backward_list(kind_coarse, packed_bwd_coarse, acts_c, bws + L.grads, ws.raw_c, bws + L.g_raw_c, r.list[0],
+                                             r.counts, n * n_coarse, bws + L.partial, grad_params_coarse, hs))) return rc;
+    }
+    if (want_f) {
+        if ((rc = launch_composite_bwd(n, S, ws.raw_f, ws.z_f, rays, g_rgb_f, g_depth_f, g_acc_f, nullptr, bws + L.g_raw_f, hs))) return rc;
+        float* fine_total[2 * kMaxLayers];
+        const bool add = shared && want_c;                       // one field: coarse-pass total += fine-pass total
+        if (add) scratch_params(kind_fine, bws + L.fine_total, fine_total);
+        if ((rc = launch_field_backward_list(kind_fine, packed_bwd[1], acts_f, bws + L.grads, ws.raw_f, bws + L.g_raw_f, r.list[1],
+                                             r.counts + 1, n * S, bws + L.partial, add ? fine_total : grads[1], hs))) return rc;
+        if (add && (rc = add_param_grads(kind_fine, grad_params_coarse, fine_total, hs))) return rc;
+    }
+    if (fields_written) *fields_written = shared ? MI_WROTE_COARSE : (want_c ? MI_WROTE_COARSE : 0) | (want_f ? MI_WROTE_FINE : 0);
+    return MI_OK;
+}
+
+}  // extern "C"

@@ -148,9 +148,9 @@ static void pass_specs(int kind_c, int kind_f, const Geometry& G, int64_t rp_c, 
 }
 
 // How many leading ranges of each pass keep their layer inputs within saved_bytes (autograd._forward_pass's loop,
-// coarse pass first, one budget).
-static void plan_kept(const PassSpec P[2], const Geometry& G, int64_t saved_bytes, int64_t kept[2]) {
-    int64_t budget = saved_bytes;
+// coarse pass first, one budget).  Returns the floats the coarse pass keeps: the second pass's kept inputs follow them.
+static int64_t plan_kept(const PassSpec P[2], const Geometry& G, int64_t saved_bytes, int64_t kept[2]) {
+    int64_t budget = saved_bytes, coarse_floats = 0;
     for (int p = 0; p < 2; ++p) {
         kept[p] = 0;
         if (!P[p].exists) continue;
@@ -164,7 +164,9 @@ static void plan_kept(const PassSpec P[2], const Geometry& G, int64_t saved_byte
             budget -= need;
             ++kept[p];
         }
+        if (p == 0) coarse_floats = (saved_bytes - budget) / 4;
     }
+    return coarse_floats;
 }
 
 static int64_t param_numel(int kind, int i) {
@@ -173,7 +175,7 @@ static int64_t param_numel(int kind, int i) {
 }
 
 // a scratch copy of a kind's parameter gradients: tensor after tensor, each starting on a 64-float block
-static int64_t param_floats(int kind) {
+int64_t param_floats(int kind) {
     int64_t f = 0;
     for (int i = 0; i < 2 * field_kind(kind).n_layers; ++i) f += align64(param_numel(kind, i));
     return f;
@@ -312,11 +314,26 @@ static int forward_pass(const PassSpec& P, const Geometry& G, const float* packe
 }
 
 // Parameter-gradient pointers of a kind laid out in a scratch region (param_floats order).
-static void scratch_params(int kind, float* base, float* out[2 * kMaxLayers]) {
+void scratch_params(int kind, float* base, float* out[2 * kMaxLayers]) {
     for (int i = 0; i < 2 * field_kind(kind).n_layers; ++i) {
         out[i] = base;
         base += align64(param_numel(kind, i));
     }
+}
+
+// dst[i] += src[i] over a kind's parameter gradients (_foreach_add_): entered into acc, whose flush the caller owns, so
+// that a FiLM row or table that belongs to the same sum goes out in the same launch
+static int add_param_grads(Accumulator& acc, int kind, float* const* dst, float* const* src) {
+    for (int i = 0; i < 2 * field_kind(kind).n_layers; ++i)
+        if (int rc = acc.add(dst[i], src[i], param_numel(kind, i))) return rc;
+    return MI_OK;
+}
+
+// ... and as a launch of its own
+int add_param_grads(int kind, float* const* dst, float* const* src, hipStream_t stream) {
+    Accumulator acc(stream);
+    if (int rc = add_param_grads(acc, kind, dst, src)) return rc;
+    return acc.flush();
 }
 
 struct PassIO {
@@ -336,7 +353,6 @@ static int backward_pass(const PassSpec& P, const Geometry& G, const PassIO& io,
                          float* const* dst, float* film_dst, float* bws, const BwdLayout& L, void* stream) {
     const Ranges R = make_ranges(P.kind, G.n_groups, G.rpg, P.S, P.range_points);
     const FieldKind& K = field_kind(P.kind);
-    const int n_params = 2 * K.n_layers;
     const int64_t film_fl = film_floats(P.kind);   // one group's rows of the FiLM table
     const int64_t acts_f = region_total(K.acts);
     const int S = P.S;
@@ -371,7 +387,7 @@ static int backward_pass(const PassSpec& P, const Geometry& G, const PassIO& io,
                                         R.film ? io.params : nullptr, hs))) return rc;
         if (k > 0) {                                   // _foreach_add_(total, out); a later part adds to its image's row
             Accumulator acc(hs);
-            for (int i = 0; i < n_params; ++i) acc.add(dst[i], range_out[i], param_numel(P.kind, i));
+            if ((rc = add_param_grads(acc, P.kind, dst, range_out))) return rc;
             if (add_to_row) acc.add(film_dst + g0 * film_fl, bws + L.film_row, film_fl);
             if ((rc = acc.flush())) return rc;
         }
@@ -510,17 +526,8 @@ int mi_render_rays_backward(int kind_coarse, const float* packed_coarse, const f
     }
     if (!run_c && !run_f) return MI_OK;
     int64_t kept[2];
-    plan_kept(P, G, saved_bytes, kept);
     const float* saved_f = (const float*)saved;
-    const float* saved_pass[2] = {saved_f, saved_f};
-    {   // the second pass's kept inputs follow the coarse pass's
-        const Ranges R = make_ranges(P[0].kind, G.n_groups, G.rpg, P[0].S, P[0].range_points);
-        for (int64_t k = 0; k < kept[0]; ++k) {
-            int64_t r0, r1;
-            R.get(k, r0, r1);
-            saved_pass[1] += region_total(field_kind(P[0].kind).acts) * (r1 - r0) * P[0].S;
-        }
-    }
+    const float* saved_pass[2] = {saved_f, saved_f + plan_kept(P, G, saved_bytes, kept)};
     const State st = carve_state(const_cast<void*>(workspace), G);
     float* bws = (float*)bwd_workspace;
     const int64_t n = G.n;
@@ -586,239 +593,11 @@ int mi_render_rays_backward(int kind_coarse, const float* packed_coarse, const f
         if ((rc = backward_pass(P[1], G, io_s, film, rays, fine_total, film_kind ? bws + L.film_pass : nullptr, bws, L,
                                 stream))) return rc;
         Accumulator acc(hs);                                   // _foreach_add_(grads_c, grads_f); grad_film += fine pass's
-        for (int i = 0; i < 2 * field_kind(kind_coarse).n_layers; ++i)
-            acc.add(grad_params_coarse[i], fine_total[i], param_numel(kind_coarse, i));
+        if ((rc = add_param_grads(acc, kind_coarse, grad_params_coarse, fine_total))) return rc;
         if (film_kind) acc.add(grad_film, bws + L.film_pass, n_groups * film_floats(kind_coarse));
         if ((rc = acc.flush())) return rc;
     }
     if (fields_written) *fields_written = MI_WROTE_COARSE | (is_film(kind_coarse) ? MI_WROTE_FILM : 0);
-    return MI_OK;
-}
-
-}  // extern "C"
-
-// ---- training with an occupancy grid: mi_render_rays_occupancy_train / _backward ---------------------------------------------------
-// mi_render_rays_occupancy with the list-driven forwards keeping their layer inputs, and its backward.  Deliberately small:
-// one range per pass (each pass keeps its own ascending list, its count and its compact saved rows at worst-case capacity),
-// nothing is recomputed, one group, no FiLM.  One field for both passes runs as two passes of that field over all their listed
-// points (no merge, as at inference with a grid); its two gradient sums are added with the Accumulator.
-namespace mi {
-
-// behind RenderWorkspace::base_bytes(): the coarse list, the fine list (each with its scan slots), the two counts
-struct OccTrainLists {
-    int64_t ints_c, ints_f;
-    OccTrainLists(int64_t n, int nc, int nf)
-        : ints_c(align64(occupancy_ordered_list_ints(n * nc))), ints_f(align64(occupancy_ordered_list_ints(n * ((int64_t)nc + nf)))) {}
-    int64_t bytes() const { return (ints_c + ints_f + align64(2)) * (int64_t)sizeof(int); }
-    int* list_c(void* ws, int64_t base) const { return (int*)((char*)ws + base); }
-    int* list_f(void* ws, int64_t base) const { return list_c(ws, base) + ints_c; }
-    int* counts(void* ws, int64_t base) const { return list_f(ws, base) + ints_f; }
-};
-
-// the backward workspace, in floats: dL/d(raw) of both composites, one pass's dA rows and dW scratch, one field: the fine
-// pass's parameter gradients
-struct OccBwdLayout {
-    int64_t g_raw_c, g_raw_f, grads, partial, fine_total, total;
-    OccBwdLayout(int kind_c, int kind_f, bool shared, int64_t n, int nc, int nf) {
-        const int64_t pc = n * nc, pf = n * ((int64_t)nc + nf);
-        int64_t f = 0;
-        auto take = [&](int64_t x) { const int64_t o = f; f += align64(x); return o; };
-        const int64_t gc = pc * region_total(field_kind(kind_c).grads), gf = pf * region_total(field_kind(kind_f).grads);
-        const int64_t bc = bwd_partial_floats_kind(kind_c, pc), bf = bwd_partial_floats_kind(kind_f, pf);
-        g_raw_c = take(pc * 4);
-        g_raw_f = take(pf * 4);
-        grads = take(gc > gf ? gc : gf);
-        partial = take(bc > bf ? bc : bf);
-        fine_total = take(shared ? param_floats(kind_c) : 0);
-        total = f;
-    }
-};
-
-static int check_occ_train(const char* fn, int kind_c, int kind_f, int64_t n, int nc, int nf) {
-    if (n < 0 || nc < 3 || nf < 0) { set_error("%s: bad sizes (n >= 0, Nc >= 3, Nf >= 0)", fn); return MI_EINVAL; }
-    if (bad_kind(kind_c) || bad_kind(kind_f)) return MI_EINVAL;
-    if (!has_list_kernel(kind_c) || !has_list_kernel(kind_f)) {
-        set_error("%s: kinds %d / %d: training with a grid is built for NeRF, SirenNeRF and TinyNeRF, not for FiLM kinds", fn, kind_c, kind_f);
-        return MI_EINVAL;
-    }
-    if (n > 0x7fffffffLL / (nc + nf)) {
-        set_error("%s: n * (Nc + Nf) = %lld * %d exceeds 2^31 - 1 (the list holds int point indices)", fn, (long long)n, nc + nf);
-        return MI_EINVAL;
-    }
-    return MI_OK;
-}
-
-static int64_t occ_train_saved_bytes(int kind_c, int kind_f, int64_t n, int nc, int nf) {
-    return 4 * (region_total(field_kind(kind_c).acts) * n * nc + region_total(field_kind(kind_f).acts) * n * ((int64_t)nc + nf));
-}
-
-static int check_occ_buffers(const char* fn, int kind_c, int kind_f, int64_t n, int nc, int nf, const void* workspace,
-                             int64_t workspace_bytes, const void* saved, int64_t saved_bytes) {
-    const int64_t need = RenderWorkspace(n, nc, nf).base_bytes() + OccTrainLists(n, nc, nf).bytes();
-    if (!workspace || workspace_bytes < need) {
-        set_error("%s: workspace of %lld bytes, mi_render_workspace_bytes + mi_render_occupancy_train_extra_bytes say %lld", fn,
-                  (long long)workspace_bytes, (long long)need);
-        return MI_EINVAL;
-    }
-    const int64_t sv = occ_train_saved_bytes(kind_c, kind_f, n, nc, nf);
-    if (!saved || saved_bytes < sv) {
-        set_error("%s: saved buffer of %lld bytes, mi_render_occupancy_train_saved_bytes says %lld", fn, (long long)saved_bytes, (long long)sv);
-        return MI_EINVAL;
-    }
-    return MI_OK;
-}
-
-// The grid's words must live on the device the call launches on.  Only a pointer the runtime knows as device memory of
-// ANOTHER device is refused; anything the runtime cannot classify is left to the launch.
-static int check_grid_device(const char* fn, const uint32_t* bits) {
-    hipPointerAttribute_t attr;
-    int dev = 0;
-    if (hipPointerGetAttributes(&attr, bits) != hipSuccess || hipGetDevice(&dev) != hipSuccess) {
-        (void)hipGetLastError();
-        return MI_OK;
-    }
-    if (attr.type == hipMemoryTypeDevice && attr.device != dev) {
-        set_error("%s: the occupancy grid is on device %d, the call runs on device %d", fn, attr.device, dev);
-        return MI_EINVAL;
-    }
-    return MI_OK;
-}
-
-}  // namespace mi
-
-extern "C" {
-
-int64_t mi_render_occupancy_train_extra_bytes(int64_t n, int n_coarse, int n_fine) {
-    if (n <= 0 || n_coarse < 1 || n_fine < 0 || n > 0x7fffffffLL / ((int64_t)n_coarse + n_fine)) return 0;
-    return OccTrainLists(n, n_coarse, n_fine).bytes();
-}
-
-int64_t mi_render_occupancy_train_saved_bytes(int kind_coarse, int kind_fine, int64_t n, int n_coarse, int n_fine) {
-    if (int rc = check_occ_train("mi_render_occupancy_train_saved_bytes", kind_coarse, kind_fine, n, n_coarse, n_fine)) return rc;
-    return occ_train_saved_bytes(kind_coarse, kind_fine, n, n_coarse, n_fine);
-}
-
-int64_t mi_render_occupancy_backward_workspace_bytes(int kind_coarse, int kind_fine, int shared, int64_t n, int n_coarse, int n_fine) {
-    if (int rc = check_occ_train("mi_render_occupancy_backward_workspace_bytes", kind_coarse, kind_fine, n, n_coarse, n_fine)) return rc;
-    if (n == 0) return 0;
-    return OccBwdLayout(kind_coarse, kind_fine, shared != 0, n, n_coarse, n_fine).total * (int64_t)sizeof(float);
-}
-
-int mi_render_rays_occupancy_train(int kind_coarse, const float* packed_coarse, int kind_fine, const float* packed_fine,
-                                   const float* rays, int64_t n, float near_, float far_, int n_coarse, int n_fine,
-                                   const float* z_lin, const float* u_lin, const float* t_rand, uint64_t seed, uint64_t ray0,
-                                   const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell, float* rgb_c,
-                                   float* depth_c, float* acc_c, float* rgb_f, float* depth_f, float* acc_f, int* evaluated,
-                                   void* workspace, int64_t workspace_bytes, void* saved, int64_t saved_bytes, void* stream) {
-    const char* fn = "mi_render_rays_occupancy_train";
-    if (int rc = check_occ_train(fn, kind_coarse, kind_fine, n, n_coarse, n_fine)) return rc;
-    if (!dims || dims[0] < 1 || dims[1] < 1 || dims[2] < 1 || (int64_t)dims[0] * dims[1] * dims[2] > 0x7fffffffLL) {
-        set_error("%s: bad grid dims (each >= 1, their product within an int)", fn);
-        return MI_EINVAL;
-    }
-    if (!packed_coarse || !packed_fine || !rays || !bits || !lo || !inv_cell || !rgb_c || !depth_c || !acc_c || !rgb_f || !depth_f ||
-        !acc_f) {
-        set_error("%s: null pointer argument", fn);
-        return MI_EINVAL;
-    }
-    if (n == 0) return MI_OK;
-    if (int rc = check_occ_buffers(fn, kind_coarse, kind_fine, n, n_coarse, n_fine, workspace, workspace_bytes, saved, saved_bytes)) return rc;
-    if (int rc = check_grid_device(fn, bits)) return rc;
-    const RenderWorkspace layout(n, n_coarse, n_fine);
-    const RenderWorkspace::Regions ws = layout.carve(workspace);
-    const OccTrainLists LL(n, n_coarse, n_fine);
-    const int64_t base = layout.base_bytes();
-    int* list_c = LL.list_c(workspace, base);
-    int* list_f = LL.list_f(workspace, base);
-    int* counts = LL.counts(workspace, base);
-    float* acts_c = (float*)saved;
-    float* acts_f = acts_c + region_total(field_kind(kind_coarse).acts) * n * n_coarse;
-    const int S = n_coarse + n_fine;
-    hipStream_t hs = (hipStream_t)stream;
-    int rc;
-    if ((rc = mi_sample_coarse(n, near_, far_, n_coarse, z_lin, t_rand, seed, ray0, ws.z_c, stream))) return rc;
-    if ((rc = launch_occupancy_mark_rays_ordered(bits, dims, lo, inv_cell, rays, ws.z_c, n, n_coarse, list_c, counts, ws.raw_c, hs))) return rc;
-    if ((rc = mi_field_eval_rays_list_train(kind_coarse, packed_coarse, rays, ws.z_c, n, n_coarse, list_c, counts, ws.raw_c, acts_c, stream))) return rc;
-    if ((rc = mi_composite(n, n_coarse, ws.raw_c, ws.z_c, rays, rgb_c, depth_c, acc_c, ws.w_c, stream))) return rc;
-    if ((rc = mi_sample_fine(n, near_, far_, n_coarse, n_fine, z_lin, u_lin, ws.z_c, ws.w_c, nullptr, ws.z_f, stream))) return rc;
-    if ((rc = launch_occupancy_mark_rays_ordered(bits, dims, lo, inv_cell, rays, ws.z_f, n, S, list_f, counts + 1, ws.raw_f, hs))) return rc;
-    if ((rc = mi_field_eval_rays_list_train(kind_fine, packed_fine, rays, ws.z_f, n, S, list_f, counts + 1, ws.raw_f, acts_f, stream))) return rc;
-    if ((rc = mi_composite(n, S, ws.raw_f, ws.z_f, rays, rgb_f, depth_f, acc_f, nullptr, stream))) return rc;
-    if (evaluated && hipMemcpyAsync(evaluated, counts, 2 * sizeof(int), hipMemcpyDeviceToDevice, hs) != hipSuccess) {
-        set_error("%s: copy of the evaluated counts failed", fn);
-        return MI_EHIP;
-    }
-    return MI_OK;
-}
-
-int mi_render_rays_occupancy_backward(int kind_coarse, const float* packed_bwd_coarse, int kind_fine,
-                                      const float* packed_bwd_fine, int shared, const float* rays, int64_t n, int n_coarse,
-                                      int n_fine, const void* workspace, int64_t workspace_bytes, const void* saved,
-                                      int64_t saved_bytes, const float* g_rgb_c, const float* g_depth_c, const float* g_acc_c,
-                                      const float* g_rgb_f, const float* g_depth_f, const float* g_acc_f,
-                                      float* const* grad_params_coarse, float* const* grad_params_fine, void* bwd_workspace,
-                                      int64_t bwd_workspace_bytes, int* fields_written, void* stream) {
-    const char* fn = "mi_render_rays_occupancy_backward";
-    if (fields_written) *fields_written = 0;
-    if (int rc = check_occ_train(fn, kind_coarse, kind_fine, n, n_coarse, n_fine)) return rc;
-    if (shared && kind_coarse != kind_fine) { set_error("%s: one field for both passes has one kind (%d and %d)", fn, kind_coarse, kind_fine); return MI_EINVAL; }
-    if (n == 0) return MI_OK;
-    const bool want_c = g_rgb_c || g_depth_c || g_acc_c, want_f = g_rgb_f || g_depth_f || g_acc_f;
-    if (!rays) { set_error("%s: null pointer argument", fn); return MI_EINVAL; }
-    const int kinds[2] = {kind_coarse, kind_fine};
-    const float* packed_bwd[2] = {packed_bwd_coarse, shared ? packed_bwd_coarse : packed_bwd_fine};
-    float* const* grads[2] = {grad_params_coarse, shared ? grad_params_coarse : grad_params_fine};
-    const bool wants[2] = {want_c, want_f};
-    for (int f = 0; f < 2; ++f) {
-        if (!wants[f]) continue;
-        const char* which = f && !shared ? "fine" : "coarse";
-        if (!packed_bwd[f]) { set_error("%s: the %s field has no transposed stream", fn, which); return MI_EINVAL; }
-        if (!grads[f]) { set_error("%s: the %s field gets a cotangent but has no gradient array", fn, which); return MI_EINVAL; }
-        for (int i = 0; i < 2 * field_kind(kinds[f]).n_layers; ++i)
-            if (!grads[f][i]) { set_error("%s: %s gradient pointer %d is null", fn, which, i); return MI_EINVAL; }
-    }
-    if (int rc = check_occ_buffers(fn, kind_coarse, kind_fine, n, n_coarse, n_fine, workspace, workspace_bytes, saved, saved_bytes)) return rc;
-    const OccBwdLayout L(kind_coarse, kind_fine, shared != 0, n, n_coarse, n_fine);
-    if (!bwd_workspace || bwd_workspace_bytes < L.total * (int64_t)sizeof(float)) {
-        set_error("%s: backward workspace of %lld bytes, mi_render_occupancy_backward_workspace_bytes says %lld", fn,
-                  (long long)bwd_workspace_bytes, (long long)(L.total * (int64_t)sizeof(float)));
-        return MI_EINVAL;
-    }
-    if (!want_c && !want_f) return MI_OK;
-    const RenderWorkspace layout(n, n_coarse, n_fine);
-    const RenderWorkspace::Regions ws = layout.carve(const_cast<void*>(workspace));
-    const OccTrainLists LL(n, n_coarse, n_fine);
-    const int64_t base = layout.base_bytes();
-    void* wsp = const_cast<void*>(workspace);
-    const int* list_c = LL.list_c(wsp, base);
-    const int* list_f = LL.list_f(wsp, base);
-    const int* counts = LL.counts(wsp, base);
-    const float* acts_c = (const float*)saved;
-    const float* acts_f = acts_c + region_total(field_kind(kind_coarse).acts) * n * n_coarse;
-    const int S = n_coarse + n_fine;
-    float* bws = (float*)bwd_workspace;
-    hipStream_t hs = (hipStream_t)stream;
-    int rc;
-    if (want_c) {
-        if ((rc = mi_composite_bwd(n, n_coarse, ws.raw_c, ws.z_c, rays, g_rgb_c, g_depth_c, g_acc_c, nullptr, bws + L.g_raw_c, stream))) return rc;
-        if ((rc = launch_field_backward_list(kind_coarse, packed_bwd_coarse, acts_c, bws + L.grads, ws.raw_c, bws + L.g_raw_c, list_c,
-                                             counts, n * n_coarse, bws + L.partial, grad_params_coarse, hs))) return rc;
-    }
-    if (want_f) {
-        if ((rc = mi_composite_bwd(n, S, ws.raw_f, ws.z_f, rays, g_rgb_f, g_depth_f, g_acc_f, nullptr, bws + L.g_raw_f, stream))) return rc;
-        float* fine_total[2 * kMaxLayers];
-        const bool add = shared && want_c;                       // one field: coarse-pass total += fine-pass total
-        if (add) scratch_params(kind_fine, bws + L.fine_total, fine_total);
-        if ((rc = launch_field_backward_list(kind_fine, packed_bwd[1], acts_f, bws + L.grads, ws.raw_f, bws + L.g_raw_f, list_f,
-                                             counts + 1, n * S, bws + L.partial, add ? fine_total : grads[1], hs))) return rc;
-        if (add) {
-            Accumulator acc(hs);
-            for (int i = 0; i < 2 * field_kind(kind_fine).n_layers; ++i)
-                if ((rc = acc.add(grad_params_coarse[i], fine_total[i], param_numel(kind_fine, i)))) return rc;
-            if ((rc = acc.flush())) return rc;
-        }
-    }
-    if (fields_written) *fields_written = shared ? MI_WROTE_COARSE : (want_c ? MI_WROTE_COARSE : 0) | (want_f ? MI_WROTE_FINE : 0);
     return MI_OK;
 }
 

@@ -67,6 +67,14 @@ class OccupancyGrid:
                 and bits.numel() == self.words):
             raise _lib.MiRenderError(f"occupancy grid bits: a contiguous int32 device tensor of {self.words} words")
         self.bits = bits
+        self._c = None
+
+    def c_args(self):
+        """(dims, lo, inv_cell) as the three ctypes arrays every grid-reading call of the library takes.  Made on first use and
+        kept on the grid, with the numpy arrays they point into."""
+        if self._c is None:
+            self._c = (_i3(self.dims), _f3(self.lo), _f3(self.inv_cell))
+        return tuple(p for _, p in self._c)
 
     @property
     def cells(self) -> int:

@@ -24,12 +24,6 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib, fields, ops, render_core
-from .occupancy import _f3, _i3
-
-
-def _grid_args(grid):
-    (_, pdims), (_, plo), (_, pinv) = _i3(grid.dims), _f3(grid.lo), _f3(grid.inv_cell)
-    return pdims, plo, pinv
 
 
 class _OccupancyRenderFn(torch.autograd.Function):
@@ -42,8 +36,7 @@ class _OccupancyRenderFn(torch.autograd.Function):
         dev = pf_c.device
         n = rays.shape[0]
         shared = pf_c is pf_f
-        outs = [torch.empty(s, dtype=torch.float32, device=dev) for s in ((n, 3), (n,), (n,), (n, 3), (n,), (n,))]
-        counts = torch.zeros(2, dtype=torch.int32, device=dev)
+        outs, counts, zl, ul = ops._occupancy_call_buffers(n, near, far, nc, nf, dev)
         ws_bytes = int(lib.mi_render_workspace_bytes(n, nc, nf) + lib.mi_render_occupancy_train_extra_bytes(n, nc, nf))
         sv_bytes = int(lib.mi_render_occupancy_train_saved_bytes(pf_c.kind, pf_f.kind, n, nc, nf))
         if sv_bytes < 0:
@@ -51,14 +44,11 @@ class _OccupancyRenderFn(torch.autograd.Function):
         # owned by this call (not the shared inference workspace): the backward reads both
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         saved = torch.empty(sv_bytes, dtype=torch.uint8, device=dev)
-        zl = ops.linspace_table(near, far, nc, dev)
-        ul = ops.linspace_table(0.0, 1.0, nf, dev)
-        pdims, plo, pinv = _grid_args(grid)
         with torch.cuda.device(dev):
             _lib.check(lib.mi_render_rays_occupancy_train(
                 pf_c.kind, _lib.ptr(pf_c.refresh()), pf_f.kind, _lib.ptr(pf_f.refresh()), _lib.ptr(rays), n, float(near),
                 float(far), nc, nf, _lib.ptr(zl), _lib.ptr(ul), _lib.ptr(t_rand), int(seed) & (2 ** 64 - 1), int(ray0),
-                _lib.ptr(grid.bits), pdims, plo, pinv, *[_lib.ptr(o) for o in outs], _lib.ptr(counts), _lib.ptr(ws), ws_bytes,
+                _lib.ptr(grid.bits), *grid.c_args(), *[_lib.ptr(o) for o in outs], _lib.ptr(counts), _lib.ptr(ws), ws_bytes,
                 _lib.ptr(saved), sv_bytes, _lib.stream_ptr(dev)), "mi_render_rays_occupancy_train")
         ctx.pf_c, ctx.pf_f, ctx.shared, ctx.n, ctx.nc, ctx.nf = pf_c, pf_f, shared, n, nc, nf
         ctx.rays, ctx.ws, ctx.saved, ctx.counts = rays, ws, saved, counts
@@ -126,19 +116,9 @@ def render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, fi
     nc, nf = int(coarse_sample_num), int(fine_sample_num)
     needs_grad = torch.is_grad_enabled() and any(p.requires_grad for p in pf_c.params + pf_f.params)
     if not needs_grad:
-        with torch.no_grad():
-            if not return_counts:
-                return render_core.render_rays(rays, near, far, coarse_model, fine_model, nc, nf, t_rand=t_rand, seed=seed,
-                                               ray0=ray0, grid=grid)
-            # the call render_core.render_rays(grid=) makes, keeping the counts it drops: one call, so counts is [1, 2]
-            r = torch.as_tensor(rays).to(device=dev, dtype=torch.float32).reshape(-1, 2, 3).contiguous()
-            if seed is None and t_rand is None:
-                seed = render_core._fresh_seed()
-            if r.shape[0] == 0:
-                return (render_core.render_rays(r, near, far, coarse_model, fine_model, nc, nf, t_rand=t_rand, seed=seed),
-                        torch.zeros((0, 2), dtype=torch.int32, device=dev))
-            outs, counts = ops.render_rays_occupancy(pf_c, pf_f, r, near, far, nc, nf, grid, t_rand, seed or 0, ray0=ray0)
-            return outs, counts[None]
+        with torch.no_grad():                       # one call, so counts is [1, 2] ([0, 2] without rays)
+            return render_core._render_rays(rays, near, far, coarse_model, fine_model, nc, nf, t_rand=t_rand, seed=seed,
+                                            ray0=ray0, grid=grid, return_counts=return_counts)
     rays = torch.as_tensor(rays).detach().to(device=dev, dtype=torch.float32).reshape(-1, 2, 3).contiguous()
     n = rays.shape[0]
     if seed is None and t_rand is None:

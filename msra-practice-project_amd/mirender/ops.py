@@ -230,6 +230,15 @@ class _Workspace:
         return b
 
 
+def _occupancy_call_buffers(n, near, far, n_coarse, n_fine, device, coarse_outputs=True):
+    """What both calls with a grid are handed besides their workspace: (the six outputs - None in the coarse slots when they are
+    not wanted -, counts int32 [2], z_lin, u_lin)."""
+    outs = [torch.empty(s, dtype=torch.float32, device=device) if coarse_outputs or k >= 3 else None
+            for k, s in enumerate(((n, 3), (n,), (n,), (n, 3), (n,), (n,)))]
+    return (outs, torch.zeros(2, dtype=torch.int32, device=device), linspace_table(near, far, n_coarse, device),
+            linspace_table(0.0, 1.0, n_fine, device))
+
+
 def render_rays_fused(pf_c: PackedField, pf_f: PackedField, rays: torch.Tensor, near: float, far: float,
                       n_coarse: int, n_fine: int, film=None, t_rand=None, seed: int = 0, exact_linspace: bool = True,
                       ray0: int = 0, coarse_outputs: bool = True):
@@ -285,7 +294,6 @@ def render_rays_occupancy(pf_c: PackedField, pf_f: PackedField, rays: torch.Tens
     `grid` (mirender.occupancy.OccupancyGrid), or outside its box, counts as raw = 0 and is not evaluated; everything else is
     render_rays_fused.  Returns (the 6-tuple, counts): counts is a device int32 [2], the samples the coarse and the fine pass
     evaluated.  coarse_outputs=False: the coarse slots come back as None."""
-    from .occupancy import _f3, _i3
     lib = _lib.load()
     dev = pf_c.device
     if is_film(pf_c.kind) or is_film(pf_f.kind):
@@ -296,9 +304,7 @@ def render_rays_occupancy(pf_c: PackedField, pf_f: PackedField, rays: torch.Tens
         t_rand = _f32c(t_rand, dev)
         if tuple(t_rand.shape) != (n, n_coarse):
             raise _lib.MiRenderError(f"t_rand must be [{n},{n_coarse}]")
-    outs = [torch.empty(s, dtype=torch.float32, device=dev) if coarse_outputs or k >= 3 else None
-            for k, s in enumerate(((n, 3), (n,), (n,), (n, 3), (n,), (n,)))]
-    counts = torch.zeros(2, dtype=torch.int32, device=dev)
+    outs, counts, zl, ul = _occupancy_call_buffers(n, near, far, n_coarse, n_fine, dev, coarse_outputs)
     ws_bytes = lib.mi_render_workspace_bytes(n, n_coarse, n_fine) + lib.mi_render_occupancy_extra_bytes(n, n_coarse, n_fine)
     guard = None
     if os.environ.get("MI_DEBUG_GUARDS") == "1":       # sentinel zone behind the workspace, checked after the call
@@ -307,14 +313,11 @@ def render_rays_occupancy(pf_c: PackedField, pf_f: PackedField, rays: torch.Tens
         guard = ws[int(ws_bytes):]
     else:
         ws = _Workspace.get(dev, ws_bytes)
-    zl = linspace_table(near, far, n_coarse, dev)
-    ul = linspace_table(0.0, 1.0, n_fine, dev)
-    (_, pdims), (_, plo), (_, pinv) = _i3(grid.dims), _f3(grid.lo), _f3(grid.inv_cell)
     with torch.cuda.device(dev):
         _lib.check(lib.mi_render_rays_occupancy(pf_c.kind, _lib.ptr(pf_c.refresh()), pf_f.kind, _lib.ptr(pf_f.refresh()),
                                                 _lib.ptr(rays), n, float(near), float(far), n_coarse, n_fine, _lib.ptr(zl),
                                                 _lib.ptr(ul), _lib.ptr(t_rand), int(seed) & (2 ** 64 - 1), int(ray0),
-                                                _lib.ptr(grid.bits), pdims, plo, pinv, *[_lib.ptr(o) for o in outs],
+                                                _lib.ptr(grid.bits), *grid.c_args(), *[_lib.ptr(o) for o in outs],
                                                 _lib.ptr(counts), _lib.ptr(ws), int(ws_bytes), _lib.stream_ptr(dev)),
                    "mi_render_rays_occupancy")
     if guard is not None and not bool((guard == 0xA5).all()):

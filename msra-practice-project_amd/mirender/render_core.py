@@ -134,9 +134,10 @@ def render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, fi
 
 
 def _render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, fine_sample_num, *,
-                 t_rand=None, seed=None, film=None, ray0=0, coarse_outputs=True, grid=None):
+                 t_rand=None, seed=None, film=None, ray0=0, coarse_outputs=True, grid=None, return_counts=False):
     """render_rays; coarse_outputs=False lets the fused inference path skip what only the coarse outputs need
-    (ops.render_rays_fused), which may then return None in their slots.  The fine outputs are the same bits."""
+    (ops.render_rays_fused), which may then return None in their slots.  The fine outputs are the same bits.
+    return_counts=True (with a grid): (the outputs, int32 [calls, 2], the samples each pass evaluated; [0, 2] without rays)."""
     dev = _device_of(coarse_model, fine_model, rays=rays)
     rays = torch.as_tensor(rays).to(device=dev, dtype=torch.float32).reshape(-1, 2, 3).contiguous()
     nc, nf = int(coarse_sample_num), int(fine_sample_num)
@@ -146,8 +147,9 @@ def _render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, f
     if grid is not None:
         _check_grid(grid, pf_c, pf_f, film)
         if rays.shape[0]:
-            return ops.render_rays_occupancy(pf_c, pf_f, rays, near, far, nc, nf, grid, t_rand, seed or 0, ray0=ray0,
-                                             coarse_outputs=coarse_outputs)[0]
+            outs, counts = ops.render_rays_occupancy(pf_c, pf_f, rays, near, far, nc, nf, grid, t_rand, seed or 0, ray0=ray0,
+                                                     coarse_outputs=coarse_outputs)
+            return (outs, counts[None]) if return_counts else outs
     if rays.shape[0] == 0:
         # no rays (an empty batch, a rank of a group larger than the frame): six empty outputs; under autograd they hang
         # off the parameters with zero gradients, so a loss over an empty shard still backpropagates
@@ -163,7 +165,7 @@ def _render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, f
         if torch.is_grad_enabled() and leaves:
             zero = sum(p.reshape(-1)[:1].sum() for p in leaves) * 0.0
             outs = [o + zero for o in outs]
-        return tuple(outs)
+        return (tuple(outs), torch.zeros((0, 2), dtype=torch.int32, device=dev)) if return_counts else tuple(outs)
     if pf_c is not None and pf_f is not None:
         needs_grad = torch.is_grad_enabled() and any(p.requires_grad for p in pf_c.params + pf_f.params)
         if fields.is_film(pf_c.kind) or fields.is_film(pf_f.kind):

@@ -2,7 +2,8 @@
 mirender.occupancy_train).  Bit equality wherever rows are independent of each other.
 
     1 mi_occupancy_mark_rays_ordered   list == the ascending indices of the restatement's mask; the count; unlisted raw rows
-                                       zeroed, listed rows untouched; two runs give the same list
+                                       zeroed, listed rows untouched; two runs give the same list; against the atomic mark
+                                       around the 4096-point workgroup: the same points, count and raw
     2 mi_field_eval_rays_list_train    raw[list[e]] and saved row e == mi_field_eval_rays_train's rows list[e], every region;
                                        rows at and past the count and unlisted raw rows keep a NaN sentinel
     3 the counted chain                every dA region, row e == the plain chain's row list[e]
@@ -11,8 +12,8 @@ mirender.occupancy_train).  Bit equality wherever rows are independent of each o
                                        all points gives mi_field_backward's bits
     5 the pair with an all-ones grid   outputs and every gradient == the plain training path's; one shared field: outputs ==,
                                        gradients gated (its sums run over other rows)
-    6 the pair with a partial grid     outputs == mi_render_rays_occupancy; gradients against tests/occupancy_train_ref.py through
-                                       parity.gate_grad's hard gate (sharp and plain heads; one shared field, also at full
+    6 the pair with a partial grid     outputs == mi_render_rays_occupancy (also from C, across a mark workgroup); gradients
+                                       against tests/occupancy_train_ref.py through parity.gate_grad's hard gate (sharp and plain heads; one shared field, also at full
                                        occupancy); two runs equal; an all-zero grid gives gradients exactly 0
     7 the Python surface               chunks by max_points, no_grad, what is not built, ten optimiser steps
 """
@@ -133,6 +134,53 @@ def test_ordered_mark(n, s):
         assert torch.equal(lists[0], lists[1])                            # two runs: the same list
         seen.add("none" if c == 0 else "all" if c == n * s else "some")
     assert seen == {"none", "all", "some"}
+
+
+def _mark(ordered, grid, rays, z, sentinel):
+    """One of the two marks over rays x z: (list[:count] on the host, count, raw after the call), raw prefilled with `sentinel`."""
+    from mirender import _lib
+    lib = _lib.load()
+    n, s = z.shape
+    ints = lib.mi_occupancy_ordered_list_ints(n, s) if ordered else n * s
+    lst = torch.full((ints,), -1, dtype=torch.int32, device=dev())
+    count = torch.full((1,), 12345, dtype=torch.int32, device=dev())
+    raw = torch.full((n, s, 4), sentinel, device=dev())
+    call = lib.mi_occupancy_mark_rays_ordered if ordered else lib.mi_occupancy_mark_rays
+    d, lo, inv = _grid_args(grid)
+    rc = call(_lib.ptr(grid.bits), d, lo, inv, _lib.ptr(rays), _lib.ptr(z), n, s, _lib.ptr(lst), _lib.ptr(count), _lib.ptr(raw),
+              _lib.stream_ptr(dev()))
+    assert rc == 0, lib.mi_last_error()
+    c = int(count.item())
+    return lst.cpu()[:c], c, raw
+
+
+# 1, then either side of the mark kernels' 4096-point workgroup, then a third workgroup with a short tail
+@pytest.mark.parametrize("n,s", [(1, 1), (819, 5), (1024, 4), (241, 17), (1171, 7)])
+def test_the_two_marks_agree(n, s):
+    """mi_occupancy_mark_rays (one atomic per workgroup, any order) and mi_occupancy_mark_rays_ordered (count, scan, scatter) on
+    the same grid, rays and depths: the same set of points, the same count, the same raw afterwards."""
+    assert n * s in (1, 4095, 4096, 4097, 2 * 4096 + 5)
+    sentinel = -7.25
+    rays = _rays(n)
+    z = (NEAR + (FAR - NEAR) * torch.rand(n, s, generator=torch.Generator().manual_seed(11))).to(dev())
+    # one point: a grid that lists it and one that does not; otherwise a grid that lists a part of the points
+    names = ("ones", "zeros") if n * s == 1 else ("random",)
+    for name in names:
+        grid = _grid(_dense(name, (16, 16, 16)), BOX)
+        got_a, c_a, raw_a = _mark(False, grid, rays, z, sentinel)
+        got_o, c_o, raw_o = _mark(True, grid, rays, z, sentinel)
+        print(f"marks {n}x{s} {name}: {c_a} / {c_o} of {n * s} listed")
+        if n * s == 1:
+            assert c_a == (1 if name == "ones" else 0)
+        else:
+            assert 0 < c_a < n * s
+        assert c_a == c_o
+        assert torch.equal(torch.sort(got_a).values, got_o), (n, s, name)
+        assert _same(raw_a, raw_o), (n, s, name)
+        listed = torch.zeros(n * s, dtype=torch.bool)
+        listed[got_o.to(torch.int64)] = True
+        rows = raw_o.cpu().reshape(-1, 4)
+        assert bool((rows[~listed] == 0).all()) and bool((rows[listed] == sentinel).all()), (n, s, name)
 
 
 # ---- 2. - 4. the list-driven training forward and the counted backward --------------------------------------------------------
@@ -360,6 +408,48 @@ def test_pair_with_an_all_ones_grid_equals_plain_training(case):
     for f in range(2):
         for i, (a, b) in enumerate(zip(gg[f], gw[f])):
             assert _same(a, b), (case, "coarse" if f == 0 else "fine", i)
+
+
+@pytest.mark.parametrize("kinds", [("nerf", "nerf"), ("tiny_nerf", "siren_nerf")])
+def test_training_forward_is_the_inference_call(kinds):
+    """mi_render_rays_occupancy_train against mi_render_rays_occupancy on the same inputs and a partial grid: the six outputs
+    and the two counts bit for bit (every listed row of both list-driven forwards has mi_field_eval_rays' bits, and the
+    composite is the same kernel on the same raw).  200 rays at 8 + 16 samples: the coarse pass's 1 600 points lie inside one
+    workgroup of the mark kernels, the fine pass's 4 800 cross into a second."""
+    from mirender import _lib, ops
+    lib = _lib.load()
+    n, nc, nf = 200, 8, 16
+    pf_c, pf_f = _field(kinds[0], 5)[1], _field(kinds[1], 6)[1]
+    rays = _rays(n)
+    tr = synth.t_rand(n, nc, seed=9).to(dev())
+    grid = _grid(_dense("random", (16, 16, 16)), BOX)
+    d, lo, inv = _grid_args(grid)
+    zl, ul = ops.linspace_table(NEAR, FAR, nc, dev()), ops.linspace_table(0.0, 1.0, nf, dev())
+    base = lib.mi_render_workspace_bytes(n, nc, nf)
+    results = []
+    for train in (False, True):
+        outs = [torch.full(s, NAN, device=dev()) for s in ((n, 3), (n,), (n,), (n, 3), (n,), (n,))]
+        counts = torch.full((2,), -1, dtype=torch.int32, device=dev())
+        extra = lib.mi_render_occupancy_train_extra_bytes(n, nc, nf) if train else lib.mi_render_occupancy_extra_bytes(n, nc, nf)
+        ws = torch.empty(base + extra, dtype=torch.uint8, device=dev())
+        head = (pf_c.kind, _lib.ptr(pf_c.refresh()), pf_f.kind, _lib.ptr(pf_f.refresh()), _lib.ptr(rays), n, NEAR, FAR, nc, nf,
+                _lib.ptr(zl), _lib.ptr(ul), _lib.ptr(tr), 0, 0, _lib.ptr(grid.bits), d, lo, inv, *[_lib.ptr(o) for o in outs],
+                _lib.ptr(counts), _lib.ptr(ws), base + extra)
+        if train:
+            sv = lib.mi_render_occupancy_train_saved_bytes(pf_c.kind, pf_f.kind, n, nc, nf)
+            saved = torch.empty(sv, dtype=torch.uint8, device=dev())
+            rc = lib.mi_render_rays_occupancy_train(*head, _lib.ptr(saved), sv, _lib.stream_ptr(dev()))
+        else:
+            rc = lib.mi_render_rays_occupancy(*head, _lib.stream_ptr(dev()))
+        assert rc == 0, lib.mi_last_error()
+        torch.cuda.synchronize()
+        results.append((outs, counts.tolist()))
+    (want, wc), (got, gc) = results
+    print(f"{kinds}: evaluated {wc} of {[n * nc, n * (nc + nf)]}")
+    assert 0 < wc[0] < n * nc and 0 < wc[1] < n * (nc + nf), wc
+    assert gc == wc
+    for k in range(6):
+        assert _same(got[k], want[k]), (kinds, k)
 
 
 def _stage_depths(pf_c, rays, nc, nf, grid, dense, tr):
