@@ -172,3 +172,70 @@ def ptr(t):
 
 def stream_ptr(device=None):
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# The calling conventions of the package, each said once.  A new entry point plugs in here: its launches go through
+# call(), its *_bytes / *_floats queries through query(), its caller-sized buffers through guarded() / check_guard().
+# ----------------------------------------------------------------------------------------------------------------
+def call(name: str, device, *args):
+    """Launch entry point `name` on `device`: the device is selected, the calling thread's current stream of that device is
+    appended as the last argument (where every launching entry point of include/mi_render.h takes it) and a non-zero
+    return raises MiRenderError under the same name."""
+    with torch.cuda.device(device):
+        check(getattr(load(), name)(*args, stream_ptr(device)), name)
+
+
+def query(name: str, *args) -> int:
+    """A *_bytes / *_floats / *_ints / *_words size query: the int, or MiRenderError with mi_last_error() when the library
+    answers with a negative error code (which must never reach torch.empty as a size)."""
+    n = int(getattr(load(), name)(*args))
+    if n < 0:
+        check(n, name)
+    return n
+
+
+def ptr_array(tensors):
+    """void*[len] of the tensors' device pointers (NULL for a None entry); valid while the caller keeps the tensors."""
+    return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def seed64(seed) -> int:
+    """A Python int of any sign as the uint64 the Philox-keyed entry points take."""
+    return int(seed) & (2 ** 64 - 1)
+
+
+def f32c(t, device):
+    """A tensor as the library reads it: detached, fp32, contiguous, on `device` (None stays None)."""
+    return None if t is None else t.detach().to(device=device, dtype=torch.float32).contiguous()
+
+
+# MI_DEBUG_GUARDS=1 (tests/test_gpu_guards.py): every buffer whose size the caller takes from a query gets GUARD_BYTES of a
+# sentinel byte behind it, checked after the call - the library never allocates, so a kernel writing past what a query
+# promised would otherwise corrupt a neighbouring tensor silently.  The check is the only place that reads back.
+GUARD_BYTES = 16384
+_SENTINEL = 0xA5
+
+
+def guards_on() -> bool:
+    return os.environ.get("MI_DEBUG_GUARDS") == "1"
+
+
+def guarded(n: int, dtype, device):
+    """(torch.empty(n, dtype) on device, None); with MI_DEBUG_GUARDS=1 (the first n units of a buffer whose tail is the
+    sentinel, that whole buffer - for check_guard after the call)."""
+    n = int(n)
+    if not guards_on():
+        return torch.empty(n, dtype=dtype, device=device), None
+    whole = torch.empty(n + GUARD_BYTES // dtype.itemsize, dtype=dtype, device=device)
+    whole[n:].view(torch.uint8).fill_(_SENTINEL)
+    return whole[:n], whole
+
+
+def check_guard(whole, what: str):
+    """Raise if the library touched the sentinel tail of guarded()'s `whole` (None: guards are off), naming the buffer."""
+    if whole is None:
+        return
+    hit = (whole[whole.numel() - GUARD_BYTES // whole.dtype.itemsize:].view(torch.uint8) != _SENTINEL).nonzero()
+    if hit.numel():
+        raise MiRenderError(f"{what}: the library wrote {int(hit[-1]) + 1} bytes past the end of the buffer")

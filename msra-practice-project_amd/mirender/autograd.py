@@ -10,13 +10,13 @@ carry no gradient into the coarse pass.
 """
 from __future__ import annotations
 
-import ctypes
 import os
 import sys
 
 import torch
 
 from . import _lib, fields, ops
+from ._lib import f32c as _f32c, ptr as _p
 
 CHUNK_BYTES = 48 << 30         # saved activations + per-layer gradients per ray range (288 GB of HBM)
 SAVE_COARSE_BYTES = 48 << 30   # layer inputs the forward may keep for the coarse pass (no recompute in backward) ...
@@ -25,42 +25,17 @@ RESERVE_FIXED_BYTES = 16 << 30   # what backward needs besides the kept inputs a
 #                                  raw / depths / their gradients, the allocator's rounding
 
 
-# MI_DEBUG_GUARDS=1 (tests/test_gpu_guards.py): every scratch / row buffer handed to the library gets GUARD extra floats of a
-# sentinel at its end, checked after the call - the library never allocates, so a kernel writing past what a *_floats()
-# query promised would otherwise corrupt a neighbouring tensor silently.
-GUARD = 4096
-_SENTINEL = 12345.678
-
-
 def _guarded(n: int, dev):
-    """torch.empty(n) fp32 on dev; with MI_DEBUG_GUARDS=1: (n + GUARD) with the tail set to the sentinel."""
-    import os
-    if os.environ.get("MI_DEBUG_GUARDS") != "1":
-        return torch.empty(int(n), dtype=torch.float32, device=dev), None
-    buf = torch.empty(int(n) + GUARD, dtype=torch.float32, device=dev)
-    buf[int(n):] = _SENTINEL
-    return buf[:int(n)], buf
+    """The fp32 row / scratch buffers of this module, under _lib's MI_DEBUG_GUARDS convention: (n floats, whole | None)."""
+    return _lib.guarded(n, torch.float32, dev)
 
 
-def _check_guard(whole, what: str):
-    if whole is not None and not bool((whole[-GUARD:] == _SENTINEL).all()):
-        bad = int((whole[-GUARD:] != _SENTINEL).nonzero()[-1]) + 1
-        raise _lib.MiRenderError(f"{what}: the library wrote {bad} floats past the end of the buffer")
+_check_guard = _lib.check_guard
 
 
 def _max_points_per_chunk(pf) -> int:
-    lib = _lib.load()
-    per_point = 4 * (lib.mi_field_train_acts_floats(pf.kind) + lib.mi_field_train_grads_floats(pf.kind))
+    per_point = 4 * (_lib.query("mi_field_train_acts_floats", pf.kind) + _lib.query("mi_field_train_grads_floats", pf.kind))
     return max(4096, CHUNK_BYTES // per_point)
-
-
-def _groups(pf, film, n_rays):
-    if not fields.is_film(pf.kind):
-        return None, 1, n_rays
-    f = film.detach().to(device=pf.device, dtype=torch.float32).contiguous().reshape(-1, fields.film_layers(pf.kind), 512)
-    if n_rays % f.shape[0]:
-        raise _lib.MiRenderError("rays must split evenly over the FiLM groups (images)")
-    return f, f.shape[0], n_rays // f.shape[0]
 
 
 def _shape(rays, z):
@@ -82,22 +57,17 @@ def _forward_plain(pf: fields.PackedField, rays, z, film):
 
 def _forward_saving(pf: fields.PackedField, rays, z, film):
     """Field forward that also keeps every layer's input (training forward).  Returns (raw, acts)."""
-    lib = _lib.load()
     dev = pf.device
     n, s = _shape(rays, z)
-    pts = n * s
-    f, groups, rpg = _groups(pf, film, n)
-    acts, acts_g = _guarded(lib.mi_field_train_acts_floats(pf.kind) * pts, dev)
+    f, groups, rpg = fields.film_groups(pf, film, n)
+    acts, acts_g = _guarded(_lib.query("mi_field_train_acts_floats", pf.kind) * n * s, dev)
     raw = torch.empty((n, s, 4), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        if z is None:
-            _lib.check(lib.mi_field_eval_points_train(pf.kind, _lib.ptr(pf.refresh()), _lib.ptr(f), _lib.ptr(rays), groups, rpg,
-                                                      _lib.ptr(raw), _lib.ptr(acts), _lib.stream_ptr(dev)),
-                       "mi_field_eval_points_train")
-        else:
-            _lib.check(lib.mi_field_eval_rays_train(pf.kind, _lib.ptr(pf.refresh()), _lib.ptr(f), _lib.ptr(rays), _lib.ptr(z),
-                                                    groups, rpg, s, _lib.ptr(raw), _lib.ptr(acts), _lib.stream_ptr(dev)),
-                       "mi_field_eval_rays_train")
+    if z is None:
+        _lib.call("mi_field_eval_points_train", dev, pf.kind, _p(pf.refresh()), _p(f), _p(rays), groups, rpg, _p(raw),
+                  _p(acts))
+    else:
+        _lib.call("mi_field_eval_rays_train", dev, pf.kind, _p(pf.refresh()), _p(f), _p(rays), _p(z), groups, rpg, s,
+                  _p(raw), _p(acts))
     _check_guard(acts_g, "saved layer inputs (mi_field_train_acts_floats)")
     return raw, acts
 
@@ -105,7 +75,7 @@ def _forward_saving(pf: fields.PackedField, rays, z, film):
 def _chunk_ranges(pf: fields.PackedField, n: int, s: int, film):
     """The pass split into ray ranges whose saved activations + gradients fit CHUNK_BYTES (whole FiLM groups per
     range).  Forward and backward use the same split, so a range saved in the forward is found again."""
-    f_all, groups, rpg = _groups(pf, film, n)
+    f_all, groups, rpg = fields.film_groups(pf, film, n)
     max_rays = max(1, _max_points_per_chunk(pf) // s)
     if f_all is None or max_rays >= rpg:
         step = max_rays if f_all is None else (max_rays // rpg) * rpg          # whole FiLM groups per range
@@ -140,11 +110,10 @@ def _forward_pass(pf: fields.PackedField, rays, z, film, cap: int, all_or_nothin
     """raw [n,S,4] of the pass, plus {range index: saved layer inputs} for as many leading ranges as the budget
     holds (with all_or_nothing: for every range or for none); the rest is evaluated by the plain kernel and
     recomputed range by range in backward."""
-    lib = _lib.load()
     n, s = _shape(rays, z)
-    per_point = 4 * lib.mi_field_train_acts_floats(pf.kind)
+    per_point = 4 * _lib.query("mi_field_train_acts_floats", pf.kind)
     f_all, rpg, ranges = _chunk_ranges(pf, n, s, film)
-    per_point_bwd = per_point + 4 * lib.mi_field_train_grads_floats(pf.kind)
+    per_point_bwd = per_point + 4 * _lib.query("mi_field_train_grads_floats", pf.kind)
     budget = _save_budget(pf.device, cap, per_point_bwd * s * max(r1 - r0 for r0, r1 in ranges))
     if all_or_nothing and per_point * n * s > budget:
         budget = 0
@@ -180,16 +149,14 @@ def _field_backward(pf: fields.PackedField, rays, z, raw, g_raw, film, saved=Non
     receives the gradient of the pass's geometric inputs, range by range from the buffers each range's backward leaves
     behind - g_rays [n,2,3], ADDED to, for points on rays (mi_field_input_grad_rays); g_x [M,6], overwritten, for
     free-standing points (mi_field_input_grad)."""
-    lib = _lib.load()
     dev = pf.device
-    grads_f = lib.mi_field_train_grads_floats(pf.kind)
+    grads_f = _lib.query("mi_field_train_grads_floats", pf.kind)
     n, s = _shape(rays, z)
     f_all, rpg, ranges = _chunk_ranges(pf, n, s, film)
     saved = {} if saved is None else saved
     total = None
     g_film = None if f_all is None else torch.empty_like(f_all)
     packed_bwd = pf.refresh_bwd()
-    stream = _lib.stream_ptr(dev)
     srcs = pf._sources() if input_grad is not None else None          # contiguous fp32 views of the live parameters
 
     def one_range(k, r0, r1):
@@ -206,31 +173,25 @@ def _field_backward(pf: fields.PackedField, rays, z, raw, g_raw, film, saved=Non
             # a part of an image adds to that image's row; the first part (and whole groups) overwrite
             add_to_row = part_of_group and r0 % rpg != 0
             g_c = torch.empty_like(f_c) if add_to_row else g_film[g0:g0 + ng]
-            fp = torch.empty(lib.mi_field_film_partial_floats_kind(pf.kind, ng, ppg), dtype=torch.float32, device=dev)
+            fp = torch.empty(_lib.query("mi_field_film_partial_floats_kind", pf.kind, ng, ppg), dtype=torch.float32,
+                             device=dev)
         gws, gws_g = _guarded(grads_f * pts, dev)
-        part, part_g = _guarded(lib.mi_field_bwd_partial_floats_kind(pf.kind, pts), dev)
+        part, part_g = _guarded(_lib.query("mi_field_bwd_partial_floats_kind", pf.kind, pts), dev)
         out = [torch.empty_like(p) for p in pf.params]
         if k in saved:
             acts_c, raw_c = saved.pop(k), raw[r0:r1]
         else:
             raw_c, acts_c = _forward_saving(pf, rays[r0:r1], _cut(z, r0, r1), f_c)
-        arr = (ctypes.c_void_p * len(out))(*[t.data_ptr() for t in out])
         # FiLM kinds: d gamma = <W, dW_image> + b . db_image needs the parameters themselves
-        par = (ctypes.c_void_p * len(out))(*[p.data_ptr() for p in pf.params]) if f_all is not None else None
-        with torch.cuda.device(dev):
-            _lib.check(lib.mi_field_backward(pf.kind, _lib.ptr(packed_bwd), _lib.ptr(f_c), _lib.ptr(acts_c), _lib.ptr(gws),
-                                             _lib.ptr(raw_c), _lib.ptr(g_raw[r0:r1]), ng, ppg, _lib.ptr(part),
-                                             _lib.ptr(fp), arr, par, len(out), _lib.ptr(g_c), stream), "mi_field_backward")
-            if input_grad is not None:
-                src = (ctypes.c_void_p * len(srcs))(*[t.data_ptr() for t in srcs])
-                if z is None:
-                    _lib.check(lib.mi_field_input_grad(pf.kind, src, len(srcs), _lib.ptr(f_c), _lib.ptr(acts_c), _lib.ptr(gws),
-                                                       ng, ppg, _lib.ptr(input_grad[r0:r1]), stream), "mi_field_input_grad")
-                else:
-                    _lib.check(lib.mi_field_input_grad_rays(pf.kind, src, len(srcs), _lib.ptr(f_c), _lib.ptr(acts_c),
-                                                            _lib.ptr(gws), _lib.ptr(rays[r0:r1]), _lib.ptr(z[r0:r1]), ng,
-                                                            (r1 - r0) // ng, s, 1, _lib.ptr(input_grad[r0:r1]), stream),
-                               "mi_field_input_grad_rays")
+        par = _lib.ptr_array(pf.params) if f_all is not None else None
+        _lib.call("mi_field_backward", dev, pf.kind, _p(packed_bwd), _p(f_c), _p(acts_c), _p(gws), _p(raw_c),
+                  _p(g_raw[r0:r1]), ng, ppg, _p(part), _p(fp), _lib.ptr_array(out), par, len(out), _p(g_c))
+        if input_grad is not None and z is None:
+            _lib.call("mi_field_input_grad", dev, pf.kind, _lib.ptr_array(srcs), len(srcs), _p(f_c), _p(acts_c), _p(gws),
+                      ng, ppg, _p(input_grad[r0:r1]))
+        elif input_grad is not None:
+            _lib.call("mi_field_input_grad_rays", dev, pf.kind, _lib.ptr_array(srcs), len(srcs), _p(f_c), _p(acts_c),
+                      _p(gws), _p(rays[r0:r1]), _p(z[r0:r1]), ng, (r1 - r0) // ng, s, 1, _p(input_grad[r0:r1]))
         del acts_c
         _check_guard(gws_g, "per-layer gradients (mi_field_train_grads_floats)")
         _check_guard(part_g, "backward scratch (mi_field_bwd_partial_floats)")
@@ -264,31 +225,33 @@ def _field_backward(pf: fields.PackedField, rays, z, raw, g_raw, film, saved=Non
     return total, g_film
 
 
-def _composite_bwd(raw, z, rays, g_rgb, g_depth, g_acc, g_w=None):
-    lib = _lib.load()
+def _composite_bwd(raw, z, rays, g_rgb, g_depth, g_acc, g_w=None, g_rays=None, want_raw=True):
+    """Compositing backward: dL/d(raw) (mi_composite_bwd); then, with `g_rays` (mirender.pose), its ray part: compositing's
+    gradient to the ray directions (dists = delta_z |d|, render.py:91-93) ADDED to g_rays (mi_composite_bwd_rays)."""
     dev = raw.device
     n, s = z.shape
-    g_raw = torch.empty_like(raw)
-    c = lambda t: None if t is None else t.detach().to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731
-    g_rgb, g_depth, g_acc, g_w = c(g_rgb), c(g_depth), c(g_acc), c(g_w)
-    with torch.cuda.device(dev):
-        _lib.check(lib.mi_composite_bwd(n, s, _lib.ptr(raw), _lib.ptr(z), _lib.ptr(rays), _lib.ptr(g_rgb),
-                                        _lib.ptr(g_depth), _lib.ptr(g_acc), _lib.ptr(g_w), _lib.ptr(g_raw),
-                                        _lib.stream_ptr(dev)), "mi_composite_bwd")
+    gs = [_f32c(g, dev) for g in (g_rgb, g_depth, g_acc, g_w)]        # kept to the end: `args` holds their addresses only
+    args = (n, s, _p(raw), _p(z), _p(rays), *[_p(g) for g in gs])
+    g_raw = torch.empty_like(raw) if want_raw else None
+    if want_raw:
+        _lib.call("mi_composite_bwd", dev, *args, _p(g_raw))
+    if g_rays is not None:
+        _lib.call("mi_composite_bwd_rays", dev, *args, 1, _p(g_rays))
     return g_raw
 
 
 def _composite_bwd_rays(raw, z, rays, g_rgb, g_depth, g_acc, g_rays, g_w=None):
-    """mirender.pose: adds compositing's gradient to the ray directions (dists = delta_z |d|, render.py:91-93) to g_rays."""
-    lib = _lib.load()
-    dev = raw.device
-    n, s = z.shape
-    c = lambda t: None if t is None else t.detach().to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731
-    g_rgb, g_depth, g_acc, g_w = c(g_rgb), c(g_depth), c(g_acc), c(g_w)
-    with torch.cuda.device(dev):
-        _lib.check(lib.mi_composite_bwd_rays(n, s, _lib.ptr(raw), _lib.ptr(z), _lib.ptr(rays), _lib.ptr(g_rgb),
-                                             _lib.ptr(g_depth), _lib.ptr(g_acc), _lib.ptr(g_w), 1, _lib.ptr(g_rays),
-                                             _lib.stream_ptr(dev)), "mi_composite_bwd_rays")
+    """The ray part of _composite_bwd on its own."""
+    _composite_bwd(raw, z, rays, g_rgb, g_depth, g_acc, g_w, g_rays, want_raw=False)
+
+
+def _check_versions(now, then, what: str):
+    """backward re-reads the live weights (transposed stream, recomputed ranges) while raw and the kept layer inputs date
+    from the forward: a parameter updated in between would give silently mixed gradients.  PyTorch raises for its own
+    saved tensors in this situation; so do we."""
+    if now != then:
+        raise RuntimeError(f"{what}: a field parameter was modified in place (or replaced) after the forward pass that "
+                           "this backward belongs to")
 
 
 class _RenderRaysFn(torch.autograd.Function):
@@ -341,44 +304,27 @@ class _RenderRaysFn(torch.autograd.Function):
         # the gradient to the rays - from each compositing pass (|d| in the distances) and each field pass (o + d z, d / |d|)
         rays, z_c, raw_c, z_f, raw_f, z_s, raw_s, pos = ctx.saved_tensors
         pf_c, pf_f = ctx.pf_c, ctx.pf_f
-        if (pf_c.versions(), pf_f.versions()) != ctx.versions:
-            # backward re-reads the live weights (transposed stream, recomputed ranges) while raw and the kept layer
-            # inputs date from the forward: a parameter updated in between would give silently mixed gradients.
-            # PyTorch raises for its own saved tensors in this situation; so do we.
-            raise RuntimeError("render_rays backward: a field parameter was modified in place (or replaced) after the "
-                               "forward pass that this backward belongs to")
-        grads_c = grads_f = gfilm_c = gfilm_f = None
-        want_c = any(g is not None for g in (g_rgb_c, g_depth_c, g_acc_c))
-        want_f = any(g is not None for g in (g_rgb_f, g_depth_f, g_acc_f))
-        if not ctx.shared:
-            if want_c:
-                g_raw = _composite_bwd(raw_c, z_c, rays, g_rgb_c, g_depth_c, g_acc_c)
-                if g_rays is not None:
-                    _composite_bwd_rays(raw_c, z_c, rays, g_rgb_c, g_depth_c, g_acc_c, g_rays)
-                grads_c, gfilm_c = _field_backward(pf_c, rays, z_c, raw_c, g_raw, ctx.film, ctx.acts_c, g_rays)
-            if want_f:
-                g_raw = _composite_bwd(raw_f, z_f, rays, g_rgb_f, g_depth_f, g_acc_f)
-                if g_rays is not None:
-                    _composite_bwd_rays(raw_f, z_f, rays, g_rgb_f, g_depth_f, g_acc_f, g_rays)
-                grads_f, gfilm_f = _field_backward(pf_f, rays, z_f, raw_f, g_raw, ctx.film, ctx.acts_f, g_rays)
+        _check_versions((pf_c.versions(), pf_f.versions()), ctx.versions, "render_rays backward")
+
+        def composite_bwd(raw, z, gs):          # dL/d(raw) of one compositing pass, then its ray part; None: no gradient
+            return _composite_bwd(raw, z, rays, *gs, g_rays=g_rays) if any(g is not None for g in gs) else None
+
+        def field_bwd(pf, z, raw, g_raw, acts):
+            return (None, None) if g_raw is None else _field_backward(pf, rays, z, raw, g_raw, ctx.film, acts, g_rays)
+
+        gs_c, gs_f = (g_rgb_c, g_depth_c, g_acc_c), (g_rgb_f, g_depth_f, g_acc_f)
+        if not ctx.shared:                      # each pass on its own: compositing backward, then the field's
+            grads_c, gfilm_c = field_bwd(pf_c, z_c, raw_c, composite_bwd(raw_c, z_c, gs_c), ctx.acts_c)
+            grads_f, gfilm_f = field_bwd(pf_f, z_f, raw_f, composite_bwd(raw_f, z_f, gs_f), ctx.acts_f)
         else:
-            g_c = _composite_bwd(raw_c, z_c, rays, g_rgb_c, g_depth_c, g_acc_c) if want_c else None
-            if want_c and g_rays is not None:
-                _composite_bwd_rays(raw_c, z_c, rays, g_rgb_c, g_depth_c, g_acc_c, g_rays)
-            g_s = None
-            if want_f:
-                g_f = _composite_bwd(raw_f, z_f, rays, g_rgb_f, g_depth_f, g_acc_f)
-                if g_rays is not None:
-                    _composite_bwd_rays(raw_f, z_f, rays, g_rgb_f, g_depth_f, g_acc_f, g_rays)
-                if ctx.nf > 0:
-                    g_c, g_s = ops.split_grad(g_f, pos, ctx.nc, g_c)      # onto the coarse outputs' own gradient, if any
-                else:
-                    g_c = g_f if g_c is None else g_c.add_(g_f)
-                del g_f
-            if g_c is not None:
-                grads_c, gfilm_c = _field_backward(pf_c, rays, z_c, raw_c, g_c, ctx.film, ctx.acts_c, g_rays)
-            if g_s is not None:
-                grads_f, gfilm_f = _field_backward(pf_f, rays, z_s, raw_s, g_s, ctx.film, ctx.acts_f, g_rays)
+            g_c, g_f, g_s = composite_bwd(raw_c, z_c, gs_c), composite_bwd(raw_f, z_f, gs_f), None
+            if g_f is not None and ctx.nf > 0:
+                g_c, g_s = ops.split_grad(g_f, pos, ctx.nc, g_c)          # onto the coarse outputs' own gradient, if any
+            elif g_f is not None:
+                g_c = g_f if g_c is None else g_c.add_(g_f)
+            del g_f
+            grads_c, gfilm_c = field_bwd(pf_c, z_c, raw_c, g_c, ctx.acts_c)
+            grads_f, gfilm_f = field_bwd(pf_f, z_s, raw_s, g_s, ctx.acts_f)
         ctx.acts_c = ctx.acts_f = None          # release the saved activations
         if pf_c is pf_f:
             if grads_c is not None and grads_f is not None:
@@ -399,9 +345,9 @@ class _RenderRaysFn(torch.autograd.Function):
 
 def render_rays_train(pf_c, pf_f, rays, near, far, nc, nf, film, t_rand, seed, ray0=0):
     """render_rays with gradients to the field parameters and the FiLM table (6-tuple like render.py:147)."""
-    params = list(pf_c.params) if pf_c is pf_f else list(pf_c.params) + list(pf_f.params)
     return _RenderRaysFn.apply(pf_c, pf_f, rays.detach(), float(near), float(far), int(nc), int(nf), film,
-                               None if t_rand is None else t_rand.detach(), int(seed), int(ray0), *params)
+                               None if t_rand is None else t_rand.detach(), int(seed), int(ray0),
+                               *fields.pair_params(pf_c, pf_f))
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -432,8 +378,7 @@ class _CompositeFn(torch.autograd.Function):
         raw, z, rays = ctx.saved_tensors
         if all(g is None for g in (g_rgb, g_depth, g_acc, g_w)):
             return None, None, None
-        dev = raw.device
-        raw32, z32, rays32 = (t.to(device=dev, dtype=torch.float32).contiguous() for t in (raw, z, rays))
+        raw32, z32, rays32 = (_f32c(t, raw.device) for t in (raw, z, rays))
         return _composite_bwd(raw32, z32, rays32, g_rgb, g_depth, g_acc, g_w).to(raw.dtype).reshape(raw.shape), None, None
 
 
@@ -450,7 +395,9 @@ def composite(raw, z, rays, want_weights: bool = True):
 class _FieldFn(torch.autograd.Function):
     """network(inputs) of ONE pass for a fused kind - on rays (`z` [n,S]) or on free-standing points (`z` None, `rays` =
     x [M,6]) - with gradients to its parameters and to the FiLM table: the saving forward / backward chain / dW GEMMs of
-    _RenderRaysFn, one pass at a time (a mixed pair's fused side; a fused module called on its own)."""
+    _RenderRaysFn, one pass at a time (a mixed pair's fused side; a fused module called on its own).  backward's
+    `input_grad` is never passed by autograd: mirender.pose's function over free-standing points calls it with True and
+    gets dL/dx (mi_field_input_grad) in the slot of `rays` as well."""
 
     @staticmethod
     def forward(ctx, pf, rays, z, film, *params):
@@ -460,34 +407,26 @@ class _FieldFn(torch.autograd.Function):
         return raw
 
     @staticmethod
-    def backward(ctx, g_raw):
+    def backward(ctx, g_raw, input_grad=False):
         rays, raw = ctx.saved_tensors[:2]
         z = None if ctx.points else ctx.saved_tensors[2]
         pf = ctx.pf
-        if pf.versions() != ctx.versions:
-            raise RuntimeError("field backward: a field parameter was modified in place (or replaced) after the forward "
-                               "pass that this backward belongs to")
-        grads, g_film = _field_backward(pf, rays, z, raw, g_raw.to(torch.float32).contiguous(), ctx.film, ctx.acts)
+        _check_versions(pf.versions(), ctx.versions, "field backward")
+        g_x = torch.empty_like(rays) if input_grad else None
+        grads, g_film = _field_backward(pf, rays, z, raw, g_raw.to(torch.float32).contiguous(), ctx.film, ctx.acts, g_x)
         ctx.acts = None
         if g_film is not None:
             g_film = g_film.reshape(ctx.film.shape) if ctx.needs_input_grad[3] else None
-        return (None, None, None, g_film) + tuple(grads)
-
-
-def _field_wants_grad(pf, film) -> bool:
-    return torch.is_grad_enabled() and (any(p.requires_grad for p in pf.params) or
-                                        (isinstance(film, torch.Tensor) and film.requires_grad))
+        return (None, g_x if ctx.needs_input_grad[1] else None, None, g_film) + tuple(grads)
 
 
 def field_eval_rays(pf, rays, z, film=None):
     """ops.field_eval_rays (raw [n,S,4]) with autograd history towards the field's parameters and the FiLM table."""
     _no_grad_input(z, "z_vals")
     _no_grad_input(rays, "rays")
-    if not _field_wants_grad(pf, film):
+    if not fields.needs_graph(film, pf):
         return ops.field_eval_rays(pf, rays, z, film)
-    dev = pf.device
-    rays = rays.detach().to(device=dev, dtype=torch.float32).contiguous()
-    z = z.detach().to(device=dev, dtype=torch.float32).contiguous()
+    rays, z = _f32c(rays, pf.device), _f32c(z, pf.device)
     return _FieldFn.apply(pf, rays, z, film if fields.is_film(pf.kind) else None, *pf.params)
 
 
@@ -495,11 +434,11 @@ def field_eval_points(pf, x, film=None):
     """fields.eval_points (network(x [M,6]) -> [M,4], nerf/render.py:73) with autograd history towards the parameters and
     the FiLM table.  No gradient with respect to x: nothing on the reference's path asks for one."""
     _no_grad_input(x, "the field's input points")
-    if not _field_wants_grad(pf, film):
+    if not fields.needs_graph(film, pf):
         return fields.eval_points(pf, x, film)
     if x.dim() != 2 or x.shape[1] != 6:
         raise _lib.MiRenderError(f"expected inputs [M,6], got {tuple(x.shape)}")
-    x = x.detach().to(device=pf.device, dtype=torch.float32).contiguous()
+    x = _f32c(x, pf.device)
     if x.shape[0] == 0:
         return fields.eval_points(pf, x, film) + sum(p.reshape(-1)[:1].sum() for p in pf.params if p.requires_grad) * 0.0
     return _FieldFn.apply(pf, x, None, film if fields.is_film(pf.kind) else None, *pf.params).reshape(-1, 4)

@@ -16,7 +16,6 @@ Two jobs:
 """
 from __future__ import annotations
 
-import ctypes
 import math
 import warnings
 import weakref
@@ -252,7 +251,7 @@ class PackedField:
         if dev.type != "cuda":
             raise _lib.MiRenderError("the fused renderer needs the model on a ROCm device (model.cuda())")
         self.device = dev
-        self.packed = torch.empty(_lib.load().mi_field_packed_floats(self.kind), dtype=torch.float32, device=dev)
+        self.packed = torch.empty(_lib.query("mi_field_packed_floats", self.kind), dtype=torch.float32, device=dev)
         self.packed_bwd = None
         self._versions = self._versions_bwd = None
 
@@ -292,15 +291,12 @@ class PackedField:
         vers = self.versions()
         if vers == self._versions_bwd:
             return self.packed_bwd
-        lib = _lib.load()
         if self.packed_bwd is None:
-            self.packed_bwd = torch.empty(lib.mi_field_packed_bwd_floats(self.kind), dtype=torch.float32,
+            self.packed_bwd = torch.empty(_lib.query("mi_field_packed_bwd_floats", self.kind), dtype=torch.float32,
                                           device=self.device)
         srcs = self._sources()
-        arr = (ctypes.c_void_p * len(srcs))(*[t.data_ptr() for t in srcs])
-        with torch.cuda.device(self.device):
-            _lib.check(lib.mi_field_pack_bwd(self.kind, arr, len(srcs), self.w_0, _lib.ptr(self.packed_bwd),
-                                             _lib.stream_ptr(self.device)), "mi_field_pack_bwd")
+        _lib.call("mi_field_pack_bwd", self.device, self.kind, _lib.ptr_array(srcs), len(srcs), self.w_0,
+                  _lib.ptr(self.packed_bwd))
         self._keep_bwd = srcs
         self._versions_bwd = vers
         return self.packed_bwd
@@ -310,12 +306,8 @@ class PackedField:
         vers = self.versions()
         if vers == self._versions:
             return self.packed
-        lib = _lib.load()
         srcs = self._sources()
-        arr = (ctypes.c_void_p * len(srcs))(*[t.data_ptr() for t in srcs])
-        with torch.cuda.device(self.device):
-            _lib.check(lib.mi_field_pack(self.kind, arr, len(srcs), self.w_0, _lib.ptr(self.packed),
-                                         _lib.stream_ptr(self.device)), "mi_field_pack")
+        _lib.call("mi_field_pack", self.device, self.kind, _lib.ptr_array(srcs), len(srcs), self.w_0, _lib.ptr(self.packed))
         self._keep = srcs
         self._versions = vers
         return self.packed
@@ -393,25 +385,50 @@ def film_table(model) -> torch.Tensor:
     return torch.cat([torch.cat([g.reshape(-1), b.reshape(-1)]) for g, b in fp]).reshape(1, rows, 512)
 
 
+def film_groups(pf: PackedField, film, n: int, what: str = "rays must split evenly over the FiLM groups (images)"):
+    """How a call over `n` units (rays, or free-standing points) reads its FiLM table: (the table [groups,rows,512] as the
+    library reads it, groups, units per group) - (None, 1, n) for the kinds without FiLM, whatever `film` holds."""
+    if not is_film(pf.kind):
+        return None, 1, n
+    if film is None:
+        raise ValueError
+    film = _lib.f32c(film, pf.device).reshape(-1, film_layers(pf.kind), 512)
+    groups = film.shape[0]
+    if n % groups:
+        raise _lib.MiRenderError(what)
+    return film, groups, n // groups
+
+
+def resolve_film(film, *fields_and_models):
+    """The FiLM table of a call over (PackedField or None, model) pairs - one model, or the coarse / fine pair: None when
+    no field is a FiLM kind; else an explicit `film` wins, and without one the first FiLM model's own table is read
+    (film_table: ValueError when unset)."""
+    for pf, model in fields_and_models:
+        if pf is not None and is_film(pf.kind):
+            return film_table(model) if film is None else film
+    return None
+
+
+def pair_params(pf_c, pf_f) -> list:
+    """The parameters a call over the (coarse, fine) pair differentiates: once when one field serves both passes."""
+    return list(pf_c.params) if pf_c is pf_f else list(pf_c.params) + list(pf_f.params)
+
+
+def needs_graph(film, *pfs) -> bool:
+    """Does a call over these fields (and this FiLM table, if any) have to record a graph?"""
+    return torch.is_grad_enabled() and (any(p.requires_grad for pf in pfs for p in pf.params)
+                                        or (isinstance(film, torch.Tensor) and film.requires_grad))
+
+
 def eval_points(pf: PackedField, x: torch.Tensor, film: torch.Tensor | None = None) -> torch.Tensor:
     """network(x[M,6]) -> [M,4] on the fused kernel (replaces the model call at render.py:73)."""
-    lib = _lib.load()
     if x.dim() != 2 or x.shape[1] != 6:
         raise _lib.MiRenderError(f"expected inputs [M,6], got {tuple(x.shape)}")
-    x = x.detach().to(device=pf.device, dtype=torch.float32).contiguous()
+    x = _lib.f32c(x, pf.device)
     out = torch.empty((x.shape[0], 4), dtype=torch.float32, device=pf.device)
-    groups, ppg = 1, x.shape[0]
-    if is_film(pf.kind):
-        if film is None:
-            raise ValueError
-        film = film.detach().to(device=pf.device, dtype=torch.float32).contiguous().reshape(-1, film_layers(pf.kind), 512)
-        groups = film.shape[0]
-        if x.shape[0] % groups:
-            raise _lib.MiRenderError("points must split evenly over the FiLM groups")
-        ppg = x.shape[0] // groups
-    with torch.cuda.device(pf.device):
-        _lib.check(lib.mi_field_eval_points(pf.kind, _lib.ptr(pf.refresh()), _lib.ptr(film), _lib.ptr(x), groups,
-                                            ppg, _lib.ptr(out), _lib.stream_ptr(pf.device)), "mi_field_eval_points")
+    film, groups, ppg = film_groups(pf, film, x.shape[0], "points must split evenly over the FiLM groups")
+    _lib.call("mi_field_eval_points", pf.device, pf.kind, _lib.ptr(pf.refresh()), _lib.ptr(film), _lib.ptr(x), groups, ppg,
+              _lib.ptr(out))
     return out
 
 

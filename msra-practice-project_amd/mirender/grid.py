@@ -13,12 +13,10 @@ from . import _lib, fields
 
 def grid_points(n: int, voxel_origin, voxel_size: float, head: int, count: int, device) -> torch.Tensor:
     """Rows [head, head+count) of create_mesh's `samples` table (utils.py:57-71) + a zero view direction: [count,6]."""
-    lib = _lib.load()
     origin = np.ascontiguousarray(np.asarray(voxel_origin, dtype=np.float32).reshape(3))
     pts = torch.empty((count, 6), dtype=torch.float32, device=device)
-    with torch.cuda.device(device):
-        _lib.check(lib.mi_grid_points(int(n), origin.ctypes.data_as(ctypes.c_void_p), float(voxel_size), int(head),
-                                      int(count), _lib.ptr(pts), _lib.stream_ptr(device)), "mi_grid_points")
+    _lib.call("mi_grid_points", device, int(n), origin.ctypes.data_as(ctypes.c_void_p), float(voxel_size), int(head),
+              int(count), _lib.ptr(pts))
     return pts
 
 
@@ -29,8 +27,7 @@ def density_grid(decoder, n: int = 256, max_batch: int = 64 ** 3, voxel_origin=(
     pf = fields.as_packed_field(decoder)
     if voxel_size is None:
         voxel_size = 0.2 / (n - 1)                       # utils.py:55
-    if film is None and fields.is_film(pf.kind):
-        film = fields.film_table(decoder)
+    film = fields.resolve_film(film, (pf, decoder))
     total = n ** 3
     out = torch.empty(total, dtype=torch.float32, device=pf.device)
     head = 0

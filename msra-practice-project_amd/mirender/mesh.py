@@ -40,24 +40,23 @@ def marching_cubes(volume, level: float = 0.0, spacing=(1.0, 1.0, 1.0), gradient
     sp = (ctypes.c_double * 3)(*(float(s) for s in spacing))
     lib = _lib.load()
     dev = volume.device
+    ws = torch.empty(_lib.query("mi_mc_workspace_bytes", nx, ny, nz), dtype=torch.uint8, device=dev)
+    nv, nf = ctypes.c_int64(), ctypes.c_int64()
+    # not _lib.call: one of this entry point's return codes is not an error of the library but skimage's ValueError
     with torch.cuda.device(dev):
-        ws = torch.empty(int(lib.mi_mc_workspace_bytes(nx, ny, nz)), dtype=torch.uint8, device=dev)
-        stream = _lib.stream_ptr(dev)
-        nv, nf = ctypes.c_int64(), ctypes.c_int64()
         rc = lib.mi_marching_cubes_count(_lib.ptr(volume), nx, ny, nz, float(level), _lib.ptr(ws), ctypes.byref(nv),
-                                         ctypes.byref(nf), stream)
-        if rc == _ERANGE:
-            raise ValueError(RANGE_ERROR)
-        _lib.check(rc, "mi_marching_cubes_count")
-        verts = torch.empty((nv.value, 3), dtype=torch.float32, device=dev)
-        normals = torch.empty((nv.value, 3), dtype=torch.float32, device=dev)
-        values = torch.empty((nv.value,), dtype=torch.float32, device=dev)
-        faces = torch.empty((nf.value, 3), dtype=torch.int32, device=dev)
-        if nv.value:
-            _lib.check(lib.mi_marching_cubes_emit(_lib.ptr(volume), nx, ny, nz, float(level), sp,
-                                                  int(gradient_direction == "descent"), _lib.ptr(ws), _lib.ptr(verts),
-                                                  _lib.ptr(faces), _lib.ptr(normals), _lib.ptr(values), stream),
-                       "mi_marching_cubes_emit")
+                                         ctypes.byref(nf), _lib.stream_ptr(dev))
+    if rc == _ERANGE:
+        raise ValueError(RANGE_ERROR)
+    _lib.check(rc, "mi_marching_cubes_count")
+    verts = torch.empty((nv.value, 3), dtype=torch.float32, device=dev)
+    normals = torch.empty((nv.value, 3), dtype=torch.float32, device=dev)
+    values = torch.empty((nv.value,), dtype=torch.float32, device=dev)
+    faces = torch.empty((nf.value, 3), dtype=torch.int32, device=dev)
+    if nv.value:
+        _lib.call("mi_marching_cubes_emit", dev, _lib.ptr(volume), nx, ny, nz, float(level), sp,
+                  int(gradient_direction == "descent"), _lib.ptr(ws), _lib.ptr(verts), _lib.ptr(faces), _lib.ptr(normals),
+                  _lib.ptr(values))
     return verts, faces, normals, values
 
 

@@ -6,7 +6,6 @@ size_average=True)`, `SSIM(window_size, size_average)`; images are NCHW float te
 """
 from __future__ import annotations
 
-import ctypes
 from math import exp
 
 import torch
@@ -30,24 +29,20 @@ def create_window(window_size: int, channel: int) -> torch.Tensor:
 
 def image_metrics(img1: torch.Tensor, img2: torch.Tensor, window_size: int = 11) -> torch.Tensor:
     """[N,2] device tensor: per image (mse, mean ssim) of img1 vs img2, both [N,C,H,W] fp32 on the device."""
-    lib = _lib.load()
     if img1.dim() != 4 or img1.shape != img2.shape:
         raise _lib.MiRenderError("image_metrics expects two [N,C,H,W] tensors of the same shape")
     if not img1.is_cuda or img2.device != img1.device:
         raise _lib.MiRenderError("image_metrics needs both images on the same ROCm device (there is no CPU path)")
     dev = img1.device
-    a = img1.detach().to(torch.float32).contiguous()
-    b = img2.detach().to(torch.float32).contiguous()
+    a, b = _lib.f32c(img1, dev), _lib.f32c(img2, dev)
     n, c, h, w = a.shape
     win = gaussian(window_size, 1.5).contiguous()
     if win.device.type != "cpu" or win.dtype != torch.float32:
         raise _lib.MiRenderError("the SSIM window must be a CPU fp32 tensor (mi_image_metrics reads it on the host)")
-    ws = torch.empty(lib.mi_image_metrics_workspace_floats(n, c, h, w), dtype=torch.float32, device=dev)
+    ws = torch.empty(_lib.query("mi_image_metrics_workspace_floats", n, c, h, w), dtype=torch.float32, device=dev)
     out = torch.empty((n, 2), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.mi_image_metrics(_lib.ptr(a), _lib.ptr(b), n, c, h, w,
-                                        ctypes.c_void_p(win.data_ptr()), int(window_size), _lib.ptr(ws), _lib.ptr(out),
-                                        _lib.stream_ptr(dev)), "mi_image_metrics")
+    _lib.call("mi_image_metrics", dev, _lib.ptr(a), _lib.ptr(b), n, c, h, w, _lib.ptr(win), int(window_size), _lib.ptr(ws),
+              _lib.ptr(out))
     return out
 
 

@@ -115,7 +115,6 @@ class OccupancyGrid:
         if pf is None or fields.is_film(pf.kind):
             raise _lib.MiRenderError("OccupancyGrid.from_field: needs a NeRF, SirenNeRF or TinyNeRF field (a FiLM field's "
                                      "table is per image, a per-scene grid has no meaning there)")
-        lib = _lib.load()
         dev = pf.device
         dims = (int(resolution),) * 3 if np.ndim(resolution) == 0 else tuple(int(r) for r in resolution)
         k = int(supersample)
@@ -123,24 +122,19 @@ class OccupancyGrid:
         _, pdims = _i3(dims)
         _, plo = _f3(lo32)
         _, pcell = _f3((hi32 - lo32) / np.float32(dims))
-        words = lib.mi_occupancy_words(pdims)
-        if words < 0:
-            _lib.check(int(words), "mi_occupancy_words")
+        words = _lib.query("mi_occupancy_words", pdims)
         cells, k3 = dims[0] * dims[1] * dims[2], k ** 3
         per = max(1, int(max_batch) // k3)
         sigma = torch.empty(cells * k3, dtype=torch.float32, device=dev)
-        with torch.no_grad(), torch.cuda.device(dev):
+        with torch.no_grad():
             for head in range(0, cells, per):
                 count = min(per, cells - head)
                 pts = torch.empty((count * k3, 6), dtype=torch.float32, device=dev)
-                _lib.check(lib.mi_occupancy_cell_points(pdims, plo, pcell, k, head, count, _lib.ptr(pts), _lib.stream_ptr(dev)),
-                           "mi_occupancy_cell_points")
+                _lib.call("mi_occupancy_cell_points", dev, pdims, plo, pcell, k, head, count, _lib.ptr(pts))
                 sigma[head * k3:(head + count) * k3] = fields.eval_points(pf, pts)[:, 3]
             bits = torch.empty(words, dtype=torch.int32, device=dev)
-            ws_bytes = lib.mi_occupancy_pack_workspace_bytes(pdims, int(dilate))
-            if ws_bytes < 0:
-                _lib.check(int(ws_bytes), "mi_occupancy_pack_workspace_bytes")
-            ws = torch.empty(int(ws_bytes), dtype=torch.uint8, device=dev)
-            _lib.check(lib.mi_occupancy_pack(_lib.ptr(sigma), pdims, k, float(threshold), int(dilate), _lib.ptr(bits),
-                                             _lib.ptr(ws), int(ws_bytes), _lib.stream_ptr(dev)), "mi_occupancy_pack")
+            ws_bytes = _lib.query("mi_occupancy_pack_workspace_bytes", pdims, int(dilate))
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            _lib.call("mi_occupancy_pack", dev, _lib.ptr(sigma), pdims, k, float(threshold), int(dilate), _lib.ptr(bits),
+                      _lib.ptr(ws), ws_bytes)
         return cls(bits, lo32, hi32, dims)

@@ -26,30 +26,35 @@ from torch.autograd.function import once_differentiable
 from . import _lib, fields, ops, render_core
 
 
+def _check_kept(ctx):
+    """MI_DEBUG_GUARDS=1: the two buffers the forward keeps for the backward, after either call wrote or read them."""
+    _lib.check_guard(ctx.ws_g, "occupancy training workspace (mi_render_occupancy_train_extra_bytes)")
+    _lib.check_guard(ctx.saved_g, "occupancy training saved rows (mi_render_occupancy_train_saved_bytes)")
+
+
 class _OccupancyRenderFn(torch.autograd.Function):
     """One call of the pair over n rays: forward keeps the workspace (z, raw, weights, the two lists and counts) and the
     compact saved rows; backward hands the six cotangents to mi_render_rays_occupancy_backward."""
 
     @staticmethod
     def forward(ctx, pf_c, pf_f, rays, near, far, nc, nf, grid, t_rand, seed, ray0, *params):
-        lib = _lib.load()
         dev = pf_c.device
         n = rays.shape[0]
         shared = pf_c is pf_f
-        outs, counts, zl, ul = ops._occupancy_call_buffers(n, near, far, nc, nf, dev)
-        ws_bytes = int(lib.mi_render_workspace_bytes(n, nc, nf) + lib.mi_render_occupancy_train_extra_bytes(n, nc, nf))
-        sv_bytes = int(lib.mi_render_occupancy_train_saved_bytes(pf_c.kind, pf_f.kind, n, nc, nf))
-        if sv_bytes < 0:
-            _lib.check(sv_bytes, "mi_render_occupancy_train_saved_bytes")
+        outs = ops._render_outputs(n, dev)
+        counts = torch.zeros(2, dtype=torch.int32, device=dev)
+        zl, ul = ops._lin_tables(near, far, nc, nf, dev)
+        ws_bytes = (_lib.query("mi_render_workspace_bytes", n, nc, nf)
+                    + _lib.query("mi_render_occupancy_train_extra_bytes", n, nc, nf))
+        sv_bytes = _lib.query("mi_render_occupancy_train_saved_bytes", pf_c.kind, pf_f.kind, n, nc, nf)
         # owned by this call (not the shared inference workspace): the backward reads both
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        saved = torch.empty(sv_bytes, dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.mi_render_rays_occupancy_train(
-                pf_c.kind, _lib.ptr(pf_c.refresh()), pf_f.kind, _lib.ptr(pf_f.refresh()), _lib.ptr(rays), n, float(near),
-                float(far), nc, nf, _lib.ptr(zl), _lib.ptr(ul), _lib.ptr(t_rand), int(seed) & (2 ** 64 - 1), int(ray0),
-                _lib.ptr(grid.bits), *grid.c_args(), *[_lib.ptr(o) for o in outs], _lib.ptr(counts), _lib.ptr(ws), ws_bytes,
-                _lib.ptr(saved), sv_bytes, _lib.stream_ptr(dev)), "mi_render_rays_occupancy_train")
+        ws, ctx.ws_g = _lib.guarded(ws_bytes, torch.uint8, dev)
+        saved, ctx.saved_g = _lib.guarded(sv_bytes, torch.uint8, dev)
+        _lib.call("mi_render_rays_occupancy_train", dev, pf_c.kind, _lib.ptr(pf_c.refresh()), pf_f.kind,
+                  _lib.ptr(pf_f.refresh()), _lib.ptr(rays), n, float(near), float(far), nc, nf, _lib.ptr(zl), _lib.ptr(ul),
+                  _lib.ptr(t_rand), _lib.seed64(seed), int(ray0), _lib.ptr(grid.bits), *grid.c_args(),
+                  *[_lib.ptr(o) for o in outs], _lib.ptr(counts), _lib.ptr(ws), ws_bytes, _lib.ptr(saved), sv_bytes)
+        _check_kept(ctx)
         ctx.pf_c, ctx.pf_f, ctx.shared, ctx.n, ctx.nc, ctx.nf = pf_c, pf_f, shared, n, nc, nf
         ctx.rays, ctx.ws, ctx.saved, ctx.counts = rays, ws, saved, counts
         ctx.mark_non_differentiable(counts)
@@ -58,24 +63,24 @@ class _OccupancyRenderFn(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g_rgb_c, g_depth_c, g_acc_c, g_rgb_f, g_depth_f, g_acc_f, _g_counts=None):
-        lib = _lib.load()
         pf_c, pf_f, n, nc, nf = ctx.pf_c, ctx.pf_f, ctx.n, ctx.nc, ctx.nf
         dev = pf_c.device
+        # not _lib.f32c: under once_differentiable the cotangents carry no graph, and a detach each is time on this step's clock
         gs = [None if g is None else g.to(device=dev, dtype=torch.float32).contiguous()
               for g in (g_rgb_c, g_depth_c, g_acc_c, g_rgb_f, g_depth_f, g_acc_f)]
         grads_c = [torch.empty_like(p) for p in pf_c.params]
         grads_f = None if ctx.shared else [torch.empty_like(p) for p in pf_f.params]
-        arr_c = (ctypes.c_void_p * len(grads_c))(*[g.data_ptr() for g in grads_c])
-        arr_f = None if grads_f is None else (ctypes.c_void_p * len(grads_f))(*[g.data_ptr() for g in grads_f])
-        bws_bytes = int(lib.mi_render_occupancy_backward_workspace_bytes(pf_c.kind, pf_f.kind, int(ctx.shared), n, nc, nf))
-        bws = torch.empty(bws_bytes, dtype=torch.uint8, device=dev)
+        bws_bytes = _lib.query("mi_render_occupancy_backward_workspace_bytes", pf_c.kind, pf_f.kind, int(ctx.shared), n, nc,
+                               nf)
+        bws, bws_g = _lib.guarded(bws_bytes, torch.uint8, dev)
         written = ctypes.c_int(0)
-        with torch.cuda.device(dev):
-            _lib.check(lib.mi_render_rays_occupancy_backward(
-                pf_c.kind, _lib.ptr(pf_c.refresh_bwd()), pf_f.kind, None if ctx.shared else _lib.ptr(pf_f.refresh_bwd()),
-                int(ctx.shared), _lib.ptr(ctx.rays), n, nc, nf, _lib.ptr(ctx.ws), ctx.ws.numel(), _lib.ptr(ctx.saved),
-                ctx.saved.numel(), *[_lib.ptr(g) for g in gs], arr_c, arr_f, _lib.ptr(bws), bws_bytes, ctypes.byref(written),
-                _lib.stream_ptr(dev)), "mi_render_rays_occupancy_backward")
+        _lib.call("mi_render_rays_occupancy_backward", dev, pf_c.kind, _lib.ptr(pf_c.refresh_bwd()), pf_f.kind,
+                  None if ctx.shared else _lib.ptr(pf_f.refresh_bwd()), int(ctx.shared), _lib.ptr(ctx.rays), n, nc, nf,
+                  _lib.ptr(ctx.ws), ctx.ws.numel(), _lib.ptr(ctx.saved), ctx.saved.numel(), *[_lib.ptr(g) for g in gs],
+                  _lib.ptr_array(grads_c), None if grads_f is None else _lib.ptr_array(grads_f), _lib.ptr(bws), bws_bytes,
+                  ctypes.byref(written))
+        _check_kept(ctx)
+        _lib.check_guard(bws_g, "occupancy backward workspace (mi_render_occupancy_backward_workspace_bytes)")
         gc = tuple(grads_c) if written.value & 1 else (None,) * len(grads_c)
         gf = () if ctx.shared else (tuple(grads_f) if written.value & 2 else (None,) * len(grads_f))
         return (None,) * 11 + gc + gf
@@ -114,20 +119,16 @@ def render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, fi
     _check(grid, coarse_model, fine_model, pf_c, pf_f, rays)
     dev = pf_c.device
     nc, nf = int(coarse_sample_num), int(fine_sample_num)
-    needs_grad = torch.is_grad_enabled() and any(p.requires_grad for p in pf_c.params + pf_f.params)
-    if not needs_grad:
+    if not fields.needs_graph(None, pf_c, pf_f):
         with torch.no_grad():                       # one call, so counts is [1, 2] ([0, 2] without rays)
             return render_core._render_rays(rays, near, far, coarse_model, fine_model, nc, nf, t_rand=t_rand, seed=seed,
                                             ray0=ray0, grid=grid, return_counts=return_counts)
-    rays = torch.as_tensor(rays).detach().to(device=dev, dtype=torch.float32).reshape(-1, 2, 3).contiguous()
+    rays = ops._f32c(torch.as_tensor(rays), dev).reshape(-1, 2, 3)
     n = rays.shape[0]
     if seed is None and t_rand is None:
         seed = render_core._fresh_seed()
-    if t_rand is not None:
-        t_rand = torch.as_tensor(t_rand).detach().to(device=dev, dtype=torch.float32).contiguous()
-        if tuple(t_rand.shape) != (n, nc):
-            raise _lib.MiRenderError(f"t_rand must be [{n},{nc}]")
-    params = list(pf_c.params) if pf_c is pf_f else list(pf_c.params) + list(pf_f.params)
+    t_rand = ops._t_rand(t_rand, n, nc, dev)
+    params = fields.pair_params(pf_c, pf_f)
     step = n if not max_points else max(1, int(max_points) // (2 * nc + nf))
     if n == 0:                                      # no rays: render_core's empty outputs, hanging off the parameters
         outs = render_core.render_rays(rays, near, far, coarse_model, fine_model, nc, nf, t_rand=t_rand, seed=seed, ray0=ray0)

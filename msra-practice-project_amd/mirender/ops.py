@@ -7,17 +7,13 @@ from __future__ import annotations
 
 import ctypes
 import functools
-import os
 
 import numpy as np
 import torch
 
 from . import _lib
-from .fields import PackedField, film_layers, is_film
-
-
-def _f32c(t, device):
-    return t.detach().to(device=device, dtype=torch.float32).contiguous()
+from ._lib import f32c as _f32c, ptr as _p
+from .fields import PackedField, film_groups, is_film
 
 
 @functools.lru_cache(maxsize=64)
@@ -35,20 +31,42 @@ def linspace_table(start, end, steps, device):
     return _linspace_table(float(start), float(end), int(steps), str(device))
 
 
+def _lin_tables(near, far, n_coarse, n_fine, device, exact_linspace=True):
+    """(z_lin, u_lin): the coarse depths' and the inverse CDF's linspace tables, (None, None) when the kernels are to
+    evaluate them."""
+    if not exact_linspace:
+        return None, None
+    return linspace_table(near, far, n_coarse, device), linspace_table(0.0, 1.0, n_fine, device)
+
+
+def _t_rand(t_rand, n, n_coarse, device):
+    """The injected jitter as the library reads it, checked against the call's shape (None stays None)."""
+    if t_rand is None:
+        return None
+    t_rand = _f32c(torch.as_tensor(t_rand), device)
+    if tuple(t_rand.shape) != (n, n_coarse):
+        raise _lib.MiRenderError(f"t_rand must be [{n},{n_coarse}]")
+    return t_rand
+
+
+def _render_outputs(n, device, coarse_outputs=True):
+    """The six outputs of a render call (rgb, depth, acc of the coarse, then of the fine pass), None in the coarse slots
+    when they are not wanted."""
+    return [torch.empty(s, dtype=torch.float32, device=device) if coarse_outputs or k >= 3 else None
+            for k, s in enumerate(((n, 3), (n,), (n,), (n, 3), (n,), (n,)))]
+
+
 def gen_rays(width: int, height: int, focal, c2w, device, ray0: int = 0, n: int | None = None) -> torch.Tensor:
     """get_rays (nerf/render.py:7-23) generated on the device in render_image's flattened order
     (render.py:151-154).  Returns rays [n,2,3]."""
-    lib = _lib.load()
     n = width * height - ray0 if n is None else n
     c2w = np.ascontiguousarray(np.asarray(c2w)[:3, :4], dtype=np.float32)
     # NumPy >= 2 promotion: an np.float64 focal promotes the whole expression to fp64 (pi_GAN/modules.py:127),
     # a Python float keeps it fp32 (nerf/show_nerf.py:16)
     f64 = isinstance(focal, np.floating) and np.dtype(type(focal)) == np.float64
     rays = torch.empty((n, 2, 3), dtype=torch.float32, device=device)
-    with torch.cuda.device(device):
-        _lib.check(lib.mi_gen_rays(int(width), int(height), float(focal),
-                                   c2w.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), int(ray0), int(n),
-                                   _lib.ptr(rays), int(f64), _lib.stream_ptr(device)), "mi_gen_rays")
+    _lib.call("mi_gen_rays", device, int(width), int(height), float(focal),
+              c2w.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), int(ray0), int(n), _p(rays), int(f64))
     return rays
 
 
@@ -57,23 +75,16 @@ def sample_coarse(n: int, near: float, far: float, n_coarse: int, device, t_rand
     """Stratified depths z[n,Nc] (render.py:123-132).  t_rand[n,Nc] injects the jitter; otherwise an
     in-kernel Philox stream keyed by (``seed``, ``ray0`` + ray index, sample) is used, ``ray0`` being the index of
     the first ray in the caller's full ray list (so the jitter of a frame does not depend on how it is split)."""
-    lib = _lib.load()
     z = torch.empty((n, n_coarse), dtype=torch.float32, device=device)
-    if t_rand is not None:
-        t_rand = _f32c(t_rand, device)
-        if tuple(t_rand.shape) != (n, n_coarse):
-            raise _lib.MiRenderError(f"t_rand must be [{n},{n_coarse}]")
+    t_rand = _t_rand(t_rand, n, n_coarse, device)
     zl = linspace_table(near, far, n_coarse, device) if exact_linspace else None
-    with torch.cuda.device(device):
-        _lib.check(lib.mi_sample_coarse(n, float(near), float(far), n_coarse, _lib.ptr(zl), _lib.ptr(t_rand),
-                                        int(seed) & (2 ** 64 - 1), int(ray0), _lib.ptr(z), _lib.stream_ptr(device)),
-                   "mi_sample_coarse")
+    _lib.call("mi_sample_coarse", device, n, float(near), float(far), n_coarse, _p(zl), _p(t_rand), _lib.seed64(seed),
+              int(ray0), _p(z))
     return z
 
 
 def composite(raw: torch.Tensor, z: torch.Tensor, rays: torch.Tensor, want_weights: bool = True):
     """raw_to_outputs (render.py:78-103): returns rgb[n,3], depth[n], acc[n], weights[n,S]|None."""
-    lib = _lib.load()
     dev = raw.device
     n, s = z.shape
     raw, z, rays = _f32c(raw, dev), _f32c(z, dev), _f32c(rays, dev)
@@ -81,9 +92,7 @@ def composite(raw: torch.Tensor, z: torch.Tensor, rays: torch.Tensor, want_weigh
     depth = torch.empty((n,), dtype=torch.float32, device=dev)
     acc = torch.empty((n,), dtype=torch.float32, device=dev)
     w = torch.empty((n, s), dtype=torch.float32, device=dev) if want_weights else None
-    with torch.cuda.device(dev):
-        _lib.check(lib.mi_composite(n, s, _lib.ptr(raw), _lib.ptr(z), _lib.ptr(rays), _lib.ptr(rgb), _lib.ptr(depth),
-                                    _lib.ptr(acc), _lib.ptr(w), _lib.stream_ptr(dev)), "mi_composite")
+    _lib.call("mi_composite", dev, n, s, _p(raw), _p(z), _p(rays), _p(rgb), _p(depth), _p(acc), _p(w))
     return rgb, depth, acc, w
 
 
@@ -91,18 +100,14 @@ def sample_fine(z_coarse: torch.Tensor, weights: torch.Tensor, near: float, far:
                 want_samples: bool = False, exact_linspace: bool = True):
     """sample_pdf(mids, weights[...,1:-1], Nf) + detach + sort(cat) (render.py:140-142).
     Returns z_fine[n,Nc+Nf] (and z_samples[n,Nf] when asked)."""
-    lib = _lib.load()
     dev = z_coarse.device
     n, nc = z_coarse.shape
     z_coarse, weights = _f32c(z_coarse, dev), _f32c(weights, dev)
     z_fine = torch.empty((n, nc + n_fine), dtype=torch.float32, device=dev)
     zs = torch.empty((n, n_fine), dtype=torch.float32, device=dev) if want_samples else None
-    zl = linspace_table(near, far, nc, dev) if exact_linspace else None
-    ul = linspace_table(0.0, 1.0, n_fine, dev) if exact_linspace else None
-    with torch.cuda.device(dev):
-        _lib.check(lib.mi_sample_fine(n, float(near), float(far), nc, n_fine, _lib.ptr(zl), _lib.ptr(ul),
-                                      _lib.ptr(z_coarse), _lib.ptr(weights), _lib.ptr(zs), _lib.ptr(z_fine),
-                                      _lib.stream_ptr(dev)), "mi_sample_fine")
+    zl, ul = _lin_tables(near, far, nc, n_fine, dev, exact_linspace)
+    _lib.call("mi_sample_fine", dev, n, float(near), float(far), nc, n_fine, _p(zl), _p(ul), _p(z_coarse), _p(weights),
+              _p(zs), _p(z_fine))
     return (z_fine, zs) if want_samples else z_fine
 
 
@@ -110,39 +115,31 @@ def sample_fine_pos(z_coarse: torch.Tensor, weights: torch.Tensor, near: float, 
                     exact_linspace: bool = True):
     """sample_fine that also says where every input went: (z_fine [n,Nc+Nf], z_samples [n,Nf], pos [n,Nc+Nf] int32 with
     pos[e] = index in z_fine of z_coarse[e] (e < Nc) or z_samples[e - Nc]).  For one field shared by both passes."""
-    lib = _lib.load()
     dev = z_coarse.device
     n, nc = z_coarse.shape
     z_coarse, weights = _f32c(z_coarse, dev), _f32c(weights, dev)
     z_fine = torch.empty((n, nc + n_fine), dtype=torch.float32, device=dev)
     zs = torch.empty((n, n_fine), dtype=torch.float32, device=dev)
     pos = torch.empty((n, nc + n_fine), dtype=torch.int32, device=dev)
-    zl = linspace_table(near, far, nc, dev) if exact_linspace else None
-    ul = linspace_table(0.0, 1.0, n_fine, dev) if exact_linspace else None
-    with torch.cuda.device(dev):
-        _lib.check(lib.mi_sample_fine_pos(n, float(near), float(far), nc, n_fine, _lib.ptr(zl), _lib.ptr(ul),
-                                          _lib.ptr(z_coarse), _lib.ptr(weights), _lib.ptr(zs), _lib.ptr(z_fine), _lib.ptr(pos),
-                                          _lib.stream_ptr(dev)), "mi_sample_fine_pos")
+    zl, ul = _lin_tables(near, far, nc, n_fine, dev, exact_linspace)
+    _lib.call("mi_sample_fine_pos", dev, n, float(near), float(far), nc, n_fine, _p(zl), _p(ul), _p(z_coarse),
+              _p(weights), _p(zs), _p(z_fine), _p(pos))
     return z_fine, zs, pos
 
 
 def merge_raw(raw_c: torch.Tensor, raw_s: torch.Tensor, pos: torch.Tensor) -> torch.Tensor:
     """raw_fine [n,Nc+Nf,4] in sorted order from the coarse pass's raw [n,Nc,4] and the field at z_samples [n,Nf,4]."""
-    lib = _lib.load()
     dev = raw_c.device
     n, nc = raw_c.shape[0], raw_c.shape[1]
     nf = pos.shape[1] - nc
     raw_f = torch.empty((n, nc + nf, 4), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.mi_merge_raw(n, nc, nf, _lib.ptr(raw_c), _lib.ptr(raw_s) if nf else None, _lib.ptr(pos),
-                                    _lib.ptr(raw_f), _lib.stream_ptr(dev)), "mi_merge_raw")
+    _lib.call("mi_merge_raw", dev, n, nc, nf, _p(raw_c), _p(raw_s) if nf else None, _p(pos), _p(raw_f))
     return raw_f
 
 
 def split_grad(g_raw_f: torch.Tensor, pos: torch.Tensor, nc: int, g_raw_c: torch.Tensor | None = None):
     """The transpose of merge_raw: (g_raw_coarse [n,Nc,4] - added onto `g_raw_c` in place when given -, g_raw_samples
     [n,Nf,4])."""
-    lib = _lib.load()
     dev = g_raw_f.device
     n, s = pos.shape
     nf = s - nc
@@ -150,15 +147,12 @@ def split_grad(g_raw_f: torch.Tensor, pos: torch.Tensor, nc: int, g_raw_c: torch
     if g_raw_c is None:
         g_raw_c = torch.empty((n, nc, 4), dtype=torch.float32, device=dev)
     g_s = torch.empty((n, nf, 4), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.mi_split_grad(n, nc, nf, _lib.ptr(g_raw_f), _lib.ptr(pos), _lib.ptr(g_raw_c), int(acc),
-                                     _lib.ptr(g_s) if nf else None, _lib.stream_ptr(dev)), "mi_split_grad")
+    _lib.call("mi_split_grad", dev, n, nc, nf, _p(g_raw_f), _p(pos), _p(g_raw_c), int(acc), _p(g_s) if nf else None)
     return g_raw_c, g_s
 
 
 def sample_pdf(bins: torch.Tensor, weights: torch.Tensor, n_samples: int) -> torch.Tensor:
     """sample_pdf(bins[n,nb], weights[n,nb-1], N) -> [n,N] (render.py:27-56), any bins."""
-    lib = _lib.load()
     dev = bins.device
     bins, weights = _f32c(bins, dev), _f32c(weights, dev)
     n, nb = bins.shape
@@ -166,35 +160,18 @@ def sample_pdf(bins: torch.Tensor, weights: torch.Tensor, n_samples: int) -> tor
         raise _lib.MiRenderError("weights must be [n, len(bins)-1]")
     out = torch.empty((n, n_samples), dtype=torch.float32, device=dev)
     ul = linspace_table(0.0, 1.0, n_samples, dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.mi_sample_pdf(n, nb, n_samples, _lib.ptr(bins), _lib.ptr(weights), _lib.ptr(ul), _lib.ptr(out),
-                                     _lib.stream_ptr(dev)), "mi_sample_pdf")
+    _lib.call("mi_sample_pdf", dev, n, nb, n_samples, _p(bins), _p(weights), _p(ul), _p(out))
     return out
-
-
-def _film_for(pf: PackedField, film, n_rays):
-    if not is_film(pf.kind):
-        return None, 1, n_rays
-    if film is None:
-        raise ValueError
-    film = _f32c(film, pf.device).reshape(-1, film_layers(pf.kind), 512)
-    groups = film.shape[0]
-    if n_rays % groups:
-        raise _lib.MiRenderError("rays must split evenly over the FiLM groups (images)")
-    return film, groups, n_rays // groups
 
 
 def field_eval_rays(pf: PackedField, rays: torch.Tensor, z: torch.Tensor, film=None) -> torch.Tensor:
     """run_network on points o + d*z with view dirs d/|d| (render.py:122,134-135), fused.  raw[n,S,4]."""
-    lib = _lib.load()
     dev = pf.device
     rays, z = _f32c(rays, dev), _f32c(z, dev)
     n, s = z.shape
-    film, groups, rpg = _film_for(pf, film, n)
+    film, groups, rpg = film_groups(pf, film, n)
     raw = torch.empty((n, s, 4), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.mi_field_eval_rays(pf.kind, _lib.ptr(pf.refresh()), _lib.ptr(film), _lib.ptr(rays), _lib.ptr(z),
-                                          groups, rpg, s, _lib.ptr(raw), _lib.stream_ptr(dev)), "mi_field_eval_rays")
+    _lib.call("mi_field_eval_rays", dev, pf.kind, _p(pf.refresh()), _p(film), _p(rays), _p(z), groups, rpg, s, _p(raw))
     return raw
 
 
@@ -230,13 +207,13 @@ class _Workspace:
         return b
 
 
-def _occupancy_call_buffers(n, near, far, n_coarse, n_fine, device, coarse_outputs=True):
-    """What both calls with a grid are handed besides their workspace: (the six outputs - None in the coarse slots when they are
-    not wanted -, counts int32 [2], z_lin, u_lin)."""
-    outs = [torch.empty(s, dtype=torch.float32, device=device) if coarse_outputs or k >= 3 else None
-            for k, s in enumerate(((n, 3), (n,), (n,), (n, 3), (n,), (n,)))]
-    return (outs, torch.zeros(2, dtype=torch.int32, device=device), linspace_table(near, far, n_coarse, device),
-            linspace_table(0.0, 1.0, n_fine, device))
+def _workspace(device, nbytes):
+    """(workspace of at least `nbytes`, what _lib.check_guard takes after the call): the cached one of this (device,
+    stream); with MI_DEBUG_GUARDS=1 a fresh one of exactly `nbytes` with a sentinel tail, so an overrun cannot hide in
+    what an earlier, larger call left behind."""
+    if _lib.guards_on():
+        return _lib.guarded(nbytes, torch.uint8, device)
+    return _Workspace.get(device, nbytes), None
 
 
 def render_rays_fused(pf_c: PackedField, pf_f: PackedField, rays: torch.Tensor, near: float, far: float,
@@ -246,44 +223,28 @@ def render_rays_fused(pf_c: PackedField, pf_f: PackedField, rays: torch.Tensor, 
     Returns the reference's 6-tuple.  coarse_outputs=False: the caller discards the coarse pass's outputs, which come back
     as None; with two different fields the library then runs the coarse field's sigma-only forward (mi_render_rays).
     The fine outputs are the same bits either way."""
-    lib = _lib.load()
     dev = pf_c.device
     rays = _f32c(rays, dev).reshape(-1, 2, 3)
     n = rays.shape[0]
-    film, groups, rpg = _film_for(pf_c, film, n) if is_film(pf_c.kind) else _film_for(pf_f, film, n)
-    if t_rand is not None:
-        t_rand = _f32c(t_rand, dev)
-        if tuple(t_rand.shape) != (n, n_coarse):
-            raise _lib.MiRenderError(f"t_rand must be [{n},{n_coarse}]")
-    outs = [torch.empty(s, dtype=torch.float32, device=dev) if coarse_outputs or k >= 3 else None
-            for k, s in enumerate(((n, 3), (n,), (n,), (n, 3), (n,), (n,)))]
-    ws_bytes = lib.mi_render_workspace_bytes(n, n_coarse, n_fine)
+    film, groups, rpg = film_groups(pf_c if is_film(pf_c.kind) else pf_f, film, n)
+    t_rand = _t_rand(t_rand, n, n_coarse, dev)
+    outs = _render_outputs(n, dev, coarse_outputs)
+    ws_bytes = _lib.query("mi_render_workspace_bytes", n, n_coarse, n_fine)
     if pf_c is pf_f and n_fine > 0:
         # one field for both passes: with room for z_samples / their raw values / the merge positions the library evaluates
         # the Nf new depths only (mi_render_rays, include/mi_render.h); without it the plain path, same results
-        ws_bytes += lib.mi_render_shared_field_extra_bytes(n, n_coarse, n_fine)
-    elif lib.mi_field_has_deferred_colour(pf_f.kind) == 1:
+        ws_bytes += _lib.query("mi_render_shared_field_extra_bytes", n, n_coarse, n_fine)
+    elif _lib.load().mi_field_has_deferred_colour(pf_f.kind) == 1:
         # two fields: with room for one chunk's live list the library runs the fine pass's colour branch on the points with
         # sigma > 0 only (0 bytes with Nf = 0); without it the whole forward, same results.  The list is min(n * S, 2^22)
         # rows of 1 028 bytes: 4.02 GiB from 21 846 rays of 192 samples on, kept with the workspace between calls
-        ws_bytes += lib.mi_render_deferred_colour_extra_bytes(n, n_coarse, n_fine)
-    guard = None
-    if os.environ.get("MI_DEBUG_GUARDS") == "1":       # sentinel zone behind the workspace, checked after the call
-        ws = torch.empty(int(ws_bytes) + 16384, dtype=torch.uint8, device=dev)
-        ws[int(ws_bytes):] = 0xA5
-        guard = ws[int(ws_bytes):]
-    else:
-        ws = _Workspace.get(dev, ws_bytes)
-    zl = linspace_table(near, far, n_coarse, dev) if exact_linspace else None
-    ul = linspace_table(0.0, 1.0, n_fine, dev) if exact_linspace else None
-    with torch.cuda.device(dev):
-        _lib.check(lib.mi_render_rays(pf_c.kind, _lib.ptr(pf_c.refresh()), pf_f.kind, _lib.ptr(pf_f.refresh()),
-                                      _lib.ptr(film), _lib.ptr(rays), groups, rpg, float(near), float(far),
-                                      n_coarse, n_fine, _lib.ptr(zl), _lib.ptr(ul), _lib.ptr(t_rand),
-                                      int(seed) & (2 ** 64 - 1), int(ray0), *[_lib.ptr(o) for o in outs], _lib.ptr(ws),
-                                      int(ws_bytes), _lib.stream_ptr(dev)), "mi_render_rays")
-    if guard is not None and not bool((guard == 0xA5).all()):
-        raise _lib.MiRenderError("mi_render_rays wrote past mi_render_workspace_bytes")
+        ws_bytes += _lib.query("mi_render_deferred_colour_extra_bytes", n, n_coarse, n_fine)
+    ws, ws_g = _workspace(dev, ws_bytes)
+    zl, ul = _lin_tables(near, far, n_coarse, n_fine, dev, exact_linspace)
+    _lib.call("mi_render_rays", dev, pf_c.kind, _p(pf_c.refresh()), pf_f.kind, _p(pf_f.refresh()), _p(film), _p(rays),
+              groups, rpg, float(near), float(far), n_coarse, n_fine, _p(zl), _p(ul), _p(t_rand), _lib.seed64(seed),
+              int(ray0), *[_p(o) for o in outs], _p(ws), ws_bytes)
+    _lib.check_guard(ws_g, "mi_render_rays workspace (mi_render_workspace_bytes)")
     return tuple(outs)
 
 
@@ -294,32 +255,20 @@ def render_rays_occupancy(pf_c: PackedField, pf_f: PackedField, rays: torch.Tens
     `grid` (mirender.occupancy.OccupancyGrid), or outside its box, counts as raw = 0 and is not evaluated; everything else is
     render_rays_fused.  Returns (the 6-tuple, counts): counts is a device int32 [2], the samples the coarse and the fine pass
     evaluated.  coarse_outputs=False: the coarse slots come back as None."""
-    lib = _lib.load()
     dev = pf_c.device
     if is_film(pf_c.kind) or is_film(pf_f.kind):
         raise _lib.MiRenderError("rendering with an occupancy grid is not built for FiLM fields")
     rays = _f32c(rays, dev).reshape(-1, 2, 3)
     n = rays.shape[0]
-    if t_rand is not None:
-        t_rand = _f32c(t_rand, dev)
-        if tuple(t_rand.shape) != (n, n_coarse):
-            raise _lib.MiRenderError(f"t_rand must be [{n},{n_coarse}]")
-    outs, counts, zl, ul = _occupancy_call_buffers(n, near, far, n_coarse, n_fine, dev, coarse_outputs)
-    ws_bytes = lib.mi_render_workspace_bytes(n, n_coarse, n_fine) + lib.mi_render_occupancy_extra_bytes(n, n_coarse, n_fine)
-    guard = None
-    if os.environ.get("MI_DEBUG_GUARDS") == "1":       # sentinel zone behind the workspace, checked after the call
-        ws = torch.empty(int(ws_bytes) + 16384, dtype=torch.uint8, device=dev)
-        ws[int(ws_bytes):] = 0xA5
-        guard = ws[int(ws_bytes):]
-    else:
-        ws = _Workspace.get(dev, ws_bytes)
-    with torch.cuda.device(dev):
-        _lib.check(lib.mi_render_rays_occupancy(pf_c.kind, _lib.ptr(pf_c.refresh()), pf_f.kind, _lib.ptr(pf_f.refresh()),
-                                                _lib.ptr(rays), n, float(near), float(far), n_coarse, n_fine, _lib.ptr(zl),
-                                                _lib.ptr(ul), _lib.ptr(t_rand), int(seed) & (2 ** 64 - 1), int(ray0),
-                                                _lib.ptr(grid.bits), *grid.c_args(), *[_lib.ptr(o) for o in outs],
-                                                _lib.ptr(counts), _lib.ptr(ws), int(ws_bytes), _lib.stream_ptr(dev)),
-                   "mi_render_rays_occupancy")
-    if guard is not None and not bool((guard == 0xA5).all()):
-        raise _lib.MiRenderError("mi_render_rays_occupancy wrote past its workspace")
+    t_rand = _t_rand(t_rand, n, n_coarse, dev)
+    outs = _render_outputs(n, dev, coarse_outputs)
+    counts = torch.zeros(2, dtype=torch.int32, device=dev)
+    zl, ul = _lin_tables(near, far, n_coarse, n_fine, dev)
+    ws_bytes = (_lib.query("mi_render_workspace_bytes", n, n_coarse, n_fine)
+                + _lib.query("mi_render_occupancy_extra_bytes", n, n_coarse, n_fine))
+    ws, ws_g = _workspace(dev, ws_bytes)
+    _lib.call("mi_render_rays_occupancy", dev, pf_c.kind, _p(pf_c.refresh()), pf_f.kind, _p(pf_f.refresh()), _p(rays), n,
+              float(near), float(far), n_coarse, n_fine, _p(zl), _p(ul), _p(t_rand), _lib.seed64(seed), int(ray0),
+              _p(grid.bits), *grid.c_args(), *[_p(o) for o in outs], _p(counts), _p(ws), ws_bytes)
+    _lib.check_guard(ws_g, "mi_render_rays_occupancy workspace (mi_render_occupancy_extra_bytes)")
     return tuple(outs), counts

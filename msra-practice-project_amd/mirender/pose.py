@@ -18,7 +18,6 @@ The depths carry no gradient to the rays: the stratified ones do not depend on t
 """
 from __future__ import annotations
 
-import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -95,18 +94,14 @@ def render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, fi
         detached = rays.detach() if isinstance(rays, torch.Tensor) else rays
         return render_core.render_rays(detached, near, far, coarse_model, fine_model, coarse_sample_num, fine_sample_num,
                                        t_rand=t_rand, seed=seed, film=film, ray0=ray0)
-    dev = pf_c.device
-    rays = rays.to(device=dev, dtype=torch.float32).reshape(-1, 2, 3).contiguous()
+    # not ops._f32c, which detaches: the graph to `rays` has to survive into the Function
+    rays = rays.to(device=pf_c.device, dtype=torch.float32).reshape(-1, 2, 3).contiguous()
     if seed is None and t_rand is None:
         seed = render_core._fresh_seed()
-    if fields.is_film(pf_c.kind) or fields.is_film(pf_f.kind):
-        if film is None:
-            film = fields.film_table(coarse_model if fields.is_film(pf_c.kind) else fine_model)
-    else:
-        film = None
-    params = list(pf_c.params) if pf_c is pf_f else list(pf_c.params) + list(pf_f.params)
+    film = fields.resolve_film(film, (pf_c, coarse_model), (pf_f, fine_model))
     return _RenderRaysPoseFn.apply(pf_c, pf_f, rays, float(near), float(far), int(coarse_sample_num), int(fine_sample_num),
-                                   film, None if t_rand is None else t_rand.detach(), int(seed or 0), int(ray0), *params)
+                                   film, None if t_rand is None else t_rand.detach(), int(seed or 0), int(ray0),
+                                   *fields.pair_params(pf_c, pf_f))
 
 
 def render_image_tensor(width, height, focal, c2w, near, far, coarse_model, fine_model, coarse_sample_num,
@@ -129,31 +124,15 @@ def render_image_tensor(width, height, focal, c2w, near, far, coarse_model, fine
 
 
 class _FieldPointsFn(torch.autograd.Function):
-    """network(x [M,6]) of a fused kind with gradients to x (mi_field_input_grad), its parameters and the FiLM table."""
+    """autograd._FieldFn over free-standing points (pf, x [M,6], None, film, *params) whose backward also returns dL/dx
+    (mi_field_input_grad): the same forward, the same backward calls plus the input gradient after each range's."""
 
-    @staticmethod
-    def forward(ctx, pf, x, film, *params):
-        xd = x.detach()
-        raw, ctx.acts = autograd._forward_pass(pf, xd, None, film, autograd.SAVE_FINE_BYTES)
-        ctx.pf, ctx.film, ctx.versions = pf, None if film is None else film.detach(), pf.versions()
-        ctx.save_for_backward(xd, raw)
-        return raw
+    forward = staticmethod(autograd._FieldFn.forward)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g_raw):
-        x, raw = ctx.saved_tensors
-        pf = ctx.pf
-        if pf.versions() != ctx.versions:
-            raise RuntimeError("field backward: a field parameter was modified in place (or replaced) after the forward "
-                               "pass that this backward belongs to")
-        g_x = torch.empty_like(x)
-        grads, g_film = autograd._field_backward(pf, x, None, raw, g_raw.to(torch.float32).contiguous(), ctx.film, ctx.acts,
-                                                 input_grad=g_x)
-        ctx.acts = None
-        if g_film is not None:
-            g_film = g_film.reshape(ctx.film.shape) if ctx.needs_input_grad[2] else None
-        return (None, g_x if ctx.needs_input_grad[1] else None, g_film) + tuple(grads)
+        return autograd._FieldFn.backward(ctx, g_raw, input_grad=True)
 
 
 def field_eval_points(pf_or_module, x, film=None):
@@ -165,12 +144,8 @@ def field_eval_points(pf_or_module, x, film=None):
                                  "its own forward")
     if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[1] != 6:
         raise _lib.MiRenderError(f"expected inputs [M,6], got {tuple(getattr(x, 'shape', ()))}")
-    if fields.is_film(pf.kind):
-        if film is None:
-            film = fields.film_table(pf_or_module)
-    else:
-        film = None
+    film = fields.resolve_film(film, (pf, pf_or_module))
     if not (torch.is_grad_enabled() and x.requires_grad) or x.shape[0] == 0:
         return autograd.field_eval_points(pf, x.detach(), film)
-    x = x.to(device=pf.device, dtype=torch.float32).contiguous()
-    return _FieldPointsFn.apply(pf, x, film, *pf.params).reshape(-1, 4)
+    x = x.to(device=pf.device, dtype=torch.float32).contiguous()          # not detached: the graph to x has to survive
+    return _FieldPointsFn.apply(pf, x, None, film, *pf.params).reshape(-1, 4)

@@ -100,9 +100,7 @@ def _eval_pass(model, pf, rays, z, film):
     if pf is None:
         return _generic_field(model, rays, z)
     from . import autograd
-    if fields.is_film(pf.kind) and film is None:
-        film = fields.film_table(model)
-    return autograd.field_eval_rays(pf, rays, z, film if fields.is_film(pf.kind) else None)
+    return autograd.field_eval_rays(pf, rays, z, fields.resolve_film(film, (pf, model)))
 
 
 def _check_grid(grid, pf_c, pf_f, film):
@@ -113,7 +111,7 @@ def _check_grid(grid, pf_c, pf_f, film):
     if fields.is_film(pf_c.kind) or fields.is_film(pf_f.kind):
         raise _lib.MiRenderError("rendering with an occupancy grid is not built for FiLM fields (a FiLM field's table is per "
                                  "image, a per-scene grid has no meaning there)")
-    if torch.is_grad_enabled() and any(p.requires_grad for p in pf_c.params + pf_f.params):
+    if fields.needs_graph(None, pf_c, pf_f):
         raise _lib.MiRenderError("rendering with an occupancy grid is not built for calls that need gradients (training): "
                                  "call it under torch.no_grad()")
     if torch.device(grid.device) != torch.device(pf_c.device):
@@ -139,6 +137,7 @@ def _render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, f
     (ops.render_rays_fused), which may then return None in their slots.  The fine outputs are the same bits.
     return_counts=True (with a grid): (the outputs, int32 [calls, 2], the samples each pass evaluated; [0, 2] without rays)."""
     dev = _device_of(coarse_model, fine_model, rays=rays)
+    # not ops._f32c, which detaches: on the generic path the graph to `rays` has to survive
     rays = torch.as_tensor(rays).to(device=dev, dtype=torch.float32).reshape(-1, 2, 3).contiguous()
     nc, nf = int(coarse_sample_num), int(fine_sample_num)
     if seed is None and t_rand is None:
@@ -167,14 +166,8 @@ def _render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, f
             outs = [o + zero for o in outs]
         return (tuple(outs), torch.zeros((0, 2), dtype=torch.int32, device=dev)) if return_counts else tuple(outs)
     if pf_c is not None and pf_f is not None:
-        needs_grad = torch.is_grad_enabled() and any(p.requires_grad for p in pf_c.params + pf_f.params)
-        if fields.is_film(pf_c.kind) or fields.is_film(pf_f.kind):
-            if film is None:
-                film = fields.film_table(coarse_model if fields.is_film(pf_c.kind) else fine_model)
-            needs_grad = needs_grad or (torch.is_grad_enabled() and film.requires_grad)
-        else:
-            film = None
-        if needs_grad:
+        film = fields.resolve_film(film, (pf_c, coarse_model), (pf_f, fine_model))
+        if fields.needs_graph(film, pf_c, pf_f):
             from . import autograd
             return autograd.render_rays_train(pf_c, pf_f, rays, near, far, nc, nf, film, t_rand, seed or 0, ray0)
         return ops.render_rays_fused(pf_c, pf_f, rays, near, far, nc, nf, film, t_rand, seed or 0, ray0=ray0,

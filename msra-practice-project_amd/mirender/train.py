@@ -29,7 +29,6 @@ class RayBank:
 
     def __init__(self, images, poses, focal: float, device="cuda", white_bkgd: bool = True, generator=None,
                  reshuffle: bool = True):
-        lib = _lib.load()
         dev = torch.device(device)
         images = torch.as_tensor(np.asarray(images) if not isinstance(images, torch.Tensor) else images)
         images = images.to(device=dev, dtype=torch.float32).contiguous()
@@ -41,9 +40,8 @@ class RayBank:
         self.width, self.height, self.generator, self.reshuffle = w, h, generator, reshuffle
         self.table = torch.empty((n * h * w, 10), dtype=torch.float32, device=dev)
         f64 = isinstance(focal, np.floating) and np.dtype(type(focal)) == np.float64      # as ops.gen_rays
-        with torch.cuda.device(dev):
-            _lib.check(lib.mi_ray_bank(w, h, float(focal), _lib.ptr(poses), _lib.ptr(images), int(white_bkgd), n,
-                                       _lib.ptr(self.table), int(f64), _lib.stream_ptr(dev)), "mi_ray_bank")
+        _lib.call("mi_ray_bank", dev, w, h, float(focal), _lib.ptr(poses), _lib.ptr(images), int(white_bkgd), n,
+                  _lib.ptr(self.table), int(f64))
         self.batch_idx = 0
 
     def __len__(self):
@@ -71,18 +69,14 @@ class RayBank:
 class _NerfLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rgb_c, acc_c, rgb_f, acc_f, target, use_alpha, use_fine):
-        lib = _lib.load()
         dev = rgb_f.device
-        f = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731
-        rgb_c, acc_c, rgb_f, acc_f, target = f(rgb_c), f(acc_c), f(rgb_f), f(acc_f), f(target)
+        rgb_c, acc_c, rgb_f, acc_f, target = (_lib.f32c(t, dev) for t in (rgb_c, acc_c, rgb_f, acc_f, target))
         n = rgb_f.shape[0]
         grads = [torch.empty_like(t) for t in (rgb_c, acc_c, rgb_f, acc_f)]
-        ws = torch.empty(lib.mi_nerf_loss_workspace_floats(n), dtype=torch.float32, device=dev)
+        ws = torch.empty(_lib.query("mi_nerf_loss_workspace_floats", n), dtype=torch.float32, device=dev)
         out = torch.empty(4, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.mi_nerf_loss(n, _lib.ptr(rgb_c), _lib.ptr(acc_c), _lib.ptr(rgb_f), _lib.ptr(acc_f),
-                                        _lib.ptr(target), int(use_alpha), int(use_fine), *[_lib.ptr(g) for g in grads],
-                                        _lib.ptr(ws), _lib.ptr(out), _lib.stream_ptr(dev)), "mi_nerf_loss")
+        _lib.call("mi_nerf_loss", dev, n, _lib.ptr(rgb_c), _lib.ptr(acc_c), _lib.ptr(rgb_f), _lib.ptr(acc_f),
+                  _lib.ptr(target), int(use_alpha), int(use_fine), *[_lib.ptr(g) for g in grads], _lib.ptr(ws), _lib.ptr(out))
         ctx.save_for_backward(*grads)
         ctx.mark_non_differentiable(out)
         return out[0].clone(), out
@@ -153,7 +147,6 @@ class FusedAdam:
 
     @torch.no_grad()
     def step(self):
-        lib = _lib.load()
         g = self.param_groups[0]
         lr, (beta1, beta2), eps = float(g["lr"]), g["betas"], float(g["eps"])
         if g.get("weight_decay") or g.get("amsgrad") or g.get("maximize"):
@@ -178,20 +171,16 @@ class FusedAdam:
             st = self.state[p]
             if st["exp_avg"].device != dev:        # the moments follow the parameters (raw pointers go to the kernel)
                 st["exp_avg"], st["exp_avg_sq"] = st["exp_avg"].to(dev), st["exp_avg_sq"].to(dev)
-        arr = lambda ts: (ctypes.c_void_p * len(ts))(*[x.data_ptr() for x in ts])  # noqa: E731
+        arr = _lib.ptr_array
         kinds = (ctypes.c_int * len(self.fields))(*[pf.kind for pf in self.fields])
         numel = (ctypes.c_int64 * n)(*[p.numel() for p in self.params])
         # the streams must hold the current parameters before their changed entries are scattered into them
         fwd = [pf.refresh() for pf in self.fields]
         bwd = [pf.refresh_bwd() if pf.packed_bwd is not None else None for pf in self.fields]
-        pfwd = (ctypes.c_void_p * len(fwd))(*[x.data_ptr() for x in fwd])
-        pbwd = (ctypes.c_void_p * len(bwd))(*[None if x is None else x.data_ptr() for x in bwd])
-        with torch.cuda.device(dev):
-            _lib.check(lib.mi_adam_step(len(self.fields), kinds, arr(self.params), arr(grads),
-                                        arr([self.state[p]["exp_avg"] for p in self.params]),
-                                        arr([self.state[p]["exp_avg_sq"] for p in self.params]), numel,
-                                        -lr / bc1, 1 - beta1, beta2, 1 - beta2, eps, bc2_sqrt, pfwd, pbwd,
-                                        _lib.stream_ptr(dev)), "mi_adam_step")
+        _lib.call("mi_adam_step", dev, len(self.fields), kinds, arr(self.params), arr(grads),
+                  arr([self.state[p]["exp_avg"] for p in self.params]),
+                  arr([self.state[p]["exp_avg_sq"] for p in self.params]), numel,
+                  -lr / bc1, 1 - beta1, beta2, 1 - beta2, eps, bc2_sqrt, arr(fwd), arr(bwd))
         for p in self.params:
             self.state[p]["step"] += 1
         # the kernel wrote parameters and streams together; torch's version counters did not move, so the lazily

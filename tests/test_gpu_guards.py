@@ -55,6 +55,38 @@ def test_render_workspace_is_never_overrun(monkeypatch, kind, n, nc, nf):
         assert torch.equal(a, b)
 
 
+@pytest.mark.parametrize("kind", ["nerf", "tiny_nerf"])
+@pytest.mark.parametrize("n,nc,nf", [(1, 3, 0), (129, 8, 16), (300, 16, 8)])
+@pytest.mark.parametrize("occupied", ["ones", "lower_half"])
+def test_occupancy_training_buffers_are_never_overrun(monkeypatch, kind, n, nc, nf, occupied):
+    """Training with an occupancy grid hands the library three caller-sized buffers (workspace, saved rows, backward
+    workspace): a sentinel zone behind each must survive the forward and the backward call, and outputs and gradients must
+    be the bits of the unguarded call.  One ray, one ray past a 128-point tile, ragged slabs."""
+    from mirender import fields, occupancy, occupancy_train
+    models = [fields.field_from_state_dict(synth.state_dict(kind, seed=s, sharp="medium", bias_jitter=0.05), dev()) for s in (3, 4)]
+    params = [p for m in models for p in m.parameters()]
+    rays = torch.from_numpy(R.rays_from_camera(40, 40, 55.0, synth.pose_degrees(4.0, 10.0, -30.0))[:n]).to(dev())
+    dense = np.ones((8, 8, 8), bool)
+    if occupied == "lower_half":
+        dense[:, :, 4:] = False
+    grid = occupancy.OccupancyGrid.from_dense(dense, (-4.0,) * 3, (4.0,) * 3, dev())    # the box holds every sample
+    tr = synth.t_rand(n, nc, seed=7).to(dev())
+
+    def run():
+        outs = occupancy_train.render_rays(rays, 2.0, 6.0, models[0], models[1], nc, nf, grid=grid, t_rand=tr)
+        loss = outs[3].square().mean() + outs[0].mean() + outs[5].mean() + outs[4].mean()
+        return outs, torch.autograd.grad(loss, params, allow_unused=True)
+    plain_outs, plain_grads = run()
+    monkeypatch.setenv("MI_DEBUG_GUARDS", "1")
+    outs, grads = run()                                                  # raises if a guard fires
+    torch.cuda.synchronize()
+    assert all(o.requires_grad for o in outs)
+    for a, b in zip(plain_outs + plain_grads, outs + grads):
+        assert (a is None and b is None) or torch.equal(a, b)
+    if occupied == "ones":                                               # every sample is listed: the gradients are there
+        assert all(g is not None for g in grads) and any(bool(g.abs().sum() > 0) for g in grads)
+
+
 def test_guard_catches_an_overrun(monkeypatch):
     """The check itself: a buffer whose sentinel zone was touched is reported."""
     from mirender import _lib, autograd as A
