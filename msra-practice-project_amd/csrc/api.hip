@@ -14,7 +14,7 @@ static thread_local char g_err[512] = "";
 static thread_local hipEvent_t g_mlp_ev[4] = {nullptr, nullptr, nullptr, nullptr};
 #ifdef MI_PROFILE_STAMPS
 static unsigned long long* g_stamps = nullptr;
-extern unsigned long long* g_bwd_stamps;          // field_mlp_bwd.hip
+extern unsigned long long* g_bwd_stamps;          // field_bwd_chain.hip
 #endif
 
 void set_error(const char* fmt, ...) {

@@ -18,7 +18,8 @@ ARCH = "gfx950"
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
 SOURCES = {
     "field_mlp.hip": [],
-    "field_mlp_bwd.hip": [],
+    "field_bwd_chain.hip": [],
+    "field_bwd_dw.hip": [],
     "ray_grad.hip": [],
     # un-fused mul/add like the torch / NumPy ops these kernels restate
     "render_stages.hip": ["-ffp-contract=off"],
@@ -30,7 +31,7 @@ SOURCES = {
     "occupancy_path.hip": [],
     "api.hip": [],
 }
-HEADERS = ["field_layout.h", "field_kinds.h", "mi_common.h", "mesh_cube.h", "mi_math.h", "field_mlp_device.h", os.path.join("..", "..", "include", "mi_render.h")]
+HEADERS = ["field_layout.h", "field_kinds.h", "mi_common.h", "mesh_cube.h", "mi_math.h", "field_mlp_device.h", "field_bwd.h", os.path.join("..", "..", "include", "mi_render.h")]
 
 
 def _stale(target, deps):
@@ -78,7 +79,7 @@ def build(force=False, verbose=True, always=()):
             print(f"[build] {src}: COMPILED for {ARCH} ({why})", flush=True)
         else:
             print(f"[build] {src}: REUSED {os.path.relpath(o, PKG)} (newer than its source and every header)", flush=True)
-    # the translation units are independent (the two MLP files take minutes each): compile them side by side
+    # the translation units are independent (field_mlp.hip and field_bwd_chain.hip take minutes each): compile them side by side
     from concurrent.futures import ThreadPoolExecutor
 
     def run(cmd):

@@ -3,7 +3,7 @@
 // (its parameter shapes, its packed weight streams, its training buffers, and its layer GRAPH: which saved input and which
 // weight columns every linear layer multiplies, and where its dA rows live) is read from here.  The graph is stated once,
 // by two builders (with_nerf_graph, make_film_kind), checked at compile time (graph_ok) and read by one host-side walker
-// (for_each_block): the weight-gradient jobs of field_mlp_bwd.hip and the input gradients of ray_grad.hip are derived
+// (for_each_block): the weight-gradient jobs of field_bwd_dw.hip and the input gradients of ray_grad.hip are derived
 // from it.  The packed streams are held against the graph segment by segment (segments_ok), and the fused MLP kernels read
 // their stage shapes from the same segments (field_layout.h).  Host only but for those compile-time reads: the kernels get
 // pointers and strides, and constant memory holds the PackTables alone.

@@ -150,7 +150,7 @@ struct DeferArgs {
 // The two packed weight streams of a field kind (field_layout.h): forward order, and transposed for the backward chain.
 enum StreamDir : int { STREAM_FWD = 0, STREAM_BWD = 1 };
 
-// host launchers (field_mlp.hip, field_mlp_bwd.hip, render_stages.hip, eval_stages.hip, adam_step.hip)
+// host launchers (field_mlp.hip, field_bwd_dw.hip, render_stages.hip, eval_stages.hip, adam_step.hip)
 // sigma_only: the kind's sigma-only instance (has_sigma_only_kernel), which writes sigma alone to a.out [M]
 int launch_mlp(int kind, const MlpArgs& a, int64_t n_groups, hipStream_t stream, bool sigma_only = false);
 bool has_sigma_only_kernel(int kind);

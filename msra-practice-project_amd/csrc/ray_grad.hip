@@ -2,7 +2,7 @@
 // through `network(inputs)` to `pts = o + d z` and `view = d / |d|` (nerf/render.py:93,122,134) - the gradient camera pose
 // refinement is built on.  Opt-in: only mirender/pose.py calls these.
 //
-// The backward chain (field_mlp_bwd.hip) has already written dL/d(pre-activation) of every linear layer as
+// The backward chain (field_bwd_chain.hip) has already written dL/d(pre-activation) of every linear layer as
 // [point][feature] rows into grads_ws (field_layout.h nerf_grads() .. film_grads_depth()); the gradient of a point's six
 // inputs is one more small contraction of the rows of the INPUT-CONSUMING layers with those layers' input columns.  Which
 // layers those are, their dA regions, weight columns and saved encoding rows are read from the kind's layer graph

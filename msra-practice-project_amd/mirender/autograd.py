@@ -5,7 +5,7 @@ Forward = the training kernels, which also keep every layer's input, for as many
 holds, and the inference kernels for the rest.  Backward, per pass that received a gradient: compositing
 backward -> dL/d(raw); then range by range (so memory stays bounded whatever the batch): the field forward is
 re-run if the range was not kept, the backward chain produces every layer's dA, and the point-contraction GEMMs
-reduce them to the weight gradients (csrc/field_mlp_bwd.hip).  z_samples is detached like the reference (render.py:141), so the fine depths
+reduce them to the weight gradients (csrc/field_bwd_chain.hip, csrc/field_bwd_dw.hip).  z_samples is detached like the reference (render.py:141), so the fine depths
 carry no gradient into the coarse pass.
 """
 from __future__ import annotations

@@ -242,7 +242,7 @@ def film_depth_network(n: int, use_dir: bool) -> list:
                   L(n + 2, [(f"X{n}", 0, 256, 0, "thin", True)], "sigmoid", (0, 3), ("heads", 0, 3))]
 
 
-# ---- the planner (BwdBatcher::slabs_for / slab_pts_for, csrc/field_mlp_bwd.hip) ----------------------------------------
+# ---- the planner (BwdBatcher::slabs_for / slab_pts_for, csrc/field_bwd_dw.hip) ----------------------------------------
 def slabs_for(P: int, njobs: int, per_cu: int = 1) -> int:
     s = min((256 * per_cu + njobs - 1) // njobs, 256 * per_cu)
     return max(1, min(s, (P + 255) // 256))

@@ -297,7 +297,7 @@ def _stage_c_film(case, kind, st, lay):
     return ok
 
 
-KFS = 256 * 256 + 256          # one 256-wide FiLM layer's T_l and s_l in the FiLM scratch (field_mlp_bwd.hip)
+KFS = 256 * 256 + 256          # one 256-wide FiLM layer's T_l and s_l in the FiLM scratch (field_bwd_dw.hip)
 
 
 def _film_scratch(case, st, l, T_parts, s, s_b):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Build container: where does a kernel wait on an LDS read it has only just issued?
 
-    python tools/isa_lds_waits.py msra-practice-project_amd/csrc/_obj/field_mlp_bwd.o [kernel-name-filter]
+    python tools/isa_lds_waits.py msra-practice-project_amd/csrc/_obj/field_bwd_chain.o [kernel-name-filter]
 
 For every `s_waitcnt` that waits for LDS (lgkmcnt(N)) the script works out which ds_read it really waits for - the
 (N+1)-th youngest outstanding one - and estimates the issue cycles between that read and the wait (MFMA 64, transcendental

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Build container: per-kernel instruction statistics of a compiled translation unit (object with a .hip_fatbin section).
 
-    python tools/isa_stats.py msra-practice-project_amd/csrc/_obj/field_mlp_bwd.o [kernel-name-filter]
+    python tools/isa_stats.py msra-practice-project_amd/csrc/_obj/field_bwd_chain.o [kernel-name-filter]
 
 Prints, per kernel: instructions, MFMAs, v_accvgpr_read / write (AGPR<->VGPR moves: more reads than accumulator
 registers means the register allocator is shuffling values through AGPRs), scratch loads / stores (spills: each reload
