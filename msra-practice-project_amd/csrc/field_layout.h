@@ -61,7 +61,7 @@ __host__ __device__ inline int vec_slot(int f) {
 // ---- the stream as SEGMENTS: what one layer step of a fused kernel consumes -----------------------------------------
 // A segment is a run of aux items (VEC / PLAIN) followed by the K blocks (CHUNK items) of ONE weight.  Aux items
 // accumulate; a bias opens a new segment when the current one has aux items and no K blocks (the K = 3 first layer of the
-// sin kinds has no K blocks at all); a run of CHUNKs of one parameter ends the segment.  The kernels of field_mlp.hip /
+// sin kinds has no K blocks at all); a run of CHUNKs of one parameter ends the segment.  The kernels of field_mlp_*.hip /
 // field_bwd_chain.hip take every piece count, K-block count, row-block count and aux-piece index from this view of the table
 // the pack kernel fills the stream from, and static_assert the structure the view cannot express (which segments one loop
 // body serves, that the segments they issue are the whole table) next to its use; segments_ok (field_kinds.h) holds
@@ -151,7 +151,7 @@ constexpr Segments segments(const PackTable& t) {
 // Per-kind recipes.  params[2*i] / params[2*i+1] = weight / bias of linear layer i in the
 // state-dict order listed per kind below (same order as oracle/fields.py SPECS).
 // The fused kernels consume the stream in exactly this order, and that is enforced at compile time: every stage shape
-// and aux-piece index in field_mlp.hip / field_bwd_chain.hip is read from the segment view (segments(), above) of the table
+// and aux-piece index in field_mlp_*.hip / field_bwd_chain.hip is read from the segment view (segments(), above) of the table
 // built here, each kernel static_asserts that the segments it issues are the whole table (the sigma-only instances: the
 // sigma prefix), and segments_ok (field_kinds.h) holds every table against its kind's layer graph.
 // ---------------------------------------------------------------------------------------

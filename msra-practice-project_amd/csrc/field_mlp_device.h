@@ -1,5 +1,5 @@
 // field_mlp_device.h - device building blocks shared by the fused field-MLP forward
-// (field_mlp.hip) and backward-chain (field_bwd_chain.hip) kernels: LDS map, DMA stages, the 32-wide
+// (field_mlp_*.hip) and backward-chain (field_bwd_chain.hip) kernels: LDS map, DMA stages, the 32-wide
 // K-block MFMA step, register<->row-major activation I/O.  See field_mlp.hip for the design.
 #pragma once
 #include <hip/hip_runtime.h>

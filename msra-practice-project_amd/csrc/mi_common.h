@@ -106,7 +106,7 @@ struct DeferredColourBuf {
     }
 };
 
-// arguments of the fused field-MLP kernels (field_mlp.hip)
+// arguments of the fused field-MLP kernels (field_mlp_*.hip; launched by field_mlp.hip)
 struct MlpArgs {
     const float* packed;    // packed weight stream (field_layout.h)
     const float* film;      // [groups][film_depth + 1][512] or null

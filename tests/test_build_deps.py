@@ -1,0 +1,76 @@
+"""csrc/build.py decides what to recompile from the dependency file the compiler wrote for each translation unit
+(-MD -MF): the parser, and the staleness rule on files with set times.  No compiler, a temporary directory."""
+import importlib.util
+import os
+
+PKG = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "msra-practice-project_amd")
+
+
+def _build_module():
+    spec = importlib.util.spec_from_file_location("mi_csrc_build", os.path.join(PKG, "csrc", "build.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+B = _build_module()
+
+
+def _touch(path, t):
+    with open(path, "a"):
+        pass
+    os.utime(path, (t, t))
+    return str(path)
+
+
+def _unit(tmp_path, listed=("a.h", "b.h")):
+    """A unit whose object (time 100) is newer than its source and both listed headers (time 50); returns obj, src, depfile."""
+    src = _touch(tmp_path / "unit.hip", 50)
+    hdrs = [_touch(tmp_path / h, 50) for h in listed]
+    obj = _touch(tmp_path / "unit.o", 100)
+    dep = tmp_path / "unit.d"
+    dep.write_text(f"{obj}: {src} \\\n  " + " \\\n  ".join(hdrs) + "\n")
+    return obj, src, str(dep)
+
+
+def test_parse_depfile_continuation_lines():
+    text = "_obj/unit.o: csrc/unit.hip csrc/a.h \\\n  /opt/include/hip/hip_runtime.h csrc/with\\ space.h\n"
+    assert B.parse_depfile(text) == ["csrc/unit.hip", "csrc/a.h", "/opt/include/hip/hip_runtime.h", "csrc/with space.h"]
+    assert B.parse_depfile("") == []
+
+
+def test_fresh_unit_is_reused(tmp_path):
+    obj, src, dep = _unit(tmp_path)
+    assert B.unit_stale(obj, src, dep) is None
+
+
+def test_listed_header_newer_than_object_is_stale(tmp_path):
+    obj, src, dep = _unit(tmp_path)
+    _touch(tmp_path / "b.h", 200)
+    assert B.unit_stale(obj, src, dep)
+
+
+def test_source_newer_than_object_is_stale(tmp_path):
+    obj, src, dep = _unit(tmp_path)
+    _touch(src, 200)
+    assert B.unit_stale(obj, src, dep)
+
+
+def test_unlisted_file_newer_is_not_stale(tmp_path):
+    obj, src, dep = _unit(tmp_path)
+    _touch(tmp_path / "unrelated.h", 200)
+    assert B.unit_stale(obj, src, dep) is None
+
+
+def test_missing_depfile_is_stale(tmp_path):
+    obj, src, dep = _unit(tmp_path)
+    os.remove(dep)
+    assert B.unit_stale(obj, src, dep)
+
+
+def test_missing_object_or_listed_file_is_stale(tmp_path):
+    obj, src, dep = _unit(tmp_path)
+    os.remove(tmp_path / "a.h")
+    assert B.unit_stale(obj, src, dep)
+    os.remove(obj)
+    assert B.unit_stale(obj, src, dep)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Build container: compare the gfx950 code of two builds of one translation unit, kernel by kernel.
 
-    python tools/isa_diff.py old/field_mlp.o new/field_mlp.o [kernel-name-filter] [--rename PATTERN REPLACEMENT]
+    python tools/isa_diff.py old/field_mlp_nerf.o new/field_mlp_nerf.o [kernel-name-filter] [--rename PATTERN REPLACEMENT]
 
 For every kernel in both objects: its disassembly (llvm-objdump -d --no-show-raw-insn --no-leading-addr, `//` comments
 stripped) and its metadata (VGPR / AGPR / SGPR counts, spills, LDS, scratch from llvm-readelf --notes).  The 32-bit
