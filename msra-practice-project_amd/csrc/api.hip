@@ -1,17 +1,15 @@
-// api.hip - extern "C" surface of libmirender.so (see include/mi_render.h).
-// Argument validation lives here; kernels assume validated shapes.
+// api.hip - the one-stage calls of libmirender.so's extern "C" surface (include/mi_render.h): error state, the field-kind
+// registry, pack, the field and stage wrappers, metrics, loss, ray bank, Adam, events.  Argument validation lives here; kernels
+// assume validated shapes.  The render paths are render_path.hip, train_path.hip and occupancy_path.hip.
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
 
-#include "../../include/mi_render.h"
-#include "field_kinds.h"
-#include "mi_common.h"
+#include "render_path.h"
 
 namespace mi {
 
 static thread_local char g_err[512] = "";
-static thread_local hipEvent_t g_mlp_ev[4] = {nullptr, nullptr, nullptr, nullptr};
 #ifdef MI_PROFILE_STAMPS
 static unsigned long long* g_stamps = nullptr;
 extern unsigned long long* g_bwd_stamps;          // field_bwd_chain.hip
@@ -33,18 +31,6 @@ int check_launch(const char* what) {
     return MI_OK;
 }
 
-int copy_render_outputs(const char* fn, int64_t n, float* rgb_dst, float* depth_dst, float* acc_dst, const float* rgb_src,
-                        const float* depth_src, const float* acc_src, hipStream_t stream) {
-    const struct { float* dst; const float* src; int64_t floats; } copies[3] = {
-        {rgb_dst, rgb_src, n * 3}, {depth_dst, depth_src, n}, {acc_dst, acc_src, n}};
-    for (const auto& c : copies)
-        if (c.dst && hipMemcpyAsync(c.dst, c.src, c.floats * sizeof(float), hipMemcpyDeviceToDevice, stream) != hipSuccess) {
-            set_error("%s: output alias copy failed", fn);
-            return MI_EHIP;
-        }
-    return MI_OK;
-}
-
 const FieldKind& field_kind(int kind) {
     if (is_fixed_kind(kind)) return kFieldKinds[kind];
     struct DepthKinds {
@@ -58,14 +44,9 @@ const FieldKind& field_kind(int kind) {
     return depth.k[film_depth(kind) - kFilmDepthMin][kind & 1];
 }
 
-static int eval_common(int kind, const float* packed, const float* film, const float* a, const float* z,
-                       int64_t n_groups, int64_t ppg, int64_t rpg, int S, int mode, float* out, hipStream_t s,
-                       float* save = nullptr, bool sigma_only = false) {
-    if (bad_kind(kind)) return MI_EINVAL;
-    if (!packed || !a || !out || (mode == 1 && !z)) { set_error("null pointer argument"); return MI_EINVAL; }
-    if (is_film(kind) && !film) { set_error("FiLM kind needs a film table"); return MI_EINVAL; }
-    if (n_groups < 0 || ppg < 0) { set_error("negative size"); return MI_EINVAL; }
-    if (n_groups == 0 || ppg == 0) return MI_OK;
+// one launch of the fused forward, arguments already checked (the render paths call it from their field steps)
+int eval_field(int kind, const float* packed, const float* film, const float* a, const float* z, int64_t n_groups, int64_t ppg,
+               int64_t rpg, int S, int mode, float* out, hipStream_t s, float* save, bool sigma_only) {
     MlpArgs args;
     args.packed = packed; args.film = is_film(kind) ? film : nullptr; args.a = a; args.z = z; args.out = out;
     args.points_per_group = ppg; args.rays_per_group = rpg; args.tiles_per_group = (ppg + 127) / 128;
@@ -80,114 +61,16 @@ static int eval_common(int kind, const float* packed, const float* film, const f
     return launch_mlp(kind, args, n_groups, s, sigma_only);
 }
 
-// Samples per window of the sigma-only coarse pass of mi_render_rays (a power of two that divides 128, the point tile).
-#ifndef MI_COARSE_WINDOW_LOG2
-#define MI_COARSE_WINDOW_LOG2 3
-#endif
-constexpr int kCoarseWindowLog2 = MI_COARSE_WINDOW_LOG2;
-constexpr int kCoarseWindow = 1 << kCoarseWindowLog2;
-static_assert(kCoarseWindow >= 1 && 128 % kCoarseWindow == 0, "a tile is 128 / kCoarseWindow rays x one window");
-
-// The sigma-only coarse pass, front to back in windows of kCoarseWindow samples: window r evaluates the field at its
-// samples of the rays that are still live, then the resumable weights composite (render_stages.hip) writes the window's
-// weights and drops every ray whose transmittance has reached zero - all its later weights are exactly 0 whatever the
-// field says there, so the field is not asked.  Same weights / depth_c / acc_c bits as one whole pass.  A caller that
-// asks for neither depth_c nor acc_c leaves sample_fine as the weights' only reader, and a ray is dropped as soon as no
-// later weight can change w + kPdfEps there (kStopBelowPdfEps, mi_common.h): same z_fine bits, far fewer points.
-// Everything is launched with worst-case grids from host values only (no read-back: graph-capturable); `scratch` is the
-// part of raw_c's region behind the compact sigma buffer: two live lists [n] and one count per window.
-static int coarse_sigma_windows(int kind, const float* packed, const float* rays, const float* z_c, int64_t n, int n_coarse,
-                                float* sigma, int* scratch, float* depth_c, float* acc_c, float* w_c, hipStream_t hs) {
-    const int rounds = (n_coarse + kCoarseWindow - 1) / kCoarseWindow;
-    int* list[2] = {scratch, scratch + n};
-    int* counts = scratch + 2 * n;
-    const double stop = depth_c || acc_c ? kStopZeroWeight : kStopBelowPdfEps;
-    if (hipMemsetAsync(counts, 0, sizeof(int) * rounds, hs) != hipSuccess) { set_error("mi_render_rays: hipMemsetAsync failed"); return MI_EHIP; }
-    MlpArgs args = {};
-    args.packed = packed; args.a = rays; args.z = z_c; args.out = sigma;
-    args.n_samples = n_coarse; args.mode = 1; args.n_rays = n; args.win_log2 = kCoarseWindowLog2;
-    for (int r = 0; r < rounds; ++r) {
-        const int k0 = r * kCoarseWindow, k1 = k0 + kCoarseWindow < n_coarse ? k0 + kCoarseWindow : n_coarse;
-        const bool last = r == rounds - 1;
-        args.live_rays = r ? list[r & 1] : nullptr;          // window 0: every ray
-        args.live_count = r ? counts + r : nullptr;
-        args.win_k0 = k0;
-        int rc;
-        if ((rc = launch_mlp_window(kind, args, hs))) return rc;
-        if ((rc = launch_composite_weights_window(n, n_coarse, sigma, z_c, rays, depth_c, acc_c, w_c, args.live_rays,
-                                                  args.live_count, last ? nullptr : list[(r + 1) & 1],
-                                                  last ? nullptr : counts + r + 1, k0, k1, stop, hs))) return rc;
-    }
-    return MI_OK;
-}
-
-// Points per chunk of the fine pass's deferred colour branch (the row buffer holds that many 1 KiB rows).
-#ifndef MI_COLOUR_CHUNK_ROWS_LOG2
-#define MI_COLOUR_CHUNK_ROWS_LOG2 22
-#endif
-constexpr int64_t kColourChunkRows = (int64_t)1 << MI_COLOUR_CHUNK_ROWS_LOG2;
-static int64_t g_colour_chunk_rows = 0;               // mi_render_set_colour_chunk_rows: 0 = kColourChunkRows
-static int64_t colour_chunk_rows() { return g_colour_chunk_rows > 0 ? g_colour_chunk_rows : kColourChunkRows; }
-
-// kinds with the two kernels, point indices that fit the live list's ints
-static bool can_defer_colour(int kind, int64_t n, int S) { return has_deferred_colour_kernels(kind) && n > 0 && S > 0 && n * S <= 0x7fffffffLL; }
-
-// The field over n rays of S samples with its colour branch deferred to the points with sigma > 0, in chunks of whole rays:
-// per chunk a trunk-and-spill launch ({0, 0, 0, sigma} for every point, H8 rows and indices of the live ones into `extra`)
-// and a colour launch over that list.  A point with sigma == 0 keeps r = g = b = 0: its weight is exactly 0, so 0 * rgb
-// is the +0 that any finite colour gives.  Every chunk has its own count, cleared by one memset node; all launches on `hs`
-// with grids from host values (no read-back: graph-capturable).  `extra`: DeferredColourBuf(n, S, colour_chunk_rows()).
-static int eval_rays_deferred_colour(int kind, const float* packed, const float* rays, const float* z, int64_t n, int S,
-                                     float* raw, void* extra, hipStream_t hs) {
-    const DeferredColourBuf buf(n, S, colour_chunk_rows());
-    const DeferredColourBuf::Regions r = buf.carve(extra);
-    if (hipMemsetAsync(r.counts, 0, sizeof(int) * buf.n_chunks, hs) != hipSuccess) { set_error("deferred colour: hipMemsetAsync failed"); return MI_EHIP; }
-    MlpArgs args = {};
-    args.packed = packed; args.n_samples = S; args.mode = 1;
-    for (int64_t i = 0; i < buf.n_chunks; ++i) {
-        const int64_t r0 = i * buf.chunk_rays, nr = n - r0 < buf.chunk_rays ? n - r0 : buf.chunk_rays;
-        args.a = rays + r0 * 6; args.z = z + r0 * S; args.out = raw + r0 * S * 4;
-        args.rays_per_group = nr; args.points_per_group = nr * S; args.tiles_per_group = (nr * S + 127) / 128;
-        args.save_points = nr * S;
-        const DeferArgs d = {r.rows, r.idx, r.counts + i};
-        int rc;
-        if ((rc = launch_mlp_trunk_spill(kind, args, d, hs))) return rc;
-        if ((rc = launch_mlp_colour(kind, args, d, hs))) return rc;
-    }
-    return MI_OK;
-}
-
-// dims >= 1 with a product below 2^31 (a cell's bit index is an int); the product, or 0 with the error set
-static int64_t occupancy_cells(const char* fn, const int* dims) {
-    if (!dims) { set_error("%s: null grid dims", fn); return 0; }
-    int64_t cells = 1;
-    for (int c = 0; c < 3; ++c) {
-        if (dims[c] < 1) { set_error("%s: grid dims %d x %d x %d (each must be at least 1)", fn, dims[0], dims[1], dims[2]); return 0; }
-        cells *= dims[c];                                  // < 2^31 * 2^31 before the check below
-        if (cells >= (int64_t)1 << 31) { set_error("%s: grid dims %d x %d x %d (2^31 cells or more)", fn, dims[0], dims[1], dims[2]); return 0; }
-    }
-    return cells;
-}
-
-// the one place a grid is checked: its dims first, then its three pointers
-int occupancy_grid_args(const char* fn, const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell,
-                        OccupancyGridArgs* grid) {
-    if (!occupancy_cells(fn, dims)) return MI_EINVAL;
-    if (!bits || !lo || !inv_cell) { set_error("%s: null pointer argument", fn); return MI_EINVAL; }
-    for (int d = 0; d < 3; ++d) { grid->cells.dims[d] = dims[d]; grid->cells.lo[d] = lo[d]; grid->cells.inv_cell[d] = inv_cell[d]; }
-    grid->bits = bits;
-    return MI_OK;
-}
-
-// the field at the points of a device-counted list: a mode-1 launch of one group of n rays x S samples; acts: the listed
-// points' layer inputs are kept there (training), null = inference
-int eval_rays_list(int kind, const float* packed, const float* rays, const float* z, int64_t n, int S, const int* list,
-                   const int* count, float* raw, float* acts, hipStream_t hs) {
-    MlpArgs args = {};
-    args.packed = packed; args.a = rays; args.z = z; args.out = raw;
-    args.points_per_group = n * S; args.rays_per_group = n; args.tiles_per_group = (n * S + 127) / 128;
-    args.n_samples = S; args.mode = 1; args.save = acts; args.save_points = n * S; args.n_rays = n;
-    return launch_mlp_list(kind, args, list, count, hs);
+// the checks of the one-stage field wrappers, then the launch
+static int eval_common(int kind, const float* packed, const float* film, const float* a, const float* z,
+                       int64_t n_groups, int64_t ppg, int64_t rpg, int S, int mode, float* out, hipStream_t s,
+                       float* save = nullptr) {
+    if (bad_kind(kind)) return MI_EINVAL;
+    if (!packed || !a || !out || (mode == 1 && !z)) { set_error("null pointer argument"); return MI_EINVAL; }
+    if (is_film(kind) && !film) { set_error("FiLM kind needs a film table"); return MI_EINVAL; }
+    if (n_groups < 0 || ppg < 0) { set_error("negative size"); return MI_EINVAL; }
+    if (n_groups == 0 || ppg == 0) return MI_OK;
+    return eval_field(kind, packed, film, a, z, n_groups, ppg, rpg, S, mode, out, s, save);
 }
 
 }  // namespace mi
@@ -249,35 +132,7 @@ int mi_field_eval_rays(int kind, const float* packed, const float* film, const f
                        raw, (hipStream_t)stream);
 }
 
-int64_t mi_render_deferred_colour_extra_bytes(int64_t n, int n_coarse, int n_fine) {
-    if (n <= 0 || n_coarse < 1 || n_fine <= 0) return 0;
-    return DeferredColourBuf(n, (int64_t)n_coarse + n_fine, colour_chunk_rows()).bytes();
-}
-
 int mi_field_has_deferred_colour(int kind) { return bad_kind(kind) ? MI_EINVAL : has_deferred_colour_kernels(kind) ? 1 : 0; }
-
-void mi_render_set_colour_chunk_rows(int64_t rows) { g_colour_chunk_rows = rows > 0 ? rows : 0; }
-
-int mi_field_eval_rays_deferred(int kind, const float* packed, const float* film, const float* rays, const float* z,
-                                int64_t n_groups, int64_t rays_per_group, int n_samples, float* raw, void* extra,
-                                int64_t extra_bytes, void* stream) {
-    (void)film;
-    if (bad_kind(kind)) return MI_EINVAL;
-    if (n_samples <= 0 || n_groups < 0 || rays_per_group < 0) { set_error("mi_field_eval_rays_deferred: bad sizes"); return MI_EINVAL; }
-    const int64_t n = n_groups * rays_per_group;
-    if (n == 0) return MI_OK;
-    if (!packed || !rays || !z || !raw || !extra) { set_error("mi_field_eval_rays_deferred: null pointer argument"); return MI_EINVAL; }
-    if (!can_defer_colour(kind, n, n_samples)) {
-        set_error("mi_field_eval_rays_deferred: kind %d has no deferred colour branch, or n * n_samples exceeds 2^31 - 1", kind);
-        return MI_EINVAL;
-    }
-    const int64_t need = DeferredColourBuf(n, n_samples, colour_chunk_rows()).bytes();
-    if (extra_bytes < need) {
-        set_error("mi_field_eval_rays_deferred: buffer of %lld bytes, needs %lld", (long long)extra_bytes, (long long)need);
-        return MI_EINVAL;
-    }
-    return eval_rays_deferred_colour(kind, packed, rays, z, n, n_samples, raw, extra, (hipStream_t)stream);
-}
 
 int64_t mi_occupancy_words(const int* dims) {
     const int64_t cells = occupancy_cells("mi_occupancy_words", dims);
@@ -465,103 +320,6 @@ int mi_sample_pdf(int64_t n, int n_bins, int n_samples, const float* bins, const
         return MI_EINVAL;
     }
     return launch_sample_pdf(n, n_bins, n_samples, bins, weights, u_lin, samples, (hipStream_t)stream);
-}
-
-int64_t mi_render_workspace_bytes(int64_t n, int n_coarse, int n_fine) {
-    return RenderWorkspace(n, n_coarse, n_fine).base_bytes();
-}
-
-int64_t mi_render_shared_field_extra_bytes(int64_t n, int n_coarse, int n_fine) {
-    return RenderWorkspace(n, n_coarse, n_fine).shared_extra_bytes();
-}
-
-int mi_render_rays(int kind_coarse, const float* packed_coarse, int kind_fine, const float* packed_fine,
-                   const float* film, const float* rays, int64_t n_groups, int64_t rays_per_group, float near_,
-                   float far_, int n_coarse, int n_fine, const float* z_lin, const float* u_lin, const float* t_rand,
-                   uint64_t seed, uint64_t ray0, float* rgb_c, float* depth_c, float* acc_c, float* rgb_f,
-                   float* depth_f, float* acc_f, void* workspace, int64_t workspace_bytes, void* stream) {
-    if (n_groups < 0 || rays_per_group < 0 || n_coarse < 1 || n_fine < 0) { set_error("mi_render_rays: bad sizes"); return MI_EINVAL; }
-    if (n_groups * rays_per_group == 0) return MI_OK;          // no rays: nothing to launch, no buffer is touched
-    // the coarse outputs are optional: rgb_c NULL = the coarse colours are not wanted, and then depth_c / acc_c each may be
-    // NULL too; with rgb_c, all three
-    if (!workspace || !rays || (rgb_c && (!depth_c || !acc_c)) || !rgb_f || !depth_f || !acc_f) {
-        set_error("mi_render_rays: null pointer argument");
-        return MI_EINVAL;
-    }
-    const int64_t n = n_groups * rays_per_group;
-    const int S = n_coarse + n_fine;
-    const RenderWorkspace layout(n, n_coarse, n_fine);
-    const int64_t base_bytes = layout.base_bytes();
-    if (workspace_bytes < base_bytes) {
-        set_error("mi_render_rays: workspace of %lld bytes, mi_render_workspace_bytes says %lld", (long long)workspace_bytes,
-                  (long long)base_bytes);
-        return MI_EINVAL;
-    }
-    const RenderWorkspace::Regions ws = layout.carve(workspace);
-    float *z_c = ws.z_c, *raw_c = ws.raw_c, *w_c = ws.w_c, *z_f = ws.z_f, *raw_f = ws.raw_f;
-    const bool shared = kind_fine == kind_coarse && packed_fine == packed_coarse;
-    // Without the coarse colours and with a coarse field of its own, the coarse pass only feeds sample_fine its weights,
-    // which depend on sigma alone: the sigma-only forward writes sigma [n,Nc] compactly at the start of raw_c's region.
-    // A shared field's coarse raw values are merged into the fine pass (or are its outputs with Nf = 0): whole forward.
-    // The other three quarters of the region hold the windowed pass's live lists and counts: 2 n + ceil(Nc / window) ints
-    // <= 3 n Nc floats whenever Nc >= 2.
-    const bool sigma_only = !rgb_c && !shared && has_sigma_only_kernel(kind_coarse);
-    int rc;
-    if ((rc = mi_sample_coarse(n, near_, far_, n_coarse, z_lin, t_rand, seed, ray0, z_c, stream))) return rc;
-    hipStream_t hs = (hipStream_t)stream;
-    if (g_mlp_ev[0]) (void)hipEventRecord(g_mlp_ev[0], hs);
-    // more than one window, and ray indices that fit the live lists' ints: the windowed pass (weights included)
-    const bool windowed = sigma_only && n_coarse > kCoarseWindow && n <= 0x7fffffffLL;
-    if (windowed) {
-        if ((rc = coarse_sigma_windows(kind_coarse, packed_coarse, rays, z_c, n, n_coarse, raw_c, (int*)(raw_c + n * n_coarse),
-                                       depth_c, acc_c, w_c, hs))) return rc;
-    } else if (sigma_only) {
-        if ((rc = eval_common(kind_coarse, packed_coarse, film, rays, z_c, n_groups, rays_per_group * n_coarse, rays_per_group,
-                              n_coarse, 1, raw_c, hs, nullptr, true))) return rc;
-    } else if ((rc = mi_field_eval_rays(kind_coarse, packed_coarse, film, rays, z_c, n_groups, rays_per_group, n_coarse, raw_c,
-                                        stream))) {
-        return rc;
-    }
-    if (g_mlp_ev[1]) (void)hipEventRecord(g_mlp_ev[1], hs);
-    if (n_fine == 0 && shared) {
-        // render.py:140-145 with Nf = 0 and one model: sort(z_coarse) == z_coarse, so the second pass would
-        // re-evaluate identical inputs: the coarse pass's composite IS the fine outputs, and the coarse
-        // outputs asked for are copies of them.
-        if ((rc = mi_composite(n, n_coarse, raw_c, z_c, rays, rgb_f, depth_f, acc_f, w_c, stream))) return rc;
-        return copy_render_outputs("mi_render_rays", n, rgb_c, depth_c, acc_c, rgb_f, depth_f, acc_f, hs);
-    }
-    if (rgb_c) rc = mi_composite(n, n_coarse, raw_c, z_c, rays, rgb_c, depth_c, acc_c, w_c, stream);
-    else if (windowed) rc = MI_OK;                                   // coarse_sigma_windows wrote w_c / depth_c / acc_c
-    else if (sigma_only) rc = launch_composite_weights(n, n_coarse, raw_c, 1, z_c, rays, depth_c, acc_c, w_c, hs);
-    else rc = launch_composite_weights(n, n_coarse, raw_c + 3, 4, z_c, rays, depth_c, acc_c, w_c, hs);     // raw's sigma channel
-    if (rc) return rc;
-    if (shared && workspace_bytes >= base_bytes + layout.shared_extra_bytes()) {
-        // One field for both passes: Nc of the fine pass's Nc + Nf points are the coarse pass's points - evaluate the Nf
-        // new ones only and merge (render_stages.hip: merge_raw_kernel).  Needs the extra workspace regions; a caller
-        // that did not provide them gets the plain path below (same results).
-        float *z_s = ws.z_s, *raw_s = ws.raw_s;
-        int* pos = ws.pos;
-        if ((rc = mi_sample_fine_pos(n, near_, far_, n_coarse, n_fine, z_lin, u_lin, z_c, w_c, z_s, z_f, pos, stream))) return rc;
-        if (g_mlp_ev[2]) (void)hipEventRecord(g_mlp_ev[2], hs);
-        if ((rc = mi_field_eval_rays(kind_fine, packed_fine, film, rays, z_s, n_groups, rays_per_group, n_fine, raw_s, stream)))
-            return rc;
-        if (g_mlp_ev[3]) (void)hipEventRecord(g_mlp_ev[3], hs);
-        if ((rc = mi_merge_raw(n, n_coarse, n_fine, raw_c, raw_s, pos, raw_f, stream))) return rc;
-        return mi_composite(n, S, raw_f, z_f, rays, rgb_f, depth_f, acc_f, nullptr, stream);
-    }
-    if ((rc = mi_sample_fine(n, near_, far_, n_coarse, n_fine, z_lin, u_lin, z_c, w_c, nullptr, z_f, stream))) return rc;
-    if (g_mlp_ev[2]) (void)hipEventRecord(g_mlp_ev[2], hs);
-    // A fine field of its own, in a workspace that also holds mi_render_deferred_colour_extra_bytes (behind base_bytes, where
-    // the shared path's regions would lie): the colour branch runs on the points with sigma > 0 only.  A caller that did not
-    // provide the extra gets the whole forward (same results).
-    const int64_t defer_bytes = mi_render_deferred_colour_extra_bytes(n, n_coarse, n_fine);
-    if (!shared && defer_bytes > 0 && can_defer_colour(kind_fine, n, S) && workspace_bytes >= base_bytes + defer_bytes)
-        rc = eval_rays_deferred_colour(kind_fine, packed_fine, rays, z_f, n, S, raw_f, (char*)workspace + base_bytes, hs);
-    else
-        rc = mi_field_eval_rays(kind_fine, packed_fine, film, rays, z_f, n_groups, rays_per_group, S, raw_f, stream);
-    if (rc) return rc;
-    if (g_mlp_ev[3]) (void)hipEventRecord(g_mlp_ev[3], hs);
-    return mi_composite(n, S, raw_f, z_f, rays, rgb_f, depth_f, acc_f, nullptr, stream);
 }
 
 int mi_composite_bwd(int64_t n, int n_samples, const float* raw, const float* z, const float* rays,
@@ -761,10 +519,6 @@ int mi_event_elapsed_ms(void* start, void* stop, float* ms) {
         return MI_EHIP;
     }
     return MI_OK;
-}
-void mi_render_set_mlp_events(void* start_coarse, void* stop_coarse, void* start_fine, void* stop_fine) {
-    g_mlp_ev[0] = (hipEvent_t)start_coarse; g_mlp_ev[1] = (hipEvent_t)stop_coarse;
-    g_mlp_ev[2] = (hipEvent_t)start_fine; g_mlp_ev[3] = (hipEvent_t)stop_fine;
 }
 
 }  // extern "C"

@@ -33,6 +33,8 @@ SOURCES = {
     "occupancy.hip": ["-ffp-contract=off"],
     "adam_step.hip": [],
     "mesh_stages.hip": [],
+    # host code of the render paths (render_path.h, which no kernel unit includes) and the one-stage calls
+    "render_path.hip": [],
     "train_path.hip": [],
     "occupancy_path.hip": [],
     "api.hip": [],

@@ -1,4 +1,5 @@
-// mi_common.h - small shared helpers for the libmirender kernels (gfx950 only).
+// mi_common.h - what the kernel units of libmirender share (gfx950 only): device helpers, kernel argument structs, the launcher
+// declarations and the stop constants.  What only the host units of the render paths share is in render_path.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -23,9 +24,6 @@ __device__ __forceinline__ void static_for(F&& f) {
 // error plumbing for the C ABI (api.hip)
 void set_error(const char* fmt, ...);
 int check_launch(const char* what);
-// one field with Nf = 0: the fine outputs and the coarse outputs are one composite's; copies it to every non-null dst
-int copy_render_outputs(const char* fn, int64_t n, float* rgb_dst, float* depth_dst, float* acc_dst, const float* rgb_src,
-                        const float* depth_src, const float* acc_src, hipStream_t stream);
 
 // hipFuncSetAttribute configures the CURRENT device's copy of a kernel, so "once" means once per device ordinal:
 // a process that drives several GPUs (DataParallel's thread per replica, pi_GAN/train.py:50) sets it on each.
@@ -50,61 +48,6 @@ public:
 
 // floats rounded up to whole 64-float (256-byte) blocks: every workspace region starts on one
 constexpr int64_t align64(int64_t x) { return (x + 63) / 64 * 64; }
-
-// The workspace of mi_render_rays / mi_render_rays_train for n rays of Nc + Nf samples: the five regions of
-// mi_render_workspace_bytes, then the three that one field for both passes adds (mi_render_shared_field_extra_bytes) - or,
-// in their place, what two fields' deferred colour branch adds (DeferredColourBuf below, mi_render_deferred_colour_extra_bytes).
-struct RenderWorkspace {
-    struct Regions {
-        float *z_c, *raw_c, *w_c, *z_f, *raw_f;       // [n,Nc] [n,Nc,4] [n,Nc] [n,S] [n,S,4]
-        float *z_s, *raw_s;                           // [n,Nf] [n,Nf,4]
-        int* pos;                                     // [n,S]
-    };
-    static constexpr int kBase = 5, kAll = 8;
-    int64_t floats[kAll];
-    RenderWorkspace(int64_t n, int nc, int nf)
-        : floats{n * nc, n * nc * 4, n * nc, n * ((int64_t)nc + nf), n * ((int64_t)nc + nf) * 4,
-                 n * nf, n * nf * 4, n * ((int64_t)nc + nf)} {}
-    int64_t bytes(int first, int last) const {
-        int64_t f = 0;
-        for (int i = first; i < last; ++i) f += align64(floats[i]);
-        return f * (int64_t)sizeof(float);
-    }
-    int64_t base_bytes() const { return bytes(0, kBase); }
-    int64_t shared_extra_bytes() const { return bytes(kBase, kAll); }
-    // the shared-field regions lie behind base_bytes(): theirs to use only in a workspace that holds them
-    Regions carve(void* base) const {
-        float* p[kAll];
-        float* ws = (float*)base;
-        for (int i = 0; i < kAll; ++i) { p[i] = ws; ws += align64(floats[i]); }
-        return {p[0], p[1], p[2], p[3], p[4], p[5], p[6], (int*)p[7]};
-    }
-};
-
-// The buffer of the fine pass's deferred colour branch (mi_render_deferred_colour_extra_bytes), for n rays of S samples
-// evaluated in chunks of whole rays of at most chunk_rows points (one ray where S is larger): the H8 rows [cap][256] and the
-// point indices [cap] of one chunk's live list (worst case: every point of the chunk live), and one count per chunk.  In a
-// render workspace it lies behind base_bytes(), where the shared-field regions lie: the two paths exclude each other.
-struct DeferredColourBuf {
-    struct Regions { float* rows; int* idx; int* counts; };
-    int64_t chunk_rays, n_chunks, cap;
-    DeferredColourBuf(int64_t n, int64_t S, int64_t chunk_rows) {
-        chunk_rays = chunk_rows / (S > 0 ? S : 1);
-        if (chunk_rays < 1) chunk_rays = 1;
-        if (chunk_rays > n) chunk_rays = n;
-        n_chunks = chunk_rays > 0 ? (n + chunk_rays - 1) / chunk_rays : 0;
-        // A chunk uses chunk_rays * S rows.  Where that falls short of chunk_rows (S does not divide it) the buffer is still
-        // sized for chunk_rows, so that its size is the documented min(n * S, chunk_rows) rows: slack of less than one ray.
-        cap = chunk_rays * S;
-        if (cap < chunk_rows) cap = chunk_rows < n * S ? chunk_rows : n * S;
-    }
-    int64_t bytes() const { return (align64(cap * 256) + align64(cap) + align64(n_chunks)) * (int64_t)sizeof(float); }
-    Regions carve(void* base) const {
-        float* rows = (float*)base;
-        int* idx = (int*)(rows + align64(cap * 256));
-        return {rows, idx, idx + align64(cap)};
-    }
-};
 
 // arguments of the fused field-MLP kernels (field_mlp_*.hip; launched by field_mlp.hip)
 struct MlpArgs {
@@ -131,7 +74,7 @@ struct MlpArgs {
     int win_log2;
 };
 
-// The live list of one chunk of the fine pass (DeferredColourBuf): the trunk-and-spill instance appends to it, the colour-branch
+// The live list of one chunk of the fine pass (DeferredColourBuf, render_path.h): the trunk-and-spill instance appends to it, the colour-branch
 // kernel reads it.  Point indices are relative to the launch's a.out / a.z (the chunk's first point is 0).
 struct DeferArgs {
     float* rows;            // [entries][256] H8 (the last trunk layer's activation) of the listed points
@@ -170,11 +113,9 @@ int64_t occupancy_pack_workspace_bytes(int64_t cells, int dilate);
 int launch_occupancy_pack(const float* sigma, const int* dims, int k, float threshold, int dilate, uint32_t* bits,
                           void* workspace, hipStream_t stream);
 // ... and reading one.  A grid as the kernels take it: box and cells by value (MarkArgs, a kernel argument) and the device words.
-// occupancy_grid_args (api.hip) is the one place a caller's grid is checked (dims first, then the pointers) and copied into one.
+// occupancy_grid_args (render_path.h) is the one place a caller's grid is checked and copied into one.
 struct MarkArgs { int dims[3]; float lo[3], inv_cell[3]; };
 struct OccupancyGridArgs { MarkArgs cells; const uint32_t* bits; };
-int occupancy_grid_args(const char* fn, const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell,
-                        OccupancyGridArgs* grid);
 // The samples of n rays x S depths that lie in occupied cells, appended to `list` (point indices ray * S + k,
 // any order) and counted in the device int `count`, which the call clears; the raw rows [n*S][4] of the others are zeroed
 // (raw may be null).  n * S fits an int (the caller checks).
@@ -194,19 +135,12 @@ int launch_occupancy_mark_rays_ordered(const OccupancyGridArgs& grid, const floa
 // regions' stride), rows at and past the count are not written.
 bool has_list_kernel(int kind);
 int launch_mlp_list(int kind, const MlpArgs& a, const int* list, const int* count, hipStream_t stream);
-// api.hip: launch_mlp_list over one group of n rays x S samples; acts null = inference, else the saved rows' destination
-int eval_rays_list(int kind, const float* packed, const float* rays, const float* z, int64_t n, int S, const int* list,
-                   const int* count, float* raw, float* acts, hipStream_t stream);
 // Backward of a field over the first *count rows of compact acts (launch_mlp_list with a.save): the chain reads raw / g_raw at
 // rows list[e], writes dA rows e; the weight-gradient kernels contract rows [0, *count) in n_slabs slabs planned from the
 // capacity, each counted_slab_pts(*count, n_slabs) long.  Non-FiLM kinds.  No host read-back.
 int launch_field_backward_list(int kind, const float* packed_bwd, const float* acts, float* grads, const float* raw,
                                const float* g_raw, const int* list, const int* count, int64_t capacity, float* partial,
                                float* const* gp, hipStream_t stream);
-// train_path.hip: a scratch copy of a kind's parameter gradients (its floats; its tensors, out[2 * n_layers]); dst[i] += src[i]
-int64_t param_floats(int kind);
-void scratch_params(int kind, float* base, float** out);
-int add_param_grads(int kind, float* const* dst, float* const* src, hipStream_t stream);
 int64_t bwd_partial_floats(int64_t P);
 int64_t film_partial_floats(int64_t n_groups, int64_t points_per_group);
 int64_t bwd_partial_floats_kind(int kind, int64_t P);                      // ... of any kind (deeper FiLM kinds need more)

@@ -1,18 +1,51 @@
 // occupancy_path.hip - rendering and training with an occupancy grid through the C ABI (include/mi_render.h):
 // mi_render_rays_occupancy, mi_render_rays_occupancy_train, mi_render_rays_occupancy_backward and their size queries.
-// One sequence (run_passes) serves both forwards: per pass, mark the samples in occupied cells into a device-counted list,
-// evaluate the field at the listed points alone, composite.  Training differs in three values: the ordered mark, a field that
-// keeps the listed points' layer inputs, and a list per pass (OccLists), which the backward reads.  It is deliberately small:
+// Both forwards run the sequence of every render path (run_render_passes, render_path.h) with one field step (occupancy_forward):
+// per pass, mark the samples in occupied cells into a device-counted list and evaluate the field at the listed points alone.
+// Training differs in three values: the ordered mark, a field that keeps the listed points' layer inputs, and a list per pass
+// (OccLists), which the backward reads.  The grid checks of every call that reads one (occupancy_grid_args) and the list-driven
+// field launch (eval_rays_list) are here too, for the stage wrappers of api.hip as well.  It is deliberately small:
 // one range per pass, nothing recomputed, one group, no FiLM; one field for both passes runs as two passes of that field over
 // all their listed points (no merge, as at inference) and its two gradient sums are added.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/mi_render.h"
-#include "field_kinds.h"
-#include "mi_common.h"
+#include "render_path.h"
 
 namespace mi {
+
+// dims >= 1 with a product below 2^31 (a cell's bit index is an int); the product, or 0 with the error set
+int64_t occupancy_cells(const char* fn, const int* dims) {
+    if (!dims) { set_error("%s: null grid dims", fn); return 0; }
+    int64_t cells = 1;
+    for (int c = 0; c < 3; ++c) {
+        if (dims[c] < 1) { set_error("%s: grid dims %d x %d x %d (each must be at least 1)", fn, dims[0], dims[1], dims[2]); return 0; }
+        cells *= dims[c];                                  // < 2^31 * 2^31 before the check below
+        if (cells >= (int64_t)1 << 31) { set_error("%s: grid dims %d x %d x %d (2^31 cells or more)", fn, dims[0], dims[1], dims[2]); return 0; }
+    }
+    return cells;
+}
+
+// the one place a grid is checked: its dims first, then its three pointers
+int occupancy_grid_args(const char* fn, const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell,
+                        OccupancyGridArgs* grid) {
+    if (!occupancy_cells(fn, dims)) return MI_EINVAL;
+    if (!bits || !lo || !inv_cell) { set_error("%s: null pointer argument", fn); return MI_EINVAL; }
+    for (int d = 0; d < 3; ++d) { grid->cells.dims[d] = dims[d]; grid->cells.lo[d] = lo[d]; grid->cells.inv_cell[d] = inv_cell[d]; }
+    grid->bits = bits;
+    return MI_OK;
+}
+
+// the field at the points of a device-counted list: a mode-1 launch of one group of n rays x S samples; acts: the listed
+// points' layer inputs are kept there (training), null = inference
+int eval_rays_list(int kind, const float* packed, const float* rays, const float* z, int64_t n, int S, const int* list,
+                   const int* count, float* raw, float* acts, hipStream_t hs) {
+    MlpArgs args = {};
+    args.packed = packed; args.a = rays; args.z = z; args.out = raw;
+    args.points_per_group = n * S; args.rays_per_group = n; args.tiles_per_group = (n * S + 127) / 128;
+    args.n_samples = S; args.mode = 1; args.save = acts; args.save_points = n * S; args.n_rays = n;
+    return launch_mlp_list(kind, args, list, count, hs);
+}
 
 // The region behind RenderWorkspace::base_bytes(), in ints, each part on a 64-int block.  Inference: one list of n (Nc + Nf)
 // ints that the passes fill in turn.  Training: an ascending list per pass, each with its scan slots
@@ -38,16 +71,15 @@ struct OccBwdLayout {
     int64_t g_raw_c, g_raw_f, grads, partial, fine_total, total;
     OccBwdLayout(int kind_c, int kind_f, bool shared, int64_t n, int nc, int nf) {
         const int64_t pc = n * nc, pf = n * ((int64_t)nc + nf);
-        int64_t f = 0;
-        auto take = [&](int64_t x) { const int64_t o = f; f += align64(x); return o; };
+        RegionAllocator ws;
         const int64_t gc = pc * region_total(field_kind(kind_c).grads), gf = pf * region_total(field_kind(kind_f).grads);
         const int64_t bc = bwd_partial_floats_kind(kind_c, pc), bf = bwd_partial_floats_kind(kind_f, pf);
-        g_raw_c = take(pc * 4);
-        g_raw_f = take(pf * 4);
-        grads = take(gc > gf ? gc : gf);
-        partial = take(bc > bf ? bc : bf);
-        fine_total = take(shared ? param_floats(kind_c) : 0);
-        total = f;
+        g_raw_c = ws.take(pc * 4);
+        g_raw_f = ws.take(pf * 4);
+        grads = ws.take(gc > gf ? gc : gf);
+        partial = ws.take(bc > bf ? bc : bf);
+        fine_total = ws.take(shared ? param_floats(kind_c) : 0);
+        total = ws.floats;
     }
     int64_t bytes() const { return total * (int64_t)sizeof(float); }
 };
@@ -117,28 +149,20 @@ static int check_grid_device(const char* fn, const uint32_t* bits) {
 // one pass of the sequence: its field, where its list and count go, and where the listed points' layer inputs go (null: inference)
 struct OccPass { int kind; const float* packed; int* list; int* count; float* acts; };
 
-// The grid-driven sequence: sample coarse, mark, list-driven field, composite, sample fine, mark, list-driven field, composite,
-// copy the counts.  Everything is already checked; launches only, grids from host values (no read-back).  out: rgb_c, depth_c,
-// acc_c, rgb_f, depth_f, acc_f; without rgb_c the coarse composite gives the weights alone (depth_c / acc_c where asked for).
-static int run_passes(const char* fn, const OccPass pass[2], bool ordered, const OccupancyGridArgs& grid, const float* rays,
-                      int64_t n, float near_, float far_, int nc, int nf, const float* z_lin, const float* u_lin,
-                      const float* t_rand, uint64_t seed, uint64_t ray0, float* const out[6], int* evaluated,
-                      const RenderWorkspace::Regions& ws, hipStream_t hs) {
-    const int S = nc + nf;
-    const auto field = [&](const OccPass& p, const float* z, int samples, float* raw) -> int {
-        const auto mark = ordered ? launch_occupancy_mark_rays_ordered : launch_occupancy_mark_rays;
-        if (int rc = mark(grid, rays, z, n, samples, p.list, p.count, raw, hs)) return rc;
-        return eval_rays_list(p.kind, p.packed, rays, z, n, samples, p.list, p.count, raw, p.acts, hs);
+// The grid-driven forward: the sequence of every render path, always with the whole fine pass (one field runs as two passes of
+// that field, Nf = 0 included), its field step = mark, then the list-driven field; then the copy of the two counts.  Everything is
+// already checked.  ordered: the ascending mark that training needs.  Without io.rgb_c the coarse composite gives the weights alone.
+static int occupancy_forward(const char* fn, const OccPass pass[2], bool ordered, const OccupancyGridArgs& grid, int64_t n, int nc,
+                             int nf, const RenderIO& io, int* evaluated, const RenderWorkspace::Regions& ws, hipStream_t hs) {
+    const auto field = [&](const OccPass& p) {
+        return [&, p](const float* z, int samples, float* raw) -> int {
+            const auto mark = ordered ? launch_occupancy_mark_rays_ordered : launch_occupancy_mark_rays;
+            if (int rc = mark(grid, io.rays, z, n, samples, p.list, p.count, raw, hs)) return rc;
+            return eval_rays_list(p.kind, p.packed, io.rays, z, n, samples, p.list, p.count, raw, p.acts, hs);
+        };
     };
-    int rc;
-    if ((rc = launch_sample_coarse(n, near_, far_, nc, z_lin, t_rand, seed, ray0, ws.z_c, hs))) return rc;
-    if ((rc = field(pass[0], ws.z_c, nc, ws.raw_c))) return rc;
-    if (out[0]) rc = launch_composite(n, nc, ws.raw_c, ws.z_c, rays, out[0], out[1], out[2], ws.w_c, hs);
-    else rc = launch_composite_weights(n, nc, ws.raw_c + 3, 4, ws.z_c, rays, out[1], out[2], ws.w_c, hs);   // raw's sigma channel
-    if (rc) return rc;
-    if ((rc = launch_sample_fine(n, near_, far_, nc, nf, z_lin, u_lin, ws.z_c, ws.w_c, nullptr, ws.z_f, nullptr, hs))) return rc;
-    if ((rc = field(pass[1], ws.z_f, S, ws.raw_f))) return rc;
-    if ((rc = launch_composite(n, S, ws.raw_f, ws.z_f, rays, out[3], out[4], out[5], nullptr, hs))) return rc;
+    if (int rc = run_render_passes(fn, RenderCall(1, n, nc, nf, false), FINE_WHOLE, io, ws, COARSE_RAW, field(pass[0]), field(pass[1]), hs))
+        return rc;
     // the two counts are neighbours in the workspace (OccLists)
     if (evaluated && hipMemcpyAsync(evaluated, pass[0].count, 2 * sizeof(int), hipMemcpyDeviceToDevice, hs) != hipSuccess) {
         set_error("%s: copy of the evaluated counts failed", fn);
@@ -193,9 +217,8 @@ int mi_render_rays_occupancy(int kind_coarse, const float* packed_coarse, int ki
     const RenderWorkspace layout(n, n_coarse, n_fine);
     const OccLists::Regions r = OccLists(false, n, n_coarse, n_fine).carve(workspace, layout.base_bytes());
     const OccPass pass[2] = {{kind_coarse, packed_coarse, r.list[0], r.counts, nullptr}, {kind_fine, packed_fine, r.list[1], r.counts + 1, nullptr}};
-    float* const out[6] = {rgb_c, depth_c, acc_c, rgb_f, depth_f, acc_f};
-    return run_passes(fn, pass, false, grid, rays, n, near_, far_, n_coarse, n_fine, z_lin, u_lin, t_rand, seed, ray0, out, evaluated,
-                      layout.carve(workspace), (hipStream_t)stream);
+    const RenderIO io{rays, near_, far_, z_lin, u_lin, t_rand, seed, ray0, rgb_c, depth_c, acc_c, rgb_f, depth_f, acc_f};
+    return occupancy_forward(fn, pass, false, grid, n, n_coarse, n_fine, io, evaluated, layout.carve(workspace), (hipStream_t)stream);
 }
 
 int mi_render_rays_occupancy_train(int kind_coarse, const float* packed_coarse, int kind_fine, const float* packed_fine,
@@ -222,9 +245,8 @@ int mi_render_rays_occupancy_train(int kind_coarse, const float* packed_coarse, 
     float* acts = (float*)saved;
     const OccPass pass[2] = {{kind_coarse, packed_coarse, r.list[0], r.counts, acts},
                              {kind_fine, packed_fine, r.list[1], r.counts + 1, acts + saved_floats_coarse(kind_coarse, n, n_coarse)}};
-    float* const out[6] = {rgb_c, depth_c, acc_c, rgb_f, depth_f, acc_f};
-    return run_passes(fn, pass, true, grid, rays, n, near_, far_, n_coarse, n_fine, z_lin, u_lin, t_rand, seed, ray0, out, evaluated,
-                      layout.carve(workspace), (hipStream_t)stream);
+    const RenderIO io{rays, near_, far_, z_lin, u_lin, t_rand, seed, ray0, rgb_c, depth_c, acc_c, rgb_f, depth_f, acc_f};
+    return occupancy_forward(fn, pass, true, grid, n, n_coarse, n_fine, io, evaluated, layout.carve(workspace), (hipStream_t)stream);
 }
 
 int mi_render_rays_occupancy_backward(int kind_coarse, const float* packed_bwd_coarse, int kind_fine,
@@ -247,11 +269,7 @@ int mi_render_rays_occupancy_backward(int kind_coarse, const float* packed_bwd_c
     const bool wants[2] = {want_c, want_f};
     for (int f = 0; f < 2; ++f) {
         if (!wants[f]) continue;
-        const char* which = f && !shared ? "fine" : "coarse";
-        if (!packed_bwd[f]) { set_error("%s: the %s field has no transposed stream", fn, which); return MI_EINVAL; }
-        if (!grads[f]) { set_error("%s: the %s field gets a cotangent but has no gradient array", fn, which); return MI_EINVAL; }
-        for (int i = 0; i < 2 * field_kind(kinds[f]).n_layers; ++i)
-            if (!grads[f][i]) { set_error("%s: %s gradient pointer %d is null", fn, which, i); return MI_EINVAL; }
+        if (int rc = check_field_grads(fn, f && !shared ? "fine" : "coarse", kinds[f], packed_bwd[f], grads[f])) return rc;
     }
     if (int rc = check_buffers(fn, OCC_BACKWARD, kind_coarse, kind_fine, shared != 0, n, n_coarse, n_fine, workspace, workspace_bytes,
                                saved, saved_bytes, bwd_workspace, bwd_workspace_bytes)) return rc;
@@ -280,7 +298,7 @@ int mi_render_rays_occupancy_backward(int kind_coarse, const float* packed_bwd_c
                                              r.counts + 1, n * S, bws + L.partial, add ? fine_total : grads[1], hs))) return rc;
         if (add && (rc = add_param_grads(kind_fine, grad_params_coarse, fine_total, hs))) return rc;
     }
-    if (fields_written) *fields_written = shared ? MI_WROTE_COARSE : (want_c ? MI_WROTE_COARSE : 0) | (want_f ? MI_WROTE_FINE : 0);
+    if (fields_written) *fields_written = fields_written_word(shared != 0, want_c, want_f, false);
     return MI_OK;
 }
 

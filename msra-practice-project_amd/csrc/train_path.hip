@@ -16,9 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/mi_render.h"
-#include "field_kinds.h"
-#include "mi_common.h"
+#include "render_path.h"
 
 namespace mi {
 
@@ -126,12 +124,6 @@ static void range_groups(const Ranges& R, int64_t r0, int64_t r1, int64_t& g0, i
 }
 
 // ---- the two passes of one call ------------------------------------------------------------------------------------
-struct Geometry {
-    int64_t n_groups, rpg, n;
-    int nc, nf;
-    bool shared;
-};
-
 struct PassSpec {
     bool exists;
     int kind;
@@ -141,20 +133,20 @@ struct PassSpec {
 
 // pass 0 = coarse (Nc samples); pass 1 = fine over Nc + Nf (two fields), the Nf new depths (one field), none (one
 // field with Nf = 0: the fine pass is the coarse pass)
-static void pass_specs(int kind_c, int kind_f, const Geometry& G, int64_t rp_c, int64_t rp_f, PassSpec P[2]) {
-    P[0] = {true, kind_c, G.nc, rp_c};
-    if (!G.shared) P[1] = {true, kind_f, G.nc + G.nf, rp_f};
-    else P[1] = {G.nf > 0, kind_c, G.nf, rp_f};
+static void pass_specs(int kind_c, int kind_f, const RenderCall& G, int64_t rp_c, int64_t rp_f, PassSpec P[2]) {
+    P[0] = {true, kind_c, G.Nc, rp_c};
+    if (!G.shared) P[1] = {true, kind_f, G.Nc + G.Nf, rp_f};
+    else P[1] = {G.Nf > 0, kind_c, G.Nf, rp_f};
 }
 
 // How many leading ranges of each pass keep their layer inputs within saved_bytes (autograd._forward_pass's loop,
 // coarse pass first, one budget).  Returns the floats the coarse pass keeps: the second pass's kept inputs follow them.
-static int64_t plan_kept(const PassSpec P[2], const Geometry& G, int64_t saved_bytes, int64_t kept[2]) {
+static int64_t plan_kept(const PassSpec P[2], const RenderCall& G, int64_t saved_bytes, int64_t kept[2]) {
     int64_t budget = saved_bytes, coarse_floats = 0;
     for (int p = 0; p < 2; ++p) {
         kept[p] = 0;
         if (!P[p].exists) continue;
-        const Ranges R = make_ranges(P[p].kind, G.n_groups, G.rpg, P[p].S, P[p].range_points);
+        const Ranges R = make_ranges(P[p].kind, G.n_groups, G.rays_per_group, P[p].S, P[p].range_points);
         const int64_t per_ray = 4 * region_total(field_kind(P[p].kind).acts) * (int64_t)P[p].S;
         for (int64_t k = 0, c = R.count(); k < c; ++k) {
             int64_t r0, r1;
@@ -190,7 +182,7 @@ struct BwdLayout {
     int64_t total;
 };
 
-static BwdLayout bwd_layout(const PassSpec P[2], const Geometry& G) {
+static BwdLayout bwd_layout(const PassSpec P[2], const RenderCall& G) {
     int64_t sz_acts = 0, sz_raw = 0, sz_grads = 0, sz_part = 0, sz_fpart = 0, sz_params = 0;
     bool any_film = false;
     int64_t film_fl = 0;                           // one group's rows of the FiLM table (two FiLM fields: the same depth)
@@ -198,7 +190,7 @@ static BwdLayout bwd_layout(const PassSpec P[2], const Geometry& G) {
         if (!P[p].exists) continue;
         if (film_floats(P[p].kind) > film_fl) film_fl = film_floats(P[p].kind);
         const FieldKind& K = field_kind(P[p].kind);
-        const Ranges R = make_ranges(P[p].kind, G.n_groups, G.rpg, P[p].S, P[p].range_points);
+        const Ranges R = make_ranges(P[p].kind, G.n_groups, G.rays_per_group, P[p].S, P[p].range_points);
         // every range has the shape of the first, the last, or (parts of images) the last part of an image
         const int64_t probes[3] = {0, R.count() - 1, R.parts ? R.per_group - 1 : 0};
         for (int64_t k : probes) {
@@ -220,29 +212,28 @@ static BwdLayout bwd_layout(const PassSpec P[2], const Geometry& G) {
         sz_params = param_floats(P[p].kind) > sz_params ? param_floats(P[p].kind) : sz_params;
     }
     BwdLayout L{};
-    int64_t f = 0;
-    auto take = [&](int64_t x) { const int64_t o = f; f += align64(x); return o; };
+    RegionAllocator ws;
     const int64_t n = G.n;
-    L.g_raw_c = take(n * G.nc * 4);
-    L.g_raw_f = take(n * (int64_t)(G.nc + G.nf) * 4);
-    L.g_raw_s = take(G.shared ? n * G.nf * 4 : 0);
-    L.range_params = take(sz_params);
-    L.fine_total = take(G.shared && G.nf > 0 ? param_floats(P[0].kind) : 0);
-    L.film_pass = take(any_film ? G.n_groups * film_fl : 0);
-    L.film_row = take(any_film ? film_fl : 0);
-    L.acts = take(sz_acts);
-    L.raw = take(sz_raw);
-    L.grads = take(sz_grads);
-    L.partial = take(sz_part);
-    L.film_partial = take(sz_fpart);
-    L.total = f;
+    L.g_raw_c = ws.take(n * G.Nc * 4);
+    L.g_raw_f = ws.take(n * (int64_t)(G.Nc + G.Nf) * 4);
+    L.g_raw_s = ws.take(G.shared ? n * G.Nf * 4 : 0);
+    L.range_params = ws.take(sz_params);
+    L.fine_total = ws.take(G.shared && G.Nf > 0 ? param_floats(P[0].kind) : 0);
+    L.film_pass = ws.take(any_film ? G.n_groups * film_fl : 0);
+    L.film_row = ws.take(any_film ? film_fl : 0);
+    L.acts = ws.take(sz_acts);
+    L.raw = ws.take(sz_raw);
+    L.grads = ws.take(sz_grads);
+    L.partial = ws.take(sz_part);
+    L.film_partial = ws.take(sz_fpart);
+    L.total = ws.floats;
     return L;
 }
 
 // The forward's state in the mi_render_rays workspace (one field adds z_samples, raw_samples, pos).
 using State = RenderWorkspace::Regions;
 
-static State carve_state(void* workspace, const Geometry& G) { return RenderWorkspace(G.n, G.nc, G.nf).carve(workspace); }
+static State carve_state(void* workspace, const RenderCall& G) { return RenderWorkspace(G.n, G.Nc, G.Nf).carve(workspace); }
 
 // Checks shared by the size queries and both entry points.  shared: one field for both passes.
 static int check_common(const char* fn, int kind_c, int kind_f, int64_t n_groups, int64_t rpg, int nc, int nf,
@@ -264,8 +255,8 @@ static int check_common(const char* fn, int kind_c, int kind_f, int64_t n_groups
     return MI_OK;
 }
 
-static int check_state(const char* fn, const Geometry& G, int64_t workspace_bytes, const void* saved, int64_t saved_bytes) {
-    const RenderWorkspace layout(G.n, G.nc, G.nf);
+static int check_state(const char* fn, const RenderCall& G, int64_t workspace_bytes, const void* saved, int64_t saved_bytes) {
+    const RenderWorkspace layout(G.n, G.Nc, G.Nf);
     const int64_t need = layout.base_bytes() + (G.shared ? layout.shared_extra_bytes() : 0);
     if (workspace_bytes < need) {
         set_error("%s: workspace of %lld bytes, need %lld (mi_render_workspace_bytes%s)", fn, (long long)workspace_bytes,
@@ -281,9 +272,9 @@ static int check_state(const char* fn, const Geometry& G, int64_t workspace_byte
 
 // One pass of the training forward (autograd._forward_pass): the kept ranges through the saving kernel, the rest
 // through the plain one (finishing the image the kept ranges stopped inside first).  raw [n,S,4].
-static int forward_pass(const PassSpec& P, const Geometry& G, const float* packed, const float* film, const float* rays,
-                        const float* z, float* raw, int64_t kept, float*& saved, void* stream) {
-    const Ranges R = make_ranges(P.kind, G.n_groups, G.rpg, P.S, P.range_points);
+static int forward_pass(const PassSpec& P, const RenderCall& G, const float* packed, const float* film, const float* rays,
+                        const float* z, float* raw, int64_t kept, float*& saved, hipStream_t hs) {
+    const Ranges R = make_ranges(P.kind, G.n_groups, G.rays_per_group, P.S, P.range_points);
     const int64_t acts = region_total(field_kind(P.kind).acts);
     const int64_t film_fl = film_floats(P.kind);   // one group's rows of the FiLM table
     const int S = P.S;
@@ -293,22 +284,21 @@ static int forward_pass(const PassSpec& P, const Geometry& G, const float* packe
         int64_t r0, r1, g0, ng;
         R.get(k, r0, r1);
         range_groups(R, r0, r1, g0, ng);
-        if ((rc = mi_field_eval_rays_train(P.kind, packed, R.film ? film + g0 * film_fl : nullptr, rays + r0 * 6,
-                                           z + r0 * S, ng, (r1 - r0) / ng, S, raw + r0 * S * 4, saved, stream))) return rc;
+        if ((rc = eval_field_rays(P.kind, packed, R.film ? film + g0 * film_fl : nullptr, rays + r0 * 6, z + r0 * S, ng,
+                                  (r1 - r0) / ng, S, raw + r0 * S * 4, hs, saved))) return rc;
         saved += acts * (r1 - r0) * S;
         r_done = r1;
     }
     if (r_done < R.n && R.film && r_done % R.rpg) {
         const int64_t r_next = (r_done / R.rpg + 1) * R.rpg;
-        if ((rc = mi_field_eval_rays(P.kind, packed, film + (r_done / R.rpg) * film_fl, rays + r_done * 6, z + r_done * S,
-                                     1, r_next - r_done, S, raw + r_done * S * 4, stream))) return rc;
+        if ((rc = eval_field_rays(P.kind, packed, film + (r_done / R.rpg) * film_fl, rays + r_done * 6, z + r_done * S, 1,
+                                  r_next - r_done, S, raw + r_done * S * 4, hs))) return rc;
         r_done = r_next;
     }
     if (r_done < R.n) {
         const int64_t ng = R.film ? (R.n - r_done) / R.rpg : 1;
-        if ((rc = mi_field_eval_rays(P.kind, packed, R.film ? film + (r_done / R.rpg) * film_fl : nullptr,
-                                     rays + r_done * 6, z + r_done * S, ng, (R.n - r_done) / ng, S, raw + r_done * S * 4,
-                                     stream))) return rc;
+        if ((rc = eval_field_rays(P.kind, packed, R.film ? film + (r_done / R.rpg) * film_fl : nullptr, rays + r_done * 6,
+                                  z + r_done * S, ng, (R.n - r_done) / ng, S, raw + r_done * S * 4, hs))) return rc;
     }
     return MI_OK;
 }
@@ -349,14 +339,13 @@ struct PassIO {
 
 // One pass of the backward (autograd._field_backward): range by range, gradients to dst (n_params device pointers) and,
 // FiLM kinds, the pass's table gradient to film_dst [n_groups,9,512].
-static int backward_pass(const PassSpec& P, const Geometry& G, const PassIO& io, const float* film, const float* rays,
-                         float* const* dst, float* film_dst, float* bws, const BwdLayout& L, void* stream) {
-    const Ranges R = make_ranges(P.kind, G.n_groups, G.rpg, P.S, P.range_points);
+static int backward_pass(const PassSpec& P, const RenderCall& G, const PassIO& io, const float* film, const float* rays,
+                         float* const* dst, float* film_dst, float* bws, const BwdLayout& L, hipStream_t hs) {
+    const Ranges R = make_ranges(P.kind, G.n_groups, G.rays_per_group, P.S, P.range_points);
     const FieldKind& K = field_kind(P.kind);
     const int64_t film_fl = film_floats(P.kind);   // one group's rows of the FiLM table
     const int64_t acts_f = region_total(K.acts);
     const int S = P.S;
-    hipStream_t hs = (hipStream_t)stream;
     float* range_out[2 * kMaxLayers];
     scratch_params(P.kind, bws + L.range_params, range_out);
     const float* saved = io.saved;
@@ -376,8 +365,8 @@ static int backward_pass(const PassSpec& P, const Geometry& G, const PassIO& io,
             raw_k = io.raw + r0 * S * 4;
             saved += acts_f * pts;
         } else {
-            if ((rc = mi_field_eval_rays_train(P.kind, io.packed, f_c, rays + r0 * 6, io.z + r0 * S, ng, (r1 - r0) / ng, S,
-                                               bws + L.raw, bws + L.acts, stream))) return rc;
+            if ((rc = eval_field_rays(P.kind, io.packed, f_c, rays + r0 * 6, io.z + r0 * S, ng, (r1 - r0) / ng, S, bws + L.raw, hs,
+                                      bws + L.acts))) return rc;
             acts = bws + L.acts;
             raw_k = bws + L.raw;
         }
@@ -415,7 +404,7 @@ int64_t mi_render_backward_workspace_bytes(int kind_coarse, int kind_fine, int s
                                            int64_t range_points_fine) {
     if (int rc = check_common("mi_render_backward_workspace_bytes", kind_coarse, kind_fine, n_groups, rays_per_group,
                               n_coarse, n_fine, range_points_coarse, range_points_fine)) return rc;
-    const Geometry G{n_groups, rays_per_group, n_groups * rays_per_group, n_coarse, n_fine, shared != 0};
+    const RenderCall G(n_groups, rays_per_group, n_coarse, n_fine, shared != 0);
     if (G.n == 0) return 0;
     PassSpec P[2];
     pass_specs(kind_coarse, shared ? kind_coarse : kind_fine, G, range_points_coarse, range_points_fine, P);
@@ -432,8 +421,8 @@ int mi_render_rays_train(int kind_coarse, const float* packed_coarse, int kind_f
     const char* fn = "mi_render_rays_train";
     if (int rc = check_common(fn, kind_coarse, kind_fine, n_groups, rays_per_group, n_coarse, n_fine, range_points_coarse,
                               range_points_fine)) return rc;
-    const bool shared = kind_coarse == kind_fine && packed_coarse == packed_fine;
-    const Geometry G{n_groups, rays_per_group, n_groups * rays_per_group, n_coarse, n_fine, shared};
+    const bool shared = one_field(kind_coarse, packed_coarse, kind_fine, packed_fine);
+    const RenderCall G(n_groups, rays_per_group, n_coarse, n_fine, shared);
     if (G.n == 0) return MI_OK;
     if (!workspace || !rays || !packed_coarse || !packed_fine || !rgb_c || !depth_c || !acc_c || !rgb_f || !depth_f || !acc_f) {
         set_error("%s: null pointer argument", fn);
@@ -445,29 +434,14 @@ int mi_render_rays_train(int kind_coarse, const float* packed_coarse, int kind_f
     pass_specs(kind_coarse, kind_fine, G, range_points_coarse, range_points_fine, P);
     int64_t kept[2];
     plan_kept(P, G, saved_bytes, kept);
-    const State st = carve_state(workspace, G);
-    const int64_t n = G.n;
-    const int S = n_coarse + n_fine;
     float* sv = (float*)saved;
-    int rc;
-    // the stage sequence of mi_render_rays (api.hip), with the field passes keeping their layer inputs
-    if ((rc = mi_sample_coarse(n, near_, far_, n_coarse, z_lin, t_rand, seed, ray0, st.z_c, stream))) return rc;
-    if ((rc = forward_pass(P[0], G, packed_coarse, film, rays, st.z_c, st.raw_c, kept[0], sv, stream))) return rc;
-    if ((rc = mi_composite(n, n_coarse, st.raw_c, st.z_c, rays, rgb_c, depth_c, acc_c, st.w_c, stream))) return rc;
-    if (shared && n_fine == 0) {                   // the fine pass IS the coarse pass (mi_render_rays aliases it)
-        return copy_render_outputs(fn, n, rgb_f, depth_f, acc_f, rgb_c, depth_c, acc_c, (hipStream_t)stream);
-    }
-    if (shared) {                                  // the Nf new depths only, merged into sorted order
-        if ((rc = mi_sample_fine_pos(n, near_, far_, n_coarse, n_fine, z_lin, u_lin, st.z_c, st.w_c, st.z_s, st.z_f, st.pos,
-                                     stream))) return rc;
-        if ((rc = forward_pass(P[1], G, packed_fine, film, rays, st.z_s, st.raw_s, kept[1], sv, stream))) return rc;
-        if ((rc = mi_merge_raw(n, n_coarse, n_fine, st.raw_c, st.raw_s, st.pos, st.raw_f, stream))) return rc;
-    } else {
-        if ((rc = mi_sample_fine(n, near_, far_, n_coarse, n_fine, z_lin, u_lin, st.z_c, st.w_c, nullptr, st.z_f, stream)))
-            return rc;
-        if ((rc = forward_pass(P[1], G, packed_fine, film, rays, st.z_f, st.raw_f, kept[1], sv, stream))) return rc;
-    }
-    return mi_composite(n, S, st.raw_f, st.z_f, rays, rgb_f, depth_f, acc_f, nullptr, stream);
+    hipStream_t hs = (hipStream_t)stream;
+    // the sequence of mi_render_rays, with field steps that keep their layer inputs; check_state demands the shared-field
+    // regions of one field, so its fine pass is the Nf new depths (or, with Nf = 0, the coarse pass)
+    const auto coarse_field = [&](const float* z, int, float* raw) { return forward_pass(P[0], G, packed_coarse, film, rays, z, raw, kept[0], sv, hs); };
+    const auto fine_field = [&](const float* z, int, float* raw) { return forward_pass(P[1], G, packed_fine, film, rays, z, raw, kept[1], sv, hs); };
+    const RenderIO io{rays, near_, far_, z_lin, u_lin, t_rand, seed, ray0, rgb_c, depth_c, acc_c, rgb_f, depth_f, acc_f};
+    return run_render_passes(fn, G, fine_plan(shared, n_fine, true), io, carve_state(workspace, G), COARSE_RAW, coarse_field, fine_field, hs);
 }
 
 int mi_render_rays_backward(int kind_coarse, const float* packed_coarse, const float* packed_bwd_coarse,
@@ -484,8 +458,8 @@ int mi_render_rays_backward(int kind_coarse, const float* packed_coarse, const f
     if (fields_written) *fields_written = 0;
     if (int rc = check_common(fn, kind_coarse, kind_fine, n_groups, rays_per_group, n_coarse, n_fine, range_points_coarse,
                               range_points_fine)) return rc;
-    const bool shared = kind_coarse == kind_fine && packed_coarse == packed_fine;
-    const Geometry G{n_groups, rays_per_group, n_groups * rays_per_group, n_coarse, n_fine, shared};
+    const bool shared = one_field(kind_coarse, packed_coarse, kind_fine, packed_fine);
+    const RenderCall G(n_groups, rays_per_group, n_coarse, n_fine, shared);
     if (G.n == 0) return MI_OK;
     const bool want_c = g_rgb_c || g_depth_c || g_acc_c;
     const bool want_f = g_rgb_f || g_depth_f || g_acc_f;
@@ -509,10 +483,7 @@ int mi_render_rays_backward(int kind_coarse, const float* packed_coarse, const f
                 if (!params[f][i]) { set_error("%s: %s parameter pointer %d is null", fn, which, i); return MI_EINVAL; }
         }
         if (!runs[f]) continue;
-        if (!packed_bwd[f]) { set_error("%s: the %s field has no transposed stream", fn, which); return MI_EINVAL; }
-        if (!grads[f]) { set_error("%s: the %s field gets a cotangent but has no gradient array", fn, which); return MI_EINVAL; }
-        for (int i = 0; i < np; ++i)
-            if (!grads[f][i]) { set_error("%s: %s gradient pointer %d is null", fn, which, i); return MI_EINVAL; }
+        if (int rc = check_field_grads(fn, which, kinds[f], packed_bwd[f], grads[f])) return rc;
         if (is_film(kinds[f]) && !grad_film) { set_error("%s: FiLM kind needs grad_film", fn); return MI_EINVAL; }
     }
     if (int rc = check_state(fn, G, workspace_bytes, saved, saved_bytes)) return rc;
@@ -538,18 +509,18 @@ int mi_render_rays_backward(int kind_coarse, const float* packed_coarse, const f
     int rc;
     if (!shared) {
         if (want_c) {
-            if ((rc = mi_composite_bwd(n, n_coarse, st.raw_c, st.z_c, rays, g_rgb_c, g_depth_c, g_acc_c, nullptr, g_raw_c,
-                                       stream))) return rc;
+            if ((rc = launch_composite_bwd(n, n_coarse, st.raw_c, st.z_c, rays, g_rgb_c, g_depth_c, g_acc_c, nullptr, g_raw_c,
+                                           hs))) return rc;
             const PassIO io{packed_coarse, packed_bwd_coarse, params_coarse, st.z_c, st.raw_c, g_raw_c, saved_pass[0], kept[0]};
-            if ((rc = backward_pass(P[0], G, io, film, rays, grad_params_coarse, grad_film, bws, L, stream))) return rc;
+            if ((rc = backward_pass(P[0], G, io, film, rays, grad_params_coarse, grad_film, bws, L, hs))) return rc;
             film_written = is_film(kind_coarse);
         }
         if (want_f) {
-            if ((rc = mi_composite_bwd(n, S, st.raw_f, st.z_f, rays, g_rgb_f, g_depth_f, g_acc_f, nullptr, g_raw_f, stream)))
+            if ((rc = launch_composite_bwd(n, S, st.raw_f, st.z_f, rays, g_rgb_f, g_depth_f, g_acc_f, nullptr, g_raw_f, hs)))
                 return rc;
             const PassIO io{packed_fine, packed_bwd_fine, params_fine, st.z_f, st.raw_f, g_raw_f, saved_pass[1], kept[1]};
             float* film_dst = film_written ? bws + L.film_pass : grad_film;
-            if ((rc = backward_pass(P[1], G, io, film, rays, grad_params_fine, film_dst, bws, L, stream))) return rc;
+            if ((rc = backward_pass(P[1], G, io, film, rays, grad_params_fine, film_dst, bws, L, hs))) return rc;
             if (film_written && is_film(kind_fine)) {          // grad_film = coarse pass + fine pass
                 Accumulator acc(hs);
                 acc.add(grad_film, bws + L.film_pass, n_groups * film_floats(kind_coarse));
@@ -557,22 +528,21 @@ int mi_render_rays_backward(int kind_coarse, const float* packed_coarse, const f
             }
             film_written |= is_film(kind_fine);
         }
-        if (fields_written) *fields_written = (want_c ? MI_WROTE_COARSE : 0) | (want_f ? MI_WROTE_FINE : 0) |
-                                              (film_written ? MI_WROTE_FILM : 0);
+        if (fields_written) *fields_written = fields_written_word(false, want_c, want_f, film_written);
         return MI_OK;
     }
     // one field: the coarse points get what the coarse outputs and the fine outputs send them (mi_split_grad), the new
     // samples get the rest; each set goes through the field's backward once and the two totals are added
     const float* g_c = g_raw_c;
-    if (want_c && (rc = mi_composite_bwd(n, n_coarse, st.raw_c, st.z_c, rays, g_rgb_c, g_depth_c, g_acc_c, nullptr, g_raw_c,
-                                         stream))) return rc;
+    if (want_c && (rc = launch_composite_bwd(n, n_coarse, st.raw_c, st.z_c, rays, g_rgb_c, g_depth_c, g_acc_c, nullptr, g_raw_c,
+                                             hs))) return rc;
     if (want_f) {
         const bool fine_sorted = n_fine > 0;                   // Nf = 0: the fine pass is the coarse pass
-        if ((rc = mi_composite_bwd(n, fine_sorted ? S : n_coarse, fine_sorted ? st.raw_f : st.raw_c,
+        if ((rc = launch_composite_bwd(n, fine_sorted ? S : n_coarse, fine_sorted ? st.raw_f : st.raw_c,
                                    fine_sorted ? st.z_f : st.z_c, rays, g_rgb_f, g_depth_f, g_acc_f, nullptr, g_raw_f,
-                                   stream))) return rc;
+                                       hs))) return rc;
         if (fine_sorted) {
-            if ((rc = mi_split_grad(n, n_coarse, n_fine, g_raw_f, st.pos, g_raw_c, want_c ? 1 : 0, bws + L.g_raw_s, stream)))
+            if ((rc = launch_split_grad(n, n_coarse, n_fine, g_raw_f, st.pos, g_raw_c, want_c ? 1 : 0, bws + L.g_raw_s, hs)))
                 return rc;
         } else if (want_c) {                                   // g_raw = coarse g_raw + fine g_raw
             Accumulator acc(hs);
@@ -583,7 +553,7 @@ int mi_render_rays_backward(int kind_coarse, const float* packed_coarse, const f
         }
     }
     const PassIO io_c{packed_coarse, packed_bwd_coarse, params_coarse, st.z_c, st.raw_c, g_c, saved_pass[0], kept[0]};
-    if ((rc = backward_pass(P[0], G, io_c, film, rays, grad_params_coarse, grad_film, bws, L, stream))) return rc;
+    if ((rc = backward_pass(P[0], G, io_c, film, rays, grad_params_coarse, grad_film, bws, L, hs))) return rc;
     if (run_f) {
         float* fine_total[2 * kMaxLayers];
         scratch_params(kind_coarse, bws + L.fine_total, fine_total);
@@ -591,13 +561,13 @@ int mi_render_rays_backward(int kind_coarse, const float* packed_coarse, const f
                           kept[1]};
         const bool film_kind = is_film(kind_coarse);
         if ((rc = backward_pass(P[1], G, io_s, film, rays, fine_total, film_kind ? bws + L.film_pass : nullptr, bws, L,
-                                stream))) return rc;
+                                hs))) return rc;
         Accumulator acc(hs);                                   // _foreach_add_(grads_c, grads_f); grad_film += fine pass's
         if ((rc = add_param_grads(acc, kind_coarse, grad_params_coarse, fine_total))) return rc;
         if (film_kind) acc.add(grad_film, bws + L.film_pass, n_groups * film_floats(kind_coarse));
         if ((rc = acc.flush())) return rc;
     }
-    if (fields_written) *fields_written = MI_WROTE_COARSE | (is_film(kind_coarse) ? MI_WROTE_FILM : 0);
+    if (fields_written) *fields_written = fields_written_word(true, true, false, is_film(kind_coarse));
     return MI_OK;
 }
 

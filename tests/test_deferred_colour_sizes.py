@@ -3,7 +3,7 @@ mi_render_workspace_bytes - one chunk's worst-case live list (a 1 KiB H8 row and
 per chunk.  No GPU, no compute call."""
 from mirender import _lib as binding
 
-CHUNK = 1 << 22          # kColourChunkRows of csrc/api.hip
+CHUNK = 1 << 22          # kColourChunkRows of csrc/render_path.hip
 
 
 def _lib():

@@ -1,7 +1,7 @@
 """GPU: with no coarse output asked for, mi_render_rays stops a coarse ray as soon as the fine sampler cannot see its
 later weights - and no fine output bit moves.
 
-With rgb_c = depth_c = acc_c = NULL and two different fields, the windowed coarse pass (csrc/api.hip) produces w_c alone,
+With rgb_c = depth_c = acc_c = NULL and two different fields, the windowed coarse pass (csrc/render_path.hip) produces w_c alone,
 and sample_fine reads a weight only as w + 1e-5f.  The resumable weights composite then drops a ray at the first window
 boundary whose fp64 running product is <= 2^-42 (kStopBelowPdfEps, csrc/mi_common.h carries the proof; the float32 side
 of it is tests/test_sampler_stop_host.py): every later weight is below 2^-41 and vanishes in that sum.  The weights
@@ -30,7 +30,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import render_ref as R, synth  # noqa: E402
 
-WINDOW = 8          # kCoarseWindow of csrc/api.hip
+WINDOW = 8          # kCoarseWindow of csrc/render_path.hip
 STOP = 2.0 ** -42   # kStopBelowPdfEps of csrc/mi_common.h
 ZERO = 2.0 ** -151  # kStopZeroWeight
 NEAR, FAR = 2.0, 6.0

@@ -1,7 +1,7 @@
 """GPU: mi_render_rays skips field evaluations whose compositing weight is exactly zero - and no output bit moves.
 
 With rgb_c = NULL and two different fields the coarse pass runs front to back in windows of WINDOW samples
-(kCoarseWindow, csrc/api.hip): after each window the resumable weights composite drops every ray whose running
+(kCoarseWindow, csrc/render_path.hip): after each window the resumable weights composite drops every ray whose running
 transmittance has reached zero, and the field is not evaluated behind that point.  Those samples' weights are exactly 0
 whatever the field says there, so rgb_f / depth_f / acc_f and depth_c / acc_c must be the SAME BITS as the unskipped
 computation.  The yardstick is that computation assembled from the staged calls, which take no such shortcut:
@@ -29,7 +29,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import render_ref as R, synth  # noqa: E402
 
-WINDOW = 8          # kCoarseWindow of csrc/api.hip
+WINDOW = 8          # kCoarseWindow of csrc/render_path.hip
 NEAR, FAR = 2.0, 6.0
 
 
