@@ -17,8 +17,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "field_kinds.h"
-#include "mi_common.h"
+#include "field_kinds_host.h"
+#include "launchers.h"
 
 namespace mi {
 

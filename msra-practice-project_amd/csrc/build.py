@@ -91,7 +91,7 @@ def build_profile(verbose=True, variant=None, defines=()):
 def build(force=False, verbose=True, always=(), defines=(), obj_dir=OBJ, out=OUT):
     """Compile what is stale (everything with force; the translation units named in `always` regardless) and link.
     Prints, per translation unit, whether it was COMPILED or REUSED - the record of what a given run of the build
-    check really exercised - and returns the library's path.  A variant build passes its extra `defines` (-D switches),
+    check really exercised - then each compiled unit's own wall seconds, and returns the library's path.  A variant build passes its extra `defines` (-D switches),
     an object directory of its own (staleness does not see the switches) and its output path."""
     import time
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -117,9 +117,14 @@ def build(force=False, verbose=True, always=(), defines=(), obj_dir=OBJ, out=OUT
     def run(cmd):
         if verbose:
             print(" ".join(cmd), flush=True)
+        t0 = time.time()
         subprocess.check_call(cmd, timeout=1800)
+        return time.time() - t0
     with ThreadPoolExecutor(max_workers=min(len(jobs), 16, int(os.environ.get("MAX_JOBS", 16))) or 1) as pool:
-        list(pool.map(run, jobs))
+        took = list(pool.map(run, jobs))
+    # each compiled unit's own wall seconds (side by side, so they add up to more than the total below)
+    for cmd, s in zip(jobs, took):
+        print(f"[build] {os.path.basename(cmd[-3])}: {s:.0f} s", flush=True)
     if force or _stale(out, objs):
         cmd = [hipcc, "-shared", "-fPIC", f"--offload-arch={ARCH}", *objs, "-o", out]
         if verbose:
@@ -142,7 +147,7 @@ def build_host_example(verbose=True):
     for name in ("cabi_host", "cabi_train_host"):
         src = os.path.join(root, "tests", "cabi", name + ".cpp")
         out = os.path.join(root, "tests", "cabi", name)
-        if _stale(out, [src, OUT, os.path.join(root, "include", "mi_render.h")]):
+        if _stale(out, [src, OUT, os.path.join(root, "include", "mi_render.h"), os.path.join(root, "include", "mi_render_kinds.h")]):
             cmd = [hipcc, "-O2", "-std=c++17", "-Wall", "-I", os.path.join(root, "include"), src, "-L", os.path.dirname(OUT),
                    "-lmirender", "-Wl,-rpath,$ORIGIN/../../msra-practice-project_amd/mirender", "-o", out]
             if verbose:

@@ -12,7 +12,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "mi_common.h"
+#include "launchers.h"
+#include "mi_host.h"
 
 namespace mi {
 

@@ -6,8 +6,9 @@
 #include <stdint.h>
 
 #include "field_bwd.h"
-#include "field_kinds.h"
+#include "field_kinds_host.h"
 #include "field_mlp_device.h"
+#include "launchers.h"
 
 #include <type_traits>
 

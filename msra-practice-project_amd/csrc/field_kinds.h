@@ -1,18 +1,17 @@
-// field_kinds.h - the field-kind registry: one compile-time descriptor per MI_FIELD_* kind (include/mi_render.h),
+// field_kinds.h - the field-kind registry: one compile-time descriptor per MI_FIELD_* kind (include/mi_render_kinds.h),
 // indexed by the kind's value.  Everything the host code and the pack / Adam kernels need to know about a kind
 // (its parameter shapes, its packed weight streams, its training buffers, and its layer GRAPH: which saved input and which
 // weight columns every linear layer multiplies, and where its dA rows live) is read from here.  The graph is stated once,
 // by two builders (with_nerf_graph, make_film_kind), checked at compile time (graph_ok) and read by one host-side walker
-// (for_each_block): the weight-gradient jobs of field_bwd_dw.hip and the input gradients of ray_grad.hip are derived
-// from it.  The packed streams are held against the graph segment by segment (segments_ok), and the fused MLP kernels read
+// (for_each_block, field_kinds_host.h): the weight-gradient jobs of field_bwd_dw.hip and the input gradients of ray_grad.hip
+// are derived from it.  The packed streams are held against the graph segment by segment (segments_ok), and the fused MLP kernels read
 // their stage shapes from the same segments (field_layout.h).  Host only but for those compile-time reads: the kernels get
 // pointers and strides, and constant memory holds the PackTables alone.
 #pragma once
 #include <stdint.h>
 
-#include "../../include/mi_render.h"
+#include "../../include/mi_render_kinds.h"
 #include "field_layout.h"
-#include "mi_common.h"
 
 namespace mi {
 
@@ -163,7 +162,7 @@ static_assert(kFieldKinds[MI_FIELD_SIREN_NERF].macs() == 559616, "SirenNeRF MACs
 static_assert(kFieldKinds[MI_FIELD_FILM_SIREN_NERF].macs() == 526848, "FilmSirenNeRF MACs per point");
 static_assert(kFieldKinds[MI_FIELD_FILM_SIREN_NERF_NODIR].macs() == 526080, "FilmSirenNeRF (no dir) MACs per point");
 static_assert(kFieldKinds[MI_FIELD_TINY_NERF].macs() == 248448, "TinyNeRF MACs per point");
-// the depth kinds are not table rows (see field_kind() below); their two ends are checked here all the same
+// the depth kinds are not table rows (see field_kind(), field_kinds_host.h); their two ends are checked here all the same
 static_assert(region_total(film_acts_depth(8)) == region_total(film_acts()) && region_total(film_grads_depth(8)) == region_total(film_grads()) &&
               film_grads_depth(8).n == film_grads().n, "depth 8 is the literal layout");
 static_assert(make_film_kind(8, true).macs() == 526848 && make_film_kind(8, false).macs() == 526080, "depth 8 is kinds 2 / 3");
@@ -351,7 +350,7 @@ static_assert(nerf_acts().relu_switch0() == 12 && tiny_acts().relu_switch0() == 
 // ---- MI_FIELD_FILM_DEPTH kinds -------------------------------------------------------------------------------------
 // A depth kind is no row of kFieldKinds and has no table in constant memory (adam_step.hip keeps one PackTable pair per
 // fixed kind there, about 11 KB each; eighteen more do not fit in 64 KB).  The host reads a depth kind's descriptor from
-// field_kind(); the kernels take the depth as a run-time argument and compute stream items with film_item().
+// field_kind() (field_kinds_host.h); the kernels take the depth as a run-time argument and compute stream items with film_item().
 constexpr bool is_depth_id(int kind) { return kind >= 0x100 && kind < 0x200; }
 constexpr int depth_of_id(int kind) { return (kind - 0x100) >> 1; }
 constexpr bool is_depth_kind(int kind) {
@@ -369,49 +368,5 @@ constexpr int film_depth(int kind) { return is_depth_kind(kind) ? depth_of_id(ki
 constexpr bool film_use_dir(int kind) { return is_depth_kind(kind) ? (kind & 1) != 0 : kind == MI_FIELD_FILM_SIREN_NERF; }
 constexpr int film_layers(int kind) { return is_film(kind) ? film_depth(kind) + 1 : 0; }
 constexpr int64_t film_floats(int kind) { return (int64_t)film_layers(kind) * kFilmRow; }   // one group's rows of the FiLM table
-
-// Validates a kind from the C ABI; sets the error message if it names none.
-inline bool bad_kind(int kind) {
-    if (is_depth_id(kind) && !is_depth_kind(kind)) {
-        set_error("FiLM depth kind 0x%x: hidden_layers = %d is outside the supported range %d..%d", kind, depth_of_id(kind),
-                  kFilmDepthMin, kFilmDepthMax);
-        return true;
-    }
-    if (!is_fixed_kind(kind) && !is_depth_kind(kind)) { set_error("unknown field kind %d", kind); return true; }
-    return false;
-}
-
-// Descriptor of a VALID kind, fixed or depth (api.hip builds the depth kinds' once, on first use).
-const FieldKind& field_kind(int kind);
-
-
-// ---- the graph's walker (host) -----------------------------------------------------------------------------------------
-// One (layer, input) block of a kind's graph over P points, as pointers and strides: dW[rows][w_ld] at column w_col0 is
-// sum_p dA[p][da_c0 + r] X[p][x_c0 + c].  The bias gradient rides with the layer's hidden input, or with its only input.
-struct GraphBlock {
-    int layer;                                 // parameter pair: weight 2 * layer, bias 2 * layer + 1
-    int cls;                                   // SrcClass of the input
-    bool head, bias;
-    int da_region;                             // FiLM kinds, non-head layers: the layer's FiLM row
-    const float* dA; int da_ld, da_c0, rows;   // [points][da_ld] rows of grads; valid rows of dW
-    const float* X; int x_ld, x_c0, cols;      // [points][x_ld] rows of acts; valid columns of the block
-    int w_ld, w_col0;
-};
-// Visits every block in layer order, inputs in weight-column order.  Rows start at point p0 of the P the buffers hold (a
-// FiLM image's first point).  Null buffers give null-based pointers for plan-only runs: never dereferenced.
-template <class F>
-void for_each_block(const FieldKind& K, const float* acts, const float* grads, int64_t P, int64_t p0, F&& f) {
-    for (int i = 0; i < K.n_layers; ++i) {
-        const LayerGraph& g = K.graph[i];
-        for (int j = 0, wcol = 0; j < g.n_in; wcol += g.in[j++].width()) {
-            const LayerInput& in = g.in[j];
-            const int da_ld = K.grads.width[g.da_region], x_ld = K.acts.width[in.region];
-            f(GraphBlock{i, in.cls, g.head, in.cls == SRC_HIDDEN || g.n_in == 1, g.da_region,
-                         grads + (int64_t)region_offset(K.grads, g.da_region) * P + p0 * da_ld, da_ld, g.da_c0, g.da_c1 - g.da_c0,
-                         acts + (int64_t)region_offset(K.acts, in.region) * P + p0 * x_ld, x_ld, in.c0, in.width(),
-                         K.dims[i][1], wcol});
-        }
-    }
-}
 
 }  // namespace mi

@@ -20,9 +20,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "field_kinds.h"
+#include "field_kinds_host.h"
 #include "field_mlp_device.h"
 #include "field_mlp_instances.h"
+#include "launchers.h"
 
 namespace mi {
 

@@ -6,7 +6,8 @@
 #include <stdint.h>
 
 #include "field_layout.h"
-#include "mi_common.h"
+#include "mi_device.h"
+#include "mi_host.h"
 #include "mi_math.h"
 
 namespace mi {

@@ -2,8 +2,8 @@
 // kind's kernel is instantiated in, and each unit's rows of the instance table.  A row holds one kernel address per variant
 // (null: no such instance), constant-initialised in the unit that defines the kernels.
 #pragma once
-#include "../../include/mi_render.h"
-#include "mi_common.h"
+#include "../../include/mi_render_kinds.h"
+#include "mi_device.h"
 
 namespace mi {
 

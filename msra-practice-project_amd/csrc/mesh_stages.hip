@@ -16,8 +16,9 @@
 #include <stdint.h>
 
 #include "../../include/mi_render.h"
+#include "launchers.h"
 #include "mesh_cube.h"
-#include "mi_common.h"
+#include "mi_host.h"
 
 namespace mi {
 

@@ -11,7 +11,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "mi_common.h"
+#include "launchers.h"
+#include "mi_host.h"
 
 namespace mi {
 
@@ -110,7 +111,7 @@ int launch_occupancy_pack(const float* sigma, const int* dims, int k, float thre
     return check_launch("occupancy_pack");
 }
 
-// ---- reading a grid: which samples of a pass are evaluated (mi_occupancy_mark_rays; MarkArgs: mi_common.h) ----------------------
+// ---- reading a grid: which samples of a pass are evaluated (mi_occupancy_mark_rays; MarkArgs: launchers.h) -----------------------
 // The rule every layer of rendering with a grid is tested against.  The point is the one the fused forward evaluates
 // (field_mlp_device.h: load_point, p = o + d z, a multiply and an add), placed by t = (p - lo) * inv_cell (a subtract and a
 // multiply); inside iff 0 <= t < G on every axis, so a NaN is not inside; its cell is floor(t).

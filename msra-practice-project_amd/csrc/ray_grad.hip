@@ -37,7 +37,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "field_kinds.h"
+#include "field_kinds_host.h"
+#include "launchers.h"
 
 namespace mi {
 

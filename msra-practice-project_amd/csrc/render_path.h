@@ -6,8 +6,8 @@
 //   - the checks and helpers that more than one path uses.
 #pragma once
 #include "../../include/mi_render.h"
-#include "field_kinds.h"
-#include "mi_common.h"
+#include "field_kinds_host.h"
+#include "launchers.h"
 
 namespace mi {
 

@@ -44,7 +44,7 @@ static_assert(kCoarseWindow >= 1 && 128 % kCoarseWindow == 0, "a tile is 128 / k
 // weights and drops every ray whose transmittance has reached zero - all its later weights are exactly 0 whatever the
 // field says there, so the field is not asked.  Same weights / depth_c / acc_c bits as one whole pass.  A caller that
 // asks for neither depth_c nor acc_c leaves sample_fine as the weights' only reader, and a ray is dropped as soon as no
-// later weight can change w + kPdfEps there (kStopBelowPdfEps, mi_common.h): same z_fine bits, far fewer points.
+// later weight can change w + kPdfEps there (kStopBelowPdfEps, launchers.h): same z_fine bits, far fewer points.
 // Everything is launched with worst-case grids from host values only (no read-back: graph-capturable); `scratch` is the
 // part of raw_c's region behind the compact sigma buffer: two live lists [n] and one count per window.
 static int coarse_sigma_windows(int kind, const float* packed, const float* rays, const float* z_c, int64_t n, int n_coarse,

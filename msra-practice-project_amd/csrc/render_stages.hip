@@ -20,7 +20,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "mi_common.h"
+#include "launchers.h"
+#include "mi_host.h"
 
 namespace mi {
 
@@ -210,7 +211,7 @@ __global__ __launch_bounds__(256) void composite_weights_kernel(int64_t n, int S
 // The weights form made resumable, for a coarse pass evaluated front to back in windows of samples (mi_render_rays): the
 // call behind the window [k0, k1) runs the passes over samples [0, k1) of every live ray under dispatch_G's G for S, a
 // sample >= k1 standing in as w = 0, and writes the weights of [k0, k1).  Then it decides the ray against `stop`, the
-// caller's threshold (mi_common.h: kStopZeroWeight = 2^-151, or kStopBelowPdfEps = 2^-42 when sample_fine is the weights'
+// caller's threshold (launchers.h: kStopZeroWeight = 2^-151, or kStopBelowPdfEps = 2^-42 when sample_fine is the weights'
 // only reader - the argument why it then sees the same bits stands there).  With 2^-151:
 //   * D, the fp64 running product in front of sample k1, is <= 2^-151: every later sample's (float)(T * excl) is 0.0f
 //     whatever its sigma is.  The factors f = (1-alpha)+1e-10f are <= 1 (sigma >= 0, ascending depths), so the exact
@@ -495,7 +496,7 @@ __device__ __forceinline__ uint64_t sort_key(float v, int i) {
 
 // ---------------------------------------------------------------------------------------
 // The inverse-CDF draw of sample_pdf (render.py:27-56), one wave per ray, in two parts around cdf_like_cumsum.
-// pdf[j] = (w[j] + kPdfEps) / sum_j (w[j] + kPdfEps), j < nw, kPdfEps = 1e-5 (mi_common.h): strided partial sums, xor
+// pdf[j] = (w[j] + kPdfEps) / sum_j (w[j] + kPdfEps), j < nw, kPdfEps = 1e-5 (launchers.h): strided partial sums, xor
 // reduction, one division per entry.
 // ---------------------------------------------------------------------------------------
 __device__ __forceinline__ void normalise_pdf(const float* __restrict__ w, int nw, int lane, float* pdf) {

@@ -200,16 +200,19 @@ def test_faithful_restatement_passes_where_the_mutations_fail():
 # ---- the window limit ---------------------------------------------------------------------------------------------------------
 def test_window_limit_is_stated_once_and_refused_as_einval():
     """include/mi_render.h, the argument check and the launcher name the same limit (odd, <= 31); anything else is
-    MI_EINVAL before any launch (no GPU needed: the arguments are refused first)."""
+    MI_EINVAL (stated in include/mi_render_kinds.h, which mi_render.h includes) before any launch (no GPU needed: the
+    arguments are refused first)."""
     import os
     import re
     from mirender import _lib
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     header = open(os.path.join(root, "include", "mi_render.h")).read()
+    kinds = open(os.path.join(root, "include", "mi_render_kinds.h")).read()
     stages = open(os.path.join(root, "msra-practice-project_amd", "csrc", "eval_stages.hip")).read()
     assert f"window_size (odd, <= {E.MAX_WINDOW})" in header
     assert int(re.search(r"constexpr int kMaxWindow = (\d+);", stages).group(1)) == E.MAX_WINDOW
-    assert int(re.search(r"#define MI_EINVAL \((-\d+)\)", header).group(1)) == -1
+    assert '#include "mi_render_kinds.h"' in header and "#define MI_EINVAL" not in header
+    assert int(re.search(r"#define MI_EINVAL \((-\d+)\)", kinds).group(1)) == -1
     lib = _lib.load()
     buf = (ctypes.c_float * 64)()
     p = ctypes.cast(buf, ctypes.c_void_p)

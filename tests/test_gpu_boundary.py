@@ -91,7 +91,7 @@ def test_model_moved_to_cpu_and_back_repacks():
 @pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two GPUs in one process (DataParallel's layout)")
 def test_two_devices_two_threads_one_process():
     """One process driving two GPUs from two threads (pi_GAN/train.py:50): the 148 KiB dynamic-LDS attribute of the
-    MLP kernels is per device (csrc/mi_common.h:PerDeviceOnce); both devices must render, train and agree."""
+    MLP kernels is per device (csrc/mi_host.h:PerDeviceOnce); both devices must render, train and agree."""
     from mirender import fields, render_core
     sd = synth.state_dict("nerf", 5, "medium", 0.05)
     outs, errs = [None, None], []

@@ -3,7 +3,7 @@ later weights - and no fine output bit moves.
 
 With rgb_c = depth_c = acc_c = NULL and two different fields, the windowed coarse pass (csrc/render_path.hip) produces w_c alone,
 and sample_fine reads a weight only as w + 1e-5f.  The resumable weights composite then drops a ray at the first window
-boundary whose fp64 running product is <= 2^-42 (kStopBelowPdfEps, csrc/mi_common.h carries the proof; the float32 side
+boundary whose fp64 running product is <= 2^-42 (kStopBelowPdfEps, csrc/launchers.h carries the proof; the float32 side
 of it is tests/test_sampler_stop_host.py): every later weight is below 2^-41 and vanishes in that sum.  The weights
 behind the stop are written as zeros, which are NOT the unskipped weights - but z_fine, and with it rgb_f / depth_f /
 acc_f, must be the SAME BITS as the unskipped computation.  A call that asks for depth_c or acc_c keeps the exact
@@ -31,7 +31,7 @@ pytestmark = pytest.mark.gpu
 from oracle import render_ref as R, synth  # noqa: E402
 
 WINDOW = 8          # kCoarseWindow of csrc/render_path.hip
-STOP = 2.0 ** -42   # kStopBelowPdfEps of csrc/mi_common.h
+STOP = 2.0 ** -42   # kStopBelowPdfEps of csrc/launchers.h
 ZERO = 2.0 ** -151  # kStopZeroWeight
 NEAR, FAR = 2.0, 6.0
 

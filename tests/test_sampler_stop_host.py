@@ -1,5 +1,5 @@
 """CPU: a coarse weight below 2^-41 is invisible to sample_pdf, so the windowed coarse pass may stop a ray once the
-transmittance in front of a window boundary is <= 2^-42 (kStopBelowPdfEps, csrc/mi_common.h) whenever sample_fine is the
+transmittance in front of a window boundary is <= 2^-42 (kStopBelowPdfEps, csrc/launchers.h) whenever sample_fine is the
 weights' only reader.
 
 sample_pdf uses a weight only as w + 1e-5f (float32, un-fused).  1e-5f lies in [2^-17, 2^-16): its ulp is 2^-40 and the
