@@ -414,6 +414,49 @@ int mi_occupancy_cell_points(const int* dims, const float* lo, const float* cell
 int mi_occupancy_pack(const float* sigma, const int* dims, int supersample, float threshold, int dilate, uint32_t* bits,
                       void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- a live grid: jittered partial updates of a per-cell density -------------------------
+ *
+ * A grid that follows a field while it trains keeps a float density per cell on the device (density [cells], all +0 at the
+ * start) next to its bits.  One update re-samples a subset of the cells at one jittered point each, folds the new sigma in
+ * with max(old * decay, new) and re-thresholds the density into the bits in place.  Nothing is read back by any of the calls.
+ *
+ * Random words: P(seed, R, j) is the Philox4x32-10 block with counter (R_lo, R_hi, j, 0) and key (seed_lo, seed_hi); word w of
+ * stream R is word w & 3 of block w >> 2 (the words of mi_sample_coarse, whose stream is the ray).
+ *
+ * mi_occupancy_draw_points: rows [row0, row0 + count) of update number `epoch`.  Row r reads stream R = (epoch << 32) | r.
+ * Its jitter is u_d = float(word_d >> 8) * 2^-24 for d = 0, 1, 2.  Its cell: mode 0 (sweep): cell = r (row0 + count <= cells);
+ * mode 1 (draw): rows r < n_uniform take cell = (word_3 * cells) >> 32 in 64-bit arithmetic, the other rows take the first of
+ * the candidates c_a = (word_{4+a} * cells) >> 32, a = 0..7, whose bit is set in bits, and c_7 if none is (no compaction, no
+ * atomic).  Its point is lo_d + (float(i_d) + u_d) * cell_d with (i_0, i_1, i_2) the cell's coordinates, the add, the multiply
+ * and the add each rounded on their own (at u = 1 - 2^-24 the inner sum may round up to i_d + 1: the far face of the cell);
+ * the direction is 0.  Outputs: cell_ids [count] (device ints) and points [count, 6], ready for mi_field_eval_points.  lo,
+ * cell: HOST, as for mi_occupancy_cell_points.  bits may be NULL when no row reads it (mode 0, or n_uniform >= row0 + count).
+ * row0 + count must not exceed 2^31.
+ *
+ * mi_occupancy_density_update: the fold, over ALL rows of one update in one call (a cell sampled in two calls would decay
+ * twice).  v_i = sigma_i > 0 ? sigma_i : +0 (so -0.0, negatives and NaN count as +0); m_c = the maximum of v_i over the rows
+ * with cell_ids[i] == c; a cell with at least one row gets density_c = fmaxf(density_c * decay, m_c), the product rounded on
+ * its own; every other cell keeps its bits.  The maximum is an integer atomic maximum on the floats' bits, so the result does
+ * not depend on the order of arrival.  decay in [0, 1].  A row whose cell id lies outside the grid is ignored.
+ *
+ * mi_occupancy_density_pack: mean = float(sum of density in fp64 / cells), summed in a fixed order (the same bits in every
+ * run); thr = relative ? fminf(threshold, mean) : threshold; a cell is occupied iff density > thr (strict); the result is
+ * dilated and packed into bits as by mi_occupancy_pack.  mean and thr stay on the device.
+ *
+ * workspace: mi_occupancy_density_workspace_bytes(dims, dilate) device bytes - 4 bytes per cell of scratch ints, 8 bytes per
+ * 4096 cells of partial sums (each of the two rounded up to whole 256-byte blocks), 256 bytes for mean and thr, and the byte
+ * planes of mi_occupancy_pack_workspace_bytes(dims, dilate).  The update needs the size for dilate = 0, so one buffer sized
+ * for the pack serves both.  Bad dims, null pointers, count < 0, a decay outside [0, 1] (or NaN), dilate < 0, rows past the
+ * grid (mode 0) or past 2^31 and a short workspace: MI_EINVAL before any launch.  count == 0 launches nothing and returns 0. */
+int mi_occupancy_draw_points(const uint32_t* bits, const int* dims, const float* lo, const float* cell, uint64_t seed,
+                             uint32_t epoch, int mode, int64_t row0, int64_t count, int64_t n_uniform, int* cell_ids,
+                             float* points, void* stream);
+int64_t mi_occupancy_density_workspace_bytes(const int* dims, int dilate);
+int mi_occupancy_density_update(const float* sigma, const int* cell_ids, int64_t count, const int* dims, float decay,
+                                float* density, void* workspace, int64_t workspace_bytes, void* stream);
+int mi_occupancy_density_pack(const float* density, const int* dims, float threshold, int relative, int dilate, uint32_t* bits,
+                              void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- rendering with a grid (inference; NeRF, SirenNeRF, TinyNeRF) ------------------------
  *
  * The one rule: with a grid, a sample whose point lies in an unoccupied cell, or outside the box [lo, hi), has

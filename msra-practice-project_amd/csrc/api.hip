@@ -173,6 +173,63 @@ int mi_occupancy_pack(const float* sigma, const int* dims, int supersample, floa
     return launch_occupancy_pack(sigma, dims, supersample, threshold, dilate, bits, workspace, (hipStream_t)stream);
 }
 
+int mi_occupancy_draw_points(const uint32_t* bits, const int* dims, const float* lo, const float* cell, uint64_t seed, uint32_t epoch,
+                             int mode, int64_t row0, int64_t count, int64_t n_uniform, int* cell_ids, float* points, void* stream) {
+    const char* fn = "mi_occupancy_draw_points";
+    const int64_t cells = occupancy_cells(fn, dims);
+    if (!cells) return MI_EINVAL;
+    if ((mode != 0 && mode != 1) || row0 < 0 || count < 0 || n_uniform < 0 || row0 > (1LL << 31) - count) {
+        set_error("%s: bad arguments (mode 0 or 1; row0, count, n_uniform >= 0; row0 + count <= 2^31)", fn);
+        return MI_EINVAL;
+    }
+    if (mode == 0 && row0 + count > cells) {
+        set_error("%s: a sweep of rows [%lld, %lld) over %lld cells", fn, (long long)row0, (long long)(row0 + count), (long long)cells);
+        return MI_EINVAL;
+    }
+    const bool reads_bits = mode == 1 && n_uniform < row0 + count;
+    if (!lo || !cell || !cell_ids || !points || (reads_bits && !bits)) { set_error("%s: null pointer argument", fn); return MI_EINVAL; }
+    return launch_occupancy_draw_points(bits, dims, lo, cell, seed, epoch, mode, row0, count, n_uniform, cell_ids, points,
+                                        (hipStream_t)stream);
+}
+
+int64_t mi_occupancy_density_workspace_bytes(const int* dims, int dilate) {
+    const int64_t cells = occupancy_cells("mi_occupancy_density_workspace_bytes", dims);
+    if (!cells) return MI_EINVAL;
+    if (dilate < 0) { set_error("mi_occupancy_density_workspace_bytes: dilate = %d", dilate); return MI_EINVAL; }
+    return occupancy_density_workspace_bytes(cells, dilate);
+}
+
+int mi_occupancy_density_update(const float* sigma, const int* cell_ids, int64_t count, const int* dims, float decay, float* density,
+                                void* workspace, int64_t workspace_bytes, void* stream) {
+    const char* fn = "mi_occupancy_density_update";
+    const int64_t cells = occupancy_cells(fn, dims);
+    if (!cells) return MI_EINVAL;
+    if (!sigma || !cell_ids || !density || !workspace) { set_error("%s: null pointer argument", fn); return MI_EINVAL; }
+    if (count < 0 || count > (1LL << 31)) { set_error("%s: count = %lld (0 .. 2^31)", fn, (long long)count); return MI_EINVAL; }
+    if (!(decay >= 0.f && decay <= 1.f)) { set_error("%s: decay = %g (needs 0 <= decay <= 1)", fn, (double)decay); return MI_EINVAL; }
+    const int64_t need = occupancy_density_workspace_bytes(cells, 0);
+    if (workspace_bytes < need) {
+        set_error("%s: workspace of %lld bytes, needs %lld", fn, (long long)workspace_bytes, (long long)need);
+        return MI_EINVAL;
+    }
+    return launch_occupancy_density_update(sigma, cell_ids, count, dims, decay, density, workspace, (hipStream_t)stream);
+}
+
+int mi_occupancy_density_pack(const float* density, const int* dims, float threshold, int relative, int dilate, uint32_t* bits,
+                              void* workspace, int64_t workspace_bytes, void* stream) {
+    const char* fn = "mi_occupancy_density_pack";
+    const int64_t cells = occupancy_cells(fn, dims);
+    if (!cells) return MI_EINVAL;
+    if (!density || !bits || !workspace) { set_error("%s: null pointer argument", fn); return MI_EINVAL; }
+    if (dilate < 0) { set_error("%s: dilate = %d", fn, dilate); return MI_EINVAL; }
+    const int64_t need = occupancy_density_workspace_bytes(cells, dilate);
+    if (workspace_bytes < need) {
+        set_error("%s: workspace of %lld bytes, needs %lld", fn, (long long)workspace_bytes, (long long)need);
+        return MI_EINVAL;
+    }
+    return launch_occupancy_density_pack(density, dims, threshold, relative, dilate, bits, workspace, (hipStream_t)stream);
+}
+
 // n * n_samples points whose indices fit the list's ints
 static int check_list_sizes(const char* fn, int64_t n, int n_samples) {
     if (n < 0 || n_samples < 1) { set_error("%s: bad sizes (n >= 0, n_samples >= 1)", fn); return MI_EINVAL; }

@@ -29,6 +29,16 @@ int launch_occupancy_cell_points(const int* dims, const float* lo, const float* 
 int64_t occupancy_pack_workspace_bytes(int64_t cells, int dilate);
 int launch_occupancy_pack(const float* sigma, const int* dims, int k, float threshold, int dilate, uint32_t* bits,
                           void* workspace, hipStream_t stream);
+// ... a live grid's density (mi_occupancy_draw_points / _density_update / _density_pack): the rows' cells and jittered points,
+// the fold of their sigma into density (the first region of the workspace: the scratch ints) and the re-thresholding into bits
+int launch_occupancy_draw_points(const uint32_t* bits, const int* dims, const float* lo, const float* cell, uint64_t seed,
+                                 uint32_t epoch, int mode, int64_t row0, int64_t count, int64_t n_uniform, int* cell_ids,
+                                 float* points, hipStream_t stream);
+int64_t occupancy_density_workspace_bytes(int64_t cells, int dilate);
+int launch_occupancy_density_update(const float* sigma, const int* cell_ids, int64_t count, const int* dims, float decay,
+                                    float* density, void* workspace, hipStream_t stream);
+int launch_occupancy_density_pack(const float* density, const int* dims, float threshold, int relative, int dilate, uint32_t* bits,
+                                  void* workspace, hipStream_t stream);
 // ... and reading one.  A grid as the kernels take it: box and cells by value (MarkArgs, a kernel argument) and the device words.
 // occupancy_grid_args (render_path.h) is the one place a caller's grid is checked and copied into one.
 struct MarkArgs { int dims[3]; float lo[3], inv_cell[3]; };

@@ -3,6 +3,8 @@
 //
 //   occupancy_cell_points_kernel  k^3 regular sub-sample points per cell, [count k^3, 6] rows for mi_field_eval_points
 //   occupancy_threshold / dilate / pack kernels   sigma at those points -> one byte per cell, dilated, packed into words
+//   occupancy_draw_points_kernel / occupancy_density_* kernels   a live grid: one jittered point in each of a drawn subset of
+//                                 the cells, the decayed-maximum fold of their sigma into a per-cell density, its re-thresholding
 //   occupancy_mark_rays_kernel    reading a grid: the samples of a render pass that lie in occupied cells, as a device-counted list
 //   occupancy_mark_ordered_kernel / occupancy_scan_blocks_kernel   the same list in ascending order, without atomics (training)
 //
@@ -13,6 +15,7 @@
 
 #include "launchers.h"
 #include "mi_host.h"
+#include "mi_philox.h"
 
 namespace mi {
 
@@ -95,13 +98,10 @@ __global__ __launch_bounds__(256) void occupancy_pack_kernel(const uint8_t* __re
 static int64_t occ_region_bytes(int64_t cells) { return (cells + 255) / 256 * 256; }
 int64_t occupancy_pack_workspace_bytes(int64_t cells, int dilate) { return occ_region_bytes(cells) * (dilate > 0 ? 2 : 1); }
 
-int launch_occupancy_pack(const float* sigma, const int* dims, int k, float threshold, int dilate, uint32_t* bits,
-                          void* workspace, hipStream_t stream) {
+// the byte plane buf[0] dilated `dilate` times (ping-pong with buf[1]) and packed into words: the end of both packs
+static int dilate_and_pack(uint8_t* const buf[2], const int* dims, int dilate, uint32_t* bits, hipStream_t stream) {
     const int cells = dims[0] * dims[1] * dims[2], words = (int)(((int64_t)cells + 31) / 32);
-    uint8_t* buf[2] = {(uint8_t*)workspace, (uint8_t*)workspace + occ_region_bytes(cells)};
     const dim3 grid((unsigned)(((int64_t)cells + 255) / 256));
-    hipLaunchKernelGGL(occupancy_threshold_kernel, grid, dim3(256), 0, stream, sigma, cells, k * k * k, threshold, buf[0]);
-    if (const int rc = check_launch("occupancy_threshold")) return rc;
     int cur = 0;
     for (int i = 0; i < dilate; ++i, cur ^= 1) {
         hipLaunchKernelGGL(occupancy_dilate_kernel, grid, dim3(256), 0, stream, buf[cur], dims[0], dims[1], dims[2], buf[cur ^ 1]);
@@ -109,6 +109,193 @@ int launch_occupancy_pack(const float* sigma, const int* dims, int k, float thre
     }
     hipLaunchKernelGGL(occupancy_pack_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, stream, buf[cur], cells, words, bits);
     return check_launch("occupancy_pack");
+}
+
+int launch_occupancy_pack(const float* sigma, const int* dims, int k, float threshold, int dilate, uint32_t* bits,
+                          void* workspace, hipStream_t stream) {
+    const int cells = dims[0] * dims[1] * dims[2];
+    uint8_t* buf[2] = {(uint8_t*)workspace, (uint8_t*)workspace + occ_region_bytes(cells)};
+    hipLaunchKernelGGL(occupancy_threshold_kernel, dim3((unsigned)(((int64_t)cells + 255) / 256)), dim3(256), 0, stream, sigma, cells,
+                       k * k * k, threshold, buf[0]);
+    if (const int rc = check_launch("occupancy_threshold")) return rc;
+    return dilate_and_pack(buf, dims, dilate, bits, stream);
+}
+
+// ---- a live grid: jittered partial re-sampling of a per-cell density, folded by a decayed maximum (include/mi_render.h) ---------
+// Row r of update `epoch` reads the words of Philox stream (epoch << 32) | r: words 0..2 are the jitter inside its cell,
+// word 3 is the cell of a uniformly drawn row, words 4..11 are the candidates of a row drawn among the occupied cells (the
+// first one whose bit is set, the last one if none is: rejection, so no compaction and no atomic).
+struct DrawArgs { int dims[3]; float lo[3], cell[3]; };
+
+__global__ __launch_bounds__(256) void occupancy_draw_points_kernel(DrawArgs a, const uint32_t* __restrict__ bits, uint32_t cells,
+                                                                    uint64_t seed, uint32_t epoch, int mode, int64_t row0,
+                                                                    int64_t count, int64_t n_uniform, int* __restrict__ cell_ids,
+                                                                    float* __restrict__ pts) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    const int64_t r = row0 + i;
+    const uint64_t stream = ((uint64_t)epoch << 32) | (uint64_t)r;
+    uint32_t cell = 0;
+    if (mode == 0) {
+        cell = (uint32_t)r;
+    } else if (r < n_uniform) {
+        cell = (uint32_t)(((uint64_t)philox_u32(seed, stream, 3) * cells) >> 32);
+    } else {
+        for (uint32_t t = 0; t < 8; ++t) {
+            cell = (uint32_t)(((uint64_t)philox_u32(seed, stream, 4 + t) * cells) >> 32);
+            if ((bits[cell >> 5] >> (cell & 31)) & 1u) break;
+        }
+    }
+    const uint32_t plane = (uint32_t)a.dims[1] * (uint32_t)a.dims[2];
+    const uint32_t c[3] = {cell / plane, (cell / (uint32_t)a.dims[2]) % (uint32_t)a.dims[1], cell % (uint32_t)a.dims[2]};
+    cell_ids[i] = (int)cell;
+    float* o = pts + i * 6;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        const float u = (float)(philox_u32(seed, stream, (uint32_t)d) >> 8) * 0x1p-24f;
+        o[d] = __fadd_rn(a.lo[d], __fmul_rn(__fadd_rn((float)c[d], u), a.cell[d]));
+        o[3 + d] = 0.f;
+    }
+}
+
+int launch_occupancy_draw_points(const uint32_t* bits, const int* dims, const float* lo, const float* cell, uint64_t seed,
+                                 uint32_t epoch, int mode, int64_t row0, int64_t count, int64_t n_uniform, int* cell_ids,
+                                 float* points, hipStream_t stream) {
+    if (count <= 0) return 0;
+    DrawArgs a;
+    for (int d = 0; d < 3; ++d) { a.dims[d] = dims[d]; a.lo[d] = lo[d]; a.cell[d] = cell[d]; }
+    const uint32_t cells = (uint32_t)(dims[0] * dims[1] * dims[2]);
+    hipLaunchKernelGGL(occupancy_draw_points_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, a, bits, cells, seed,
+                       epoch, mode, row0, count, n_uniform, cell_ids, points);
+    return check_launch("occupancy_draw_points");
+}
+
+// The fold of one update: density_c = max(density_c * decay, the largest sigma sampled in cell c), cells without a sample
+// untouched.  Three kernels: the scratch ints are set to -1 ("unsampled"); every row takes an integer atomicMax of the bits of
+// max(sigma, +0) - for non-negative floats the integer order is the float order, so the result does not depend on the order of
+// arrival, and +0 (bits 0) lies above the sentinel where -0.0 (bits 0x80000000, a negative int) would lie below it; then one
+// thread per cell folds.  A row whose cell id is outside the grid is ignored.
+__global__ __launch_bounds__(256) void occupancy_density_clear_kernel(int cells, int* __restrict__ scratch) {
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c < cells) scratch[c] = -1;
+}
+
+__global__ __launch_bounds__(256) void occupancy_density_max_kernel(const float* __restrict__ sigma, const int* __restrict__ cell_ids,
+                                                                    int64_t count, int cells, int* scratch) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    const int c = cell_ids[i];
+    if (c < 0 || c >= cells) return;
+    const float s = sigma[i];
+    const float v = s > 0.f ? s : 0.f;                          // -0.0, negatives and NaN: +0
+    atomicMax(scratch + c, __float_as_int(v));
+}
+
+__global__ __launch_bounds__(256) void occupancy_density_fold_kernel(const int* __restrict__ scratch, int cells, float decay,
+                                                                     float* __restrict__ density) {
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= cells) return;
+    const int m = scratch[c];
+    if (m < 0) return;
+    density[c] = fmaxf(__fmul_rn(density[c], decay), __int_as_float(m));
+}
+
+// The workspace of the density calls: the scratch ints of the fold; the fp64 partial sums of the pack, one per workgroup of
+// kSumBlock cells; the pack's mean and threshold (two floats); the byte planes of occupancy_pack_workspace_bytes.
+constexpr int kSumBlock = 4096;
+static int64_t round256(int64_t bytes) { return (bytes + 255) / 256 * 256; }
+static int64_t density_sum_blocks(int64_t cells) { return (cells + kSumBlock - 1) / kSumBlock; }
+static int64_t density_scratch_bytes(int64_t cells) { return round256(cells * 4); }
+static int64_t density_partial_bytes(int64_t cells) { return round256(density_sum_blocks(cells) * 8); }
+int64_t occupancy_density_workspace_bytes(int64_t cells, int dilate) {
+    return density_scratch_bytes(cells) + density_partial_bytes(cells) + 256 + occupancy_pack_workspace_bytes(cells, dilate);
+}
+
+int launch_occupancy_density_update(const float* sigma, const int* cell_ids, int64_t count, const int* dims, float decay,
+                                    float* density, void* workspace, hipStream_t stream) {
+    if (count <= 0) return 0;
+    const int cells = dims[0] * dims[1] * dims[2];
+    int* scratch = (int*)workspace;
+    const dim3 grid((unsigned)(((int64_t)cells + 255) / 256));
+    hipLaunchKernelGGL(occupancy_density_clear_kernel, grid, dim3(256), 0, stream, cells, scratch);
+    if (const int rc = check_launch("occupancy_density_clear")) return rc;
+    hipLaunchKernelGGL(occupancy_density_max_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, sigma, cell_ids, count,
+                       cells, scratch);
+    if (const int rc = check_launch("occupancy_density_max")) return rc;
+    hipLaunchKernelGGL(occupancy_density_fold_kernel, grid, dim3(256), 0, stream, scratch, cells, decay, density);
+    return check_launch("occupancy_density_fold");
+}
+
+// The mean of the density in fp64, in a fixed order so that two runs give the same bits: thread t of a workgroup adds its 16
+// cells (t, t + 256, ...) in ascending order, the 256 sums are halved in LDS (a fixed tree), and one workgroup then adds the
+// workgroups' sums in index order.  No float atomics.
+__global__ __launch_bounds__(256) void occupancy_density_sum_kernel(const float* __restrict__ density, int cells,
+                                                                    double* __restrict__ partial) {
+    __shared__ double part[256];
+    const int64_t base = (int64_t)blockIdx.x * kSumBlock + threadIdx.x;
+    double s = 0.0;
+    for (int it = 0; it < kSumBlock / 256; ++it) {
+        const int64_t c = base + it * 256;
+        if (c < cells) s += (double)density[c];
+    }
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int half = 128; half > 0; half >>= 1) {
+        if ((int)threadIdx.x < half) part[threadIdx.x] += part[threadIdx.x + half];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[blockIdx.x] = part[0];
+}
+
+// out[0] = mean = float(sum / cells), out[1] = thr = relative ? fminf(threshold, mean) : threshold
+__global__ __launch_bounds__(256) void occupancy_density_mean_kernel(const double* __restrict__ partial, int n_blocks, int cells,
+                                                                     float threshold, int relative, float* __restrict__ out) {
+    __shared__ double part[256];
+    double sum = 0.0;
+    for (int head = 0; head < n_blocks; head += 256) {
+        const int i = head + (int)threadIdx.x;
+        part[threadIdx.x] = i < n_blocks ? partial[i] : 0.0;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const int n = n_blocks - head < 256 ? n_blocks - head : 256;
+            for (int j = 0; j < n; ++j) sum += part[j];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float mean = (float)(sum / (double)cells);
+        out[0] = mean;
+        out[1] = relative ? fminf(threshold, mean) : threshold;
+    }
+}
+
+// a cell is occupied iff its density is above the device threshold (strict)
+__global__ __launch_bounds__(256) void occupancy_density_threshold_kernel(const float* __restrict__ density, int cells,
+                                                                          const float* __restrict__ mean_thr,
+                                                                          uint8_t* __restrict__ occ) {
+    const int64_t cell = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (cell >= cells) return;
+    occ[cell] = density[cell] > mean_thr[1] ? 1 : 0;
+}
+
+int launch_occupancy_density_pack(const float* density, const int* dims, float threshold, int relative, int dilate, uint32_t* bits,
+                                  void* workspace, hipStream_t stream) {
+    const int cells = dims[0] * dims[1] * dims[2];
+    const int n_blocks = (int)density_sum_blocks(cells);
+    uint8_t* at = (uint8_t*)workspace + density_scratch_bytes(cells);
+    double* partial = (double*)at;
+    float* mean_thr = (float*)(at + density_partial_bytes(cells));
+    uint8_t* planes = at + density_partial_bytes(cells) + 256;
+    uint8_t* buf[2] = {planes, planes + occ_region_bytes(cells)};
+    hipLaunchKernelGGL(occupancy_density_sum_kernel, dim3((unsigned)n_blocks), dim3(256), 0, stream, density, cells, partial);
+    if (const int rc = check_launch("occupancy_density_sum")) return rc;
+    hipLaunchKernelGGL(occupancy_density_mean_kernel, dim3(1), dim3(256), 0, stream, partial, n_blocks, cells, threshold, relative,
+                       mean_thr);
+    if (const int rc = check_launch("occupancy_density_mean")) return rc;
+    hipLaunchKernelGGL(occupancy_density_threshold_kernel, dim3((unsigned)(((int64_t)cells + 255) / 256)), dim3(256), 0, stream, density,
+                       cells, mean_thr, buf[0]);
+    if (const int rc = check_launch("occupancy_density_threshold")) return rc;
+    return dilate_and_pack(buf, dims, dilate, bits, stream);
 }
 
 // ---- reading a grid: which samples of a pass are evaluated (mi_occupancy_mark_rays; MarkArgs: launchers.h) -----------------------

@@ -21,6 +21,7 @@ _int = ctypes.c_int
 _f32 = ctypes.c_float
 _f64 = ctypes.c_double
 _u64 = ctypes.c_uint64
+_u32 = ctypes.c_uint32
 _vp = ctypes.c_void_p
 
 # name -> (restype, argtypes): every symbol include/mi_render.h declares
@@ -99,6 +100,11 @@ SIGNATURES = {
     "mi_occupancy_cell_points": (_int, [ctypes.POINTER(_int), ctypes.POINTER(_f32), ctypes.POINTER(_f32), _int, _i64, _i64,
                                         _vp, _vp]),
     "mi_occupancy_pack": (_int, [_vp, ctypes.POINTER(_int), _int, _f32, _int, _vp, _vp, _i64, _vp]),
+    "mi_occupancy_draw_points": (_int, [_vp, ctypes.POINTER(_int), ctypes.POINTER(_f32), ctypes.POINTER(_f32), _u64, _u32, _int,
+                                        _i64, _i64, _i64, _vp, _vp, _vp]),
+    "mi_occupancy_density_workspace_bytes": (_i64, [ctypes.POINTER(_int), _int]),
+    "mi_occupancy_density_update": (_int, [_vp, _vp, _i64, ctypes.POINTER(_int), _f32, _vp, _vp, _i64, _vp]),
+    "mi_occupancy_density_pack": (_int, [_vp, ctypes.POINTER(_int), _f32, _int, _int, _vp, _vp, _i64, _vp]),
     "mi_occupancy_mark_rays": (_int, [_vp, ctypes.POINTER(_int), ctypes.POINTER(_f32), ctypes.POINTER(_f32), _vp, _vp, _i64,
                                       _int, _vp, _vp, _vp, _vp]),
     "mi_field_eval_rays_list": (_int, [_int, _vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp]),

@@ -11,7 +11,8 @@ keyword `grid=` of render_rays / render_image / render_image_tensor / render_vid
 o + d * z lies in an unoccupied cell, or outside [lo, hi), counts as raw = 0 and is not evaluated (ops.render_rays_occupancy,
 mi_render_rays_occupancy).  A grid that misses cells where the field has density therefore changes the picture: build it with
 a threshold, supersampling and dilation that suit the field.  Training with a grid is the opt-in module
-mirender.occupancy_train (render_rays(..., grid=) with a graph to the fields' parameters).
+mirender.occupancy_train (render_rays(..., grid=) with a graph to the fields' parameters).  LiveOccupancyGrid keeps a grid current
+while its field trains: a per-cell density on the device, updated a part at a time and re-thresholded into the bits in place.
 """
 from __future__ import annotations
 
@@ -111,10 +112,7 @@ class OccupancyGrid:
         (at (i + 0.5) / supersample of the cell); the bits are then dilated `dilate` times by the 6-neighbourhood.  Points are
         generated on the device (mi_occupancy_cell_points), evaluated by the fused kernel in batches of `max_batch` points
         with a zero direction (sigma does not depend on it, as in grid.py) and packed by mi_occupancy_pack."""
-        pf = fields.as_packed_field(model)
-        if pf is None or fields.is_film(pf.kind):
-            raise _lib.MiRenderError("OccupancyGrid.from_field: needs a NeRF, SirenNeRF or TinyNeRF field (a FiLM field's "
-                                     "table is per image, a per-scene grid has no meaning there)")
+        pf = _grid_field(model, "OccupancyGrid.from_field")
         dev = pf.device
         dims = (int(resolution),) * 3 if np.ndim(resolution) == 0 else tuple(int(r) for r in resolution)
         k = int(supersample)
@@ -138,3 +136,81 @@ class OccupancyGrid:
             _lib.call("mi_occupancy_pack", dev, _lib.ptr(sigma), pdims, k, float(threshold), int(dilate), _lib.ptr(bits),
                       _lib.ptr(ws), ws_bytes)
         return cls(bits, lo32, hi32, dims)
+
+
+def _grid_field(model, who):
+    """The PackedField of a model a per-scene grid can be built from, or MiRenderError under the caller's name."""
+    pf = fields.as_packed_field(model)
+    if pf is None or fields.is_film(pf.kind):
+        raise _lib.MiRenderError(f"{who}: needs a NeRF, SirenNeRF or TinyNeRF field (a FiLM field's table is per image, a "
+                                 "per-scene grid has no meaning there)")
+    return pf
+
+
+class LiveOccupancyGrid:
+    """An occupancy grid that follows a field while it trains (include/mi_render.h "a live grid").
+
+        live = LiveOccupancyGrid(lo, hi, 128)                    # every cell occupied until the first update
+        live.update(fine_model)                                  # a sweep: every cell at one jittered point
+        live.update(fine_model, cells=live.grid.cells // 4)      # a partial update: half uniform, half among the occupied
+        occupancy_train.render_rays(..., grid=live.grid)
+
+    `density` (float32 [cells] on the device, +0 at the start) is folded with max(density * decay, sigma) at the cells an
+    update samples; the bits are then density > (min(threshold, mean density) if relative else threshold), dilated `dilate`
+    times.  `grid` is an ordinary OccupancyGrid whose `bits` tensor is written IN PLACE by every update: whatever holds
+    `live.grid` (a render call, a captured graph) sees the new bits, and the tensor's data_ptr never changes.  `updates`
+    counts the updates and is the epoch of the next one's random words, with `seed` their key.  update() reads nothing back;
+    when to sweep and how many rows to draw is the caller's policy (examples/train_nerf_live_grid.py shows one)."""
+
+    def __init__(self, lo, hi, resolution, device=None, *, decay=0.95, threshold=0.01, relative=True, dilate=0, seed=0):
+        dims = (int(resolution),) * 3 if np.ndim(resolution) == 0 else tuple(int(r) for r in resolution)
+        device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if min(dims) < 1:
+            raise _lib.MiRenderError(f"occupancy grid dims {dims}: each at least 1")
+        self.grid = OccupancyGrid.from_dense(np.ones(dims, dtype=bool), lo, hi, device)
+        self.decay, self.threshold, self.relative, self.dilate = float(decay), float(threshold), bool(relative), int(dilate)
+        self.seed = _lib.seed64(seed)
+        self.updates = 0
+        self.density = torch.zeros(self.grid.cells, dtype=torch.float32, device=device)
+        self._dims = _i3(dims)
+        self._lo = _f3(self.grid.lo)
+        self._cell = _f3((self.grid.hi - self.grid.lo) / np.float32(dims))
+        self._ws_bytes = _lib.query("mi_occupancy_density_workspace_bytes", self._dims[1], self.dilate)
+        self._ws = torch.empty(self._ws_bytes, dtype=torch.uint8, device=device)
+
+    def update(self, model, cells=None, occupied_share=0.5, max_batch=64 ** 3):
+        """One update.  cells=None: a sweep, every cell at one jittered point.  Otherwise `cells` rows are drawn, the first
+        cells - int(cells * occupied_share) uniformly over the grid and the others among the currently occupied cells.  The
+        points are evaluated in batches of `max_batch` by the fused kernel, as from_field does, and all rows' sigma is folded
+        in one call and packed into the grid's bits in one call."""
+        pf = _grid_field(model, "LiveOccupancyGrid.update")
+        g, dev = self.grid, self.grid.device
+        if pf.device != dev:
+            raise _lib.MiRenderError(f"LiveOccupancyGrid.update: the field is on {pf.device}, the grid on {dev}")
+        sweep = cells is None
+        rows = g.cells if sweep else int(cells)
+        if rows < 1 or not 0.0 <= float(occupied_share) <= 1.0 or int(max_batch) < 1:
+            raise _lib.MiRenderError("LiveOccupancyGrid.update: needs cells >= 1, 0 <= occupied_share <= 1, max_batch >= 1")
+        n_uniform = rows if sweep else rows - int(rows * float(occupied_share))
+        pdims, plo, pcell = self._dims[1], self._lo[1], self._cell[1]
+        ids = torch.empty(rows, dtype=torch.int32, device=dev)
+        sigma = torch.empty(rows, dtype=torch.float32, device=dev)
+        with torch.no_grad():
+            for head in range(0, rows, int(max_batch)):
+                count = min(int(max_batch), rows - head)
+                pts = torch.empty((count, 6), dtype=torch.float32, device=dev)
+                _lib.call("mi_occupancy_draw_points", dev, _lib.ptr(g.bits), pdims, plo, pcell, self.seed,
+                          self.updates & 0xFFFFFFFF, 0 if sweep else 1, head, count, n_uniform, _lib.ptr(ids[head:head + count]),
+                          _lib.ptr(pts))
+                sigma[head:head + count] = fields.eval_points(pf, pts)[:, 3]
+            _lib.call("mi_occupancy_density_update", dev, _lib.ptr(sigma), _lib.ptr(ids), rows, pdims, self.decay,
+                      _lib.ptr(self.density), _lib.ptr(self._ws), self._ws_bytes)
+            _lib.call("mi_occupancy_density_pack", dev, _lib.ptr(self.density), pdims, self.threshold, int(self.relative),
+                      self.dilate, _lib.ptr(g.bits), _lib.ptr(self._ws), self._ws_bytes)
+        self.updates += 1
+
+    def occupied_fraction(self) -> float:
+        return self.grid.occupied_fraction()
+
+    def to_dense(self) -> np.ndarray:
+        return self.grid.to_dense()
