@@ -10,6 +10,7 @@ rows to draw and how often are the caller's policy; this file shows one choice. 
 oracle/.
 
     python examples/train_nerf_live_grid.py [--steps 800] [--period 16] [--sweep-steps 256] [--resolution 64] [--dilate 1]
+                                            [--clip-probes 128]     (also clip each ray's sampling range to the grid)
 """
 import argparse
 import os
@@ -41,6 +42,8 @@ def main(argv=None):
     ap.add_argument("--size", type=int, default=32)
     ap.add_argument("--views", type=int, default=8)
     ap.add_argument("--batch", type=int, default=1024)
+    ap.add_argument("--clip-probes", type=int, default=None,
+                    help="with a grid: clip each ray's sampling range to it with this many probes (occupancy_train.render_rays' clip_probes)")
     ap.add_argument("--quiet", action="store_true")
     args = ap.parse_args(argv)
     assert torch.cuda.is_available(), "needs a ROCm device: there is no CPU path"
@@ -73,7 +76,8 @@ def main(argv=None):
         if step % args.period == 0:
             live.update(fine, cells=None if step < args.sweep_steps else live.grid.cells // 4)
         rays, rgb, alpha = bank.batch(args.batch)
-        out, counts = occupancy_train.render_rays(rays, near, far, coarse, fine, nc, nf, grid=live.grid, return_counts=True)
+        out, counts = occupancy_train.render_rays(rays, near, far, coarse, fine, nc, nf, grid=live.grid, return_counts=True,
+                                                  clip_probes=args.clip_probes)
         evaluated, possible = evaluated + counts, possible + rays.shape[0] * (2 * nc + nf)     # counts stay on the device
         loss, psnr = train.nerf_loss(out, rgb, alpha, use_alpha=False, use_fine_model=True)
         opt.zero_grad()

@@ -11,6 +11,10 @@ density settle first, `--dilate` leaves a margin of cells around it, and the reb
 three are the caller's policy, not the library's.  Only the product is imported: nothing from oracle/.
 
     python examples/train_nerf_occupancy.py [--steps 800] [--warmup 200] [--rebuild 100] [--resolution 64] [--dilate 1]
+                                            [--clip-probes 128]
+
+`--clip-probes M` also clips each ray's sampling range to the grid (M probes along the ray, one bin of margin), so the 32 + 32
+samples of a ray are placed where the grid allows density instead of over the whole [near, far].
 """
 import argparse
 import os
@@ -41,6 +45,8 @@ def main(argv=None):
     ap.add_argument("--size", type=int, default=32)
     ap.add_argument("--views", type=int, default=8)
     ap.add_argument("--batch", type=int, default=1024)
+    ap.add_argument("--clip-probes", type=int, default=None,
+                    help="with a grid: clip each ray's sampling range to it with this many probes (occupancy_train.render_rays' clip_probes)")
     ap.add_argument("--quiet", action="store_true")
     args = ap.parse_args(argv)
     assert torch.cuda.is_available(), "needs a ROCm device: there is no CPU path"
@@ -78,7 +84,8 @@ def main(argv=None):
         if grid is None:
             out = render.render_rays(rays, near, far, coarse, fine, nc, nf)
         else:
-            out, counts = occupancy_train.render_rays(rays, near, far, coarse, fine, nc, nf, grid=grid, return_counts=True)
+            out, counts = occupancy_train.render_rays(rays, near, far, coarse, fine, nc, nf, grid=grid, return_counts=True,
+                                                      clip_probes=args.clip_probes)
             evaluated, possible = evaluated + counts, possible + rays.shape[0] * (2 * nc + nf)     # counts stay on the device
         loss, psnr = train.nerf_loss(out, rgb, alpha, use_alpha=False, use_fine_model=True)
         opt.zero_grad()

@@ -555,6 +555,53 @@ int mi_render_rays_occupancy_backward(int kind_coarse, const float* packed_bwd_c
                                       float* const* grad_params_coarse, float* const* grad_params_fine, void* bwd_workspace,
                                       int64_t bwd_workspace_bytes, int* fields_written, void* stream);
 
+/* ---- clipping each ray's sampling range to the grid (NeRF, SirenNeRF, TinyNeRF) -----------
+ *
+ * The grid calls above decide WHETHER a sample is evaluated; these decide WHERE samples are placed.  The rule, for rays
+ * [n,2,3], scalars near_ < far_, a grid, probes = M in [1, 4096] and pad >= 0, every operation in fp32 and rounded on its own:
+ *   h = (far_ - near_) / float(M);  probe k in [0, M) sits at depth t_k = near_ + (float(k) + 0.5f) * h; its point is the mark
+ *   rule's p = o + d * t_k and it is occupied exactly as mi_occupancy_mark_rays decides it (a NaN is outside).
+ *   With k0 / k1 the least / greatest occupied probe: a = max(k0 - pad, 0), b = min(k1 + 1 + pad, M),
+ *   near_r = near_ + float(a) * h,  far_r = (b == M) ? far_ : near_ + float(b) * h.
+ *   A ray without an occupied probe keeps (near_, far_); the mark then culls its samples as it does without clipping.
+ * A structure thinner than h between two probes can be missed: probes and pad are the caller's, as a grid's resolution and
+ * dilation are.  A step of at most half a cell along the ray is a sound default.
+ *
+ * mi_occupancy_clip_rays: bounds [n,2] (device floats) = (near_r, far_r) of every ray.  One wave per ray; no read-back.
+ *
+ * mi_sample_coarse_bounds / mi_sample_fine_bounds: mi_sample_coarse / mi_sample_fine_pos with their arithmetic unchanged and
+ * the coarse linspace evaluated in the kernel over the ray's own range, lin(i) = linspace(bounds[r][0], bounds[r][1], Nc)[i]
+ * (ATen's scalar formula).  A z_lin table has no meaning per ray: they take none.  Bounds equal to (near_, far_) on every ray
+ * give the bits of the scalar calls with z_lin = NULL; ray r of a bounds call has the bits of the scalar call on that one ray
+ * with (near_r, far_r) and ray0 + r.  z_samples and pos are optional (NULL), as in mi_sample_fine_pos.
+ *
+ * mi_render_rays_occupancy_clip / _clip_train: mi_render_rays_occupancy / _train with probes, pad in place of z_lin: the clip
+ * first, then the same sequence with the two bounds samplers.  workspace: the unclipped call's bytes +
+ * mi_render_occupancy_clip_extra_bytes(n) (the bounds, align64(2 n) floats, BEHIND the unclipped call's regions:
+ * mi_render_rays_occupancy_backward, which reads z from the workspace and takes no near / far, serves the clipped training
+ * forward unchanged and accepts its larger workspace).  probes outside [1, 4096], pad < 0, !(near_ < far_), a NULL bounds, a
+ * short workspace, FiLM kinds and the grid checks: MI_EINVAL before any launch. */
+int mi_occupancy_clip_rays(const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell, const float* rays,
+                           int64_t n, float near_, float far_, int probes, int pad, float* bounds, void* stream);
+int mi_sample_coarse_bounds(int64_t n, const float* bounds, int n_coarse, const float* t_rand, uint64_t seed, uint64_t ray0,
+                            float* z, void* stream);
+int mi_sample_fine_bounds(int64_t n, const float* bounds, int n_coarse, int n_fine, const float* u_lin, const float* z_coarse,
+                          const float* weights, float* z_samples, float* z_fine, int* pos, void* stream);
+int64_t mi_render_occupancy_clip_extra_bytes(int64_t n);
+int mi_render_rays_occupancy_clip(int kind_coarse, const float* packed_coarse, int kind_fine, const float* packed_fine,
+                                  const float* rays, int64_t n, float near_, float far_, int n_coarse, int n_fine, int probes,
+                                  int pad, const float* u_lin, const float* t_rand, uint64_t seed, uint64_t ray0,
+                                  const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell, float* rgb_c,
+                                  float* depth_c, float* acc_c, float* rgb_f, float* depth_f, float* acc_f, int* evaluated,
+                                  void* workspace, int64_t workspace_bytes, void* stream);
+int mi_render_rays_occupancy_clip_train(int kind_coarse, const float* packed_coarse, int kind_fine, const float* packed_fine,
+                                        const float* rays, int64_t n, float near_, float far_, int n_coarse, int n_fine,
+                                        int probes, int pad, const float* u_lin, const float* t_rand, uint64_t seed,
+                                        uint64_t ray0, const uint32_t* bits, const int* dims, const float* lo,
+                                        const float* inv_cell, float* rgb_c, float* depth_c, float* acc_c, float* rgb_f,
+                                        float* depth_f, float* acc_f, int* evaluated, void* workspace, int64_t workspace_bytes,
+                                        void* saved, int64_t saved_bytes, void* stream);
+
 /* ---- measurement hooks (bench.py) ---------------------------------------------------- */
 
 /* HIP events owned by the library's HIP runtime (the one the kernels launch on), so a host

@@ -266,6 +266,17 @@ int mi_occupancy_mark_rays_ordered(const uint32_t* bits, const int* dims, const 
     return mark_rays("mi_occupancy_mark_rays_ordered", true, bits, dims, lo, inv_cell, rays, z, n, n_samples, list, count, raw, stream);
 }
 
+int mi_occupancy_clip_rays(const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell, const float* rays, int64_t n,
+                           float near_, float far_, int probes, int pad, float* bounds, void* stream) {
+    const char* fn = "mi_occupancy_clip_rays";
+    OccupancyGridArgs grid;
+    if (int rc = occupancy_grid_args(fn, bits, dims, lo, inv_cell, &grid)) return rc;
+    if (int rc = occupancy_clip_args(fn, near_, far_, probes, pad)) return rc;
+    if (n < 0) { set_error("%s: n = %lld", fn, (long long)n); return MI_EINVAL; }
+    if (!rays || !bounds) { set_error("%s: null pointer argument (rays, bounds)", fn); return MI_EINVAL; }
+    return launch_occupancy_clip_rays(grid, rays, n, near_, far_, probes, pad, bounds, (hipStream_t)stream);
+}
+
 // the two list-driven forwards: inference (acts null) and the one that keeps the listed points' layer inputs
 static int eval_rays_list_checked(const char* fn, bool train, int kind, const float* packed, const float* rays, const float* z,
                                   int64_t n, int n_samples, const int* list, const int* count, float* raw, float* acts, void* stream) {
@@ -319,6 +330,12 @@ int mi_sample_coarse(int64_t n, float near_, float far_, int n_coarse, const flo
     return launch_sample_coarse(n, near_, far_, n_coarse, z_lin, t_rand, seed, ray0, z, (hipStream_t)stream);
 }
 
+int mi_sample_coarse_bounds(int64_t n, const float* bounds, int n_coarse, const float* t_rand, uint64_t seed, uint64_t ray0,
+                            float* z, void* stream) {
+    if (n < 0 || n_coarse < 1 || !bounds || !z) { set_error("mi_sample_coarse_bounds: bad arguments (bounds and z are required)"); return MI_EINVAL; }
+    return launch_sample_coarse_bounds(n, bounds, n_coarse, t_rand, seed, ray0, z, (hipStream_t)stream);
+}
+
 int mi_composite(int64_t n, int n_samples, const float* raw, const float* z, const float* rays, float* rgb,
                  float* depth, float* acc, float* weights, void* stream) {
     if (n < 0 || n_samples < 1 || !raw || !z || !rays || !rgb || !depth || !acc) {
@@ -349,6 +366,15 @@ int mi_sample_fine_pos(int64_t n, float near_, float far_, int n_coarse, int n_f
     }
     return launch_sample_fine(n, near_, far_, n_coarse, n_fine, z_lin, u_lin, z_coarse, weights, z_samples, z_fine, pos,
                               (hipStream_t)stream);
+}
+
+int mi_sample_fine_bounds(int64_t n, const float* bounds, int n_coarse, int n_fine, const float* u_lin, const float* z_coarse,
+                          const float* weights, float* z_samples, float* z_fine, int* pos, void* stream) {
+    if (n < 0 || n_coarse < 3 || n_fine < 0 || !bounds || !z_coarse || !weights || !z_fine) {
+        set_error("mi_sample_fine_bounds: bad arguments (need Nc >= 3 and the bounds)");
+        return MI_EINVAL;
+    }
+    return launch_sample_fine_bounds(n, bounds, n_coarse, n_fine, u_lin, z_coarse, weights, z_samples, z_fine, pos, (hipStream_t)stream);
 }
 
 int mi_merge_raw(int64_t n, int n_coarse, int n_fine, const float* raw_coarse, const float* raw_samples, const int* pos,

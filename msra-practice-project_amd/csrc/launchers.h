@@ -54,6 +54,10 @@ int launch_occupancy_mark_rays(const OccupancyGridArgs& grid, const float* rays,
 int64_t occupancy_ordered_list_ints(int64_t points);
 int launch_occupancy_mark_rays_ordered(const OccupancyGridArgs& grid, const float* rays, const float* z, int64_t n, int S, int* list,
                                        int* count, float* raw, hipStream_t stream);
+// Each ray's sampling range clipped to the grid (the rule: occupancy.hip, include/mi_render.h): bounds [n,2] = (near_r, far_r),
+// (near_, far_) for a ray none of whose `probes` probes is occupied.  1 <= probes <= 4096, pad >= 0, near_ < far_ (the caller checks).
+int launch_occupancy_clip_rays(const OccupancyGridArgs& grid, const float* rays, int64_t n, float near_, float far_, int probes,
+                               int pad, float* bounds, hipStream_t stream);
 // The inference forward over a device-counted list of point indices (NeRF, SirenNeRF, TinyNeRF: has_list_kernel): a mode-1
 // launch of one group (a.a = rays, a.z and a.out [rays_per_group * n_samples]) that evaluates point list[e] for every e below
 // *count and writes its row a.out[list[e]] alone.  The grid covers every point of the launch (host values, no read-back);
@@ -152,6 +156,12 @@ int launch_sample_pdf(int64_t n, int nb, int ns, const float* bins, const float*
 int launch_sample_fine(int64_t n, float near_, float far_, int nc, int nf, const float* z_lin, const float* u_lin,
                        const float* z_coarse, const float* weights, float* z_samples, float* z_fine, int* pos,
                        hipStream_t stream);
+// ... and both samplers over a range per ray, bounds [n,2] = (near_r, far_r): the same arithmetic, the coarse linspace evaluated in
+// the kernel from the ray's own two floats (no z_lin table)
+int launch_sample_coarse_bounds(int64_t n, const float* bounds, int nc, const float* t_rand, uint64_t seed, uint64_t ray0,
+                                float* z, hipStream_t stream);
+int launch_sample_fine_bounds(int64_t n, const float* bounds, int nc, int nf, const float* u_lin, const float* z_coarse,
+                              const float* weights, float* z_samples, float* z_fine, int* pos, hipStream_t stream);
 int launch_merge_raw(int64_t n, int nc, int nf, const float* raw_c, const float* raw_s, const int* pos, float* raw_f,
                      hipStream_t stream);
 int launch_split_grad(int64_t n, int nc, int nf, const float* g_f, const int* pos, float* g_c, int accumulate_coarse,

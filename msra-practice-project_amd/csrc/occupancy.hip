@@ -7,6 +7,7 @@
 //                                 the cells, the decayed-maximum fold of their sigma into a per-cell density, its re-thresholding
 //   occupancy_mark_rays_kernel    reading a grid: the samples of a render pass that lie in occupied cells, as a device-counted list
 //   occupancy_mark_ordered_kernel / occupancy_scan_blocks_kernel   the same list in ascending order, without atomics (training)
+//   occupancy_clip_rays_kernel    reading a grid: each ray's sampling range clipped to the first and last occupied probe along it
 //
 // Small kernels next to the field evaluations between them (cells k^3 MLP points).  Compiled with -ffp-contract=off: a
 // sub-sample point is a chain of separately rounded operations, which a test restates in torch.
@@ -302,10 +303,9 @@ int launch_occupancy_density_pack(const float* density, const int* dims, float t
 // The rule every layer of rendering with a grid is tested against.  The point is the one the fused forward evaluates
 // (field_mlp_device.h: load_point, p = o + d z, a multiply and an add), placed by t = (p - lo) * inv_cell (a subtract and a
 // multiply); inside iff 0 <= t < G on every axis, so a NaN is not inside; its cell is floor(t).
-__device__ __forceinline__ bool point_occupied(const MarkArgs& g, const uint32_t* __restrict__ bits, const float* __restrict__ rays,
-                                               const float* __restrict__ z, int64_t p, int S) {
-    const float* r = rays + (p / S) * 6;
-    const float zz = z[p];
+// ... of the ray r (its six floats) at depth zz: the test itself, which the mark kernels and the clip kernel share
+__device__ __forceinline__ bool depth_occupied(const MarkArgs& g, const uint32_t* __restrict__ bits, const float* __restrict__ r,
+                                               float zz) {
     float t[3];
     bool inside = true;
 #pragma unroll
@@ -317,6 +317,12 @@ __device__ __forceinline__ bool point_occupied(const MarkArgs& g, const uint32_t
     if (!inside) return false;
     const int bit = ((int)floorf(t[0]) * g.dims[1] + (int)floorf(t[1])) * g.dims[2] + (int)floorf(t[2]);
     return (bits[bit >> 5] >> (bit & 31)) & 1u;
+}
+
+// point p = ray * S + k of a pass over rays [n,2,3] at depths z [n,S]
+__device__ __forceinline__ bool point_occupied(const MarkArgs& g, const uint32_t* __restrict__ bits, const float* __restrict__ rays,
+                                               const float* __restrict__ z, int64_t p, int S) {
+    return depth_occupied(g, bits, rays + (p / S) * 6, z[p]);
 }
 
 // One thread per point, kMarkPerThread rounds of 256 points per workgroup.  A frame's 10^8 points must not queue on the one
@@ -370,6 +376,58 @@ int launch_occupancy_mark_rays(const OccupancyGridArgs& grid, const float* rays,
     hipLaunchKernelGGL(occupancy_mark_rays_kernel, dim3((unsigned)((total + kMarkBlock - 1) / kMarkBlock)), dim3(256), 0, stream,
                        grid.cells, grid.bits, rays, z, total, S, list, count, raw);
     return check_launch("occupancy_mark_rays");
+}
+
+// ---- clipping a ray's sampling range to the grid (mi_occupancy_clip_rays) ---------------------------------------------------------
+// The rule: M probes at the midpoints of M equal bins of [near, far], h = (far - near) / float(M), t_k = near + (float(k) + 0.5f) * h,
+// each tested by depth_occupied like a sample of a pass.  With k0 / k1 the least / greatest occupied probe, a = max(k0 - pad, 0),
+// b = min(k1 + 1 + pad, M): near_r = near + float(a) * h, far_r = far itself where b == M, else near + float(b) * h.  A ray
+// without an occupied probe keeps (near, far): the mark culls its samples as it does without clipping.
+// One wave per ray, four rays per workgroup, the grid strided over the rays.  Lane l of round j tests probe 64 j + l and the
+// round's ballot is its mask: rounds run from the front until the first non-zero mask (k0 = its lowest bit), then from the back
+// down to that round (k1 = the highest bit of the first non-zero mask met), so a ray that is occupied near both ends of its
+// range reads two rounds.  Every branch is on a ballot or on the ray index: uniform over the wave.  Lanes 0 and 1 store the
+// two floats; no LDS, no atomics.
+__global__ __launch_bounds__(256) void occupancy_clip_rays_kernel(MarkArgs g, const uint32_t* __restrict__ bits,
+                                                                  const float* __restrict__ rays, int64_t n, float near_, float far_,
+                                                                  int probes, int pad, float* __restrict__ bounds) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float h = __fdiv_rn(__fsub_rn(far_, near_), (float)probes);
+    const int rounds = (probes + 63) >> 6;
+    for (int64_t ray = (int64_t)blockIdx.x * 4 + wave; ray < n; ray += (int64_t)gridDim.x * 4) {
+        const float* r = rays + ray * 6;
+        const auto round_mask = [&](int j) {
+            const int k = j * 64 + lane;
+            const float t = __fadd_rn(near_, __fmul_rn(__fadd_rn((float)k, 0.5f), h));
+            return __builtin_amdgcn_ballot_w64(k < probes && depth_occupied(g, bits, r, t));
+        };
+        int k0 = -1, k1 = -1, j0 = 0;
+        uint64_t first = 0;
+        for (; j0 < rounds; ++j0)
+            if ((first = round_mask(j0)) != 0ull) { k0 = j0 * 64 + __builtin_ctzll(first); break; }
+        for (int j = rounds - 1; k0 >= 0 && j >= j0; --j) {
+            const uint64_t m = j == j0 ? first : round_mask(j);
+            if (m != 0ull) { k1 = j * 64 + 63 - __builtin_clzll(m); break; }
+        }
+        float lo_r = near_, hi_r = far_;
+        if (k0 >= 0) {
+            const int a = k0 - pad > 0 ? k0 - pad : 0;
+            const int b = k1 + 1 + pad < probes ? k1 + 1 + pad : probes;
+            lo_r = __fadd_rn(near_, __fmul_rn((float)a, h));
+            if (b != probes) hi_r = __fadd_rn(near_, __fmul_rn((float)b, h));
+        }
+        if (lane < 2) bounds[ray * 2 + lane] = lane ? hi_r : lo_r;
+    }
+}
+
+int launch_occupancy_clip_rays(const OccupancyGridArgs& grid, const float* rays, int64_t n, float near_, float far_, int probes,
+                               int pad, float* bounds, hipStream_t stream) {
+    if (n <= 0) return 0;
+    int64_t blocks = (n + 3) / 4;
+    if (blocks > 256 * 16) blocks = 256 * 16;
+    hipLaunchKernelGGL(occupancy_clip_rays_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, grid.cells, grid.bits, rays, n, near_,
+                       far_, probes, pad, bounds);
+    return check_launch("occupancy_clip_rays");
 }
 
 // ---- the same list in ascending order, without atomics (mi_occupancy_mark_rays_ordered: training with a grid) --------------------

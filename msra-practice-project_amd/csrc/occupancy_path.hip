@@ -7,6 +7,8 @@
 // field launch (eval_rays_list) are here too, for the stage wrappers of api.hip as well.  It is deliberately small:
 // one range per pass, nothing recomputed, one group, no FiLM; one field for both passes runs as two passes of that field over
 // all their listed points (no merge, as at inference) and its two gradient sums are added.
+// The clipped forwards (mi_render_rays_occupancy_clip / _clip_train) are the same two bodies with one launch in front: each
+// ray's range clipped to the grid (launch_occupancy_clip_rays) into a bounds region behind the lists, which both samplers read.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -65,6 +67,18 @@ struct OccLists {
     }
 };
 
+// near_ < far_ (so neither is a NaN), 1 <= probes <= 4096 (64 rounds of a wave), pad >= 0
+int occupancy_clip_args(const char* fn, float near_, float far_, int probes, int pad) {
+    if (!(near_ < far_)) { set_error("%s: near = %g, far = %g (clipping needs near < far)", fn, (double)near_, (double)far_); return MI_EINVAL; }
+    if (probes < 1 || probes > 4096) { set_error("%s: probes = %d (1 to 4096)", fn, probes); return MI_EINVAL; }
+    if (pad < 0) { set_error("%s: pad = %d (at least 0)", fn, pad); return MI_EINVAL; }
+    return MI_OK;
+}
+
+// The bounds [n,2] of a clipped call (mi_render_occupancy_clip_extra_bytes): behind the OccLists region of either kind, so
+// every offset the backward reads stays where it is without them.
+static int64_t clip_bounds_bytes(int64_t n) { return align64(2 * n) * (int64_t)sizeof(float); }
+
 // the backward workspace, in floats: dL/d(raw) of both composites, one pass's dA rows and dW scratch, one field: the fine
 // pass's parameter gradients
 struct OccBwdLayout {
@@ -112,16 +126,20 @@ static int check_call(const char* fn, const char* doing, int kind_c, int kind_f,
 enum OccCall { OCC_RENDER, OCC_TRAIN, OCC_BACKWARD };
 static int check_buffers(const char* fn, OccCall call, int kind_c, int kind_f, bool shared, int64_t n, int nc, int nf,
                          const void* workspace, int64_t workspace_bytes, const void* saved = nullptr, int64_t saved_bytes = 0,
-                         const void* bwd_workspace = nullptr, int64_t bwd_workspace_bytes = 0) {
+                         const void* bwd_workspace = nullptr, int64_t bwd_workspace_bytes = 0, bool clipped = false) {
     const auto refused = [&](const char* what, const void* p, int64_t have, int64_t need, const char* query) {
         if (p && have >= need) return false;
         set_error("%s: %s of %lld bytes, %s %lld", fn, what, (long long)have, query, (long long)need);
         return true;
     };
     const bool train = call != OCC_RENDER;
-    if (refused("workspace", workspace, workspace_bytes, RenderWorkspace(n, nc, nf).base_bytes() + OccLists(train, n, nc, nf).bytes(),
-                train ? "mi_render_workspace_bytes + mi_render_occupancy_train_extra_bytes say"
-                      : "mi_render_workspace_bytes + mi_render_occupancy_extra_bytes say") ||
+    // A workspace may be larger than asked for: the backward of a clipped forward gets the forward's, bounds region included.
+    if (refused("workspace", workspace, workspace_bytes,
+                RenderWorkspace(n, nc, nf).base_bytes() + OccLists(train, n, nc, nf).bytes() + (clipped ? clip_bounds_bytes(n) : 0),
+                clipped ? (train ? "mi_render_workspace_bytes + mi_render_occupancy_train_extra_bytes + mi_render_occupancy_clip_extra_bytes say"
+                                 : "mi_render_workspace_bytes + mi_render_occupancy_extra_bytes + mi_render_occupancy_clip_extra_bytes say")
+                : train ? "mi_render_workspace_bytes + mi_render_occupancy_train_extra_bytes say"
+                        : "mi_render_workspace_bytes + mi_render_occupancy_extra_bytes say") ||
         (train && refused("saved buffer", saved, saved_bytes, saved_bytes_of(kind_c, kind_f, n, nc, nf),
                           "mi_render_occupancy_train_saved_bytes says")) ||
         (call == OCC_BACKWARD && refused("backward workspace", bwd_workspace, bwd_workspace_bytes,
@@ -152,8 +170,17 @@ struct OccPass { int kind; const float* packed; int* list; int* count; float* ac
 // The grid-driven forward: the sequence of every render path, always with the whole fine pass (one field runs as two passes of
 // that field, Nf = 0 included), its field step = mark, then the list-driven field; then the copy of the two counts.  Everything is
 // already checked.  ordered: the ascending mark that training needs.  Without io.rgb_c the coarse composite gives the weights alone.
+// clip (null: none): first the clip of every ray's range to the grid into `bounds`, which the sequence's samplers then read in
+// place of io's near_ / far_ / z_lin - a launch in front, no read-back.
+struct OccClip { int probes, pad; float* bounds; };
+
 static int occupancy_forward(const char* fn, const OccPass pass[2], bool ordered, const OccupancyGridArgs& grid, int64_t n, int nc,
-                             int nf, const RenderIO& io, int* evaluated, const RenderWorkspace::Regions& ws, hipStream_t hs) {
+                             int nf, RenderIO io, const OccClip* clip, int* evaluated, const RenderWorkspace::Regions& ws,
+                             hipStream_t hs) {
+    if (clip) {
+        if (int rc = launch_occupancy_clip_rays(grid, io.rays, n, io.near_, io.far_, clip->probes, clip->pad, clip->bounds, hs)) return rc;
+        io.bounds = clip->bounds;
+    }
     const auto field = [&](const OccPass& p) {
         return [&, p](const float* z, int samples, float* raw) -> int {
             const auto mark = ordered ? launch_occupancy_mark_rays_ordered : launch_occupancy_mark_rays;
@@ -171,11 +198,77 @@ static int occupancy_forward(const char* fn, const OccPass pass[2], bool ordered
     return MI_OK;
 }
 
+// What the clipped calls check on top of their unclipped selves: the clip's own arguments (a z_lin table has no meaning per
+// ray: they take none).  clip->bounds is set by the caller once the workspace is checked.
+static int check_clip(const char* fn, const OccClip* clip, float near_, float far_) {
+    return clip ? occupancy_clip_args(fn, near_, far_, clip->probes, clip->pad) : MI_OK;
+}
+
+// mi_render_rays_occupancy and, with clip, mi_render_rays_occupancy_clip
+static int render_inference(const char* fn, OccClip* clip, int kind_coarse, const float* packed_coarse, int kind_fine,
+                            const float* packed_fine, const float* rays, int64_t n, float near_, float far_, int n_coarse, int n_fine,
+                            const float* z_lin, const float* u_lin, const float* t_rand, uint64_t seed, uint64_t ray0,
+                            const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell, float* rgb_c, float* depth_c,
+                            float* acc_c, float* rgb_f, float* depth_f, float* acc_f, int* evaluated, void* workspace,
+                            int64_t workspace_bytes, void* stream) {
+    OccupancyGridArgs grid;
+    if (int rc = check_call(fn, "rendering", kind_coarse, kind_fine, n, n_coarse, n_fine, bits, dims, lo, inv_cell, &grid)) return rc;
+    if (int rc = check_clip(fn, clip, near_, far_)) return rc;
+    // the coarse outputs are optional, as in mi_render_rays: without rgb_c, depth_c / acc_c each may be null too
+    if (!packed_coarse || !packed_fine || !rays || !workspace || (rgb_c && (!depth_c || !acc_c)) || !rgb_f || !depth_f || !acc_f) {
+        set_error("%s: null pointer argument", fn);
+        return MI_EINVAL;
+    }
+    if (n == 0) return MI_OK;                                  // no rays: nothing to launch, no buffer is touched
+    if (int rc = check_buffers(fn, OCC_RENDER, kind_coarse, kind_fine, false, n, n_coarse, n_fine, workspace, workspace_bytes, nullptr, 0,
+                               nullptr, 0, clip != nullptr)) return rc;
+    const RenderWorkspace layout(n, n_coarse, n_fine);
+    const OccLists lists(false, n, n_coarse, n_fine);
+    const OccLists::Regions r = lists.carve(workspace, layout.base_bytes());
+    if (clip) clip->bounds = (float*)((char*)workspace + layout.base_bytes() + lists.bytes());
+    const OccPass pass[2] = {{kind_coarse, packed_coarse, r.list[0], r.counts, nullptr}, {kind_fine, packed_fine, r.list[1], r.counts + 1, nullptr}};
+    const RenderIO io{rays, near_, far_, z_lin, u_lin, t_rand, seed, ray0, rgb_c, depth_c, acc_c, rgb_f, depth_f, acc_f};
+    return occupancy_forward(fn, pass, false, grid, n, n_coarse, n_fine, io, clip, evaluated, layout.carve(workspace), (hipStream_t)stream);
+}
+
+// mi_render_rays_occupancy_train and, with clip, mi_render_rays_occupancy_clip_train
+static int render_training(const char* fn, OccClip* clip, int kind_coarse, const float* packed_coarse, int kind_fine,
+                           const float* packed_fine, const float* rays, int64_t n, float near_, float far_, int n_coarse, int n_fine,
+                           const float* z_lin, const float* u_lin, const float* t_rand, uint64_t seed, uint64_t ray0,
+                           const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell, float* rgb_c, float* depth_c,
+                           float* acc_c, float* rgb_f, float* depth_f, float* acc_f, int* evaluated, void* workspace,
+                           int64_t workspace_bytes, void* saved, int64_t saved_bytes, void* stream) {
+    OccupancyGridArgs grid;
+    if (int rc = check_call(fn, "training", kind_coarse, kind_fine, n, n_coarse, n_fine, bits, dims, lo, inv_cell, &grid)) return rc;
+    if (int rc = check_clip(fn, clip, near_, far_)) return rc;
+    if (!packed_coarse || !packed_fine || !rays || !rgb_c || !depth_c || !acc_c || !rgb_f || !depth_f || !acc_f) {
+        set_error("%s: null pointer argument", fn);
+        return MI_EINVAL;
+    }
+    if (n == 0) return MI_OK;
+    if (int rc = check_buffers(fn, OCC_TRAIN, kind_coarse, kind_fine, false, n, n_coarse, n_fine, workspace, workspace_bytes, saved,
+                               saved_bytes, nullptr, 0, clip != nullptr)) return rc;
+    // Training only: a step is one call, so one host query per step.  Inference renders a frame in many chunks and would pay
+    // the query per chunk; nobody has measured that, so mi_render_rays_occupancy leaves a grid on another device to the launch.
+    if (int rc = check_grid_device(fn, bits)) return rc;
+    const RenderWorkspace layout(n, n_coarse, n_fine);
+    const OccLists lists(true, n, n_coarse, n_fine);
+    const OccLists::Regions r = lists.carve(workspace, layout.base_bytes());
+    if (clip) clip->bounds = (float*)((char*)workspace + layout.base_bytes() + lists.bytes());
+    float* acts = (float*)saved;
+    const OccPass pass[2] = {{kind_coarse, packed_coarse, r.list[0], r.counts, acts},
+                             {kind_fine, packed_fine, r.list[1], r.counts + 1, acts + saved_floats_coarse(kind_coarse, n, n_coarse)}};
+    const RenderIO io{rays, near_, far_, z_lin, u_lin, t_rand, seed, ray0, rgb_c, depth_c, acc_c, rgb_f, depth_f, acc_f};
+    return occupancy_forward(fn, pass, true, grid, n, n_coarse, n_fine, io, clip, evaluated, layout.carve(workspace), (hipStream_t)stream);
+}
+
 }  // namespace mi
 
 using namespace mi;
 
 extern "C" {
+
+int64_t mi_render_occupancy_clip_extra_bytes(int64_t n) { return n <= 0 ? 0 : clip_bounds_bytes(n); }
 
 int64_t mi_render_occupancy_extra_bytes(int64_t n, int n_coarse, int n_fine) {
     if (n <= 0 || n_coarse < 1 || n_fine < 0) return 0;
@@ -204,21 +297,21 @@ int mi_render_rays_occupancy(int kind_coarse, const float* packed_coarse, int ki
                              const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell, float* rgb_c,
                              float* depth_c, float* acc_c, float* rgb_f, float* depth_f, float* acc_f, int* evaluated,
                              void* workspace, int64_t workspace_bytes, void* stream) {
-    const char* fn = "mi_render_rays_occupancy";
-    OccupancyGridArgs grid;
-    if (int rc = check_call(fn, "rendering", kind_coarse, kind_fine, n, n_coarse, n_fine, bits, dims, lo, inv_cell, &grid)) return rc;
-    // the coarse outputs are optional, as in mi_render_rays: without rgb_c, depth_c / acc_c each may be null too
-    if (!packed_coarse || !packed_fine || !rays || !workspace || (rgb_c && (!depth_c || !acc_c)) || !rgb_f || !depth_f || !acc_f) {
-        set_error("%s: null pointer argument", fn);
-        return MI_EINVAL;
-    }
-    if (n == 0) return MI_OK;                                  // no rays: nothing to launch, no buffer is touched
-    if (int rc = check_buffers(fn, OCC_RENDER, kind_coarse, kind_fine, false, n, n_coarse, n_fine, workspace, workspace_bytes)) return rc;
-    const RenderWorkspace layout(n, n_coarse, n_fine);
-    const OccLists::Regions r = OccLists(false, n, n_coarse, n_fine).carve(workspace, layout.base_bytes());
-    const OccPass pass[2] = {{kind_coarse, packed_coarse, r.list[0], r.counts, nullptr}, {kind_fine, packed_fine, r.list[1], r.counts + 1, nullptr}};
-    const RenderIO io{rays, near_, far_, z_lin, u_lin, t_rand, seed, ray0, rgb_c, depth_c, acc_c, rgb_f, depth_f, acc_f};
-    return occupancy_forward(fn, pass, false, grid, n, n_coarse, n_fine, io, evaluated, layout.carve(workspace), (hipStream_t)stream);
+    return render_inference("mi_render_rays_occupancy", nullptr, kind_coarse, packed_coarse, kind_fine, packed_fine, rays, n, near_, far_,
+                            n_coarse, n_fine, z_lin, u_lin, t_rand, seed, ray0, bits, dims, lo, inv_cell, rgb_c, depth_c, acc_c, rgb_f,
+                            depth_f, acc_f, evaluated, workspace, workspace_bytes, stream);
+}
+
+int mi_render_rays_occupancy_clip(int kind_coarse, const float* packed_coarse, int kind_fine, const float* packed_fine,
+                                  const float* rays, int64_t n, float near_, float far_, int n_coarse, int n_fine, int probes,
+                                  int pad, const float* u_lin, const float* t_rand, uint64_t seed, uint64_t ray0,
+                                  const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell, float* rgb_c,
+                                  float* depth_c, float* acc_c, float* rgb_f, float* depth_f, float* acc_f, int* evaluated,
+                                  void* workspace, int64_t workspace_bytes, void* stream) {
+    OccClip clip{probes, pad, nullptr};
+    return render_inference("mi_render_rays_occupancy_clip", &clip, kind_coarse, packed_coarse, kind_fine, packed_fine, rays, n, near_,
+                            far_, n_coarse, n_fine, nullptr, u_lin, t_rand, seed, ray0, bits, dims, lo, inv_cell, rgb_c, depth_c, acc_c,
+                            rgb_f, depth_f, acc_f, evaluated, workspace, workspace_bytes, stream);
 }
 
 int mi_render_rays_occupancy_train(int kind_coarse, const float* packed_coarse, int kind_fine, const float* packed_fine,
@@ -227,26 +320,21 @@ int mi_render_rays_occupancy_train(int kind_coarse, const float* packed_coarse, 
                                    const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell, float* rgb_c,
                                    float* depth_c, float* acc_c, float* rgb_f, float* depth_f, float* acc_f, int* evaluated,
                                    void* workspace, int64_t workspace_bytes, void* saved, int64_t saved_bytes, void* stream) {
-    const char* fn = "mi_render_rays_occupancy_train";
-    OccupancyGridArgs grid;
-    if (int rc = check_call(fn, "training", kind_coarse, kind_fine, n, n_coarse, n_fine, bits, dims, lo, inv_cell, &grid)) return rc;
-    if (!packed_coarse || !packed_fine || !rays || !rgb_c || !depth_c || !acc_c || !rgb_f || !depth_f || !acc_f) {
-        set_error("%s: null pointer argument", fn);
-        return MI_EINVAL;
-    }
-    if (n == 0) return MI_OK;
-    if (int rc = check_buffers(fn, OCC_TRAIN, kind_coarse, kind_fine, false, n, n_coarse, n_fine, workspace, workspace_bytes, saved,
-                               saved_bytes)) return rc;
-    // Training only: a step is one call, so one host query per step.  Inference renders a frame in many chunks and would pay
-    // the query per chunk; nobody has measured that, so mi_render_rays_occupancy leaves a grid on another device to the launch.
-    if (int rc = check_grid_device(fn, bits)) return rc;
-    const RenderWorkspace layout(n, n_coarse, n_fine);
-    const OccLists::Regions r = OccLists(true, n, n_coarse, n_fine).carve(workspace, layout.base_bytes());
-    float* acts = (float*)saved;
-    const OccPass pass[2] = {{kind_coarse, packed_coarse, r.list[0], r.counts, acts},
-                             {kind_fine, packed_fine, r.list[1], r.counts + 1, acts + saved_floats_coarse(kind_coarse, n, n_coarse)}};
-    const RenderIO io{rays, near_, far_, z_lin, u_lin, t_rand, seed, ray0, rgb_c, depth_c, acc_c, rgb_f, depth_f, acc_f};
-    return occupancy_forward(fn, pass, true, grid, n, n_coarse, n_fine, io, evaluated, layout.carve(workspace), (hipStream_t)stream);
+    return render_training("mi_render_rays_occupancy_train", nullptr, kind_coarse, packed_coarse, kind_fine, packed_fine, rays, n, near_,
+                           far_, n_coarse, n_fine, z_lin, u_lin, t_rand, seed, ray0, bits, dims, lo, inv_cell, rgb_c, depth_c, acc_c,
+                           rgb_f, depth_f, acc_f, evaluated, workspace, workspace_bytes, saved, saved_bytes, stream);
+}
+
+int mi_render_rays_occupancy_clip_train(int kind_coarse, const float* packed_coarse, int kind_fine, const float* packed_fine,
+                                        const float* rays, int64_t n, float near_, float far_, int n_coarse, int n_fine, int probes,
+                                        int pad, const float* u_lin, const float* t_rand, uint64_t seed, uint64_t ray0,
+                                        const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell, float* rgb_c,
+                                        float* depth_c, float* acc_c, float* rgb_f, float* depth_f, float* acc_f, int* evaluated,
+                                        void* workspace, int64_t workspace_bytes, void* saved, int64_t saved_bytes, void* stream) {
+    OccClip clip{probes, pad, nullptr};
+    return render_training("mi_render_rays_occupancy_clip_train", &clip, kind_coarse, packed_coarse, kind_fine, packed_fine, rays, n,
+                           near_, far_, n_coarse, n_fine, nullptr, u_lin, t_rand, seed, ray0, bits, dims, lo, inv_cell, rgb_c, depth_c,
+                           acc_c, rgb_f, depth_f, acc_f, evaluated, workspace, workspace_bytes, saved, saved_bytes, stream);
 }
 
 int mi_render_rays_occupancy_backward(int kind_coarse, const float* packed_bwd_coarse, int kind_fine,

@@ -115,6 +115,8 @@ struct RenderIO {
     const float *z_lin, *u_lin, *t_rand;
     uint64_t seed, ray0;
     float *rgb_c, *depth_c, *acc_c, *rgb_f, *depth_f, *acc_f;     // the coarse three may be null
+    // optional [n,2]: a sampling range per ray (mi_occupancy_clip_rays); both samplers then run over it, without near_ / far_ / z_lin
+    const float* bounds = nullptr;
 };
 
 // one field with Nf = 0: the fine outputs and the coarse outputs are one composite's; copies it to every non-null dst
@@ -131,7 +133,13 @@ int run_render_passes(const char* fn, const RenderCall& C, FinePlan plan, const 
     const int64_t n = C.n;
     const int nc = C.Nc, nf = C.Nf, S = nc + nf;
     int rc;
-    if ((rc = launch_sample_coarse(n, io.near_, io.far_, nc, io.z_lin, io.t_rand, io.seed, io.ray0, ws.z_c, hs))) return rc;
+    // the one branch on io.bounds: which pair of samplers the sequence runs
+    const auto sample_fine = [&](float* z_s, int* pos) {
+        return io.bounds ? launch_sample_fine_bounds(n, io.bounds, nc, nf, io.u_lin, ws.z_c, ws.w_c, z_s, ws.z_f, pos, hs)
+                         : launch_sample_fine(n, io.near_, io.far_, nc, nf, io.z_lin, io.u_lin, ws.z_c, ws.w_c, z_s, ws.z_f, pos, hs);
+    };
+    if ((rc = io.bounds ? launch_sample_coarse_bounds(n, io.bounds, nc, io.t_rand, io.seed, io.ray0, ws.z_c, hs)
+                        : launch_sample_coarse(n, io.near_, io.far_, nc, io.z_lin, io.t_rand, io.seed, io.ray0, ws.z_c, hs))) return rc;
     if ((rc = coarse_field(ws.z_c, nc, ws.raw_c))) return rc;
     if (plan == FINE_IS_COARSE) {
         if ((rc = launch_composite(n, nc, ws.raw_c, ws.z_c, io.rays, io.rgb_f, io.depth_f, io.acc_f, ws.w_c, hs))) return rc;
@@ -142,11 +150,11 @@ int run_render_passes(const char* fn, const RenderCall& C, FinePlan plan, const 
     else if (left == COARSE_SIGMA) rc = launch_composite_weights(n, nc, ws.raw_c, 1, ws.z_c, io.rays, io.depth_c, io.acc_c, ws.w_c, hs);
     if (rc) return rc;
     if (plan == FINE_NEW_SAMPLES) {
-        if ((rc = launch_sample_fine(n, io.near_, io.far_, nc, nf, io.z_lin, io.u_lin, ws.z_c, ws.w_c, ws.z_s, ws.z_f, ws.pos, hs))) return rc;
+        if ((rc = sample_fine(ws.z_s, ws.pos))) return rc;
         if ((rc = fine_field(ws.z_s, nf, ws.raw_s))) return rc;
         if ((rc = launch_merge_raw(n, nc, nf, ws.raw_c, ws.raw_s, ws.pos, ws.raw_f, hs))) return rc;
     } else {
-        if ((rc = launch_sample_fine(n, io.near_, io.far_, nc, nf, io.z_lin, io.u_lin, ws.z_c, ws.w_c, nullptr, ws.z_f, nullptr, hs))) return rc;
+        if ((rc = sample_fine(nullptr, nullptr))) return rc;
         if ((rc = fine_field(ws.z_f, S, ws.raw_f))) return rc;
     }
     return launch_composite(n, S, ws.raw_f, ws.z_f, io.rays, io.rgb_f, io.depth_f, io.acc_f, nullptr, hs);
@@ -169,6 +177,8 @@ inline int eval_field_rays(int kind, const float* packed, const float* film, con
 int64_t occupancy_cells(const char* fn, const int* dims);
 int occupancy_grid_args(const char* fn, const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell,
                         OccupancyGridArgs* grid);
+// ... and the one place the arguments of a clip are: near_ < far_ (a NaN is refused), 1 <= probes <= 4096, pad >= 0
+int occupancy_clip_args(const char* fn, float near_, float far_, int probes, int pad);
 int eval_rays_list(int kind, const float* packed, const float* rays, const float* z, int64_t n, int S, const int* list,
                    const int* count, float* raw, float* acts, hipStream_t stream);
 

@@ -8,6 +8,7 @@
 //   composite_bwd_kernel  autograd of raw_to_outputs
 //   sample_fine_kernel    sample_pdf + detach/cat/sort   nerf/render.py:27-56, 140-142
 //   sample_pdf_kernel     sample_pdf alone
+//   sample_coarse_bounds_kernel / sample_fine_kernel<true>   the two samplers over a range per ray (clipping to an occupancy grid)
 //
 // Each computation is stated once: every compositing kernel takes its weights and transmittances from composite_pass
 // (with sample_delta and ray_norm) under the G that dispatch_G picks, and both sampling kernels draw through
@@ -64,20 +65,35 @@ __device__ __forceinline__ float linspace_at(float start, float end, int steps, 
     return i < steps / 2 ? start + step * (float)i : end - step * (float)(steps - i - 1);
 }
 
-// the jitter word of sample k of a ray: philox_u32(seed, ray, k) of mi_philox.h
-__global__ void sample_coarse_kernel(int64_t n, float near_, float far_, int nc, const float* __restrict__ z_lin,
-                                     const float* __restrict__ t_rand, uint64_t seed, uint64_t ray0,
-                                     float* __restrict__ z) {
+// The stratified depth of one (ray, sample); the jitter word of sample k of a ray: philox_u32(seed, ray, k) of mi_philox.h.
+// kBounds: the linspace runs over the ray's own range bounds[ray] = (near_r, far_r) (mi_occupancy_clip_rays) instead of the
+// call's one [near_, far_]; a z_lin table has no meaning per ray and is not read.  Nothing else differs.
+template <bool kBounds>
+__device__ __forceinline__ void sample_coarse_point(int64_t n, float near_, float far_, const float* __restrict__ bounds, int nc,
+                                                    const float* __restrict__ z_lin, const float* __restrict__ t_rand,
+                                                    uint64_t seed, uint64_t ray0, float* __restrict__ z) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n * nc) return;
     const int k = (int)(t % nc);
     const int64_t ray = t / nc;
-    auto lin = [&](int i) { return z_lin ? z_lin[i] : linspace_at(near_, far_, nc, i); };
+    if constexpr (kBounds) { near_ = bounds[ray * 2]; far_ = bounds[ray * 2 + 1]; }
+    auto lin = [&](int i) { return !kBounds && z_lin ? z_lin[i] : linspace_at(near_, far_, nc, i); };
     const float zk = lin(k);
     const float lower = k == 0 ? zk : 0.5f * (zk + lin(k - 1));
     const float upper = k == nc - 1 ? zk : 0.5f * (lin(k + 1) + zk);
     const float u = t_rand ? t_rand[t] : (float)(philox_u32(seed, ray0 + (uint64_t)ray, (uint32_t)k) >> 8) * 0x1p-24f;
     z[t] = lower + (upper - lower) * u;
+}
+
+__global__ void sample_coarse_kernel(int64_t n, float near_, float far_, int nc, const float* __restrict__ z_lin,
+                                     const float* __restrict__ t_rand, uint64_t seed, uint64_t ray0,
+                                     float* __restrict__ z) {
+    sample_coarse_point<false>(n, near_, far_, nullptr, nc, z_lin, t_rand, seed, ray0, z);
+}
+
+__global__ void sample_coarse_bounds_kernel(int64_t n, const float* __restrict__ bounds, int nc, const float* __restrict__ t_rand,
+                                            uint64_t seed, uint64_t ray0, float* __restrict__ z) {
+    sample_coarse_point<true>(n, 0.f, 0.f, bounds, nc, nullptr, t_rand, seed, ray0, z);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -517,7 +533,13 @@ __device__ __forceinline__ float draw_inverse_cdf(const float* cdf, const float*
 // torch.cumsum on CPU; u = linspace(0,1,Nf), each drawn by draw_inverse_cdf;
 // then z_fine = sort(cat(z_coarse, z_samples)) by full rank counting (no sortedness assumed; -0 ranks before +0).
 // LDS per wave: cdf[Nc] | bins[Nc] | zall[Nc+Nf] | zout[Nc+Nf] (the sorted row, stored coalesced)
+// kBounds (sample_fine_bounds_kernel below): the coarse linspace runs over the ray's own range (near_r, far_r)
+// (mi_occupancy_clip_rays), so the bins are formed per ray, not once per wave in front of the ray loop.  A z_lin table has no
+// meaning per ray, and its parameter carries the bounds [n,2] instead; near_ / far_ arrive unused.  The bins of a ray are
+// written behind the closing barrier of the ray before it and first read behind two more.  The flag is on the kernel itself,
+// not on a device function under two kernels: inlined into a wrapper, the plain instance came out scheduled differently.
 // ---------------------------------------------------------------------------------------
+template <bool kBounds>
 __global__ __launch_bounds__(256) void sample_fine_kernel(int64_t n, float near_, float far_, int nc, int nf,
                                                           const float* __restrict__ z_lin,
                                                           const float* __restrict__ u_lin,
@@ -535,12 +557,17 @@ __global__ __launch_bounds__(256) void sample_fine_kernel(int64_t n, float near_
     float* zout = zall + S;
     const int nb = nc - 1;      // bins / cdf entries
     const int nw = nc - 2;      // interior weights
-    auto lin = [&](int i) { return z_lin ? z_lin[i] : linspace_at(near_, far_, nc, i); };
-    for (int j = lane; j < nb; j += 64) bins[j] = 0.5f * (lin(j + 1) + lin(j));
+    auto lin = [&](int i) { return !kBounds && z_lin ? z_lin[i] : linspace_at(near_, far_, nc, i); };
+    if constexpr (!kBounds)
+        for (int j = lane; j < nb; j += 64) bins[j] = 0.5f * (lin(j + 1) + lin(j));
 
     for (int64_t ray = (int64_t)blockIdx.x * 4 + wave; ray < n; ray += (int64_t)gridDim.x * 4) {
         const float* wr = weights + ray * nc;
         const float* zc = z_coarse + ray * nc;
+        if constexpr (kBounds) {
+            near_ = z_lin[ray * 2]; far_ = z_lin[ray * 2 + 1];             // the bounds table
+            for (int j = lane; j < nb; j += 64) bins[j] = 0.5f * (lin(j + 1) + lin(j));
+        }
         // pdf of the interior weights into zall (scratch), then per-entry sequential prefix = torch.cumsum order
         normalise_pdf(wr + 1, nw, lane, zall);
         __builtin_amdgcn_wave_barrier();
@@ -607,6 +634,7 @@ __global__ __launch_bounds__(256) void sample_fine_kernel(int64_t n, float near_
     }
 }
 
+
 // ---------------------------------------------------------------------------------------
 // sample_pdf as a free-standing function (render.py:27-56) on arbitrary per-ray bins: one wave per ray,
 // sample_fine_kernel's draw without the merge.  bins [n,nb], weights [n,nb-1] -> out [n,ns].
@@ -659,6 +687,15 @@ int launch_sample_coarse(int64_t n, float near_, float far_, int nc, const float
     hipLaunchKernelGGL(sample_coarse_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, n, near_,
                        far_, nc, z_lin, t_rand, seed, ray0, z);
     return check_launch("sample_coarse");
+}
+
+int launch_sample_coarse_bounds(int64_t n, const float* bounds, int nc, const float* t_rand, uint64_t seed, uint64_t ray0,
+                                float* z, hipStream_t stream) {
+    if (n <= 0) return 0;
+    const int64_t total = n * nc;
+    hipLaunchKernelGGL(sample_coarse_bounds_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, n, bounds, nc,
+                       t_rand, seed, ray0, z);
+    return check_launch("sample_coarse_bounds");
 }
 
 // The lanes per ray of every compositing kernel for rows of S samples, as a compile-time constant: f(integral_constant<G>).
@@ -807,17 +844,32 @@ int launch_split_grad(int64_t n, int nc, int nf, const float* g_f, const int* po
     return check_launch("split_grad");
 }
 
+// one launch of either instance of sample_fine_kernel: lin = the z_lin table (or null), with kBounds the bounds [n,2]
+template <bool kBounds>
+static int launch_sample_fine_as(const char* what, int64_t n, float near_, float far_, int nc, int nf, const float* lin,
+                                 const float* u_lin, const float* z_coarse, const float* weights, float* z_samples,
+                                 float* z_fine, int* pos, hipStream_t stream) {
+    if (n <= 0) return 0;
+    const size_t lds = (size_t)4 * (2 * nc + 2 * (nc + nf)) * sizeof(float);
+    if (lds > 64 * 1024) { set_error("%s: Nc=%d Nf=%d exceed LDS", what, nc, nf); return -1; }
+    int64_t blocks = (n + 3) / 4;
+    if (blocks > 256 * 16) blocks = 256 * 16;
+    hipLaunchKernelGGL(sample_fine_kernel<kBounds>, dim3((unsigned)blocks), dim3(256), lds, stream, n, near_, far_, nc, nf,
+                       lin, u_lin, z_coarse, weights, z_samples, z_fine, pos);
+    return check_launch(what);
+}
+
 int launch_sample_fine(int64_t n, float near_, float far_, int nc, int nf, const float* z_lin, const float* u_lin,
                        const float* z_coarse, const float* weights, float* z_samples, float* z_fine, int* pos,
                        hipStream_t stream) {
-    if (n <= 0) return 0;
-    const size_t lds = (size_t)4 * (2 * nc + 2 * (nc + nf)) * sizeof(float);
-    if (lds > 64 * 1024) { set_error("sample_fine: Nc=%d Nf=%d exceed LDS", nc, nf); return -1; }
-    int64_t blocks = (n + 3) / 4;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    hipLaunchKernelGGL(sample_fine_kernel, dim3((unsigned)blocks), dim3(256), lds, stream, n, near_, far_, nc, nf,
-                       z_lin, u_lin, z_coarse, weights, z_samples, z_fine, pos);
-    return check_launch("sample_fine");
+    return launch_sample_fine_as<false>("sample_fine", n, near_, far_, nc, nf, z_lin, u_lin, z_coarse, weights, z_samples,
+                                        z_fine, pos, stream);
+}
+
+int launch_sample_fine_bounds(int64_t n, const float* bounds, int nc, int nf, const float* u_lin, const float* z_coarse,
+                              const float* weights, float* z_samples, float* z_fine, int* pos, hipStream_t stream) {
+    return launch_sample_fine_as<true>("sample_fine_bounds", n, 0.f, 0.f, nc, nf, bounds, u_lin, z_coarse, weights, z_samples,
+                                       z_fine, pos, stream);
 }
 
 }  // namespace mi

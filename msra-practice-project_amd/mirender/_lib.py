@@ -126,6 +126,18 @@ SIGNATURES = {
     "mi_render_rays_occupancy_backward": (_int, [_int, _vp, _int, _vp, _int, _vp, _i64, _int, _int, _vp, _i64, _vp, _i64,
                                                  _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
                                                  _vp, _i64, ctypes.POINTER(_int), _vp]),
+    "mi_occupancy_clip_rays": (_int, [_vp, ctypes.POINTER(_int), ctypes.POINTER(_f32), ctypes.POINTER(_f32), _vp, _i64, _f32, _f32,
+                                      _int, _int, _vp, _vp]),
+    "mi_sample_coarse_bounds": (_int, [_i64, _vp, _int, _vp, _u64, _u64, _vp, _vp]),
+    "mi_sample_fine_bounds": (_int, [_i64, _vp, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mi_render_occupancy_clip_extra_bytes": (_i64, [_i64]),
+    "mi_render_rays_occupancy_clip": (_int, [_int, _vp, _int, _vp, _vp, _i64, _f32, _f32, _int, _int, _int, _int, _vp, _vp, _u64,
+                                             _u64, _vp, ctypes.POINTER(_int), ctypes.POINTER(_f32), ctypes.POINTER(_f32), _vp, _vp,
+                                             _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "mi_render_rays_occupancy_clip_train": (_int, [_int, _vp, _int, _vp, _vp, _i64, _f32, _f32, _int, _int, _int, _int, _vp, _vp,
+                                                   _u64, _u64, _vp, ctypes.POINTER(_int), ctypes.POINTER(_f32),
+                                                   ctypes.POINTER(_f32), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64,
+                                                   _vp]),
 }
 
 ABI_VERSION = 4      # include/mi_render.h as of this binding (mi_abi_version() of the library must equal it)

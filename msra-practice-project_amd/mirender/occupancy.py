@@ -10,7 +10,9 @@ For the kinds without FiLM (NeRF, SirenNeRF, TinyNeRF).  This module builds and 
 keyword `grid=` of render_rays / render_image / render_image_tensor / render_video (inference only): a sample whose point
 o + d * z lies in an unoccupied cell, or outside [lo, hi), counts as raw = 0 and is not evaluated (ops.render_rays_occupancy,
 mi_render_rays_occupancy).  A grid that misses cells where the field has density therefore changes the picture: build it with
-a threshold, supersampling and dilation that suit the field.  Training with a grid is the opt-in module
+a threshold, supersampling and dilation that suit the field.  With `clip_probes=` next to `grid=` the grid also places the
+samples: each ray's range is clipped to its first and last occupied probe and both passes sample inside it
+(ops.occupancy_clip_rays, mi_render_rays_occupancy_clip).  Training with a grid is the opt-in module
 mirender.occupancy_train (render_rays(..., grid=) with a graph to the fields' parameters).  LiveOccupancyGrid keeps a grid current
 while its field trains: a per-cell density on the device, updated a part at a time and re-thresholded into the bits in place.
 """

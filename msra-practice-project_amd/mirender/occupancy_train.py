@@ -37,7 +37,7 @@ class _OccupancyRenderFn(torch.autograd.Function):
     compact saved rows; backward hands the six cotangents to mi_render_rays_occupancy_backward."""
 
     @staticmethod
-    def forward(ctx, pf_c, pf_f, rays, near, far, nc, nf, grid, t_rand, seed, ray0, *params):
+    def forward(ctx, pf_c, pf_f, rays, near, far, nc, nf, grid, t_rand, seed, ray0, clip, *params):
         dev = pf_c.device
         n = rays.shape[0]
         shared = pf_c is pf_f
@@ -46,14 +46,16 @@ class _OccupancyRenderFn(torch.autograd.Function):
         zl, ul = ops._lin_tables(near, far, nc, nf, dev)
         ws_bytes = (_lib.query("mi_render_workspace_bytes", n, nc, nf)
                     + _lib.query("mi_render_occupancy_train_extra_bytes", n, nc, nf))
+        if clip is not None:                            # (probes, pad): the bounds lie behind what the backward reads
+            ws_bytes += _lib.query("mi_render_occupancy_clip_extra_bytes", n)
         sv_bytes = _lib.query("mi_render_occupancy_train_saved_bytes", pf_c.kind, pf_f.kind, n, nc, nf)
         # owned by this call (not the shared inference workspace): the backward reads both
         ws, ctx.ws_g = _lib.guarded(ws_bytes, torch.uint8, dev)
         saved, ctx.saved_g = _lib.guarded(sv_bytes, torch.uint8, dev)
-        _lib.call("mi_render_rays_occupancy_train", dev, pf_c.kind, _lib.ptr(pf_c.refresh()), pf_f.kind,
-                  _lib.ptr(pf_f.refresh()), _lib.ptr(rays), n, float(near), float(far), nc, nf, _lib.ptr(zl), _lib.ptr(ul),
-                  _lib.ptr(t_rand), _lib.seed64(seed), int(ray0), _lib.ptr(grid.bits), *grid.c_args(),
-                  *[_lib.ptr(o) for o in outs], _lib.ptr(counts), _lib.ptr(ws), ws_bytes, _lib.ptr(saved), sv_bytes)
+        _lib.call("mi_render_rays_occupancy_train" if clip is None else "mi_render_rays_occupancy_clip_train", dev, pf_c.kind,
+                  _lib.ptr(pf_c.refresh()), pf_f.kind, _lib.ptr(pf_f.refresh()), _lib.ptr(rays), n, float(near), float(far), nc,
+                  nf, *((_lib.ptr(zl),) if clip is None else clip), _lib.ptr(ul), _lib.ptr(t_rand), _lib.seed64(seed), int(ray0),
+                  _lib.ptr(grid.bits), *grid.c_args(), *[_lib.ptr(o) for o in outs], _lib.ptr(counts), _lib.ptr(ws), ws_bytes, _lib.ptr(saved), sv_bytes)
         _check_kept(ctx)
         ctx.pf_c, ctx.pf_f, ctx.shared, ctx.n, ctx.nc, ctx.nf = pf_c, pf_f, shared, n, nc, nf
         ctx.rays, ctx.ws, ctx.saved, ctx.counts = rays, ws, saved, counts
@@ -83,7 +85,7 @@ class _OccupancyRenderFn(torch.autograd.Function):
         _lib.check_guard(bws_g, "occupancy backward workspace (mi_render_occupancy_backward_workspace_bytes)")
         gc = tuple(grads_c) if written.value & 1 else (None,) * len(grads_c)
         gf = () if ctx.shared else (tuple(grads_f) if written.value & 2 else (None,) * len(grads_f))
-        return (None,) * 11 + gc + gf
+        return (None,) * 12 + gc + gf
 
 
 def _check(grid, coarse_model, fine_model, pf_c, pf_f, rays):
@@ -104,7 +106,7 @@ def _check(grid, coarse_model, fine_model, pf_c, pf_f, rays):
 
 
 def render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, fine_sample_num, *, grid, t_rand=None,
-                seed=None, ray0=0, max_points=None, return_counts=False):
+                seed=None, ray0=0, max_points=None, return_counts=False, clip_probes=None, clip_pad=1):
     """render_core.render_rays(..., grid=) with a graph to the two fields' parameters: (rgb_c, depth_c, acc_c, rgb_f, depth_f,
     acc_f); with return_counts=True (not part of render_core's signature: the example and the benchmark report it) also an
     int32 device tensor [calls, 2] of the samples each pass evaluated, under no_grad too.
@@ -112,6 +114,8 @@ def render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, fi
     max_points: the rays are cut into consecutive calls of at most max_points // (2 Nc + Nf) rays (the samples a call
     evaluates at worst; its saved rows and workspaces are sized for them) and autograd sums the calls' gradients.  `ray0`
     keeps the seeded jitter keyed by the absolute ray index, so the cut does not change a sample.
+    clip_probes (None: off), clip_pad: render_core.render_rays' keywords - each ray's range is first clipped to the grid and
+    both passes sample inside it (mi_render_rays_occupancy_clip_train); the backward is the same call, it reads the depths.
     Under torch.no_grad() (or with no parameter that requires a gradient) this is render_core.render_rays(grid=).
     A cell that is empty in `grid` gets no gradient and cannot fill up until the caller rebuilds the grid.
     Not built: FiLM kinds, generic callables, gradients to the rays (mirender.pose), render_image_dist."""
@@ -122,13 +126,15 @@ def render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, fi
     if not fields.needs_graph(None, pf_c, pf_f):
         with torch.no_grad():                       # one call, so counts is [1, 2] ([0, 2] without rays)
             return render_core._render_rays(rays, near, far, coarse_model, fine_model, nc, nf, t_rand=t_rand, seed=seed,
-                                            ray0=ray0, grid=grid, return_counts=return_counts)
+                                            ray0=ray0, grid=grid, return_counts=return_counts, clip_probes=clip_probes,
+                                            clip_pad=clip_pad)
     rays = ops._f32c(torch.as_tensor(rays), dev).reshape(-1, 2, 3)
     n = rays.shape[0]
     if seed is None and t_rand is None:
         seed = render_core._fresh_seed()
     t_rand = ops._t_rand(t_rand, n, nc, dev)
     params = fields.pair_params(pf_c, pf_f)
+    clip = None if clip_probes is None else (int(clip_probes), int(clip_pad))
     step = n if not max_points else max(1, int(max_points) // (2 * nc + nf))
     if n == 0:                                      # no rays: render_core's empty outputs, hanging off the parameters
         outs = render_core.render_rays(rays, near, far, coarse_model, fine_model, nc, nf, t_rand=t_rand, seed=seed, ray0=ray0)
@@ -138,7 +144,7 @@ def render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, fi
         r1 = min(n, r0 + step)
         res = _OccupancyRenderFn.apply(pf_c, pf_f, rays[r0:r1].contiguous(), float(near), float(far), nc, nf, grid,
                                        None if t_rand is None else t_rand[r0:r1].contiguous(), int(seed or 0),
-                                       int(ray0) + r0, *params)
+                                       int(ray0) + r0, clip, *params)
         pieces.append(res[:6])
         counts.append(res[6])
     outs = pieces[0] if len(pieces) == 1 else tuple(torch.cat([p[k] for p in pieces]) for k in range(6))

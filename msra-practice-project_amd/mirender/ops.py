@@ -127,6 +127,49 @@ def sample_fine_pos(z_coarse: torch.Tensor, weights: torch.Tensor, near: float, 
     return z_fine, zs, pos
 
 
+def occupancy_clip_rays(grid, rays: torch.Tensor, near: float, far: float, probes: int, pad: int = 1) -> torch.Tensor:
+    """Each ray's sampling range clipped to `grid` (mi_occupancy_clip_rays): bounds [n,2] = (near_r, far_r).  `probes` probes at
+    the midpoints of equal bins of [near, far] are tested like samples of a pass; the range runs from `pad` bins in front of the
+    first occupied probe to `pad` bins behind the last one, clamped to [near, far]; a ray without an occupied probe keeps
+    (near, far).  A structure thinner than (far - near) / probes between two probes can be missed: a step of at most half a
+    cell along the ray is a sound default, probes >= 2 (far - near) |d| max(inv_cell)."""
+    dev = grid.device
+    rays = _f32c(rays, dev).reshape(-1, 2, 3)
+    n = rays.shape[0]
+    bounds = torch.empty((n, 2), dtype=torch.float32, device=dev)
+    _lib.call("mi_occupancy_clip_rays", dev, _p(grid.bits), *grid.c_args(), _p(rays), n, float(near), float(far), int(probes),
+              int(pad), _p(bounds))
+    return bounds
+
+
+def sample_coarse_bounds(bounds: torch.Tensor, n_coarse: int, t_rand=None, seed: int = 0, ray0: int = 0) -> torch.Tensor:
+    """sample_coarse over a range per ray, bounds [n,2] (mi_sample_coarse_bounds): the same arithmetic, the linspace of ray r
+    evaluated in the kernel from bounds[r]."""
+    dev = bounds.device
+    bounds = _f32c(bounds, dev)
+    n = bounds.shape[0]
+    z = torch.empty((n, n_coarse), dtype=torch.float32, device=dev)
+    t_rand = _t_rand(t_rand, n, n_coarse, dev)
+    _lib.call("mi_sample_coarse_bounds", dev, n, _p(bounds), int(n_coarse), _p(t_rand), _lib.seed64(seed), int(ray0), _p(z))
+    return z
+
+
+def sample_fine_bounds(bounds: torch.Tensor, z_coarse: torch.Tensor, weights: torch.Tensor, n_fine: int, want_pos: bool = True,
+                       exact_linspace: bool = True):
+    """sample_fine_pos over a range per ray, bounds [n,2] (mi_sample_fine_bounds): (z_fine, z_samples, pos); with
+    want_pos=False the two optional outputs are not written and z_fine alone comes back."""
+    dev = z_coarse.device
+    n, nc = z_coarse.shape
+    bounds, z_coarse, weights = _f32c(bounds, dev), _f32c(z_coarse, dev), _f32c(weights, dev)
+    z_fine = torch.empty((n, nc + n_fine), dtype=torch.float32, device=dev)
+    zs = torch.empty((n, n_fine), dtype=torch.float32, device=dev) if want_pos else None
+    pos = torch.empty((n, nc + n_fine), dtype=torch.int32, device=dev) if want_pos else None
+    ul = linspace_table(0.0, 1.0, n_fine, dev) if exact_linspace else None
+    _lib.call("mi_sample_fine_bounds", dev, n, _p(bounds), nc, int(n_fine), _p(ul), _p(z_coarse), _p(weights), _p(zs), _p(z_fine),
+              _p(pos))
+    return (z_fine, zs, pos) if want_pos else z_fine
+
+
 def merge_raw(raw_c: torch.Tensor, raw_s: torch.Tensor, pos: torch.Tensor) -> torch.Tensor:
     """raw_fine [n,Nc+Nf,4] in sorted order from the coarse pass's raw [n,Nc,4] and the field at z_samples [n,Nf,4]."""
     dev = raw_c.device
@@ -250,11 +293,14 @@ def render_rays_fused(pf_c: PackedField, pf_f: PackedField, rays: torch.Tensor, 
 
 def render_rays_occupancy(pf_c: PackedField, pf_f: PackedField, rays: torch.Tensor, near: float, far: float,
                           n_coarse: int, n_fine: int, grid, t_rand=None, seed: int = 0, ray0: int = 0,
-                          coarse_outputs: bool = True):
+                          coarse_outputs: bool = True, clip_probes=None, clip_pad: int = 1):
     """render_rays with an occupancy grid (mi_render_rays_occupancy): a sample whose point lies in an unoccupied cell of
     `grid` (mirender.occupancy.OccupancyGrid), or outside its box, counts as raw = 0 and is not evaluated; everything else is
     render_rays_fused.  Returns (the 6-tuple, counts): counts is a device int32 [2], the samples the coarse and the fine pass
-    evaluated.  coarse_outputs=False: the coarse slots come back as None."""
+    evaluated.  coarse_outputs=False: the coarse slots come back as None.
+    clip_probes (None: today's call): every ray's sampling range is first clipped to the grid with that many probes and
+    `clip_pad` bins of margin (occupancy_clip_rays), and both samplers place their depths inside it
+    (mi_render_rays_occupancy_clip)."""
     dev = pf_c.device
     if is_film(pf_c.kind) or is_film(pf_f.kind):
         raise _lib.MiRenderError("rendering with an occupancy grid is not built for FiLM fields")
@@ -266,9 +312,22 @@ def render_rays_occupancy(pf_c: PackedField, pf_f: PackedField, rays: torch.Tens
     zl, ul = _lin_tables(near, far, n_coarse, n_fine, dev)
     ws_bytes = (_lib.query("mi_render_workspace_bytes", n, n_coarse, n_fine)
                 + _lib.query("mi_render_occupancy_extra_bytes", n, n_coarse, n_fine))
+    clip = clip_probes is not None
+    if clip:
+        ws_bytes += _lib.query("mi_render_occupancy_clip_extra_bytes", n)
     ws, ws_g = _workspace(dev, ws_bytes)
-    _lib.call("mi_render_rays_occupancy", dev, pf_c.kind, _p(pf_c.refresh()), pf_f.kind, _p(pf_f.refresh()), _p(rays), n,
-              float(near), float(far), n_coarse, n_fine, _p(zl), _p(ul), _p(t_rand), _lib.seed64(seed), int(ray0),
+    _lib.call("mi_render_rays_occupancy_clip" if clip else "mi_render_rays_occupancy", dev, pf_c.kind, _p(pf_c.refresh()),
+              pf_f.kind, _p(pf_f.refresh()), _p(rays), n, float(near), float(far), n_coarse, n_fine,
+              *((int(clip_probes), int(clip_pad)) if clip else (_p(zl),)), _p(ul), _p(t_rand), _lib.seed64(seed), int(ray0),
               _p(grid.bits), *grid.c_args(), *[_p(o) for o in outs], _p(counts), _p(ws), ws_bytes)
     _lib.check_guard(ws_g, "mi_render_rays_occupancy workspace (mi_render_occupancy_extra_bytes)")
     return tuple(outs), counts
+
+
+def render_rays_occupancy_clip(pf_c: PackedField, pf_f: PackedField, rays: torch.Tensor, near: float, far: float, n_coarse: int,
+                               n_fine: int, grid, probes: int, pad: int = 1, t_rand=None, seed: int = 0, ray0: int = 0,
+                               coarse_outputs: bool = True):
+    """mi_render_rays_occupancy_clip under its own name: render_rays_occupancy(..., clip_probes=probes, clip_pad=pad).  The
+    training call, mi_render_rays_occupancy_clip_train, is mirender.occupancy_train.render_rays(..., clip_probes=)."""
+    return render_rays_occupancy(pf_c, pf_f, rays, near, far, n_coarse, n_fine, grid, t_rand, seed, ray0, coarse_outputs,
+                                 clip_probes=int(probes), clip_pad=pad)

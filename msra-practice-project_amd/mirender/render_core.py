@@ -119,20 +119,24 @@ def _check_grid(grid, pf_c, pf_f, film):
 
 
 def render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, fine_sample_num, *,
-                t_rand=None, seed=None, film=None, ray0=0, grid=None):
+                t_rand=None, seed=None, film=None, ray0=0, grid=None, clip_probes=None, clip_pad=1):
     """nerf/render.py:106-147.  rays [N,2,3] -> (rgb_c, depth_c, acc_c, rgb_f, depth_f, acc_f).
     `ray0`: index of rays[0] in the caller's full ray list; the seeded jitter is keyed by (seed, ray0 + k, sample),
     so a frame rendered in pieces (chunks, GPUs) gets the jitter it would get in one call.
     `film` [b,rows,512] (FiLM fields only; rows = hidden_layers + 1, 9 for the default depth) renders b images in one call: rays are b equal consecutive groups and
     group g uses film[g]; by default the model's own film_params (one image) are used like the reference.
     `grid` (mirender.occupancy.OccupancyGrid; inference with NeRF, SirenNeRF or TinyNeRF fields): a sample in an unoccupied
-    cell, or outside the grid's box, counts as raw = 0 and is not evaluated (ops.render_rays_occupancy)."""
+    cell, or outside the grid's box, counts as raw = 0 and is not evaluated (ops.render_rays_occupancy).
+    `clip_probes` (with a grid; None: off): each ray's range [near, far] is first clipped to the grid - that many probes along
+    the ray, `clip_pad` probe bins of margin at either end (ops.occupancy_clip_rays) - and both passes place their samples
+    inside it, so the same sample counts resolve the occupied stretch more finely.  Per ray, so a split call changes no bit."""
     return _render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, fine_sample_num, t_rand=t_rand,
-                        seed=seed, film=film, ray0=ray0, grid=grid)
+                        seed=seed, film=film, ray0=ray0, grid=grid, clip_probes=clip_probes, clip_pad=clip_pad)
 
 
 def _render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, fine_sample_num, *,
-                 t_rand=None, seed=None, film=None, ray0=0, coarse_outputs=True, grid=None, return_counts=False):
+                 t_rand=None, seed=None, film=None, ray0=0, coarse_outputs=True, grid=None, return_counts=False,
+                 clip_probes=None, clip_pad=1):
     """render_rays; coarse_outputs=False lets the fused inference path skip what only the coarse outputs need
     (ops.render_rays_fused), which may then return None in their slots.  The fine outputs are the same bits.
     return_counts=True (with a grid): (the outputs, int32 [calls, 2], the samples each pass evaluated; [0, 2] without rays)."""
@@ -143,11 +147,13 @@ def _render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, f
     if seed is None and t_rand is None:
         seed = _fresh_seed()
     pf_c, pf_f = fields.as_packed_field(coarse_model), fields.as_packed_field(fine_model)
+    if clip_probes is not None and grid is None:
+        raise _lib.MiRenderError("clip_probes= clips each ray's range to an occupancy grid: it needs grid=")
     if grid is not None:
         _check_grid(grid, pf_c, pf_f, film)
         if rays.shape[0]:
             outs, counts = ops.render_rays_occupancy(pf_c, pf_f, rays, near, far, nc, nf, grid, t_rand, seed or 0, ray0=ray0,
-                                                     coarse_outputs=coarse_outputs)
+                                                     coarse_outputs=coarse_outputs, clip_probes=clip_probes, clip_pad=clip_pad)
             return (outs, counts[None]) if return_counts else outs
     if rays.shape[0] == 0:
         # no rays (an empty batch, a rank of a group larger than the frame): six empty outputs; under autograd they hang
@@ -189,7 +195,7 @@ def _render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, f
 
 
 def _render_image_device(width, height, focal, pose, near, far, coarse_model, fine_model, nc, nf, chunk,
-                         t_rand=None, seed=None, ray0=0, n_rays=None, grid=None):
+                         t_rand=None, seed=None, ray0=0, n_rays=None, grid=None, clip_probes=None, clip_pad=1):
     """Rays [ray0, ray0+n) of the image -> device tensors (rgb[n,3], depth[n], acc[n]) of the FINE pass."""
     dev = _device_of(coarse_model, fine_model)
     total = width * height
@@ -204,7 +210,7 @@ def _render_image_device(width, height, focal, pose, near, far, coarse_model, fi
         rays = ops.gen_rays(width, height, focal, pose, dev, i, m)
         tr = None if t_rand is None else t_rand[i - ray0:i - ray0 + m]   # row k of t_rand <-> ray ray0 + k
         out = _render_rays(rays, near, far, coarse_model, fine_model, nc, nf, t_rand=tr, seed=seed, ray0=i,
-                           coarse_outputs=False, grid=grid)
+                           coarse_outputs=False, grid=grid, clip_probes=clip_probes, clip_pad=clip_pad)
         parts.append(out[3:6])
     if not parts:                                          # an empty ray range (a rank of a group larger than the frame)
         return (torch.empty((0, 3), dtype=torch.float32, device=dev), torch.empty(0, dtype=torch.float32, device=dev),
@@ -215,11 +221,12 @@ def _render_image_device(width, height, focal, pose, near, far, coarse_model, fi
 
 
 def render_image(width, height, focal, pose, near, far, coarse_model, fine_model, coarse_sample_num,
-                 fine_sample_num, chunk=1024 * 16, *, t_rand=None, seed=None, grid=None):
+                 fine_sample_num, chunk=1024 * 16, *, t_rand=None, seed=None, grid=None, clip_probes=None, clip_pad=1):
     """nerf/render.py:150-167: NumPy rgb[H,W,3], depth[H,W,1], acc[H,W,1] of the fine pass."""
     with torch.no_grad():
         rgb, depth, acc = _render_image_device(width, height, focal, pose, near, far, coarse_model, fine_model,
-                                               int(coarse_sample_num), int(fine_sample_num), None, t_rand, seed, grid=grid)
+                                               int(coarse_sample_num), int(fine_sample_num), None, t_rand, seed, grid=grid,
+                                               clip_probes=clip_probes, clip_pad=clip_pad)
     return (rgb.cpu().numpy().reshape(height, width, 3), depth.cpu().numpy().reshape(height, width, 1),
             acc.cpu().numpy().reshape(height, width, 1))
 
@@ -228,15 +235,16 @@ render_image_np = render_image   # pi_GAN/render.py:209-226 is the same function
 
 
 def render_image_tensor(width, height, focal, pose, near, far, coarse_model, fine_model, coarse_sample_num,
-                        fine_sample_num, chunk=1024 * 16, *, t_rand=None, seed=None, grid=None):
+                        fine_sample_num, chunk=1024 * 16, *, t_rand=None, seed=None, grid=None, clip_probes=None, clip_pad=1):
     """pi_GAN/render.py:195-206: rgb of the fine pass as a device tensor [H,W,3] carrying the autograd graph."""
     rgb, _, _ = _render_image_device(width, height, focal, pose, near, far, coarse_model, fine_model,
-                                     int(coarse_sample_num), int(fine_sample_num), None, t_rand, seed, grid=grid)
+                                     int(coarse_sample_num), int(fine_sample_num), None, t_rand, seed, grid=grid,
+                                               clip_probes=clip_probes, clip_pad=clip_pad)
     return rgb.reshape(height, width, 3)
 
 
 def render_video(width, height, focal, poses, near, far, coarse_model, fine_model, coarse_sample_num,
-                 fine_sample_num, chunk=1024 * 16, *, t_rand=None, seed=None, grid=None):
+                 fine_sample_num, chunk=1024 * 16, *, t_rand=None, seed=None, grid=None, clip_probes=None, clip_pad=1):
     """nerf/render.py:170-182 (and the evident intent of pi_GAN/render.py:229-241, whose body unpacks
     three values from the tensor-returning render_image): stacked NumPy frames rgb[F,H,W,3], depth[F,H,W,1],
     acc[F,H,W,1].  Keyword-only extras: `t_rand` [F, H*W, Nc] injects each frame's jitter, `seed` seeds frame i with
@@ -258,7 +266,8 @@ def render_video(width, height, focal, poses, near, far, coarse_model, fine_mode
         with torch.no_grad():
             outs = _render_image_device(width, height, focal, p, near, far, coarse_model, fine_model,
                                         int(coarse_sample_num), int(fine_sample_num), None,
-                                        None if t_rand is None else t_rand[i], None if seed is None else seed + i, grid=grid)
+                                        None if t_rand is None else t_rand[i], None if seed is None else seed + i, grid=grid,
+                                        clip_probes=clip_probes, clip_pad=clip_pad)
         dev = outs[0].device
         if copy_stream is None:
             copy_stream = torch.cuda.Stream(dev)

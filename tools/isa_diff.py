@@ -6,7 +6,8 @@
 For every kernel in both objects: its disassembly (llvm-objdump -d --no-show-raw-insn --no-leading-addr, `//` comments
 stripped) and its metadata (VGPR / AGPR / SGPR counts, spills, LDS, scratch from llvm-readelf --notes).  The 32-bit
 literals of the address pairs right after s_getpc_b64 (s_add_u32 / s_addc_u32) are masked: they are pc-relative offsets
-of data in the code object and move whenever anything else in the object does.  Prints one line per kernel and exits
+of data in the code object and move whenever anything else in the object does; the `s_nop` run behind a kernel's last
+`s_endpgm` is dropped: it pads up to the next symbol's alignment and follows the kernel's place in the object.  Prints one line per kernel and exits
 non-zero if any kernel in both builds differs.  The evidence that a host-side refactor left the hot kernels alone.
 
 --rename: kernels are matched by their demangled names after re.sub(PATTERN, REPLACEMENT) on both sides, for a change that
@@ -57,6 +58,14 @@ def load(obj):
         else:
             pcrel = 0
         kernels[name].append(ins)
+    # the s_nop run behind a kernel's last s_endpgm pads up to the next symbol's alignment: it depends on where the kernel lies
+    # in the object (a template instance lies in a section of its own), not on its code
+    for v in kernels.values():
+        end = len(v)
+        while end and v[end - 1] == "s_nop 0":
+            end -= 1
+        if end and v[end - 1] == "s_endpgm":
+            del v[end:]
     return {k: (v, meta.get(k, {})) for k, v in kernels.items()}
 
 
