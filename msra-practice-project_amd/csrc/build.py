@@ -59,13 +59,17 @@ def parse_depfile(text):
 
 def unit_stale(obj, src, depfile):
     """Why a translation unit has to be compiled, or None: its object is missing, its dependency file is missing (so nothing
-    says what it includes), or the object is older than the source or any file the dependency file names."""
+    says what it includes), its dependency file does not name this source (it was written in another copy of the tree, whose
+    headers it then lists: the object and the file came along when the tree was copied), or the object is older than the source
+    or any file the dependency file names."""
     if not os.path.exists(obj):
         return "no object yet"
     if not os.path.exists(depfile):
         return "no dependency file yet"
     with open(depfile) as f:
         deps = parse_depfile(f.read())
+    if os.path.realpath(src) not in {os.path.realpath(d) for d in deps}:
+        return "its .d names another tree's copy of the source"
     t = os.path.getmtime(obj)
     if any(not os.path.exists(d) or os.path.getmtime(d) > t for d in [src] + deps):
         return "source or a file its .d names newer than the object"

@@ -447,6 +447,10 @@ __global__ __launch_bounds__(256) void composite_bwd_rays_kernel(int64_t n, int 
 // few enough bits (largest sum's exponent - smallest term's last mantissa bit <= 52), and exact sums do not depend
 // on the order of the additions: the wave then takes a shuffle scan (6 steps) instead of nb dependent additions.
 // Terms that do not qualify (inf / NaN, or a dynamic range beyond 2^(28 - log2 nb)) take the sequential order itself.
+// The bits a sum needs: fmax - fmin for the span of the exponent fields (a denormal counts as field 1, where its last bit
+// lies), 24 for a term's mantissa, log2n = bit_length(nb - 1) for adding nb - 1 < 2^log2n terms: 52 at the criterion's edge.
+// The criterion is one bit stricter than a double's 53 demand: no row with fmax - fmin = 29 - log2n can tell the two orders
+// apart either; at 30 - log2n one can (nb = 64; tests/test_sampler_ref_host.py holds both rows and the integer proof).
 // ---------------------------------------------------------------------------------------
 __device__ __forceinline__ void cdf_like_cumsum(const float* pdf, float* cdf, int nb, int lane) {
     const int nw = nb - 1;
@@ -588,6 +592,8 @@ __global__ __launch_bounds__(256) void sample_fine_kernel(int64_t n, float near_
         // sorted on every call the render path makes (stratified depths; inverse-CDF samples of an ascending u), and
         // then a rank is the element's own index in its list plus one binary search in the other list.  A ray whose
         // lists are not sorted (the stage-level entry point takes any depths) is ranked by full counting instead.
+        // The two agree wherever both apply, but for a sample of -0 next to a coarse depth of +0 (float compares hold them
+        // equal and put the coarse depth first, the key puts -0 first); ascending bins never draw a -0.
         bool sorted = true;
         for (int e = lane; e + 1 < S; e += 64)
             if (e + 1 != nc) sorted = sorted && !(zall[e + 1] < zall[e]) && zall[e] == zall[e] && zall[e + 1] == zall[e + 1];

@@ -9,7 +9,7 @@ a = max(k0 - pad, 0), b = min(k1 + 1 + pad, M), near_r = near + float(a) * h, fa
 a ray without an occupied probe keeps (near, far).
 
 With per-ray bounds the two samplers keep their arithmetic; only their linspace is linspace_at(near_r, far_r, Nc, i), the
-in-kernel ATen formula restated below.
+in-kernel ATen formula restated below.  The fine sampler itself is restated in tests/sampler_ref.py.
 """
 import numpy as np
 import torch
@@ -107,16 +107,12 @@ def sample_coarse_bounds(bounds, nc: int, t_rand) -> np.ndarray:
 
 def sample_fine_bounds(bounds, z_coarse, weights, nf: int):
     """(z_samples [n,Nf], z_fine [n,Nc+Nf]) torch fp32: sample_pdf over each ray's own bin mids, then sort(cat)
-    (render.py:140-142).  Not a bit-exact statement of the kernel's pdf sum (tests/test_gpu_boundary.py gates that stage)."""
-    b = np.asarray(bounds, F)
-    z_coarse, weights = torch.as_tensor(z_coarse).cpu().float(), torch.as_tensor(weights).cpu().float()
-    nc = z_coarse.shape[1]
-    lin = linspace_at(b[:, 0], b[:, 1], nc)
-    mids = torch.from_numpy((F(0.5) * (lin[:, 1:] + lin[:, :-1])).astype(np.float32))
-    if nf == 0:
-        return torch.empty(z_coarse.shape[0], 0), z_coarse
-    zs = R.sample_pdf(mids, weights[:, 1:-1], nf)
-    return zs, torch.sort(torch.cat([z_coarse, zs], -1), -1).values
+    (render.py:140-142), as tests/sampler_ref.py restates the kernel bit for bit (u: the torch.linspace table mirender passes)."""
+    import sampler_ref                                      # (it imports this module for linspace_at)
+    u = torch.linspace(0.0, 1.0, nf).numpy() if nf else None                     # the u table mirender injects
+    zs, zf, _ = sampler_ref.sample_fine_bounds(np.asarray(bounds, F), torch.as_tensor(z_coarse).cpu().float().numpy(),
+                                               torch.as_tensor(weights).cpu().float().numpy(), nf, u)
+    return torch.from_numpy(zs), torch.from_numpy(zf)
 
 
 # ---- the inputs of tests/test_gpu_occupancy_clip.py, built here so that the host test can check them on the CPU ---------------

@@ -74,3 +74,15 @@ def test_missing_object_or_listed_file_is_stale(tmp_path):
     assert B.unit_stale(obj, src, dep)
     os.remove(obj)
     assert B.unit_stale(obj, src, dep)
+
+
+def test_depfile_of_another_copy_of_the_tree_is_stale(tmp_path):
+    """A built tree copied elsewhere: object and dependency file come along, and the file still names the first tree's source
+    and headers - fresh, existing, and not what this tree's object would be compiled from."""
+    first, second = tmp_path / "first", tmp_path / "second"
+    first.mkdir(), second.mkdir()
+    obj, src, dep = _unit(first)
+    copy = [_touch(second / n, t) for n, t in (("unit.o", 100), ("unit.hip", 50), ("a.h", 50), ("b.h", 50))]
+    (second / "unit.d").write_text(open(dep).read())
+    assert B.unit_stale(obj, src, dep) is None
+    assert "another tree" in B.unit_stale(copy[0], copy[1], str(second / "unit.d"))

@@ -7,7 +7,7 @@ DESIGN.md 4.8).  Bit equality unless said otherwise.
     2 mi_sample_coarse_bounds        constant bounds == mi_sample_coarse(z_lin = NULL); varied bounds ray by ray == the scalar call
                                      on that single ray with ray0 + r; injected and seeded jitter; the restated formula
     3 mi_sample_fine_bounds          the same two comparisons against mi_sample_fine_pos, z_samples and pos included; a ray whose
-                                     weights are all zero
+                                     weights are all zero; the restatement of tests/sampler_ref.py
     4 mi_render_rays_occupancy_clip  == clip, coarse bounds, mark, list forward, composite, fine bounds, mark, list forward,
                                      composite; with an all-ones grid over every probe == mi_render_rays_occupancy(z_lin = NULL)
     5 the training pair              outputs == the inference call's; all-ones grid: gradients == mi_render_rays_occupancy_train's
@@ -25,6 +25,7 @@ pytestmark = pytest.mark.gpu
 import occupancy_clip_ref as cref  # noqa: E402
 import occupancy_render_ref as ref  # noqa: E402
 import occupancy_train_ref as tref  # noqa: E402
+import sampler_ref as sref  # noqa: E402
 from oracle import parity, synth  # noqa: E402
 
 NEAR, FAR = cref.NEAR, cref.FAR
@@ -168,6 +169,14 @@ def test_sample_fine_bounds(nc, nf):
         for a, b, what in zip(got, one, ("z_fine", "z_samples", "pos")):
             assert _same(a[r:r + 1], b), (nc, nf, r, what)
     assert bool((got[0][:, 1:] >= got[0][:, :-1]).all())
+    # ... and against the restatement on the CPU (tests/sampler_ref.py), so that a mistake both instances share shows too
+    ul = ops.linspace_table(0.0, 1.0, nf, "cpu")
+    want = sref.sample_fine_bounds(varied.cpu().numpy(), z_v.cpu().numpy(), w.cpu().numpy(), nf, None if ul is None else ul.numpy())
+    for a, b, what in zip(got, (want[1], want[0], want[2]), ("z_fine", "z_samples", "pos")):
+        a = a.cpu().numpy()
+        assert np.array_equal(a, b) if what == "pos" else np.array_equal(sref.bits(a), sref.bits(b)), (nc, nf, what)
+    zs_ref, zf_ref = cref.sample_fine_bounds(varied.cpu().numpy(), z_v.cpu(), w.cpu(), nf)
+    assert _same(got[0].cpu(), zf_ref) and _same(got[1].cpu(), zs_ref)
     if nf:
         assert bool((got[1] >= varied[:, :1]).all()) and bool((got[1] <= varied[:, 1:]).all())
 
