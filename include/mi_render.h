@@ -555,6 +555,40 @@ int mi_render_rays_occupancy_backward(int kind_coarse, const float* packed_bwd_c
                                       float* const* grad_params_coarse, float* const* grad_params_fine, void* bwd_workspace,
                                       int64_t bwd_workspace_bytes, int* fields_written, void* stream);
 
+/* ---- gradients to the rays with a grid (NeRF, SirenNeRF, TinyNeRF): opt-in, used by mirender/pose.py ---------------
+ *
+ * The rule: with a grid an unlisted sample's raw is the constant 0, so it sends nothing to the rays through the field; in the
+ * composite its sigma = 0 gives an exact 0 in dL/d|d| (mi_composite_bwd_rays runs on the full [n,S,4] raw, zeros included).
+ * A listed sample sends the rays exactly what it sends without a grid: g_o += g_pos, g_d += z_s g_pos + (I - v v^T) / |d| g_dir.
+ * Occupancy is piecewise constant in the rays, and so are the clipped bounds: neither carries a gradient, and the depths carry
+ * none either, as without a grid.
+ *
+ * mi_field_input_grad_rays_list: mi_field_input_grad_rays over the COMPACT rows a mi_field_backward_list call left behind
+ * (same kind / acts / grads_ws / list / count / capacity; `params` as in mi_field_input_grad).  Ray r's samples are the run
+ * [e0, e1) of the ascending list with r * n_samples <= list[e] < (r + 1) * n_samples, found on the device from *count (no
+ * read-back); entry e reads row e of every region, z[list[e]] and ray r.  Rows and list entries at and past *count are never
+ * read.  A ray with an empty run gets zeros (accumulate = 0) or keeps what it holds.  One wave owns a ray, no atomics.
+ * FiLM kinds, a NULL pointer, n * n_samples past an int and capacity != n * n_samples: MI_EINVAL before any launch.
+ *
+ * mi_render_rays_occupancy_backward_rays: mi_render_rays_occupancy_backward (same arguments, same launches, same parameter
+ * gradients bit for bit) that also writes dL/d(rays).  params_coarse / params_fine: HOST arrays of the fields' parameter
+ * tensors (device pointers, state-dict order; with shared != 0 params_fine is not read).  g_rays [n,2,3] is OVERWRITTEN in
+ * full whatever cotangents are NULL (all NULL: zeros); within it the sum runs composite coarse, field coarse, composite fine,
+ * field fine.  It reads z from the workspace, so it serves the clipped training forward unchanged.  No workspace beyond
+ * mi_render_rays_occupancy_backward's. */
+int mi_field_input_grad_rays_list(int kind, const float* const* params, int n_params, const float* acts, const float* grads_ws,
+                                  const int* list, const int* count, int64_t capacity, const float* rays, const float* z,
+                                  int64_t n, int n_samples, int accumulate, float* g_rays, void* stream);
+int mi_render_rays_occupancy_backward_rays(int kind_coarse, const float* packed_bwd_coarse, int kind_fine,
+                                           const float* packed_bwd_fine, int shared, const float* rays, int64_t n, int n_coarse,
+                                           int n_fine, const void* workspace, int64_t workspace_bytes, const void* saved,
+                                           int64_t saved_bytes, const float* g_rgb_c, const float* g_depth_c, const float* g_acc_c,
+                                           const float* g_rgb_f, const float* g_depth_f, const float* g_acc_f,
+                                           float* const* grad_params_coarse, float* const* grad_params_fine, void* bwd_workspace,
+                                           int64_t bwd_workspace_bytes, int* fields_written, const float* const* params_coarse,
+                                           int n_params_coarse, const float* const* params_fine, int n_params_fine, float* g_rays,
+                                           void* stream);
+
 /* ---- clipping each ray's sampling range to the grid (NeRF, SirenNeRF, TinyNeRF) -----------
  *
  * The grid calls above decide WHETHER a sample is evaluated; these decide WHERE samples are placed.  The rule, for rays

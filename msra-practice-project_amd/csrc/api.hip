@@ -501,6 +501,28 @@ int mi_field_input_grad_rays(int kind, const float* const* params, int n_params,
                                         accumulate, g_rays, (hipStream_t)stream);
 }
 
+int mi_field_input_grad_rays_list(int kind, const float* const* params, int n_params, const float* acts, const float* grads_ws,
+                                  const int* list, const int* count, int64_t capacity, const float* rays, const float* z,
+                                  int64_t n, int n_samples, int accumulate, float* g_rays, void* stream) {
+    const char* fn = "mi_field_input_grad_rays_list";
+    if (bad_kind(kind)) return MI_EINVAL;
+    if (!has_list_kernel(kind)) { set_error("%s: kind %d has no counted backward (NeRF, SirenNeRF, TinyNeRF have)", fn, kind); return MI_EINVAL; }
+    if (int rc = check_input_grad(fn, kind, params, n_params, nullptr, acts, grads_ws, 1, n, g_rays)) return rc;
+    if (!list || !count || !rays || !z) { set_error("%s: null pointer argument", fn); return MI_EINVAL; }
+    if (n_samples < 1) { set_error("%s: n_samples must be positive", fn); return MI_EINVAL; }
+    if (n > 0x7fffffffLL / n_samples) {
+        set_error("%s: n * n_samples = %lld * %d exceeds 2^31 - 1 (the list holds int point indices)", fn, (long long)n, n_samples);
+        return MI_EINVAL;
+    }
+    if (capacity != n * n_samples) {
+        set_error("%s: capacity %lld is not n * n_samples = %lld (the stride of the compact regions)", fn, (long long)capacity,
+                  (long long)(n * n_samples));
+        return MI_EINVAL;
+    }
+    return launch_field_input_grad_rays_list(kind, params, acts, grads_ws, list, count, rays, z, n, n_samples, accumulate, g_rays,
+                                             (hipStream_t)stream);
+}
+
 int mi_composite_bwd_rays(int64_t n, int n_samples, const float* raw, const float* z, const float* rays,
                           const float* g_rgb, const float* g_depth, const float* g_acc, const float* g_weights,
                           int accumulate, float* g_rays, void* stream) {

@@ -134,6 +134,12 @@ int launch_field_input_grad(int kind, const float* const* params, const float* f
 int launch_field_input_grad_rays(int kind, const float* const* params, const float* film, const float* acts,
                                  const float* grads, const float* rays, const float* z, int64_t n_groups,
                                  int64_t rays_per_group, int n_samples, int accumulate, float* g_rays, hipStream_t stream);
+// ... of the rays of one launch_field_backward_list call (non-FiLM kinds), from the COMPACT acts / grads rows it left behind:
+// ray r's samples are the run of the ascending list inside [r S, (r + 1) S), found on the device; entry e reads row e of every
+// region (stride: the capacity n * n_samples, which fits an int) and z[list[e]].  Sized from n; no read-back, no atomics.
+int launch_field_input_grad_rays_list(int kind, const float* const* params, const float* acts, const float* grads,
+                                      const int* list, const int* count, const float* rays, const float* z, int64_t n,
+                                      int n_samples, int accumulate, float* g_rays, hipStream_t stream);
 int64_t image_metrics_workspace_floats(int images, int channels, int H, int W);
 int launch_image_metrics(const float* img1, const float* img2, int images, int channels, int H, int W,
                          const float* window, int window_size, float* workspace, float* out, hipStream_t stream);

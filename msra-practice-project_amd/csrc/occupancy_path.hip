@@ -1,5 +1,6 @@
 // occupancy_path.hip - rendering and training with an occupancy grid through the C ABI (include/mi_render.h):
-// mi_render_rays_occupancy, mi_render_rays_occupancy_train, mi_render_rays_occupancy_backward and their size queries.
+// mi_render_rays_occupancy, mi_render_rays_occupancy_train, mi_render_rays_occupancy_backward (and its _rays form, which also
+// gives dL/d(rays): occupancy_backward) and their size queries.
 // Both forwards run the sequence of every render path (run_render_passes, render_path.h) with one field step (occupancy_forward):
 // per pass, mark the samples in occupied cells into a device-counted list and evaluate the field at the listed points alone.
 // Training differs in three values: the ordered mark, a field that keeps the listed points' layer inputs, and a list per pass
@@ -262,6 +263,89 @@ static int render_training(const char* fn, OccClip* clip, int kind_coarse, const
     return occupancy_forward(fn, pass, true, grid, n, n_coarse, n_fine, io, clip, evaluated, layout.carve(workspace), (hipStream_t)stream);
 }
 
+// a field whose input gradient a backward computes has its parameter tensors (device pointers, state-dict order), every one
+static int check_field_params(const char* fn, const char* which, int kind, const float* const* params, int n_params) {
+    if (!params) { set_error("%s: null pointer argument (the %s field's parameters)", fn, which); return MI_EINVAL; }
+    if (n_params != 2 * field_kind(kind).n_layers) {
+        set_error("%s: the %s field's kind %d expects %d parameter tensors, got %d", fn, which, kind, 2 * field_kind(kind).n_layers, n_params);
+        return MI_EINVAL;
+    }
+    for (int i = 0; i < n_params; ++i)
+        if (!params[i]) { set_error("%s: parameter %d of the %s field is null", fn, i, which); return MI_EINVAL; }
+    return MI_OK;
+}
+
+// The backward of both training forwards, stated once: mi_render_rays_occupancy_backward and, with g_rays, its _rays form.
+// Per pass with a cotangent: the composite's backward, then the field's over the pass's list.  g_rays (null: no ray output, and
+// then not one launch more) is zeroed first and receives, in autograd._RenderRaysFn.backward's order, each composite's |d| part
+// over the full raw (an unlisted sample's sigma = 0 gives an exact 0) and each field's input gradient over its list - launched
+// right behind that field's backward, whose dA rows in L.grads the next pass overwrites.
+static int occupancy_backward(const char* fn, int kind_coarse, const float* packed_bwd_coarse, int kind_fine,
+                              const float* packed_bwd_fine, int shared, const float* rays, int64_t n, int n_coarse, int n_fine,
+                              const void* workspace, int64_t workspace_bytes, const void* saved, int64_t saved_bytes,
+                              const float* g_rgb_c, const float* g_depth_c, const float* g_acc_c, const float* g_rgb_f,
+                              const float* g_depth_f, const float* g_acc_f, float* const* grad_params_coarse,
+                              float* const* grad_params_fine, void* bwd_workspace, int64_t bwd_workspace_bytes, int* fields_written,
+                              const float* const* params_coarse, int n_params_coarse, const float* const* params_fine,
+                              int n_params_fine, float* g_rays, void* stream) {
+    if (fields_written) *fields_written = 0;
+    if (int rc = check_call(fn, "training", kind_coarse, kind_fine, n, n_coarse, n_fine)) return rc;
+    if (shared && kind_coarse != kind_fine) { set_error("%s: one field for both passes has one kind (%d and %d)", fn, kind_coarse, kind_fine); return MI_EINVAL; }
+    if (n == 0) return MI_OK;
+    const bool want_c = g_rgb_c || g_depth_c || g_acc_c, want_f = g_rgb_f || g_depth_f || g_acc_f;
+    if (!rays) { set_error("%s: null pointer argument", fn); return MI_EINVAL; }
+    const float* const* params[2] = {params_coarse, shared ? params_coarse : params_fine};
+    const int n_params[2] = {n_params_coarse, shared ? n_params_coarse : n_params_fine};
+    const int kinds[2] = {kind_coarse, kind_fine};
+    const float* packed_bwd[2] = {packed_bwd_coarse, shared ? packed_bwd_coarse : packed_bwd_fine};
+    float* const* grads[2] = {grad_params_coarse, shared ? grad_params_coarse : grad_params_fine};
+    const bool wants[2] = {want_c, want_f};
+    for (int f = 0; f < 2; ++f) {
+        if (!wants[f]) continue;
+        if (int rc = check_field_grads(fn, f && !shared ? "fine" : "coarse", kinds[f], packed_bwd[f], grads[f])) return rc;
+        if (g_rays) if (int rc = check_field_params(fn, f && !shared ? "fine" : "coarse", kinds[f], params[f], n_params[f])) return rc;
+    }
+    if (int rc = check_buffers(fn, OCC_BACKWARD, kind_coarse, kind_fine, shared != 0, n, n_coarse, n_fine, workspace, workspace_bytes,
+                               saved, saved_bytes, bwd_workspace, bwd_workspace_bytes)) return rc;
+    hipStream_t hs = (hipStream_t)stream;
+    if (g_rays && hipMemsetAsync(g_rays, 0, (size_t)n * 6 * sizeof(float), hs) != hipSuccess) {
+        set_error("%s: clearing g_rays failed", fn);
+        return MI_EHIP;
+    }
+    if (!want_c && !want_f) return MI_OK;
+    const OccBwdLayout L(kind_coarse, kind_fine, shared != 0, n, n_coarse, n_fine);
+    const RenderWorkspace layout(n, n_coarse, n_fine);
+    const RenderWorkspace::Regions ws = layout.carve(const_cast<void*>(workspace));
+    const OccLists::Regions r = OccLists(true, n, n_coarse, n_fine).carve(workspace, layout.base_bytes());
+    const float* acts_c = (const float*)saved;
+    const float* acts_f = acts_c + saved_floats_coarse(kind_coarse, n, n_coarse);
+    const int S = n_coarse + n_fine;
+    float* bws = (float*)bwd_workspace;
+    int rc;
+    if (want_c) {
+        if ((rc = launch_composite_bwd(n, n_coarse, ws.raw_c, ws.z_c, rays, g_rgb_c, g_depth_c, g_acc_c, nullptr, bws + L.g_raw_c, hs))) return rc;
+        if (g_rays && (rc = launch_composite_bwd_rays(n, n_coarse, ws.raw_c, ws.z_c, rays, g_rgb_c, g_depth_c, g_acc_c, nullptr, 1, g_rays, hs))) return rc;
+        if ((rc = launch_field_backward_list(kind_coarse, packed_bwd_coarse, acts_c, bws + L.grads, ws.raw_c, bws + L.g_raw_c, r.list[0],
+                                             r.counts, n * n_coarse, bws + L.partial, grad_params_coarse, hs))) return rc;
+        if (g_rays && (rc = launch_field_input_grad_rays_list(kind_coarse, params[0], acts_c, bws + L.grads, r.list[0], r.counts, rays, ws.z_c,
+                                                              n, n_coarse, 1, g_rays, hs))) return rc;
+    }
+    if (want_f) {
+        if ((rc = launch_composite_bwd(n, S, ws.raw_f, ws.z_f, rays, g_rgb_f, g_depth_f, g_acc_f, nullptr, bws + L.g_raw_f, hs))) return rc;
+        if (g_rays && (rc = launch_composite_bwd_rays(n, S, ws.raw_f, ws.z_f, rays, g_rgb_f, g_depth_f, g_acc_f, nullptr, 1, g_rays, hs))) return rc;
+        float* fine_total[2 * kMaxLayers];
+        const bool add = shared && want_c;                       // one field: coarse-pass total += fine-pass total
+        if (add) scratch_params(kind_fine, bws + L.fine_total, fine_total);
+        if ((rc = launch_field_backward_list(kind_fine, packed_bwd[1], acts_f, bws + L.grads, ws.raw_f, bws + L.g_raw_f, r.list[1],
+                                             r.counts + 1, n * S, bws + L.partial, add ? fine_total : grads[1], hs))) return rc;
+        if (g_rays && (rc = launch_field_input_grad_rays_list(kind_fine, params[1], acts_f, bws + L.grads, r.list[1], r.counts + 1, rays, ws.z_f,
+                                                              n, S, 1, g_rays, hs))) return rc;
+        if (add && (rc = add_param_grads(kind_fine, grad_params_coarse, fine_total, hs))) return rc;
+    }
+    if (fields_written) *fields_written = fields_written_word(shared != 0, want_c, want_f, false);
+    return MI_OK;
+}
+
 }  // namespace mi
 
 using namespace mi;
@@ -344,50 +428,27 @@ int mi_render_rays_occupancy_backward(int kind_coarse, const float* packed_bwd_c
                                       const float* g_rgb_f, const float* g_depth_f, const float* g_acc_f,
                                       float* const* grad_params_coarse, float* const* grad_params_fine, void* bwd_workspace,
                                       int64_t bwd_workspace_bytes, int* fields_written, void* stream) {
-    const char* fn = "mi_render_rays_occupancy_backward";
-    if (fields_written) *fields_written = 0;
-    if (int rc = check_call(fn, "training", kind_coarse, kind_fine, n, n_coarse, n_fine)) return rc;
-    if (shared && kind_coarse != kind_fine) { set_error("%s: one field for both passes has one kind (%d and %d)", fn, kind_coarse, kind_fine); return MI_EINVAL; }
-    if (n == 0) return MI_OK;
-    const bool want_c = g_rgb_c || g_depth_c || g_acc_c, want_f = g_rgb_f || g_depth_f || g_acc_f;
-    if (!rays) { set_error("%s: null pointer argument", fn); return MI_EINVAL; }
-    const int kinds[2] = {kind_coarse, kind_fine};
-    const float* packed_bwd[2] = {packed_bwd_coarse, shared ? packed_bwd_coarse : packed_bwd_fine};
-    float* const* grads[2] = {grad_params_coarse, shared ? grad_params_coarse : grad_params_fine};
-    const bool wants[2] = {want_c, want_f};
-    for (int f = 0; f < 2; ++f) {
-        if (!wants[f]) continue;
-        if (int rc = check_field_grads(fn, f && !shared ? "fine" : "coarse", kinds[f], packed_bwd[f], grads[f])) return rc;
-    }
-    if (int rc = check_buffers(fn, OCC_BACKWARD, kind_coarse, kind_fine, shared != 0, n, n_coarse, n_fine, workspace, workspace_bytes,
-                               saved, saved_bytes, bwd_workspace, bwd_workspace_bytes)) return rc;
-    if (!want_c && !want_f) return MI_OK;
-    const OccBwdLayout L(kind_coarse, kind_fine, shared != 0, n, n_coarse, n_fine);
-    const RenderWorkspace layout(n, n_coarse, n_fine);
-    const RenderWorkspace::Regions ws = layout.carve(const_cast<void*>(workspace));
-    const OccLists::Regions r = OccLists(true, n, n_coarse, n_fine).carve(workspace, layout.base_bytes());
-    const float* acts_c = (const float*)saved;
-    const float* acts_f = acts_c + saved_floats_coarse(kind_coarse, n, n_coarse);
-    const int S = n_coarse + n_fine;
-    float* bws = (float*)bwd_workspace;
-    hipStream_t hs = (hipStream_t)stream;
-    int rc;
-    if (want_c) {
-        if ((rc = launch_composite_bwd(n, n_coarse, ws.raw_c, ws.z_c, rays, g_rgb_c, g_depth_c, g_acc_c, nullptr, bws + L.g_raw_c, hs))) return rc;
-        if ((rc = launch_field_backward_list(kind_coarse, packed_bwd_coarse, acts_c, bws + L.grads, ws.raw_c, bws + L.g_raw_c, r.list[0],
-                                             r.counts, n * n_coarse, bws + L.partial, grad_params_coarse, hs))) return rc;
-    }
-    if (want_f) {
-        if ((rc = launch_composite_bwd(n, S, ws.raw_f, ws.z_f, rays, g_rgb_f, g_depth_f, g_acc_f, nullptr, bws + L.g_raw_f, hs))) return rc;
-        float* fine_total[2 * kMaxLayers];
-        const bool add = shared && want_c;                       // one field: coarse-pass total += fine-pass total
-        if (add) scratch_params(kind_fine, bws + L.fine_total, fine_total);
-        if ((rc = launch_field_backward_list(kind_fine, packed_bwd[1], acts_f, bws + L.grads, ws.raw_f, bws + L.g_raw_f, r.list[1],
-                                             r.counts + 1, n * S, bws + L.partial, add ? fine_total : grads[1], hs))) return rc;
-        if (add && (rc = add_param_grads(kind_fine, grad_params_coarse, fine_total, hs))) return rc;
-    }
-    if (fields_written) *fields_written = fields_written_word(shared != 0, want_c, want_f, false);
-    return MI_OK;
+    return occupancy_backward("mi_render_rays_occupancy_backward", kind_coarse, packed_bwd_coarse, kind_fine, packed_bwd_fine, shared, rays, n,
+                              n_coarse, n_fine, workspace, workspace_bytes, saved, saved_bytes, g_rgb_c, g_depth_c, g_acc_c, g_rgb_f,
+                              g_depth_f, g_acc_f, grad_params_coarse, grad_params_fine, bwd_workspace, bwd_workspace_bytes, fields_written,
+                              nullptr, 0, nullptr, 0, nullptr, stream);
+}
+
+int mi_render_rays_occupancy_backward_rays(int kind_coarse, const float* packed_bwd_coarse, int kind_fine,
+                                           const float* packed_bwd_fine, int shared, const float* rays, int64_t n, int n_coarse,
+                                           int n_fine, const void* workspace, int64_t workspace_bytes, const void* saved,
+                                           int64_t saved_bytes, const float* g_rgb_c, const float* g_depth_c, const float* g_acc_c,
+                                           const float* g_rgb_f, const float* g_depth_f, const float* g_acc_f,
+                                           float* const* grad_params_coarse, float* const* grad_params_fine, void* bwd_workspace,
+                                           int64_t bwd_workspace_bytes, int* fields_written, const float* const* params_coarse,
+                                           int n_params_coarse, const float* const* params_fine, int n_params_fine, float* g_rays,
+                                           void* stream) {
+    const char* fn = "mi_render_rays_occupancy_backward_rays";
+    if (!g_rays) { if (fields_written) *fields_written = 0; set_error("%s: null pointer argument (g_rays)", fn); return MI_EINVAL; }
+    return occupancy_backward(fn, kind_coarse, packed_bwd_coarse, kind_fine, packed_bwd_fine, shared, rays, n, n_coarse, n_fine, workspace,
+                              workspace_bytes, saved, saved_bytes, g_rgb_c, g_depth_c, g_acc_c, g_rgb_f, g_depth_f, g_acc_f,
+                              grad_params_coarse, grad_params_fine, bwd_workspace, bwd_workspace_bytes, fields_written, params_coarse,
+                              n_params_coarse, params_fine, n_params_fine, g_rays, stream);
 }
 
 }  // extern "C"

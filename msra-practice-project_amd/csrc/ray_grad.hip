@@ -34,8 +34,15 @@
 // reduces across lanes once per ray: g_o = sum_s g_pos, g_d = sum_s z_s g_pos + (I - v v^T) / |d| sum_s g_dir (v = d / |d|).
 // Lanes 0..5 of that wave write the ray's six floats in one store instruction; no atomics, so a result does not depend
 // on the launch's timing.
+// The LIST instances of the two ray-form kernels (training with an occupancy grid) read COMPACT dA / E rows
+// through the ascending list of a counted backward (launch_field_backward_list): ray r's samples are the run [e0, e1) of the
+// list with r S <= list[e] < (r + 1) S, found by two wave-uniform binary searches of the device-counted list; entry e reads row
+// e of every region, z[list[e]] and the ray's own six floats.  An unlisted sample's raw is the constant 0 and sends the rays
+// nothing: the run is all a ray has.  Same per-point arithmetic, same order along the ray, same store_ray.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "field_kinds_host.h"
 #include "launchers.h"
@@ -60,6 +67,14 @@ struct InputGradArgs {
     int accumulate;
 };
 
+// ... and of the list form: rows are entries of `list` (ascending point indices, *count of them, read on the device)
+struct InputGradListArgs : InputGradArgs {
+    const int* list; const int* count;
+    int capacity;              // n * n_samples: no more entries than that, whatever *count holds
+};
+template <bool LIST>
+using InputGradArgsOf = std::conditional_t<LIST, InputGradListArgs, InputGradArgs>;
+
 constexpr int kChunk = 32;     // points of a point-form unit
 
 __device__ __forceinline__ float wave_sum(float v) {
@@ -81,6 +96,27 @@ __device__ __forceinline__ void unit_points(const InputGradArgs& a, int64_t u, i
         const int64_t left = a.points_per_group - c * kChunk;
         cnt = left < kChunk ? (int)left : kChunk;
     }
+}
+
+// first entry of list[lo .. hi) that is >= key, hi if none (wave-uniform: the loads are scalar, the list sits in L2)
+__device__ __forceinline__ int list_lower_bound(const int* list, int lo, int hi, int64_t key) {
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (list[mid] < key) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// ... and of ray u of the list form: its run of entries [p0, p0 + cnt) - rows of the compact regions; cnt = 0: none listed.
+// The second search starts at the first one's result and ends n_samples entries on at the latest.
+__device__ __forceinline__ void unit_entries(const InputGradListArgs& a, int64_t u, int64_t& p0, int& cnt) {
+    int count = *a.count;
+    count = count < 0 ? 0 : count > a.capacity ? a.capacity : count;
+    const int e0 = list_lower_bound(a.list, 0, count, u * a.n_samples);
+    const int end = count - e0 < a.n_samples ? count : e0 + a.n_samples;
+    p0 = e0;
+    cnt = list_lower_bound(a.list, e0, end, (u + 1) * a.n_samples) - e0;
 }
 
 // Lanes 0..5 write a ray's (g_o | g_d) from the ray's reduced sums (every lane holds them): so = sum g_pos,
@@ -106,8 +142,9 @@ __device__ __forceinline__ void store_ray(const InputGradArgs& a, int64_t ray, i
 // =========================================================================================
 // sin kinds: raw xyz / dir inputs, three columns per consuming layer
 // =========================================================================================
-template <bool RAYS>
-__global__ __launch_bounds__(256) void input_grad_lin_kernel(InputGradArgs a) {
+template <bool RAYS, bool LIST = false>
+__global__ __launch_bounds__(256) void input_grad_lin_kernel(InputGradArgsOf<LIST> a) {
+    static_assert(RAYS || !LIST, "the list form is a ray form");
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const bool dir_lane = a.Wd && 4 * lane < a.dir_rows;
@@ -123,9 +160,10 @@ __global__ __launch_bounds__(256) void input_grad_lin_kernel(InputGradArgs a) {
         }
     const int64_t stride = (int64_t)gridDim.x * 4;
     for (int64_t u = (int64_t)blockIdx.x * 4 + wave; u < a.units; u += stride) {
-        int64_t p0, group;
+        int64_t p0, group = 0;
         int cnt;
-        unit_points<RAYS>(a, u, p0, cnt, group);
+        if constexpr (LIST) unit_entries(a, u, p0, cnt);
+        else unit_points<RAYS>(a, u, p0, cnt, group);
         float4 g0 = {1.f, 1.f, 1.f, 1.f}, gd = {1.f, 1.f, 1.f, 1.f};
         if (a.film) {                                     // gamma of the input layer and of the rgb hidden layer
             const float* row = a.film + group * ((int64_t)a.film_rows * kFilmRow);
@@ -151,7 +189,9 @@ __global__ __launch_bounds__(256) void input_grad_lin_kernel(InputGradArgs a) {
 #pragma unroll
             for (int j = 0; j < 3; ++j) gv[j] = t.x * wd[0][j] + t.y * wd[1][j] + t.z * wd[2][j] + t.w * wd[3][j];
             if constexpr (RAYS) {
-                const float zs = a.z[p];
+                float zs;
+                if constexpr (LIST) zs = a.z[a.list[p]];                // p is the row; the depth is the point's
+                else zs = a.z[p];
 #pragma unroll
                 for (int j = 0; j < 3; ++j) { so[j] += gp[j]; sz[j] += zs * gp[j]; sv[j] += gv[j]; }
             } else {
@@ -197,8 +237,32 @@ __device__ __forceinline__ void pe_contract(float (&dE)[4], const float* const (
     }
 }
 
-template <bool RAYS>
-__global__ __launch_bounds__(kPeThreads) void input_grad_pe_kernel(InputGradArgs a) {
+// A listed point's terms added to the per-lane sums of its ray with the roundings of the plain ray form, whose compiled code
+// is the contract (tools/isa_diff.py holds it; tests/test_gpu_occupancy_pose.py holds this to it bit for bit).  There the
+// compiler fused the multiply into the add for the FIRST point of every 4-point step - tz = fma(z, t, tz) and
+// tv = fma(coef_d, dE_d e_d, tv) - and for the other three it adds the rounded products; tp takes the rounded t always.  The plain
+// form's steps start at the samples s = 0, 4, 8 .. of the ray, the list form's at every fourth ENTRY of the run: `lead` says
+// whether this point's sample index is a multiple of 4, so a listed sample is rounded as the plain form rounds it, wherever it
+// falls in the run.  Nothing here may be contracted further, hence the pragma; the two fused terms are spelled fmaf.
+__device__ __forceinline__ void add_as_plain_step(bool lead, float dEp, float ep, float coef_p, float dEd, float ed, float coef_d,
+                                                  float zs, float& tp, float& tz, float& tv) {
+#pragma clang fp contract(off)
+    const float t = (dEp * ep) * coef_p;
+    const float pd = dEd * ed;
+    tp = tp + t;
+    if (lead) {
+        tz = fmaf(zs, t, tz);
+        tv = fmaf(coef_d, pd, tv);
+    } else {
+        const float zt = zs * t, v = pd * coef_d;
+        tz = tz + zt;
+        tv = tv + v;
+    }
+}
+
+template <bool RAYS, bool LIST = false>
+__global__ __launch_bounds__(kPeThreads) void input_grad_pe_kernel(InputGradArgsOf<LIST> a) {
+    static_assert(RAYS || !LIST, "the list form is a ray form");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* L0 = lds;
     float* L5 = lds + kPePosFloats;
@@ -231,9 +295,10 @@ __global__ __launch_bounds__(kPeThreads) void input_grad_pe_kernel(InputGradArgs
 
     const int64_t stride = (int64_t)gridDim.x * (kPeThreads / 64);
     for (int64_t u = (int64_t)blockIdx.x * (kPeThreads / 64) + wave; u < a.units; u += stride) {
-        int64_t p0, group;
+        int64_t p0, group = 0;
         int cnt;
-        unit_points<RAYS>(a, u, p0, cnt, group);
+        if constexpr (LIST) unit_entries(a, u, p0, cnt);
+        else unit_points<RAYS>(a, u, p0, cnt, group);
         float tp = 0.f, tz = 0.f, tv = 0.f;                // ray form: per-lane sums over the ray's samples
         for (int s0 = 0; s0 < cnt; s0 += 4) {
             int64_t p[4];
@@ -257,7 +322,13 @@ __global__ __launch_bounds__(kPeThreads) void input_grad_pe_kernel(InputGradArgs
                 const float ep = a.e_pos[p[q] * 64 + mate_p], ed = a.e_dir[p[q] * 32 + mate_d];
                 const float t = in ? (dEp[q] * ep) * coef_p : 0.f;
                 const float v = in ? (dEd[q] * ed) * coef_d : 0.f;
-                if constexpr (RAYS) {
+                if constexpr (LIST) {
+                    if (in) {                                           // wave-uniform; p[q] is the row, the depth is the point's
+                        const int pt = a.list[p[q]];
+                        add_as_plain_step(((pt - (int)u * a.n_samples) & 3) == 0, dEp[q], ep, coef_p, dEd[q], ed, coef_d, a.z[pt], tp,
+                                          tz, tv);
+                    }
+                } else if constexpr (RAYS) {
                     const float zs = a.z[p[q]];
                     tp += t; tz += zs * t; tv += v;
                 } else if (in) {                                        // wave-uniform
@@ -289,13 +360,15 @@ __global__ __launch_bounds__(kPeThreads) void input_grad_pe_kernel(InputGradArgs
 // =========================================================================================
 static int launch_input_grad(int kind_in, const float* const* params, const float* film, const float* acts,
                              const float* grads, const float* rays, const float* z, int64_t n_groups, int64_t units_pg,
-                             int n_samples, bool ray_form, int accumulate, float* out, hipStream_t stream) {
+                             int n_samples, bool ray_form, int accumulate, float* out, hipStream_t stream,
+                             const int* list = nullptr, const int* count = nullptr) {
     const int kind = canon_kind(kind_in);
     const FieldKind& K = field_kind(kind);
     const int64_t ppg = ray_form ? units_pg * n_samples : units_pg;
     const int64_t P = n_groups * ppg;
     if (P == 0) return 0;
-    InputGradArgs a = {};
+    InputGradListArgs a = {};                           // the plain forms take its base
+    a.list = list; a.count = count; a.capacity = (int)P;    // list form: P = n * S fits an int (the caller checks)
     a.rays = rays; a.z = z; a.out = out; a.n_samples = n_samples; a.accumulate = accumulate;
     a.points_per_group = ppg;
     a.units_per_group = ray_form ? units_pg : (ppg + kChunk - 1) / kChunk;
@@ -316,14 +389,16 @@ static int launch_input_grad(int kind_in, const float* const* params, const floa
             if (q.cls == SRC_E_DIR) a.e_dir = q.X;
         }
     });
+    const InputGradArgs& plain = a;
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     if (pe) {
         const size_t lds = ((a.W5 ? 2 : 1) * kPePosFloats + kPeDirFloats) * sizeof(float);
         static_assert((2 * kPePosFloats + kPeDirFloats) * sizeof(float) <= 160 * 1024, "the weight columns fit a CU's LDS");
-        const void* fn = ray_form ? (const void*)input_grad_pe_kernel<true> : (const void*)input_grad_pe_kernel<false>;
-        static PerDeviceOnce attr_once[2];
-        const int arc = attr_once[ray_form].run([&]() {
+        const void* fn = list ? (const void*)input_grad_pe_kernel<true, true>
+                         : ray_form ? (const void*)input_grad_pe_kernel<true> : (const void*)input_grad_pe_kernel<false>;
+        static PerDeviceOnce attr_once[3];
+        const int arc = attr_once[list ? 2 : ray_form].run([&]() {
             if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)((2 * kPePosFloats + kPeDirFloats) * sizeof(float))) != hipSuccess) {
                 set_error("hipFuncSetAttribute(input_grad_pe) failed"); return -2;
@@ -334,14 +409,16 @@ static int launch_input_grad(int kind_in, const float* const* params, const floa
         const int64_t per_block = kPeThreads / 64;
         const int64_t want = (a.units + per_block - 1) / per_block;
         const dim3 grid((unsigned)(want < cus ? want : cus));
-        if (ray_form) hipLaunchKernelGGL(input_grad_pe_kernel<true>, grid, dim3(kPeThreads), lds, stream, a);
-        else hipLaunchKernelGGL(input_grad_pe_kernel<false>, grid, dim3(kPeThreads), lds, stream, a);
+        if (list) hipLaunchKernelGGL((input_grad_pe_kernel<true, true>), grid, dim3(kPeThreads), lds, stream, a);
+        else if (ray_form) hipLaunchKernelGGL(input_grad_pe_kernel<true>, grid, dim3(kPeThreads), lds, stream, plain);
+        else hipLaunchKernelGGL(input_grad_pe_kernel<false>, grid, dim3(kPeThreads), lds, stream, plain);
         return check_launch("input_grad_pe");
     }
     const int64_t want = (a.units + 3) / 4, cap = (int64_t)cus * 8;
     const dim3 grid((unsigned)(want < cap ? want : cap));
-    if (ray_form) hipLaunchKernelGGL(input_grad_lin_kernel<true>, grid, dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL(input_grad_lin_kernel<false>, grid, dim3(256), 0, stream, a);
+    if (list) hipLaunchKernelGGL((input_grad_lin_kernel<true, true>), grid, dim3(256), 0, stream, a);
+    else if (ray_form) hipLaunchKernelGGL(input_grad_lin_kernel<true>, grid, dim3(256), 0, stream, plain);
+    else hipLaunchKernelGGL(input_grad_lin_kernel<false>, grid, dim3(256), 0, stream, plain);
     return check_launch("input_grad_lin");
 }
 
@@ -356,6 +433,13 @@ int launch_field_input_grad_rays(int kind, const float* const* params, const flo
                                  int64_t rays_per_group, int n_samples, int accumulate, float* g_rays, hipStream_t stream) {
     return launch_input_grad(kind, params, film, acts, grads, rays, z, n_groups, rays_per_group, n_samples, true, accumulate,
                              g_rays, stream);
+}
+
+int launch_field_input_grad_rays_list(int kind, const float* const* params, const float* acts, const float* grads,
+                                      const int* list, const int* count, const float* rays, const float* z, int64_t n,
+                                      int n_samples, int accumulate, float* g_rays, hipStream_t stream) {
+    return launch_input_grad(kind, params, nullptr, acts, grads, rays, z, 1, n, n_samples, true, accumulate, g_rays, stream,
+                             list, count);
 }
 
 }  // namespace mi

@@ -126,6 +126,12 @@ SIGNATURES = {
     "mi_render_rays_occupancy_backward": (_int, [_int, _vp, _int, _vp, _int, _vp, _i64, _int, _int, _vp, _i64, _vp, _i64,
                                                  _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
                                                  _vp, _i64, ctypes.POINTER(_int), _vp]),
+    "mi_field_input_grad_rays_list": (_int, [_int, ctypes.POINTER(_vp), _int, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _int,
+                                             _int, _vp, _vp]),
+    "mi_render_rays_occupancy_backward_rays": (_int, [_int, _vp, _int, _vp, _int, _vp, _i64, _int, _int, _vp, _i64, _vp, _i64,
+                                                      _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                                                      _vp, _i64, ctypes.POINTER(_int), ctypes.POINTER(_vp), _int,
+                                                      ctypes.POINTER(_vp), _int, _vp, _vp]),
     "mi_occupancy_clip_rays": (_int, [_vp, ctypes.POINTER(_int), ctypes.POINTER(_f32), ctypes.POINTER(_f32), _vp, _i64, _f32, _f32,
                                       _int, _int, _vp, _vp]),
     "mi_sample_coarse_bounds": (_int, [_i64, _vp, _int, _vp, _u64, _u64, _vp, _vp]),

@@ -14,7 +14,8 @@ REBUILT.  Warm-up steps without a grid, the grid's `dilate` and the rebuild peri
 (examples/train_nerf_occupancy.py shows one).
 
 From C: mi_render_rays_occupancy_train / mi_render_rays_occupancy_backward (include/mi_render.h).  NeRF, SirenNeRF and
-TinyNeRF fields; not built: FiLM kinds, generic callables, gradients to the rays (mirender.pose), render_image_dist.
+TinyNeRF fields; not built: FiLM kinds, generic callables, render_image_dist.  Gradients to the rays with a grid are
+mirender.pose's: pose.render_rays(grid=) runs this module's forward and mi_render_rays_occupancy_backward_rays.
 """
 from __future__ import annotations
 
@@ -64,7 +65,9 @@ class _OccupancyRenderFn(torch.autograd.Function):
 
     @staticmethod
     @once_differentiable
-    def backward(ctx, g_rgb_c, g_depth_c, g_acc_c, g_rgb_f, g_depth_f, g_acc_f, _g_counts=None):
+    def backward(ctx, g_rgb_c, g_depth_c, g_acc_c, g_rgb_f, g_depth_f, g_acc_f, _g_counts=None, g_rays=None):
+        # g_rays: never passed by autograd; mirender.pose's function calls this with a tensor [n,2,3] that the _rays form of the
+        # backward (same launches, plus the ray parts behind each composite and each field) overwrites with dL/d(rays)
         pf_c, pf_f, n, nc, nf = ctx.pf_c, ctx.pf_f, ctx.n, ctx.nc, ctx.nf
         dev = pf_c.device
         # not _lib.f32c: under once_differentiable the cotangents carry no graph, and a detach each is time on this step's clock
@@ -76,29 +79,35 @@ class _OccupancyRenderFn(torch.autograd.Function):
                                nf)
         bws, bws_g = _lib.guarded(bws_bytes, torch.uint8, dev)
         written = ctypes.c_int(0)
-        _lib.call("mi_render_rays_occupancy_backward", dev, pf_c.kind, _lib.ptr(pf_c.refresh_bwd()), pf_f.kind,
-                  None if ctx.shared else _lib.ptr(pf_f.refresh_bwd()), int(ctx.shared), _lib.ptr(ctx.rays), n, nc, nf,
-                  _lib.ptr(ctx.ws), ctx.ws.numel(), _lib.ptr(ctx.saved), ctx.saved.numel(), *[_lib.ptr(g) for g in gs],
-                  _lib.ptr_array(grads_c), None if grads_f is None else _lib.ptr_array(grads_f), _lib.ptr(bws), bws_bytes,
-                  ctypes.byref(written))
+        ray_args = ()
+        if g_rays is not None:                          # the live parameters, as mi_field_input_grad_rays takes them
+            src_c, src_f = pf_c._sources(), None if ctx.shared else pf_f._sources()
+            ray_args = (_lib.ptr_array(src_c), len(src_c), None if src_f is None else _lib.ptr_array(src_f),
+                        0 if src_f is None else len(src_f), _lib.ptr(g_rays))
+        _lib.call("mi_render_rays_occupancy_backward" + ("" if g_rays is None else "_rays"), dev, pf_c.kind,
+                  _lib.ptr(pf_c.refresh_bwd()), pf_f.kind, None if ctx.shared else _lib.ptr(pf_f.refresh_bwd()), int(ctx.shared),
+                  _lib.ptr(ctx.rays), n, nc, nf, _lib.ptr(ctx.ws), ctx.ws.numel(), _lib.ptr(ctx.saved), ctx.saved.numel(),
+                  *[_lib.ptr(g) for g in gs], _lib.ptr_array(grads_c), None if grads_f is None else _lib.ptr_array(grads_f),
+                  _lib.ptr(bws), bws_bytes, ctypes.byref(written), *ray_args)
         _check_kept(ctx)
         _lib.check_guard(bws_g, "occupancy backward workspace (mi_render_occupancy_backward_workspace_bytes)")
         gc = tuple(grads_c) if written.value & 1 else (None,) * len(grads_c)
         gf = () if ctx.shared else (tuple(grads_f) if written.value & 2 else (None,) * len(grads_f))
-        return (None,) * 12 + gc + gf
+        return (None, None, g_rays) + (None,) * 9 + gc + gf
 
 
-def _check(grid, coarse_model, fine_model, pf_c, pf_f, rays):
-    """What training with an occupancy grid is not built for, said by name."""
+def _check(grid, coarse_model, fine_model, pf_c, pf_f, rays, rays_may_need_grad=False):
+    """What training with an occupancy grid is not built for, said by name.  rays_may_need_grad: mirender.pose's call, which
+    produces that gradient."""
     if pf_c is None or pf_f is None:
         raise _lib.MiRenderError("training with an occupancy grid is not built for generic callables (models with no known "
                                  "layout): both models must be NeRF, SirenNeRF or TinyNeRF fields")
     if fields.is_film(pf_c.kind) or fields.is_film(pf_f.kind):
         raise _lib.MiRenderError("training with an occupancy grid is not built for FiLM kinds (a FiLM field's table is per "
                                  "image, a per-scene grid has no meaning there)")
-    if isinstance(rays, torch.Tensor) and rays.requires_grad and torch.is_grad_enabled():
-        raise _lib.MiRenderError("training with an occupancy grid is not built for gradients to the rays (mirender.pose "
-                                 "renders without a grid)")
+    if not rays_may_need_grad and isinstance(rays, torch.Tensor) and rays.requires_grad and torch.is_grad_enabled():
+        raise _lib.MiRenderError("occupancy_train.render_rays is not built for gradients to the rays (an opt-in of "
+                                 "mirender.pose: pose.render_rays(grid=))")
     if grid is None:
         raise _lib.MiRenderError("occupancy_train.render_rays needs grid= (without one, call render_core.render_rays)")
     if torch.device(grid.device) != torch.device(pf_c.device):
@@ -118,7 +127,7 @@ def render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, fi
     both passes sample inside it (mi_render_rays_occupancy_clip_train); the backward is the same call, it reads the depths.
     Under torch.no_grad() (or with no parameter that requires a gradient) this is render_core.render_rays(grid=).
     A cell that is empty in `grid` gets no gradient and cannot fill up until the caller rebuilds the grid.
-    Not built: FiLM kinds, generic callables, gradients to the rays (mirender.pose), render_image_dist."""
+    Not built: FiLM kinds, generic callables, render_image_dist; gradients to the rays: pose.render_rays(grid=)."""
     pf_c, pf_f = fields.as_packed_field(coarse_model), fields.as_packed_field(fine_model)
     _check(grid, coarse_model, fine_model, pf_c, pf_f, rays)
     dev = pf_c.device
@@ -129,6 +138,19 @@ def render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, fi
                                             ray0=ray0, grid=grid, return_counts=return_counts, clip_probes=clip_probes,
                                             clip_pad=clip_pad)
     rays = ops._f32c(torch.as_tensor(rays), dev).reshape(-1, 2, 3)
+    if rays.shape[0] == 0:                          # no rays: render_core's empty outputs, hanging off the parameters
+        outs = render_core.render_rays(rays, near, far, coarse_model, fine_model, nc, nf, t_rand=t_rand, seed=seed, ray0=ray0)
+        return (outs, torch.zeros((0, 2), dtype=torch.int32, device=dev)) if return_counts else outs
+    outs, counts = _render_calls(_OccupancyRenderFn, pf_c, pf_f, rays, near, far, nc, nf, grid, t_rand, seed, ray0, max_points,
+                                 clip_probes, clip_pad)
+    return (outs, counts) if return_counts else outs
+
+
+def _render_calls(fn, pf_c, pf_f, rays, near, far, nc, nf, grid, t_rand, seed, ray0, max_points, clip_probes, clip_pad):
+    """The calls of one render_rays over rays [n,2,3] (n > 0, fp32 on the fields' device): consecutive slices of at most
+    max_points // (2 Nc + Nf) rays through `fn` (_OccupancyRenderFn, or mirender.pose's form of it, whose graph reaches the
+    rays): (the six outputs, the counts [calls, 2])."""
+    dev = pf_c.device
     n = rays.shape[0]
     if seed is None and t_rand is None:
         seed = render_core._fresh_seed()
@@ -136,16 +158,12 @@ def render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, fi
     params = fields.pair_params(pf_c, pf_f)
     clip = None if clip_probes is None else (int(clip_probes), int(clip_pad))
     step = n if not max_points else max(1, int(max_points) // (2 * nc + nf))
-    if n == 0:                                      # no rays: render_core's empty outputs, hanging off the parameters
-        outs = render_core.render_rays(rays, near, far, coarse_model, fine_model, nc, nf, t_rand=t_rand, seed=seed, ray0=ray0)
-        return (outs, torch.zeros((0, 2), dtype=torch.int32, device=dev)) if return_counts else outs
     pieces, counts = [], []
     for r0 in range(0, n, max(step, 1)):
         r1 = min(n, r0 + step)
-        res = _OccupancyRenderFn.apply(pf_c, pf_f, rays[r0:r1].contiguous(), float(near), float(far), nc, nf, grid,
-                                       None if t_rand is None else t_rand[r0:r1].contiguous(), int(seed or 0),
-                                       int(ray0) + r0, clip, *params)
+        res = fn.apply(pf_c, pf_f, rays[r0:r1].contiguous(), float(near), float(far), nc, nf, grid,
+                       None if t_rand is None else t_rand[r0:r1].contiguous(), int(seed or 0), int(ray0) + r0, clip, *params)
         pieces.append(res[:6])
         counts.append(res[6])
     outs = pieces[0] if len(pieces) == 1 else tuple(torch.cat([p[k] for p in pieces]) for k in range(6))
-    return (outs, torch.stack(counts)) if return_counts else outs
+    return outs, torch.stack(counts)

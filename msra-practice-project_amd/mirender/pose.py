@@ -15,13 +15,18 @@ Outputs, parameter gradients and FiLM-table gradients are the bits render_core.r
 comes from mi_composite_bwd_rays and mi_field_input_grad_rays (csrc/ray_grad.hip), range by range inside the same backward.
 The depths carry no gradient to the rays: the stratified ones do not depend on them, the resampled ones are detached
 (render.py:141) and the sort only permutes.
+
+With an occupancy grid (`grid=`, optionally `clip_probes=`; NeRF, SirenNeRF and TinyNeRF fields): the forward is
+occupancy_train's, the backward mi_render_rays_occupancy_backward_rays.  The rule: an unlisted sample's raw
+is the constant 0 and sends the rays nothing; a listed sample sends them exactly what it sends without a grid; occupancy and
+the clipped bounds are piecewise constant in the rays and carry no gradient.
 """
 from __future__ import annotations
 
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import _lib, autograd, fields, ops, render_core
+from . import _lib, autograd, fields, occupancy_train, ops, render_core
 
 
 class _GetRaysFn(torch.autograd.Function):
@@ -75,6 +80,19 @@ class _RenderRaysPoseFn(torch.autograd.Function):
         return autograd._RenderRaysFn.backward(ctx, *grads, g_rays=g_rays)
 
 
+class _OccupancyRenderPoseFn(torch.autograd.Function):
+    """occupancy_train._OccupancyRenderFn whose backward also returns dL/d(rays): the same forward, and the _rays form of the
+    same backward call (mi_render_rays_occupancy_backward_rays), which overwrites g_rays in full."""
+
+    forward = staticmethod(occupancy_train._OccupancyRenderFn.forward)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        g_rays = torch.empty_like(ctx.rays) if ctx.needs_input_grad[2] else None
+        return occupancy_train._OccupancyRenderFn.backward(ctx, *grads, g_rays=g_rays)
+
+
 def _fused_pair(coarse_model, fine_model, what: str):
     pf_c, pf_f = fields.as_packed_field(coarse_model), fields.as_packed_field(fine_model)
     if pf_c is None or pf_f is None:
@@ -84,10 +102,39 @@ def _fused_pair(coarse_model, fine_model, what: str):
     return pf_c, pf_f
 
 
+def _render_rays_grid(rays, near, far, coarse_model, fine_model, nc, nf, grid, t_rand, seed, film, ray0, clip_probes, clip_pad,
+                      max_points):
+    """render_rays with a grid: occupancy_train's checks but the one on the rays, its forward, the _rays backward."""
+    if film is not None:
+        raise _lib.MiRenderError("pose.render_rays: film= with grid= is not built (training with an occupancy grid is not "
+                                 "built for FiLM kinds)")
+    pf_c, pf_f = fields.as_packed_field(coarse_model), fields.as_packed_field(fine_model)
+    occupancy_train._check(grid, coarse_model, fine_model, pf_c, pf_f, rays, rays_may_need_grad=True)
+    kw = dict(grid=grid, t_rand=t_rand, seed=seed, ray0=ray0, max_points=max_points, clip_probes=clip_probes, clip_pad=clip_pad)
+    wants = isinstance(rays, torch.Tensor) and rays.requires_grad and torch.is_grad_enabled()
+    if not wants or rays.numel() == 0:
+        detached = rays.detach() if isinstance(rays, torch.Tensor) else rays
+        return occupancy_train.render_rays(detached, near, far, coarse_model, fine_model, nc, nf, **kw)
+    rays = rays.to(device=pf_c.device, dtype=torch.float32).reshape(-1, 2, 3).contiguous()      # the graph to `rays` survives
+    return occupancy_train._render_calls(_OccupancyRenderPoseFn, pf_c, pf_f, rays, near, far, nc, nf, grid,
+                                         None if t_rand is None else t_rand.detach(), seed, ray0, max_points, clip_probes,
+                                         clip_pad)[0]
+
+
 def render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, fine_sample_num, *,
-                t_rand=None, seed=None, film=None, ray0=0):
+                t_rand=None, seed=None, film=None, ray0=0, grid=None, clip_probes=None, clip_pad=1, max_points=None):
     """render_core.render_rays (same arguments, same six outputs bit for bit, same gradients to the parameters and the
-    FiLM table) whose graph additionally reaches `rays` [N,2,3]."""
+    FiLM table) whose graph additionally reaches `rays` [N,2,3].
+
+    grid= (an OccupancyGrid; clip_probes / clip_pad / max_points as occupancy_train.render_rays takes them): the outputs and
+    parameter gradients of occupancy_train.render_rays, and the gradient to the rays under the same rule - only the samples in
+    occupied cells send one.  NeRF, SirenNeRF and TinyNeRF fields; film= is refused.  The calls that max_points cuts the rays
+    into are disjoint ray slices, so the cut changes no bit of rays.grad."""
+    if grid is not None:
+        return _render_rays_grid(rays, near, far, coarse_model, fine_model, int(coarse_sample_num), int(fine_sample_num), grid,
+                                 t_rand, seed, film, ray0, clip_probes, clip_pad, max_points)
+    if clip_probes is not None or max_points is not None:
+        raise _lib.MiRenderError("pose.render_rays: clip_probes= and max_points= belong to grid= (there is no grid to clip to)")
     pf_c, pf_f = _fused_pair(coarse_model, fine_model, "pose.render_rays")
     wants = isinstance(rays, torch.Tensor) and rays.requires_grad and torch.is_grad_enabled()
     if not wants or rays.numel() == 0:
@@ -105,9 +152,10 @@ def render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, fi
 
 
 def render_image_tensor(width, height, focal, c2w, near, far, coarse_model, fine_model, coarse_sample_num,
-                        fine_sample_num, chunk=None, *, t_rand=None, seed=None):
+                        fine_sample_num, chunk=None, *, t_rand=None, seed=None, grid=None, clip_probes=None, clip_pad=1):
     """render_core.render_image_tensor (rgb of the fine pass [H,W,3]) with a graph to `c2w`: get_rays and render_rays of
-    this module over the frame's chunks, the jitter keyed by each chunk's first ray like render_core._render_image_device."""
+    this module over the frame's chunks, the jitter keyed by each chunk's first ray like render_core._render_image_device.
+    grid= / clip_probes= / clip_pad=: render_rays' keywords, handed to every chunk."""
     width, height = int(width), int(height)
     total = width * height
     step = render_core.MAX_RAYS_PER_LAUNCH if not chunk else max(int(chunk), 2)
@@ -118,7 +166,8 @@ def render_image_tensor(width, height, focal, c2w, near, far, coarse_model, fine
         m = min(step, total - i)
         rays = get_rays(width, height, focal, c2w, ray0=i, n=m)
         outs = render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, fine_sample_num,
-                           t_rand=None if t_rand is None else t_rand[i:i + m], seed=seed, ray0=i)
+                           t_rand=None if t_rand is None else t_rand[i:i + m], seed=seed, ray0=i, grid=grid,
+                           clip_probes=clip_probes, clip_pad=clip_pad)
         parts.append(outs[3])
     return (parts[0] if len(parts) == 1 else torch.cat(parts)).reshape(height, width, 3)
 
