@@ -219,6 +219,24 @@ def query(name: str, *args) -> int:
     return n
 
 
+def capturing() -> bool:
+    """Is the calling thread's current stream being captured into a graph?  On a host without a device torch's query raises
+    instead of answering; nothing can be captured there (the callers go on to their own "no ROCm device" errors)."""
+    try:
+        return torch.cuda.is_current_stream_capturing()
+    except RuntimeError:
+        return False
+
+
+def refuse_capture(who: str, why: str):
+    """Raise MiRenderError when the calling thread's current stream is being captured into a graph.  For the calls that hand
+    the library a value the HOST computes anew on every call (a step count, an epoch, a fresh seed): a graph records the
+    value of the captured call and every replay would repeat it - wrong results, no error.  Called before the function's
+    first launch or allocation, so a refused call leaves the capture as it was."""
+    if capturing():
+        raise MiRenderError(f"{who} cannot be captured into a graph: {why}")
+
+
 def ptr_array(tensors):
     """void*[len] of the tensors' device pointers (NULL for a None entry); valid while the caller keeps the tensors."""
     return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])

@@ -184,7 +184,12 @@ class LiveOccupancyGrid:
         """One update.  cells=None: a sweep, every cell at one jittered point.  Otherwise `cells` rows are drawn, the first
         cells - int(cells * occupied_share) uniformly over the grid and the others among the currently occupied cells.  The
         points are evaluated in batches of `max_batch` by the fused kernel, as from_field does, and all rows' sigma is folded
-        in one call and packed into the grid's bits in one call."""
+        in one call and packed into the grid's bits in one call.
+        Not under stream capture (MiRenderError): `updates` is counted on the host and goes to the kernel by value."""
+        _lib.refuse_capture("LiveOccupancyGrid.update", "the epoch of its random words (`updates`) is counted on the host and goes "
+                            "to the kernel by value, so every replay would draw the captured update's points again; call "
+                            "update() eagerly between replays (it rewrites grid.bits in place, which a graph that holds the "
+                            "grid sees)")
         pf = _grid_field(model, "LiveOccupancyGrid.update")
         g, dev = self.grid, self.grid.device
         if pf.device != dev:

@@ -128,6 +128,7 @@ def render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, fi
     Under torch.no_grad() (or with no parameter that requires a gradient) this is render_core.render_rays(grid=).
     A cell that is empty in `grid` gets no gradient and cannot fill up until the caller rebuilds the grid.
     Not built: FiLM kinds, generic callables, render_image_dist; gradients to the rays: pose.render_rays(grid=)."""
+    seed = render_core._call_seed(seed, t_rand, "occupancy_train.render_rays")
     pf_c, pf_f = fields.as_packed_field(coarse_model), fields.as_packed_field(fine_model)
     _check(grid, coarse_model, fine_model, pf_c, pf_f, rays)
     dev = pf_c.device
@@ -152,8 +153,7 @@ def _render_calls(fn, pf_c, pf_f, rays, near, far, nc, nf, grid, t_rand, seed, r
     rays): (the six outputs, the counts [calls, 2])."""
     dev = pf_c.device
     n = rays.shape[0]
-    if seed is None and t_rand is None:
-        seed = render_core._fresh_seed()
+    seed = render_core._call_seed(seed, t_rand)              # render_rays / pose.render_rays resolved it on entry: then as given
     t_rand = ops._t_rand(t_rand, n, nc, dev)
     params = fields.pair_params(pf_c, pf_f)
     clip = None if clip_probes is None else (int(clip_probes), int(clip_pad))

@@ -221,13 +221,16 @@ def field_eval_rays(pf: PackedField, rays: torch.Tensor, z: torch.Tensor, film=N
 class _Workspace:
     """Grow-only scratch for mi_render_rays (no allocation inside the library), one per (device, stream): launches
     on one stream are ordered, so they can share it; concurrent callers (DataParallel's thread per GPU,
-    pi_GAN/train.py:50, or user threads on their own streams) never do."""
+    pi_GAN/train.py:50, or user threads on their own streams) never do.  Eager calls only: a call under stream capture
+    neither reads nor fills this cache (_workspace), so no graph ever holds the address of a buffer kept here."""
     bufs: dict = {}
 
     @classmethod
     def release(cls, device=None):
         """Drop the scratch of `device` (all devices if None): it only grows otherwise (3.4 GB after an 800x800 frame).
-        Safe at any time between calls; the next render_rays allocates what it needs."""
+        Safe at any time between calls, captured graphs included: a captured call's scratch is a buffer of the graph's own
+        memory pool, not one of these, so dropping or growing the cache takes nothing from under a replay.  The next eager
+        render_rays allocates what it needs."""
         want = None if device is None else cls._name(device)
         for key in [k for k in cls.bufs if want is None or k[0] == want]:
             del cls.bufs[key]
@@ -253,9 +256,15 @@ class _Workspace:
 def _workspace(device, nbytes):
     """(workspace of at least `nbytes`, what _lib.check_guard takes after the call): the cached one of this (device,
     stream); with MI_DEBUG_GUARDS=1 a fresh one of exactly `nbytes` with a sentinel tail, so an overrun cannot hide in
-    what an earlier, larger call left behind."""
+    what an earlier, larger call left behind.
+    Under stream capture: a fresh buffer of exactly `nbytes` that the cache never sees.  The graph's private pool owns it
+    like any temporary of a captured torch op.  A cached buffer's address baked into a graph would be freed under the graph
+    by the next larger call on the stream or by _Workspace.release(), and the following replay would write into memory the
+    allocator has handed to someone else."""
     if _lib.guards_on():
         return _lib.guarded(nbytes, torch.uint8, device)
+    if _lib.capturing():
+        return torch.empty(int(nbytes), dtype=torch.uint8, device=device), None
     return _Workspace.get(device, nbytes), None
 
 

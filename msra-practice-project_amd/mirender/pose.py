@@ -130,6 +130,7 @@ def render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, fi
     parameter gradients of occupancy_train.render_rays, and the gradient to the rays under the same rule - only the samples in
     occupied cells send one.  NeRF, SirenNeRF and TinyNeRF fields; film= is refused.  The calls that max_points cuts the rays
     into are disjoint ray slices, so the cut changes no bit of rays.grad."""
+    seed = render_core._call_seed(seed, t_rand, "pose.render_rays")
     if grid is not None:
         return _render_rays_grid(rays, near, far, coarse_model, fine_model, int(coarse_sample_num), int(fine_sample_num), grid,
                                  t_rand, seed, film, ray0, clip_probes, clip_pad, max_points)
@@ -143,8 +144,6 @@ def render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, fi
                                        t_rand=t_rand, seed=seed, film=film, ray0=ray0)
     # not ops._f32c, which detaches: the graph to `rays` has to survive into the Function
     rays = rays.to(device=pf_c.device, dtype=torch.float32).reshape(-1, 2, 3).contiguous()
-    if seed is None and t_rand is None:
-        seed = render_core._fresh_seed()
     film = fields.resolve_film(film, (pf_c, coarse_model), (pf_f, fine_model))
     return _RenderRaysPoseFn.apply(pf_c, pf_f, rays, float(near), float(far), int(coarse_sample_num), int(fine_sample_num),
                                    film, None if t_rand is None else t_rand.detach(), int(seed or 0), int(ray0),
@@ -156,11 +155,10 @@ def render_image_tensor(width, height, focal, c2w, near, far, coarse_model, fine
     """render_core.render_image_tensor (rgb of the fine pass [H,W,3]) with a graph to `c2w`: get_rays and render_rays of
     this module over the frame's chunks, the jitter keyed by each chunk's first ray like render_core._render_image_device.
     grid= / clip_probes= / clip_pad=: render_rays' keywords, handed to every chunk."""
+    seed = render_core._call_seed(seed, t_rand, "pose.render_image_tensor")
     width, height = int(width), int(height)
     total = width * height
     step = render_core.MAX_RAYS_PER_LAUNCH if not chunk else max(int(chunk), 2)
-    if seed is None and t_rand is None:
-        seed = render_core._fresh_seed()
     parts = []
     for i in range(0, total, step):
         m = min(step, total - i)

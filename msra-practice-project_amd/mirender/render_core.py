@@ -49,6 +49,20 @@ def _fresh_seed() -> int:
     return int(torch.randint(0, 2 ** 62, (1,), device="cpu").item())
 
 
+def _call_seed(seed, t_rand, who="render_rays"):
+    """The seed of one call: the caller's; a fresh host draw when neither `seed` nor `t_rand` says what the jitter is.  That
+    draw is refused under stream capture (before the call launches or allocates anything): a seed goes to the kernels by
+    value, so a graph would repeat the captured call's jitter on every replay while an eager loop draws a new one per call.
+    An explicit seed= may be captured - its replays repeat that jitter, which is what the caller wrote; a loop that wants new
+    jitter per replay passes t_rand [n,Nc] and refills it in place."""
+    if seed is None and t_rand is None:
+        _lib.refuse_capture(who, "with neither seed= nor t_rand= it draws a fresh seed on the host, which goes to the kernels "
+                            "by value, so every replay would repeat the captured call's jitter; pass t_rand [n,Nc] and refill it "
+                            "in place between replays (or an explicit seed=, whose jitter every replay then repeats)")
+        return _fresh_seed()
+    return seed
+
+
 def get_rays(width, height, focal, c2w):
     """nerf/render.py:7-23.  Returns NumPy (rays_o, rays_d) [H,W,3] fp32 like the reference; the
     arithmetic runs in the HIP ray generator (bit-identical to the NumPy expression)."""
@@ -140,12 +154,11 @@ def _render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, f
     """render_rays; coarse_outputs=False lets the fused inference path skip what only the coarse outputs need
     (ops.render_rays_fused), which may then return None in their slots.  The fine outputs are the same bits.
     return_counts=True (with a grid): (the outputs, int32 [calls, 2], the samples each pass evaluated; [0, 2] without rays)."""
+    seed = _call_seed(seed, t_rand)
     dev = _device_of(coarse_model, fine_model, rays=rays)
     # not ops._f32c, which detaches: on the generic path the graph to `rays` has to survive
     rays = torch.as_tensor(rays).to(device=dev, dtype=torch.float32).reshape(-1, 2, 3).contiguous()
     nc, nf = int(coarse_sample_num), int(fine_sample_num)
-    if seed is None and t_rand is None:
-        seed = _fresh_seed()
     pf_c, pf_f = fields.as_packed_field(coarse_model), fields.as_packed_field(fine_model)
     if clip_probes is not None and grid is None:
         raise _lib.MiRenderError("clip_probes= clips each ray's range to an occupancy grid: it needs grid=")
@@ -197,13 +210,12 @@ def _render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, f
 def _render_image_device(width, height, focal, pose, near, far, coarse_model, fine_model, nc, nf, chunk,
                          t_rand=None, seed=None, ray0=0, n_rays=None, grid=None, clip_probes=None, clip_pad=1):
     """Rays [ray0, ray0+n) of the image -> device tensors (rgb[n,3], depth[n], acc[n]) of the FINE pass."""
+    seed = _call_seed(seed, t_rand, "render_image")
     dev = _device_of(coarse_model, fine_model)
     total = width * height
     n_rays = total - ray0 if n_rays is None else n_rays
     step = MAX_RAYS_PER_LAUNCH if not chunk else max(int(chunk), 2)
     step = max(step, 16384)
-    if seed is None and t_rand is None:
-        seed = _fresh_seed()
     parts = []
     for i in range(ray0, ray0 + n_rays, step):
         m = min(step, ray0 + n_rays - i)

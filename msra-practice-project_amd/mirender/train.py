@@ -147,6 +147,11 @@ class FusedAdam:
 
     @torch.no_grad()
     def step(self):
+        # before any launch or allocation: a refused step leaves the capture, the moments and the step count as they were
+        _lib.refuse_capture("FusedAdam.step", "the step count t lives on the host and the bias corrections -lr / (1 - beta1^t), "
+                            "sqrt(1 - beta2^t) go to the kernel by value, so every replay would repeat step t of the capture; "
+                            "call step() eagerly between replays (it rewrites the parameters and both packed streams in "
+                            "place, which a graph that holds them sees)")
         g = self.param_groups[0]
         lr, (beta1, beta2), eps = float(g["lr"]), g["betas"], float(g["eps"])
         if g.get("weight_decay") or g.get("amsgrad") or g.get("maximize"):
