@@ -1,14 +1,15 @@
 // occupancy_path.hip - rendering and training with an occupancy grid through the C ABI (include/mi_render.h):
 // mi_render_rays_occupancy, mi_render_rays_occupancy_train, mi_render_rays_occupancy_backward (and its _rays form, which also
 // gives dL/d(rays): occupancy_backward) and their size queries.
-// Both forwards run the sequence of every render path (run_render_passes, render_path.h) with one field step (occupancy_forward):
+// The forwards are one body (occupancy_render) over one struct of their arguments (OccArgs).  It runs the sequence of every render
+// path (run_render_passes, render_path.h) with one field step (occupancy_forward):
 // per pass, mark the samples in occupied cells into a device-counted list and evaluate the field at the listed points alone.
 // Training differs in three values: the ordered mark, a field that keeps the listed points' layer inputs, and a list per pass
 // (OccLists), which the backward reads.  The grid checks of every call that reads one (occupancy_grid_args) and the list-driven
 // field launch (eval_rays_list) are here too, for the stage wrappers of api.hip as well.  It is deliberately small:
 // one range per pass, nothing recomputed, one group, no FiLM; one field for both passes runs as two passes of that field over
 // all their listed points (no merge, as at inference) and its two gradient sums are added.
-// The clipped forwards (mi_render_rays_occupancy_clip / _clip_train) are the same two bodies with one launch in front: each
+// The clipped forwards (mi_render_rays_occupancy_clip / _clip_train) are the same body with one launch in front: each
 // ray's range clipped to the grid (launch_occupancy_clip_rays) into a bounds region behind the lists, which both samplers read.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -122,12 +123,24 @@ static int check_call(const char* fn, const char* doing, int kind_c, int kind_f,
     return grid ? occupancy_grid_args(fn, bits, dims, lo, inv_cell, grid) : MI_OK;
 }
 
+// The arguments of a grid-driven call, in the order in which the four forwards' extern "C" signatures name them (z_lin: null
+// in a clipped call, which takes probes and pad in its place; saved: the training forwards alone).  The backward fills in
+// what check_buffers reads: the kinds, the sizes, the workspace and the saved rows.
+struct OccArgs {
+    int kind_c; const float* packed_c; int kind_f; const float* packed_f;
+    const float* rays; int64_t n; float near_, far_; int nc, nf;
+    const float *z_lin, *u_lin, *t_rand; uint64_t seed, ray0;
+    const uint32_t* bits; const int* dims; const float *lo, *inv_cell;
+    float *rgb_c, *depth_c, *acc_c, *rgb_f, *depth_f, *acc_f; int* evaluated;
+    void* workspace; int64_t workspace_bytes; void* saved; int64_t saved_bytes;
+    void* stream;
+};
+
 // The caller's buffers against the size queries: the workspace always, the saved rows from the training forward on, the
-// backward workspace in the backward.
+// backward workspace (with `shared`, which sizes it) in the backward.
 enum OccCall { OCC_RENDER, OCC_TRAIN, OCC_BACKWARD };
-static int check_buffers(const char* fn, OccCall call, int kind_c, int kind_f, bool shared, int64_t n, int nc, int nf,
-                         const void* workspace, int64_t workspace_bytes, const void* saved = nullptr, int64_t saved_bytes = 0,
-                         const void* bwd_workspace = nullptr, int64_t bwd_workspace_bytes = 0, bool clipped = false) {
+static int check_buffers(const char* fn, OccCall call, const OccArgs& a, bool clipped, bool shared = false,
+                         const void* bwd_workspace = nullptr, int64_t bwd_workspace_bytes = 0) {
     const auto refused = [&](const char* what, const void* p, int64_t have, int64_t need, const char* query) {
         if (p && have >= need) return false;
         set_error("%s: %s of %lld bytes, %s %lld", fn, what, (long long)have, query, (long long)need);
@@ -135,16 +148,16 @@ static int check_buffers(const char* fn, OccCall call, int kind_c, int kind_f, b
     };
     const bool train = call != OCC_RENDER;
     // A workspace may be larger than asked for: the backward of a clipped forward gets the forward's, bounds region included.
-    if (refused("workspace", workspace, workspace_bytes,
-                RenderWorkspace(n, nc, nf).base_bytes() + OccLists(train, n, nc, nf).bytes() + (clipped ? clip_bounds_bytes(n) : 0),
+    if (refused("workspace", a.workspace, a.workspace_bytes,
+                RenderWorkspace(a.n, a.nc, a.nf).base_bytes() + OccLists(train, a.n, a.nc, a.nf).bytes() + (clipped ? clip_bounds_bytes(a.n) : 0),
                 clipped ? (train ? "mi_render_workspace_bytes + mi_render_occupancy_train_extra_bytes + mi_render_occupancy_clip_extra_bytes say"
                                  : "mi_render_workspace_bytes + mi_render_occupancy_extra_bytes + mi_render_occupancy_clip_extra_bytes say")
                 : train ? "mi_render_workspace_bytes + mi_render_occupancy_train_extra_bytes say"
                         : "mi_render_workspace_bytes + mi_render_occupancy_extra_bytes say") ||
-        (train && refused("saved buffer", saved, saved_bytes, saved_bytes_of(kind_c, kind_f, n, nc, nf),
+        (train && refused("saved buffer", a.saved, a.saved_bytes, saved_bytes_of(a.kind_c, a.kind_f, a.n, a.nc, a.nf),
                           "mi_render_occupancy_train_saved_bytes says")) ||
         (call == OCC_BACKWARD && refused("backward workspace", bwd_workspace, bwd_workspace_bytes,
-                                         OccBwdLayout(kind_c, kind_f, shared, n, nc, nf).bytes(),
+                                         OccBwdLayout(a.kind_c, a.kind_f, shared, a.n, a.nc, a.nf).bytes(),
                                          "mi_render_occupancy_backward_workspace_bytes says")))
         return MI_EINVAL;
     return MI_OK;
@@ -205,62 +218,35 @@ static int check_clip(const char* fn, const OccClip* clip, float near_, float fa
     return clip ? occupancy_clip_args(fn, near_, far_, clip->probes, clip->pad) : MI_OK;
 }
 
-// mi_render_rays_occupancy and, with clip, mi_render_rays_occupancy_clip
-static int render_inference(const char* fn, OccClip* clip, int kind_coarse, const float* packed_coarse, int kind_fine,
-                            const float* packed_fine, const float* rays, int64_t n, float near_, float far_, int n_coarse, int n_fine,
-                            const float* z_lin, const float* u_lin, const float* t_rand, uint64_t seed, uint64_t ray0,
-                            const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell, float* rgb_c, float* depth_c,
-                            float* acc_c, float* rgb_f, float* depth_f, float* acc_f, int* evaluated, void* workspace,
-                            int64_t workspace_bytes, void* stream) {
+// The four grid-driven forwards: mi_render_rays_occupancy (OCC_RENDER) and mi_render_rays_occupancy_train (OCC_TRAIN), each
+// with `clip` as its _clip form.  Inference takes the coarse outputs as optional and leaves a grid on another device to the
+// launch; training demands all six outputs and the saved rows, marks in ascending order and keeps the listed points' layer inputs.
+static int occupancy_render(const char* fn, OccCall call, OccClip* clip, const OccArgs& a) {
+    const bool train = call == OCC_TRAIN;
     OccupancyGridArgs grid;
-    if (int rc = check_call(fn, "rendering", kind_coarse, kind_fine, n, n_coarse, n_fine, bits, dims, lo, inv_cell, &grid)) return rc;
-    if (int rc = check_clip(fn, clip, near_, far_)) return rc;
-    // the coarse outputs are optional, as in mi_render_rays: without rgb_c, depth_c / acc_c each may be null too
-    if (!packed_coarse || !packed_fine || !rays || !workspace || (rgb_c && (!depth_c || !acc_c)) || !rgb_f || !depth_f || !acc_f) {
+    if (int rc = check_call(fn, train ? "training" : "rendering", a.kind_c, a.kind_f, a.n, a.nc, a.nf, a.bits, a.dims, a.lo, a.inv_cell, &grid)) return rc;
+    if (int rc = check_clip(fn, clip, a.near_, a.far_)) return rc;
+    // inference: the coarse outputs are optional, as in mi_render_rays: without rgb_c, depth_c / acc_c each may be null too.
+    // Its null workspace is refused here; training's by check_buffers, behind the n == 0 return.
+    const bool missing = train ? !a.rgb_c || !a.depth_c || !a.acc_c : !a.workspace || (a.rgb_c && (!a.depth_c || !a.acc_c));
+    if (!a.packed_c || !a.packed_f || !a.rays || missing || !a.rgb_f || !a.depth_f || !a.acc_f) {
         set_error("%s: null pointer argument", fn);
         return MI_EINVAL;
     }
-    if (n == 0) return MI_OK;                                  // no rays: nothing to launch, no buffer is touched
-    if (int rc = check_buffers(fn, OCC_RENDER, kind_coarse, kind_fine, false, n, n_coarse, n_fine, workspace, workspace_bytes, nullptr, 0,
-                               nullptr, 0, clip != nullptr)) return rc;
-    const RenderWorkspace layout(n, n_coarse, n_fine);
-    const OccLists lists(false, n, n_coarse, n_fine);
-    const OccLists::Regions r = lists.carve(workspace, layout.base_bytes());
-    if (clip) clip->bounds = (float*)((char*)workspace + layout.base_bytes() + lists.bytes());
-    const OccPass pass[2] = {{kind_coarse, packed_coarse, r.list[0], r.counts, nullptr}, {kind_fine, packed_fine, r.list[1], r.counts + 1, nullptr}};
-    const RenderIO io{rays, near_, far_, z_lin, u_lin, t_rand, seed, ray0, rgb_c, depth_c, acc_c, rgb_f, depth_f, acc_f};
-    return occupancy_forward(fn, pass, false, grid, n, n_coarse, n_fine, io, clip, evaluated, layout.carve(workspace), (hipStream_t)stream);
-}
-
-// mi_render_rays_occupancy_train and, with clip, mi_render_rays_occupancy_clip_train
-static int render_training(const char* fn, OccClip* clip, int kind_coarse, const float* packed_coarse, int kind_fine,
-                           const float* packed_fine, const float* rays, int64_t n, float near_, float far_, int n_coarse, int n_fine,
-                           const float* z_lin, const float* u_lin, const float* t_rand, uint64_t seed, uint64_t ray0,
-                           const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell, float* rgb_c, float* depth_c,
-                           float* acc_c, float* rgb_f, float* depth_f, float* acc_f, int* evaluated, void* workspace,
-                           int64_t workspace_bytes, void* saved, int64_t saved_bytes, void* stream) {
-    OccupancyGridArgs grid;
-    if (int rc = check_call(fn, "training", kind_coarse, kind_fine, n, n_coarse, n_fine, bits, dims, lo, inv_cell, &grid)) return rc;
-    if (int rc = check_clip(fn, clip, near_, far_)) return rc;
-    if (!packed_coarse || !packed_fine || !rays || !rgb_c || !depth_c || !acc_c || !rgb_f || !depth_f || !acc_f) {
-        set_error("%s: null pointer argument", fn);
-        return MI_EINVAL;
-    }
-    if (n == 0) return MI_OK;
-    if (int rc = check_buffers(fn, OCC_TRAIN, kind_coarse, kind_fine, false, n, n_coarse, n_fine, workspace, workspace_bytes, saved,
-                               saved_bytes, nullptr, 0, clip != nullptr)) return rc;
+    if (a.n == 0) return MI_OK;                                // no rays: nothing to launch, no buffer is touched
+    if (int rc = check_buffers(fn, call, a, clip != nullptr)) return rc;
     // Training only: a step is one call, so one host query per step.  Inference renders a frame in many chunks and would pay
     // the query per chunk; nobody has measured that, so mi_render_rays_occupancy leaves a grid on another device to the launch.
-    if (int rc = check_grid_device(fn, bits)) return rc;
-    const RenderWorkspace layout(n, n_coarse, n_fine);
-    const OccLists lists(true, n, n_coarse, n_fine);
-    const OccLists::Regions r = lists.carve(workspace, layout.base_bytes());
-    if (clip) clip->bounds = (float*)((char*)workspace + layout.base_bytes() + lists.bytes());
-    float* acts = (float*)saved;
-    const OccPass pass[2] = {{kind_coarse, packed_coarse, r.list[0], r.counts, acts},
-                             {kind_fine, packed_fine, r.list[1], r.counts + 1, acts + saved_floats_coarse(kind_coarse, n, n_coarse)}};
-    const RenderIO io{rays, near_, far_, z_lin, u_lin, t_rand, seed, ray0, rgb_c, depth_c, acc_c, rgb_f, depth_f, acc_f};
-    return occupancy_forward(fn, pass, true, grid, n, n_coarse, n_fine, io, clip, evaluated, layout.carve(workspace), (hipStream_t)stream);
+    if (train) if (int rc = check_grid_device(fn, a.bits)) return rc;
+    const RenderWorkspace layout(a.n, a.nc, a.nf);
+    const OccLists lists(train, a.n, a.nc, a.nf);
+    const OccLists::Regions r = lists.carve(a.workspace, layout.base_bytes());
+    if (clip) clip->bounds = (float*)((char*)a.workspace + layout.base_bytes() + lists.bytes());
+    float* acts_c = train ? (float*)a.saved : nullptr;
+    float* acts_f = train ? acts_c + saved_floats_coarse(a.kind_c, a.n, a.nc) : nullptr;
+    const OccPass pass[2] = {{a.kind_c, a.packed_c, r.list[0], r.counts, acts_c}, {a.kind_f, a.packed_f, r.list[1], r.counts + 1, acts_f}};
+    const RenderIO io{a.rays, a.near_, a.far_, a.z_lin, a.u_lin, a.t_rand, a.seed, a.ray0, a.rgb_c, a.depth_c, a.acc_c, a.rgb_f, a.depth_f, a.acc_f};
+    return occupancy_forward(fn, pass, train, grid, a.n, a.nc, a.nf, io, clip, a.evaluated, layout.carve(a.workspace), (hipStream_t)a.stream);
 }
 
 // g_rays = 0 ahead of the launches that add to it.  A kernel, not hipMemsetAsync: captured into a graph, the memset of n * 24
@@ -320,8 +306,11 @@ static int occupancy_backward(const char* fn, int kind_coarse, const float* pack
         if (int rc = check_field_grads(fn, f && !shared ? "fine" : "coarse", kinds[f], packed_bwd[f], grads[f])) return rc;
         if (g_rays) if (int rc = check_field_params(fn, f && !shared ? "fine" : "coarse", kinds[f], params[f], n_params[f])) return rc;
     }
-    if (int rc = check_buffers(fn, OCC_BACKWARD, kind_coarse, kind_fine, shared != 0, n, n_coarse, n_fine, workspace, workspace_bytes,
-                               saved, saved_bytes, bwd_workspace, bwd_workspace_bytes)) return rc;
+    OccArgs a = {};
+    a.kind_c = kind_coarse; a.kind_f = kind_fine; a.n = n; a.nc = n_coarse; a.nf = n_fine;
+    a.workspace = const_cast<void*>(workspace); a.workspace_bytes = workspace_bytes;
+    a.saved = const_cast<void*>(saved); a.saved_bytes = saved_bytes;
+    if (int rc = check_buffers(fn, OCC_BACKWARD, a, false, shared != 0, bwd_workspace, bwd_workspace_bytes)) return rc;
     hipStream_t hs = (hipStream_t)stream;
     if (g_rays) if (int rc = launch_clear_floats(n * 6, g_rays, hs)) return rc;
     if (!want_c && !want_f) return MI_OK;
@@ -387,15 +376,17 @@ int64_t mi_render_occupancy_backward_workspace_bytes(int kind_coarse, int kind_f
     return OccBwdLayout(kind_coarse, kind_fine, shared != 0, n, n_coarse, n_fine).bytes();
 }
 
+// each of the four forwards fills OccArgs in its members' order: its own parameters, null for what it does not take
 int mi_render_rays_occupancy(int kind_coarse, const float* packed_coarse, int kind_fine, const float* packed_fine,
                              const float* rays, int64_t n, float near_, float far_, int n_coarse, int n_fine,
                              const float* z_lin, const float* u_lin, const float* t_rand, uint64_t seed, uint64_t ray0,
                              const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell, float* rgb_c,
                              float* depth_c, float* acc_c, float* rgb_f, float* depth_f, float* acc_f, int* evaluated,
                              void* workspace, int64_t workspace_bytes, void* stream) {
-    return render_inference("mi_render_rays_occupancy", nullptr, kind_coarse, packed_coarse, kind_fine, packed_fine, rays, n, near_, far_,
-                            n_coarse, n_fine, z_lin, u_lin, t_rand, seed, ray0, bits, dims, lo, inv_cell, rgb_c, depth_c, acc_c, rgb_f,
-                            depth_f, acc_f, evaluated, workspace, workspace_bytes, stream);
+    return occupancy_render("mi_render_rays_occupancy", OCC_RENDER, nullptr,
+                            {kind_coarse, packed_coarse, kind_fine, packed_fine, rays, n, near_, far_, n_coarse, n_fine, z_lin, u_lin,
+                             t_rand, seed, ray0, bits, dims, lo, inv_cell, rgb_c, depth_c, acc_c, rgb_f, depth_f, acc_f, evaluated,
+                             workspace, workspace_bytes, nullptr, 0, stream});
 }
 
 int mi_render_rays_occupancy_clip(int kind_coarse, const float* packed_coarse, int kind_fine, const float* packed_fine,
@@ -405,9 +396,10 @@ int mi_render_rays_occupancy_clip(int kind_coarse, const float* packed_coarse, i
                                   float* depth_c, float* acc_c, float* rgb_f, float* depth_f, float* acc_f, int* evaluated,
                                   void* workspace, int64_t workspace_bytes, void* stream) {
     OccClip clip{probes, pad, nullptr};
-    return render_inference("mi_render_rays_occupancy_clip", &clip, kind_coarse, packed_coarse, kind_fine, packed_fine, rays, n, near_,
-                            far_, n_coarse, n_fine, nullptr, u_lin, t_rand, seed, ray0, bits, dims, lo, inv_cell, rgb_c, depth_c, acc_c,
-                            rgb_f, depth_f, acc_f, evaluated, workspace, workspace_bytes, stream);
+    return occupancy_render("mi_render_rays_occupancy_clip", OCC_RENDER, &clip,
+                            {kind_coarse, packed_coarse, kind_fine, packed_fine, rays, n, near_, far_, n_coarse, n_fine, nullptr, u_lin,
+                             t_rand, seed, ray0, bits, dims, lo, inv_cell, rgb_c, depth_c, acc_c, rgb_f, depth_f, acc_f, evaluated,
+                             workspace, workspace_bytes, nullptr, 0, stream});
 }
 
 int mi_render_rays_occupancy_train(int kind_coarse, const float* packed_coarse, int kind_fine, const float* packed_fine,
@@ -416,9 +408,10 @@ int mi_render_rays_occupancy_train(int kind_coarse, const float* packed_coarse, 
                                    const uint32_t* bits, const int* dims, const float* lo, const float* inv_cell, float* rgb_c,
                                    float* depth_c, float* acc_c, float* rgb_f, float* depth_f, float* acc_f, int* evaluated,
                                    void* workspace, int64_t workspace_bytes, void* saved, int64_t saved_bytes, void* stream) {
-    return render_training("mi_render_rays_occupancy_train", nullptr, kind_coarse, packed_coarse, kind_fine, packed_fine, rays, n, near_,
-                           far_, n_coarse, n_fine, z_lin, u_lin, t_rand, seed, ray0, bits, dims, lo, inv_cell, rgb_c, depth_c, acc_c,
-                           rgb_f, depth_f, acc_f, evaluated, workspace, workspace_bytes, saved, saved_bytes, stream);
+    return occupancy_render("mi_render_rays_occupancy_train", OCC_TRAIN, nullptr,
+                            {kind_coarse, packed_coarse, kind_fine, packed_fine, rays, n, near_, far_, n_coarse, n_fine, z_lin, u_lin,
+                             t_rand, seed, ray0, bits, dims, lo, inv_cell, rgb_c, depth_c, acc_c, rgb_f, depth_f, acc_f, evaluated,
+                             workspace, workspace_bytes, saved, saved_bytes, stream});
 }
 
 int mi_render_rays_occupancy_clip_train(int kind_coarse, const float* packed_coarse, int kind_fine, const float* packed_fine,
@@ -428,9 +421,10 @@ int mi_render_rays_occupancy_clip_train(int kind_coarse, const float* packed_coa
                                         float* depth_c, float* acc_c, float* rgb_f, float* depth_f, float* acc_f, int* evaluated,
                                         void* workspace, int64_t workspace_bytes, void* saved, int64_t saved_bytes, void* stream) {
     OccClip clip{probes, pad, nullptr};
-    return render_training("mi_render_rays_occupancy_clip_train", &clip, kind_coarse, packed_coarse, kind_fine, packed_fine, rays, n,
-                           near_, far_, n_coarse, n_fine, nullptr, u_lin, t_rand, seed, ray0, bits, dims, lo, inv_cell, rgb_c, depth_c,
-                           acc_c, rgb_f, depth_f, acc_f, evaluated, workspace, workspace_bytes, saved, saved_bytes, stream);
+    return occupancy_render("mi_render_rays_occupancy_clip_train", OCC_TRAIN, &clip,
+                            {kind_coarse, packed_coarse, kind_fine, packed_fine, rays, n, near_, far_, n_coarse, n_fine, nullptr, u_lin,
+                             t_rand, seed, ray0, bits, dims, lo, inv_cell, rgb_c, depth_c, acc_c, rgb_f, depth_f, acc_f, evaluated,
+                             workspace, workspace_bytes, saved, saved_bytes, stream});
 }
 
 int mi_render_rays_occupancy_backward(int kind_coarse, const float* packed_bwd_coarse, int kind_fine,

@@ -247,9 +247,18 @@ def seed64(seed) -> int:
     return int(seed) & (2 ** 64 - 1)
 
 
-def f32c(t, device):
-    """A tensor as the library reads it: detached, fp32, contiguous, on `device` (None stays None)."""
-    return None if t is None else t.detach().to(device=device, dtype=torch.float32).contiguous()
+def f32c(t, device, detach=True):
+    """A tensor as the library reads it: detached, fp32, contiguous, on `device` (None stays None).  detach=False keeps the
+    graph to `t`: rays or points whose gradient the call's Function produces (mirender.pose), or a callable's own torch ops
+    (the generic path)."""
+    if t is None:
+        return None
+    return (t.detach() if detach else t).to(device=device, dtype=torch.float32).contiguous()
+
+
+def wants_grad(t) -> bool:
+    """Is `t` a tensor whose gradient a call made now would have to produce?"""
+    return isinstance(t, torch.Tensor) and t.requires_grad and torch.is_grad_enabled()
 
 
 # MI_DEBUG_GUARDS=1 (tests/test_gpu_guards.py): every buffer whose size the caller takes from a query gets GUARD_BYTES of a

@@ -14,6 +14,7 @@ import os
 import sys
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib, fields, ops
 from ._lib import f32c as _f32c, ptr as _p
@@ -145,7 +146,7 @@ def _field_backward(pf: fields.PackedField, rays, z, raw, g_raw, film, saved=Non
     """Gradients of one pass: (list of tensors shaped like pf.params, grad of the FiLM table or None).
     `saved` = {range index: layer inputs kept by the forward}; the other ranges re-run the forward first, so
     memory stays bounded whatever the batch.
-    `input_grad` (mirender.pose only; None leaves this function as it is for every other caller): a tensor that also
+    `input_grad` (None: no such output, and not one launch more): a tensor that also
     receives the gradient of the pass's geometric inputs, range by range from the buffers each range's backward leaves
     behind - g_rays [n,2,3], ADDED to, for points on rays (mi_field_input_grad_rays); g_x [M,6], overwritten, for
     free-standing points (mi_field_input_grad)."""
@@ -245,15 +246,6 @@ def _composite_bwd_rays(raw, z, rays, g_rgb, g_depth, g_acc, g_rays, g_w=None):
     _composite_bwd(raw, z, rays, g_rgb, g_depth, g_acc, g_w, g_rays, want_raw=False)
 
 
-def _check_versions(now, then, what: str):
-    """backward re-reads the live weights (transposed stream, recomputed ranges) while raw and the kept layer inputs date
-    from the forward: a parameter updated in between would give silently mixed gradients.  PyTorch raises for its own
-    saved tensors in this situation; so do we."""
-    if now != then:
-        raise RuntimeError(f"{what}: a field parameter was modified in place (or replaced) after the forward pass that "
-                           "this backward belongs to")
-
-
 class _RenderRaysFn(torch.autograd.Function):
     """render_rays with autograd.  Two shapes:
 
@@ -266,7 +258,11 @@ class _RenderRaysFn(torch.autograd.Function):
       sum of what the coarse outputs and the fine outputs send them, and each set goes through the field's backward once.
       48 -> 36 field evaluations per ray forward at 12+24 (pi_GAN C4), 120 -> 108 evaluation-equivalents per training step;
       the outputs are bit-identical to evaluating all Nc + Nf points (tests/test_gpu_shared_field.py), the gradients equal
-      up to the order of two partial sums."""
+      up to the order of two partial sums.
+
+    Rays that require grad (mirender.pose's call: render_rays_train detaches them) also get their gradient - from each
+    compositing pass (|d| in the distances: mi_composite_bwd_rays) and each field pass (o + d z, d / |d|:
+    mi_field_input_grad_rays), range by range inside the same backward; otherwise not one launch more."""
 
     @staticmethod
     def forward(ctx, pf_c, pf_f, rays, near, far, nc, nf, film, t_rand, seed, ray0, *params):
@@ -292,19 +288,19 @@ class _RenderRaysFn(torch.autograd.Function):
             z_f, raw_f, ctx.acts_f = z_c, raw_c, {}
         rgb_f, depth_f, acc_f, _ = ops.composite(raw_f, z_f, rays, want_weights=False)
         ctx.pf_c, ctx.pf_f, ctx.film = pf_c, pf_f, None if film is None else film.detach()
-        ctx.versions = (pf_c.versions(), pf_f.versions())
+        ctx.versions = fields.versions_of(pf_c, pf_f)
         ctx.n_c, ctx.shared, ctx.nc, ctx.nf = len(pf_c.params), shared, nc, nf
         ctx.save_for_backward(rays, z_c, raw_c, z_f, raw_f, z_s, raw_s, pos)
         ctx.set_materialize_grads(False)
         return rgb_c, depth_c, acc_c, rgb_f, depth_f, acc_f
 
     @staticmethod
-    def backward(ctx, g_rgb_c, g_depth_c, g_acc_c, g_rgb_f, g_depth_f, g_acc_f, g_rays=None):
-        # g_rays: never passed by autograd; mirender.pose's function calls this with zeros [n,2,3] that additionally receive
-        # the gradient to the rays - from each compositing pass (|d| in the distances) and each field pass (o + d z, d / |d|)
+    @once_differentiable
+    def backward(ctx, g_rgb_c, g_depth_c, g_acc_c, g_rgb_f, g_depth_f, g_acc_f):
         rays, z_c, raw_c, z_f, raw_f, z_s, raw_s, pos = ctx.saved_tensors
         pf_c, pf_f = ctx.pf_c, ctx.pf_f
-        _check_versions((pf_c.versions(), pf_f.versions()), ctx.versions, "render_rays backward")
+        fields.check_versions(ctx.versions, "render_rays backward", pf_c, pf_f)
+        g_rays = torch.zeros_like(rays) if ctx.needs_input_grad[2] else None          # every ray launch ADDS to it
 
         def composite_bwd(raw, z, gs):          # dL/d(raw) of one compositing pass, then its ray part; None: no gradient
             return _composite_bwd(raw, z, rays, *gs, g_rays=g_rays) if any(g is not None for g in gs) else None
@@ -357,7 +353,7 @@ def render_rays_train(pf_c, pf_f, rays, near, far, nc, nf, film, t_rand, seed, r
 # compositing / the fused side of a mixed pair continue it on the HIP kernels.
 # ----------------------------------------------------------------------------------------------------------------
 def _no_grad_input(t, what: str):
-    if isinstance(t, torch.Tensor) and t.requires_grad and torch.is_grad_enabled():
+    if _lib.wants_grad(t):
         raise _lib.MiRenderError(
             f"{what} requires grad, but the compositing / field kernels produce no gradient for it: on the reference's path "
             "depths and rays never carry one (the jitter is data, z_samples is detached at nerf/render.py:141)")
@@ -386,7 +382,7 @@ def composite(raw, z, rays, want_weights: bool = True):
     """ops.composite with autograd history towards `raw` (rgb[n,3], depth[n], acc[n], weights[n,S]|None)."""
     _no_grad_input(z, "z_vals")
     _no_grad_input(rays, "rays")
-    if not (torch.is_grad_enabled() and isinstance(raw, torch.Tensor) and raw.requires_grad):
+    if not _lib.wants_grad(raw):
         return ops.composite(raw, z, rays, want_weights)
     rgb, depth, acc, w = _CompositeFn.apply(raw, z, rays)
     return rgb, depth, acc, (w if want_weights else None)
@@ -395,29 +391,33 @@ def composite(raw, z, rays, want_weights: bool = True):
 class _FieldFn(torch.autograd.Function):
     """network(inputs) of ONE pass for a fused kind - on rays (`z` [n,S]) or on free-standing points (`z` None, `rays` =
     x [M,6]) - with gradients to its parameters and to the FiLM table: the saving forward / backward chain / dW GEMMs of
-    _RenderRaysFn, one pass at a time (a mixed pair's fused side; a fused module called on its own).  backward's
-    `input_grad` is never passed by autograd: mirender.pose's function over free-standing points calls it with True and
-    gets dL/dx (mi_field_input_grad) in the slot of `rays` as well."""
+    _RenderRaysFn, one pass at a time (a mixed pair's fused side; a fused module called on its own).  Free-standing points
+    that require grad (mirender.pose.field_eval_points: field_eval_points of this module refuses them) also get dL/dx
+    (mi_field_input_grad), in the slot of `rays`."""
 
     @staticmethod
     def forward(ctx, pf, rays, z, film, *params):
         raw, ctx.acts = _forward_pass(pf, rays, z, film, SAVE_FINE_BYTES)
-        ctx.pf, ctx.film, ctx.versions, ctx.points = pf, None if film is None else film.detach(), pf.versions(), z is None
+        ctx.pf, ctx.film, ctx.points = pf, None if film is None else film.detach(), z is None
+        ctx.versions = fields.versions_of(pf)
         ctx.save_for_backward(rays, raw) if z is None else ctx.save_for_backward(rays, raw, z)
         return raw
 
     @staticmethod
-    def backward(ctx, g_raw, input_grad=False):
+    @once_differentiable
+    def backward(ctx, g_raw):
         rays, raw = ctx.saved_tensors[:2]
         z = None if ctx.points else ctx.saved_tensors[2]
         pf = ctx.pf
-        _check_versions(pf.versions(), ctx.versions, "field backward")
-        g_x = torch.empty_like(rays) if input_grad else None
+        fields.check_versions(ctx.versions, "field backward", pf)
+        # field_eval_rays refuses rays that require grad, so an input gradient is one to free-standing points
+        assert ctx.points or not ctx.needs_input_grad[1]
+        g_x = torch.empty_like(rays) if ctx.needs_input_grad[1] else None
         grads, g_film = _field_backward(pf, rays, z, raw, g_raw.to(torch.float32).contiguous(), ctx.film, ctx.acts, g_x)
         ctx.acts = None
         if g_film is not None:
             g_film = g_film.reshape(ctx.film.shape) if ctx.needs_input_grad[3] else None
-        return (None, g_x if ctx.needs_input_grad[1] else None, None, g_film) + tuple(grads)
+        return (None, g_x, None, g_film) + tuple(grads)
 
 
 def field_eval_rays(pf, rays, z, film=None):

@@ -313,6 +313,21 @@ class PackedField:
         return self.packed
 
 
+def versions_of(*pfs) -> tuple:
+    """versions() of each field of a call, as its forward records them for check_versions."""
+    return tuple(pf.versions() for pf in pfs)
+
+
+def check_versions(then, what: str, *pfs):
+    """Every backward that re-reads the live weights (transposed stream, recomputed ranges, the parameters behind an input
+    gradient) calls this first, with what its forward recorded (versions_of): raw and the kept layer inputs date from the
+    forward, so a parameter updated in between would give silently mixed gradients.  PyTorch raises for its own saved tensors
+    in this situation; so do we."""
+    if versions_of(*pfs) != then:
+        raise RuntimeError(f"{what}: a field parameter was modified in place (or replaced) after the forward pass that "
+                           "this backward belongs to")
+
+
 _field_cache: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
 
 
@@ -418,6 +433,28 @@ def needs_graph(film, *pfs) -> bool:
     """Does a call over these fields (and this FiLM table, if any) have to record a graph?"""
     return torch.is_grad_enabled() and (any(p.requires_grad for pf in pfs for p in pf.params)
                                         or (isinstance(film, torch.Tensor) and film.requires_grad))
+
+
+# how each grid call has always named what it refuses: doing -> (callables without a layout, FiLM kinds)
+_GRID_CALL_NAMES = {"rendering": ("callables with no known layout (the generic path)", "FiLM fields"),
+                    "training": ("generic callables (models with no known layout)", "FiLM kinds")}
+
+
+def refuse_grid_call(doing: str, grid, pf_c, pf_f, own=None):
+    """What a call with an occupancy grid is not built for, said by name.  doing: "rendering" (render_core) / "training"
+    (occupancy_train, pose).  own(): the caller's own refusals, which rank behind the two about the models and ahead of the
+    one about the grid's device."""
+    callables, film_kinds = _GRID_CALL_NAMES[doing]
+    if pf_c is None or pf_f is None:
+        raise _lib.MiRenderError(f"{doing} with an occupancy grid is not built for {callables}: both models must be NeRF, "
+                                 "SirenNeRF or TinyNeRF fields")
+    if is_film(pf_c.kind) or is_film(pf_f.kind):
+        raise _lib.MiRenderError(f"{doing} with an occupancy grid is not built for {film_kinds} (a FiLM field's table is per "
+                                 "image, a per-scene grid has no meaning there)")
+    if own is not None:
+        own()
+    if torch.device(grid.device) != torch.device(pf_c.device):
+        raise _lib.MiRenderError(f"the occupancy grid is on {grid.device}, the fields are on {pf_c.device}")
 
 
 def eval_points(pf: PackedField, x: torch.Tensor, film: torch.Tensor | None = None) -> torch.Tensor:

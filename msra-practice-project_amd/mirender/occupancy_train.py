@@ -35,52 +35,48 @@ def _check_kept(ctx):
 
 class _OccupancyRenderFn(torch.autograd.Function):
     """One call of the pair over n rays: forward keeps the workspace (z, raw, weights, the two lists and counts) and the
-    compact saved rows; backward hands the six cotangents to mi_render_rays_occupancy_backward."""
+    compact saved rows; backward hands the six cotangents to mi_render_rays_occupancy_backward - to its _rays form, which also
+    gives dL/d(rays), exactly when the rays the Function was applied to require grad (mirender.pose's calls: render_rays of
+    this module detaches them)."""
 
     @staticmethod
     def forward(ctx, pf_c, pf_f, rays, near, far, nc, nf, grid, t_rand, seed, ray0, clip, *params):
         dev = pf_c.device
         n = rays.shape[0]
-        shared = pf_c is pf_f
-        outs = ops._render_outputs(n, dev)
-        counts = torch.zeros(2, dtype=torch.int32, device=dev)
-        zl, ul = ops._lin_tables(near, far, nc, nf, dev)
-        ws_bytes = (_lib.query("mi_render_workspace_bytes", n, nc, nf)
-                    + _lib.query("mi_render_occupancy_train_extra_bytes", n, nc, nf))
-        if clip is not None:                            # (probes, pad): the bounds lie behind what the backward reads
-            ws_bytes += _lib.query("mi_render_occupancy_clip_extra_bytes", n)
+        # clip = (probes, pad): the bounds lie behind what the backward reads
+        ws_bytes = ops._occupancy_workspace_bytes(True, clip, n, nc, nf)
         sv_bytes = _lib.query("mi_render_occupancy_train_saved_bytes", pf_c.kind, pf_f.kind, n, nc, nf)
         # owned by this call (not the shared inference workspace): the backward reads both
         ws, ctx.ws_g = _lib.guarded(ws_bytes, torch.uint8, dev)
         saved, ctx.saved_g = _lib.guarded(sv_bytes, torch.uint8, dev)
-        _lib.call("mi_render_rays_occupancy_train" if clip is None else "mi_render_rays_occupancy_clip_train", dev, pf_c.kind,
-                  _lib.ptr(pf_c.refresh()), pf_f.kind, _lib.ptr(pf_f.refresh()), _lib.ptr(rays), n, float(near), float(far), nc,
-                  nf, *((_lib.ptr(zl),) if clip is None else clip), _lib.ptr(ul), _lib.ptr(t_rand), _lib.seed64(seed), int(ray0),
-                  _lib.ptr(grid.bits), *grid.c_args(), *[_lib.ptr(o) for o in outs], _lib.ptr(counts), _lib.ptr(ws), ws_bytes, _lib.ptr(saved), sv_bytes)
+        outs, counts = ops._occupancy_forward(True, clip, pf_c, pf_f, rays, near, far, nc, nf, grid, t_rand, seed, ray0, ws,
+                                              ws_bytes, saved)
         _check_kept(ctx)
-        ctx.pf_c, ctx.pf_f, ctx.shared, ctx.n, ctx.nc, ctx.nf = pf_c, pf_f, shared, n, nc, nf
+        ctx.pf_c, ctx.pf_f, ctx.shared, ctx.n, ctx.nc, ctx.nf = pf_c, pf_f, pf_c is pf_f, n, nc, nf
+        ctx.versions = fields.versions_of(pf_c, pf_f)
         ctx.rays, ctx.ws, ctx.saved, ctx.counts = rays, ws, saved, counts
         ctx.mark_non_differentiable(counts)
         return (*outs, counts)
 
     @staticmethod
     @once_differentiable
-    def backward(ctx, g_rgb_c, g_depth_c, g_acc_c, g_rgb_f, g_depth_f, g_acc_f, _g_counts=None, g_rays=None):
-        # g_rays: never passed by autograd; mirender.pose's function calls this with a tensor [n,2,3] that the _rays form of the
-        # backward (same launches, plus the ray parts behind each composite and each field) overwrites with dL/d(rays)
+    def backward(ctx, g_rgb_c, g_depth_c, g_acc_c, g_rgb_f, g_depth_f, g_acc_f, _g_counts=None):
         pf_c, pf_f, n, nc, nf = ctx.pf_c, ctx.pf_f, ctx.n, ctx.nc, ctx.nf
+        fields.check_versions(ctx.versions, "render_rays backward", pf_c, pf_f)
         dev = pf_c.device
-        # not _lib.f32c: under once_differentiable the cotangents carry no graph, and a detach each is time on this step's clock
-        gs = [None if g is None else g.to(device=dev, dtype=torch.float32).contiguous()
-              for g in (g_rgb_c, g_depth_c, g_acc_c, g_rgb_f, g_depth_f, g_acc_f)]
+        # under once_differentiable the cotangents carry no graph, and a detach each is time on this step's clock
+        gs = [_lib.f32c(g, dev, detach=False) for g in (g_rgb_c, g_depth_c, g_acc_c, g_rgb_f, g_depth_f, g_acc_f)]
         grads_c = [torch.empty_like(p) for p in pf_c.params]
         grads_f = None if ctx.shared else [torch.empty_like(p) for p in pf_f.params]
         bws_bytes = _lib.query("mi_render_occupancy_backward_workspace_bytes", pf_c.kind, pf_f.kind, int(ctx.shared), n, nc,
                                nf)
         bws, bws_g = _lib.guarded(bws_bytes, torch.uint8, dev)
         written = ctypes.c_int(0)
-        ray_args = ()
-        if g_rays is not None:                          # the live parameters, as mi_field_input_grad_rays takes them
+        g_rays, ray_args = None, ()
+        if ctx.needs_input_grad[2]:
+            # the _rays form: the same launches, plus the ray parts behind each composite and each field, which overwrite g_rays
+            # in full; it takes the live parameters as mi_field_input_grad_rays does
+            g_rays = torch.empty_like(ctx.rays)
             src_c, src_f = pf_c._sources(), None if ctx.shared else pf_f._sources()
             ray_args = (_lib.ptr_array(src_c), len(src_c), None if src_f is None else _lib.ptr_array(src_f),
                         0 if src_f is None else len(src_f), _lib.ptr(g_rays))
@@ -96,22 +92,16 @@ class _OccupancyRenderFn(torch.autograd.Function):
         return (None, None, g_rays) + (None,) * 9 + gc + gf
 
 
-def _check(grid, coarse_model, fine_model, pf_c, pf_f, rays, rays_may_need_grad=False):
-    """What training with an occupancy grid is not built for, said by name.  rays_may_need_grad: mirender.pose's call, which
-    produces that gradient."""
-    if pf_c is None or pf_f is None:
-        raise _lib.MiRenderError("training with an occupancy grid is not built for generic callables (models with no known "
-                                 "layout): both models must be NeRF, SirenNeRF or TinyNeRF fields")
-    if fields.is_film(pf_c.kind) or fields.is_film(pf_f.kind):
-        raise _lib.MiRenderError("training with an occupancy grid is not built for FiLM kinds (a FiLM field's table is per "
-                                 "image, a per-scene grid has no meaning there)")
-    if not rays_may_need_grad and isinstance(rays, torch.Tensor) and rays.requires_grad and torch.is_grad_enabled():
-        raise _lib.MiRenderError("occupancy_train.render_rays is not built for gradients to the rays (an opt-in of "
-                                 "mirender.pose: pose.render_rays(grid=))")
-    if grid is None:
-        raise _lib.MiRenderError("occupancy_train.render_rays needs grid= (without one, call render_core.render_rays)")
-    if torch.device(grid.device) != torch.device(pf_c.device):
-        raise _lib.MiRenderError(f"the occupancy grid is on {grid.device}, the fields are on {pf_c.device}")
+def _check(grid, pf_c, pf_f, rays, rays_may_need_grad=False):
+    """What training with an occupancy grid is not built for (fields.refuse_grid_call) and, between its refusals, this
+    module's own.  rays_may_need_grad: mirender.pose's call, which produces that gradient."""
+    def own():
+        if not rays_may_need_grad and _lib.wants_grad(rays):
+            raise _lib.MiRenderError("occupancy_train.render_rays is not built for gradients to the rays (an opt-in of "
+                                     "mirender.pose: pose.render_rays(grid=))")
+        if grid is None:
+            raise _lib.MiRenderError("occupancy_train.render_rays needs grid= (without one, call render_core.render_rays)")
+    fields.refuse_grid_call("training", grid, pf_c, pf_f, own)
 
 
 def render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, fine_sample_num, *, grid, t_rand=None,
@@ -130,7 +120,7 @@ def render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, fi
     Not built: FiLM kinds, generic callables, render_image_dist; gradients to the rays: pose.render_rays(grid=)."""
     seed = render_core._call_seed(seed, t_rand, "occupancy_train.render_rays")
     pf_c, pf_f = fields.as_packed_field(coarse_model), fields.as_packed_field(fine_model)
-    _check(grid, coarse_model, fine_model, pf_c, pf_f, rays)
+    _check(grid, pf_c, pf_f, rays)
     dev = pf_c.device
     nc, nf = int(coarse_sample_num), int(fine_sample_num)
     if not fields.needs_graph(None, pf_c, pf_f):
@@ -142,15 +132,15 @@ def render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, fi
     if rays.shape[0] == 0:                          # no rays: render_core's empty outputs, hanging off the parameters
         outs = render_core.render_rays(rays, near, far, coarse_model, fine_model, nc, nf, t_rand=t_rand, seed=seed, ray0=ray0)
         return (outs, torch.zeros((0, 2), dtype=torch.int32, device=dev)) if return_counts else outs
-    outs, counts = _render_calls(_OccupancyRenderFn, pf_c, pf_f, rays, near, far, nc, nf, grid, t_rand, seed, ray0, max_points,
+    outs, counts = _render_calls(pf_c, pf_f, rays, near, far, nc, nf, grid, t_rand, seed, ray0, max_points,
                                  clip_probes, clip_pad)
     return (outs, counts) if return_counts else outs
 
 
-def _render_calls(fn, pf_c, pf_f, rays, near, far, nc, nf, grid, t_rand, seed, ray0, max_points, clip_probes, clip_pad):
+def _render_calls(pf_c, pf_f, rays, near, far, nc, nf, grid, t_rand, seed, ray0, max_points, clip_probes, clip_pad):
     """The calls of one render_rays over rays [n,2,3] (n > 0, fp32 on the fields' device): consecutive slices of at most
-    max_points // (2 Nc + Nf) rays through `fn` (_OccupancyRenderFn, or mirender.pose's form of it, whose graph reaches the
-    rays): (the six outputs, the counts [calls, 2])."""
+    max_points // (2 Nc + Nf) rays through _OccupancyRenderFn (whose backward reaches the rays when they require grad:
+    mirender.pose's call): (the six outputs, the counts [calls, 2])."""
     dev = pf_c.device
     n = rays.shape[0]
     seed = render_core._call_seed(seed, t_rand)              # render_rays / pose.render_rays resolved it on entry: then as given
@@ -161,7 +151,7 @@ def _render_calls(fn, pf_c, pf_f, rays, near, far, nc, nf, grid, t_rand, seed, r
     pieces, counts = [], []
     for r0 in range(0, n, max(step, 1)):
         r1 = min(n, r0 + step)
-        res = fn.apply(pf_c, pf_f, rays[r0:r1].contiguous(), float(near), float(far), nc, nf, grid,
+        res = _OccupancyRenderFn.apply(pf_c, pf_f, rays[r0:r1].contiguous(), float(near), float(far), nc, nf, grid,
                        None if t_rand is None else t_rand[r0:r1].contiguous(), int(seed or 0), int(ray0) + r0, clip, *params)
         pieces.append(res[:6])
         counts.append(res[6])

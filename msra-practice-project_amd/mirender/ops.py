@@ -316,21 +316,42 @@ def render_rays_occupancy(pf_c: PackedField, pf_f: PackedField, rays: torch.Tens
     rays = _f32c(rays, dev).reshape(-1, 2, 3)
     n = rays.shape[0]
     t_rand = _t_rand(t_rand, n, n_coarse, dev)
+    clip = None if clip_probes is None else (int(clip_probes), int(clip_pad))
+    ws_bytes = _occupancy_workspace_bytes(False, clip, n, n_coarse, n_fine)
+    ws, ws_g = _workspace(dev, ws_bytes)
+    outs, counts = _occupancy_forward(False, clip, pf_c, pf_f, rays, near, far, n_coarse, n_fine, grid, t_rand, seed, ray0, ws,
+                                      ws_bytes, coarse_outputs=coarse_outputs)
+    _lib.check_guard(ws_g, "mi_render_rays_occupancy workspace (mi_render_occupancy_extra_bytes)")
+    return tuple(outs), counts
+
+
+def _occupancy_workspace_bytes(train: bool, clip, n, n_coarse, n_fine) -> int:
+    """Bytes of the workspace of a grid-driven forward: the render workspace, the lists of the inference or of the training
+    call, and with `clip` the rays' bounds behind them (which the backward of a clipped training call reads past)."""
+    extra = "mi_render_occupancy_train_extra_bytes" if train else "mi_render_occupancy_extra_bytes"
+    nbytes = _lib.query("mi_render_workspace_bytes", n, n_coarse, n_fine) + _lib.query(extra, n, n_coarse, n_fine)
+    if clip is not None:
+        nbytes += _lib.query("mi_render_occupancy_clip_extra_bytes", n)
+    return nbytes
+
+
+def _occupancy_forward(train: bool, clip, pf_c, pf_f, rays, near, far, n_coarse, n_fine, grid, t_rand, seed, ray0, ws, ws_bytes,
+                       saved=None, coarse_outputs=True):
+    """The one call site of mi_render_rays_occupancy / _clip / _train / _clip_train: (the six outputs, counts int32 [2]).
+    rays [n,2,3] and t_rand as the library reads them; clip: (probes, pad), which take z_lin's place, or None; ws of
+    ws_bytes = _occupancy_workspace_bytes(train, clip, ...) and, with train, `saved` of mi_render_occupancy_train_saved_bytes:
+    the caller's buffers, whose lifetime and guards stay the caller's."""
+    dev = pf_c.device
+    n = rays.shape[0]
     outs = _render_outputs(n, dev, coarse_outputs)
     counts = torch.zeros(2, dtype=torch.int32, device=dev)
     zl, ul = _lin_tables(near, far, n_coarse, n_fine, dev)
-    ws_bytes = (_lib.query("mi_render_workspace_bytes", n, n_coarse, n_fine)
-                + _lib.query("mi_render_occupancy_extra_bytes", n, n_coarse, n_fine))
-    clip = clip_probes is not None
-    if clip:
-        ws_bytes += _lib.query("mi_render_occupancy_clip_extra_bytes", n)
-    ws, ws_g = _workspace(dev, ws_bytes)
-    _lib.call("mi_render_rays_occupancy_clip" if clip else "mi_render_rays_occupancy", dev, pf_c.kind, _p(pf_c.refresh()),
-              pf_f.kind, _p(pf_f.refresh()), _p(rays), n, float(near), float(far), n_coarse, n_fine,
-              *((int(clip_probes), int(clip_pad)) if clip else (_p(zl),)), _p(ul), _p(t_rand), _lib.seed64(seed), int(ray0),
-              _p(grid.bits), *grid.c_args(), *[_p(o) for o in outs], _p(counts), _p(ws), ws_bytes)
-    _lib.check_guard(ws_g, "mi_render_rays_occupancy workspace (mi_render_occupancy_extra_bytes)")
-    return tuple(outs), counts
+    _lib.call("mi_render_rays_occupancy" + ("" if clip is None else "_clip") + ("_train" if train else ""), dev, pf_c.kind,
+              _p(pf_c.refresh()), pf_f.kind, _p(pf_f.refresh()), _p(rays), n, float(near), float(far), n_coarse, n_fine,
+              *((_p(zl),) if clip is None else clip), _p(ul), _p(t_rand), _lib.seed64(seed), int(ray0), _p(grid.bits),
+              *grid.c_args(), *[_p(o) for o in outs], _p(counts), _p(ws), ws_bytes,
+              *((_p(saved), saved.numel()) if train else ()))
+    return outs, counts
 
 
 def render_rays_occupancy_clip(pf_c: PackedField, pf_f: PackedField, rays: torch.Tensor, near: float, far: float, n_coarse: int,

@@ -67,32 +67,6 @@ def get_rays(width, height, focal, c2w, *, ray0: int = 0, n: int | None = None) 
     return _GetRaysFn.apply(c2w, width, height, focal, int(ray0), n)
 
 
-class _RenderRaysPoseFn(torch.autograd.Function):
-    """autograd._RenderRaysFn whose backward also returns dL/d(rays): the same forward, the same backward calls, plus
-    mi_composite_bwd_rays after each compositing backward and mi_field_input_grad_rays after each range's field backward."""
-
-    forward = staticmethod(autograd._RenderRaysFn.forward)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, *grads):
-        g_rays = torch.zeros_like(ctx.saved_tensors[0]) if ctx.needs_input_grad[2] else None
-        return autograd._RenderRaysFn.backward(ctx, *grads, g_rays=g_rays)
-
-
-class _OccupancyRenderPoseFn(torch.autograd.Function):
-    """occupancy_train._OccupancyRenderFn whose backward also returns dL/d(rays): the same forward, and the _rays form of the
-    same backward call (mi_render_rays_occupancy_backward_rays), which overwrites g_rays in full."""
-
-    forward = staticmethod(occupancy_train._OccupancyRenderFn.forward)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, *grads):
-        g_rays = torch.empty_like(ctx.rays) if ctx.needs_input_grad[2] else None
-        return occupancy_train._OccupancyRenderFn.backward(ctx, *grads, g_rays=g_rays)
-
-
 def _fused_pair(coarse_model, fine_model, what: str):
     pf_c, pf_f = fields.as_packed_field(coarse_model), fields.as_packed_field(fine_model)
     if pf_c is None or pf_f is None:
@@ -102,23 +76,30 @@ def _fused_pair(coarse_model, fine_model, what: str):
     return pf_c, pf_f
 
 
+def _not_wanted(rays, render, *args, **kw):
+    """The prelude of both forms of render_rays: rays whose gradient nobody asks for (or none at all) go, detached, to the
+    module this one extends - `render`'s outputs then; None when the graph is to reach the rays."""
+    if _lib.wants_grad(rays) and rays.numel():
+        return None
+    return render(rays.detach() if isinstance(rays, torch.Tensor) else rays, *args, **kw)
+
+
 def _render_rays_grid(rays, near, far, coarse_model, fine_model, nc, nf, grid, t_rand, seed, film, ray0, clip_probes, clip_pad,
                       max_points):
-    """render_rays with a grid: occupancy_train's checks but the one on the rays, its forward, the _rays backward."""
+    """render_rays with a grid: occupancy_train's checks but the one on the rays, and its calls on rays that keep their graph,
+    whose backward is then the _rays form."""
     if film is not None:
         raise _lib.MiRenderError("pose.render_rays: film= with grid= is not built (training with an occupancy grid is not "
                                  "built for FiLM kinds)")
     pf_c, pf_f = fields.as_packed_field(coarse_model), fields.as_packed_field(fine_model)
-    occupancy_train._check(grid, coarse_model, fine_model, pf_c, pf_f, rays, rays_may_need_grad=True)
-    kw = dict(grid=grid, t_rand=t_rand, seed=seed, ray0=ray0, max_points=max_points, clip_probes=clip_probes, clip_pad=clip_pad)
-    wants = isinstance(rays, torch.Tensor) and rays.requires_grad and torch.is_grad_enabled()
-    if not wants or rays.numel() == 0:
-        detached = rays.detach() if isinstance(rays, torch.Tensor) else rays
-        return occupancy_train.render_rays(detached, near, far, coarse_model, fine_model, nc, nf, **kw)
-    rays = rays.to(device=pf_c.device, dtype=torch.float32).reshape(-1, 2, 3).contiguous()      # the graph to `rays` survives
-    return occupancy_train._render_calls(_OccupancyRenderPoseFn, pf_c, pf_f, rays, near, far, nc, nf, grid,
-                                         None if t_rand is None else t_rand.detach(), seed, ray0, max_points, clip_probes,
-                                         clip_pad)[0]
+    occupancy_train._check(grid, pf_c, pf_f, rays, rays_may_need_grad=True)
+    outs = _not_wanted(rays, occupancy_train.render_rays, near, far, coarse_model, fine_model, nc, nf, grid=grid, t_rand=t_rand,
+                       seed=seed, ray0=ray0, max_points=max_points, clip_probes=clip_probes, clip_pad=clip_pad)
+    if outs is not None:
+        return outs
+    rays = _lib.f32c(rays, pf_c.device, detach=False).reshape(-1, 2, 3)
+    return occupancy_train._render_calls(pf_c, pf_f, rays, near, far, nc, nf, grid, None if t_rand is None else t_rand.detach(),
+                                         seed, ray0, max_points, clip_probes, clip_pad)[0]
 
 
 def render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, fine_sample_num, *,
@@ -137,17 +118,16 @@ def render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, fi
     if clip_probes is not None or max_points is not None:
         raise _lib.MiRenderError("pose.render_rays: clip_probes= and max_points= belong to grid= (there is no grid to clip to)")
     pf_c, pf_f = _fused_pair(coarse_model, fine_model, "pose.render_rays")
-    wants = isinstance(rays, torch.Tensor) and rays.requires_grad and torch.is_grad_enabled()
-    if not wants or rays.numel() == 0:
-        detached = rays.detach() if isinstance(rays, torch.Tensor) else rays
-        return render_core.render_rays(detached, near, far, coarse_model, fine_model, coarse_sample_num, fine_sample_num,
-                                       t_rand=t_rand, seed=seed, film=film, ray0=ray0)
-    # not ops._f32c, which detaches: the graph to `rays` has to survive into the Function
-    rays = rays.to(device=pf_c.device, dtype=torch.float32).reshape(-1, 2, 3).contiguous()
+    outs = _not_wanted(rays, render_core.render_rays, near, far, coarse_model, fine_model, coarse_sample_num, fine_sample_num,
+                       t_rand=t_rand, seed=seed, film=film, ray0=ray0)
+    if outs is not None:
+        return outs
+    rays = _lib.f32c(rays, pf_c.device, detach=False).reshape(-1, 2, 3)
     film = fields.resolve_film(film, (pf_c, coarse_model), (pf_f, fine_model))
-    return _RenderRaysPoseFn.apply(pf_c, pf_f, rays, float(near), float(far), int(coarse_sample_num), int(fine_sample_num),
-                                   film, None if t_rand is None else t_rand.detach(), int(seed or 0), int(ray0),
-                                   *fields.pair_params(pf_c, pf_f))
+    # autograd.render_rays_train's call, but on rays that keep their graph: the backward then also gives dL/d(rays)
+    return autograd._RenderRaysFn.apply(pf_c, pf_f, rays, float(near), float(far), int(coarse_sample_num),
+                                        int(fine_sample_num), film, None if t_rand is None else t_rand.detach(), int(seed or 0),
+                                        int(ray0), *fields.pair_params(pf_c, pf_f))
 
 
 def render_image_tensor(width, height, focal, c2w, near, far, coarse_model, fine_model, coarse_sample_num,
@@ -170,18 +150,6 @@ def render_image_tensor(width, height, focal, c2w, near, far, coarse_model, fine
     return (parts[0] if len(parts) == 1 else torch.cat(parts)).reshape(height, width, 3)
 
 
-class _FieldPointsFn(torch.autograd.Function):
-    """autograd._FieldFn over free-standing points (pf, x [M,6], None, film, *params) whose backward also returns dL/dx
-    (mi_field_input_grad): the same forward, the same backward calls plus the input gradient after each range's."""
-
-    forward = staticmethod(autograd._FieldFn.forward)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g_raw):
-        return autograd._FieldFn.backward(ctx, g_raw, input_grad=True)
-
-
 def field_eval_points(pf_or_module, x, film=None):
     """network(x [M,6]) -> [M,4] (nerf/render.py:73) on the fused kernels with a gradient to x as well as to the
     parameters and the FiLM table.  `pf_or_module`: a fused module or its PackedField."""
@@ -192,7 +160,7 @@ def field_eval_points(pf_or_module, x, film=None):
     if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[1] != 6:
         raise _lib.MiRenderError(f"expected inputs [M,6], got {tuple(getattr(x, 'shape', ()))}")
     film = fields.resolve_film(film, (pf, pf_or_module))
-    if not (torch.is_grad_enabled() and x.requires_grad) or x.shape[0] == 0:
+    if not _lib.wants_grad(x) or x.shape[0] == 0:
         return autograd.field_eval_points(pf, x.detach(), film)
-    x = x.to(device=pf.device, dtype=torch.float32).contiguous()          # not detached: the graph to x has to survive
-    return _FieldPointsFn.apply(pf, x, None, film, *pf.params).reshape(-1, 4)
+    # autograd.field_eval_points' call, but on points that keep their graph: the backward then also gives dL/dx
+    return autograd._FieldFn.apply(pf, _lib.f32c(x, pf.device, detach=False), None, film, *pf.params).reshape(-1, 4)

@@ -117,19 +117,14 @@ def _eval_pass(model, pf, rays, z, film):
     return autograd.field_eval_rays(pf, rays, z, fields.resolve_film(film, (pf, model)))
 
 
-def _check_grid(grid, pf_c, pf_f, film):
-    """What rendering with an occupancy grid is not built for, said by name."""
-    if pf_c is None or pf_f is None:
-        raise _lib.MiRenderError("rendering with an occupancy grid is not built for callables with no known layout "
-                                 "(the generic path): both models must be NeRF, SirenNeRF or TinyNeRF fields")
-    if fields.is_film(pf_c.kind) or fields.is_film(pf_f.kind):
-        raise _lib.MiRenderError("rendering with an occupancy grid is not built for FiLM fields (a FiLM field's table is per "
-                                 "image, a per-scene grid has no meaning there)")
-    if fields.needs_graph(None, pf_c, pf_f):
-        raise _lib.MiRenderError("rendering with an occupancy grid is not built for calls that need gradients (training): "
-                                 "call it under torch.no_grad()")
-    if torch.device(grid.device) != torch.device(pf_c.device):
-        raise _lib.MiRenderError(f"the occupancy grid is on {grid.device}, the fields are on {pf_c.device}")
+def _check_grid(grid, pf_c, pf_f):
+    """What rendering with an occupancy grid is not built for (fields.refuse_grid_call) and, between its refusals, this
+    module's own."""
+    def own():
+        if fields.needs_graph(None, pf_c, pf_f):
+            raise _lib.MiRenderError("rendering with an occupancy grid is not built for calls that need gradients (training): "
+                                     "call it under torch.no_grad()")
+    fields.refuse_grid_call("rendering", grid, pf_c, pf_f, own)
 
 
 def render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, fine_sample_num, *,
@@ -156,14 +151,14 @@ def _render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, f
     return_counts=True (with a grid): (the outputs, int32 [calls, 2], the samples each pass evaluated; [0, 2] without rays)."""
     seed = _call_seed(seed, t_rand)
     dev = _device_of(coarse_model, fine_model, rays=rays)
-    # not ops._f32c, which detaches: on the generic path the graph to `rays` has to survive
-    rays = torch.as_tensor(rays).to(device=dev, dtype=torch.float32).reshape(-1, 2, 3).contiguous()
+    # not detached: on the generic path the graph to `rays` has to survive
+    rays = _lib.f32c(torch.as_tensor(rays), dev, detach=False).reshape(-1, 2, 3)
     nc, nf = int(coarse_sample_num), int(fine_sample_num)
     pf_c, pf_f = fields.as_packed_field(coarse_model), fields.as_packed_field(fine_model)
     if clip_probes is not None and grid is None:
         raise _lib.MiRenderError("clip_probes= clips each ray's range to an occupancy grid: it needs grid=")
     if grid is not None:
-        _check_grid(grid, pf_c, pf_f, film)
+        _check_grid(grid, pf_c, pf_f)
         if rays.shape[0]:
             outs, counts = ops.render_rays_occupancy(pf_c, pf_f, rays, near, far, nc, nf, grid, t_rand, seed or 0, ray0=ray0,
                                                      coarse_outputs=coarse_outputs, clip_probes=clip_probes, clip_pad=clip_pad)
@@ -171,7 +166,7 @@ def _render_rays(rays, near, far, coarse_model, fine_model, coarse_sample_num, f
     if rays.shape[0] == 0:
         # no rays (an empty batch, a rank of a group larger than the frame): six empty outputs; under autograd they hang
         # off the parameters with zero gradients, so a loss over an empty shard still backpropagates
-        outs = [torch.empty(s, dtype=torch.float32, device=dev) for s in ((0, 3), (0,), (0,), (0, 3), (0,), (0,))]
+        outs = ops._render_outputs(0, dev)
         leaves = [p for m in (coarse_model, fine_model) if isinstance(m, torch.nn.Module) for p in m.parameters() if p.requires_grad]
         # ... and off the FiLM source (the mapping network's output, a GAN-inversion leaf): a rank with an empty shard must
         # hand allreduce_grads the same set of gradients as every other rank

@@ -155,6 +155,72 @@ def test_pair_params_and_needs_graph():
     assert fields.needs_graph(None, a, b) and not fields.needs_graph(None, a)
 
 
+@pytest.mark.parametrize("n", [37, 0])
+def test_occupancy_workspace_bytes_is_the_sum_of_the_library_queries(n):
+    lib, nc, nf = _lib.load(), 8, 16
+    seen = set()
+    for train in (False, True):
+        for clip in (None, (64, 1)):
+            want = lib.mi_render_workspace_bytes(n, nc, nf)
+            want += (lib.mi_render_occupancy_train_extra_bytes if train else lib.mi_render_occupancy_extra_bytes)(n, nc, nf)
+            want += lib.mi_render_occupancy_clip_extra_bytes(n) if clip else 0
+            got = ops._occupancy_workspace_bytes(train, clip, n, nc, nf)
+            assert got == want and type(got) is int and (got > 0) == (n > 0), (train, clip)
+            seen.add(got)
+    assert len(seen) == (4 if n else 1)                       # the four calls' workspaces differ; without rays there is none
+
+
+GRID_REFUSALS = {
+    "rendering": ("rendering with an occupancy grid is not built for callables with no known layout (the generic path): both "
+                  "models must be NeRF, SirenNeRF or TinyNeRF fields",
+                  "rendering with an occupancy grid is not built for FiLM fields (a FiLM field's table is per image, a per-scene "
+                  "grid has no meaning there)"),
+    "training": ("training with an occupancy grid is not built for generic callables (models with no known layout): both models "
+                 "must be NeRF, SirenNeRF or TinyNeRF fields",
+                 "training with an occupancy grid is not built for FiLM kinds (a FiLM field's table is per image, a per-scene grid "
+                 "has no meaning there)"),
+}
+
+
+@pytest.mark.parametrize("doing", sorted(GRID_REFUSALS))
+def test_refuse_grid_call_says_what_each_call_always_said(doing):
+    film_pf, plain_pf = packed(fields.FilmSirenNeRF()), packed(fields.TinyNeRF())
+    here, there = types.SimpleNamespace(device="cpu"), types.SimpleNamespace(device="cuda:1")
+    no_layout, film_kinds = GRID_REFUSALS[doing]
+
+    def said(*args):
+        with pytest.raises(_lib.MiRenderError) as e:
+            fields.refuse_grid_call(doing, *args)
+        return str(e.value)
+    assert said(here, None, plain_pf) == no_layout and said(here, plain_pf, None) == no_layout
+    assert said(here, film_pf, plain_pf) == film_kinds and said(here, plain_pf, film_pf) == film_kinds
+    assert said(there, plain_pf, plain_pf) == "the occupancy grid is on cuda:1, the fields are on cpu"
+    # the caller's own refusals rank behind the two about the models and ahead of the one about the device
+    def own():
+        raise _lib.MiRenderError("the caller's own")
+    assert said(here, None, plain_pf, own) == no_layout and said(here, film_pf, plain_pf, own) == film_kinds
+    assert said(there, plain_pf, plain_pf, own) == "the caller's own"
+    fields.refuse_grid_call(doing, here, plain_pf, plain_pf)
+
+
+def test_pose_defines_no_function_but_get_rays():
+    from mirender import pose
+    own = [name for name, v in vars(pose).items()
+           if isinstance(v, type) and issubclass(v, torch.autograd.Function) and v.__module__ == pose.__name__]
+    assert own == ["_GetRaysFn"]
+
+
+def test_wants_grad_and_f32c_keep_or_cut_the_graph():
+    x = torch.ones(2, 3, dtype=torch.float64, requires_grad=True)
+    assert _lib.wants_grad(x) and not _lib.wants_grad(x.detach()) and not _lib.wants_grad(None) and not _lib.wants_grad([1.0])
+    with torch.no_grad():
+        assert not _lib.wants_grad(x)
+    kept, cut = _lib.f32c(x.t(), "cpu", detach=False), _lib.f32c(x.t(), "cpu")
+    assert kept.requires_grad and not cut.requires_grad and torch.equal(kept.detach(), cut)
+    assert all(t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (3, 2) for t in (kept, cut))
+    assert _lib.f32c(None, "cpu", detach=False) is None
+
+
 def test_ptr_array():
     ts = [torch.zeros(3), None, torch.zeros(5, dtype=torch.int32)]
     arr = _lib.ptr_array(ts)

@@ -73,7 +73,7 @@ UNSEEDED = {
     "render_core.render_image_tensor": lambda **kw: render_core.render_image_tensor(4, 4, 5.0, None, 2.0, 6.0, None, None, 8, 16, **kw),
     "occupancy_train.render_rays": lambda **kw: occupancy_train.render_rays(RAYS, 2.0, 6.0, None, None, 8, 16, grid=None, **kw),
     "occupancy_train._render_calls": lambda seed=None, t_rand=None: occupancy_train._render_calls(
-        None, PF, PF, RAYS, 2.0, 6.0, 8, 16, None, t_rand, seed, 0, None, None, 1),
+        PF, PF, RAYS, 2.0, 6.0, 8, 16, None, t_rand, seed, 0, None, None, 1),
     "pose.render_rays": lambda **kw: pose.render_rays(RAYS, 2.0, 6.0, None, None, 8, 16, **kw),
     "pose.render_rays(grid=)": lambda **kw: pose.render_rays(RAYS, 2.0, 6.0, None, None, 8, 16, grid=object(), **kw),
     "pose.render_image_tensor": lambda **kw: pose.render_image_tensor(4, 4, 5.0, None, 2.0, 6.0, None, None, 8, 16, **kw),
