@@ -172,5 +172,7 @@ int launch_merge_raw(int64_t n, int nc, int nf, const float* raw_c, const float*
                      hipStream_t stream);
 int launch_split_grad(int64_t n, int nc, int nf, const float* g_f, const int* pos, float* g_c, int accumulate_coarse,
                       float* g_s, hipStream_t stream);
+// out[0, count) = 0.f (zero bits: an int buffer's clear too), by a kernel: a captured hipMemsetAsync does not replay reliably
+int launch_clear_floats(int64_t count, float* out, hipStream_t stream);
 
 }  // namespace mi

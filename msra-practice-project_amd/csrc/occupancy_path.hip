@@ -249,21 +249,6 @@ static int occupancy_render(const char* fn, OccCall call, OccClip* clip, const O
     return occupancy_forward(fn, pass, train, grid, a.n, a.nc, a.nf, io, clip, a.evaluated, layout.carve(a.workspace), (hipStream_t)a.stream);
 }
 
-// g_rays = 0 ahead of the launches that add to it.  A kernel, not hipMemsetAsync: captured into a graph, the memset of n * 24
-// bytes did not leave the buffer cleared for the kernels behind it when the graph was replayed - rays.grad came back with whatever
-// the graph's pool had last kept in that memory added in (tests/test_gpu_graph_occupancy.py, the pose cases at n = 67: 1 608
-// bytes, 8 over a multiple of 16, a size the runtime clears in two pieces).  Eager calls never showed it.
-__global__ __launch_bounds__(256) void clear_floats_kernel(int64_t count, float* __restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < count) out[i] = 0.f;
-}
-
-static int launch_clear_floats(int64_t count, float* out, hipStream_t hs) {
-    if (count <= 0) return MI_OK;
-    hipLaunchKernelGGL(clear_floats_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, hs, count, out);
-    return check_launch("clear_floats");
-}
-
 // a field whose input gradient a backward computes has its parameter tensors (device pointers, state-dict order), every one
 static int check_field_params(const char* fn, const char* which, int kind, const float* const* params, int n_params) {
     if (!params) { set_error("%s: null pointer argument (the %s field's parameters)", fn, which); return MI_EINVAL; }
@@ -312,6 +297,8 @@ static int occupancy_backward(const char* fn, int kind_coarse, const float* pack
     a.saved = const_cast<void*>(saved); a.saved_bytes = saved_bytes;
     if (int rc = check_buffers(fn, OCC_BACKWARD, a, false, shared != 0, bwd_workspace, bwd_workspace_bytes)) return rc;
     hipStream_t hs = (hipStream_t)stream;
+    // g_rays = 0 ahead of the launches that add to it, by a kernel (render_stages.hip: a captured memset of these n * 24 bytes
+    // did not clear them on replay - tests/test_gpu_graph_occupancy.py, the pose cases)
     if (g_rays) if (int rc = launch_clear_floats(n * 6, g_rays, hs)) return rc;
     if (!want_c && !want_f) return MI_OK;
     const OccBwdLayout L(kind_coarse, kind_fine, shared != 0, n, n_coarse, n_fine);

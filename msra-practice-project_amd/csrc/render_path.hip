@@ -53,7 +53,7 @@ static int coarse_sigma_windows(int kind, const float* packed, const float* rays
     int* list[2] = {scratch, scratch + n};
     int* counts = scratch + 2 * n;
     const double stop = depth_c || acc_c ? kStopZeroWeight : kStopBelowPdfEps;
-    if (hipMemsetAsync(counts, 0, sizeof(int) * rounds, hs) != hipSuccess) { set_error("mi_render_rays: hipMemsetAsync failed"); return MI_EHIP; }
+    if (int rc = launch_clear_floats(rounds, (float*)counts, hs)) return rc;     // render_stages.hip: why not a memset node
     MlpArgs args = {};
     args.packed = packed; args.a = rays; args.z = z_c; args.out = sigma;
     args.n_samples = n_coarse; args.mode = 1; args.n_rays = n; args.win_log2 = kCoarseWindowLog2;
@@ -86,13 +86,13 @@ static bool can_defer_colour(int kind, int64_t n, int S) { return has_deferred_c
 // The field over n rays of S samples with its colour branch deferred to the points with sigma > 0, in chunks of whole rays:
 // per chunk a trunk-and-spill launch ({0, 0, 0, sigma} for every point, H8 rows and indices of the live ones into `extra`)
 // and a colour launch over that list.  A point with sigma == 0 keeps r = g = b = 0: its weight is exactly 0, so 0 * rgb
-// is the +0 that any finite colour gives.  Every chunk has its own count, cleared by one memset node; all launches on `hs`
+// is the +0 that any finite colour gives.  Every chunk has its own count, cleared by one kernel launch; all launches on `hs`
 // with grids from host values (no read-back: graph-capturable).  `extra`: DeferredColourBuf(n, S, colour_chunk_rows()).
 static int eval_rays_deferred_colour(int kind, const float* packed, const float* rays, const float* z, int64_t n, int S,
                                      float* raw, void* extra, hipStream_t hs) {
     const DeferredColourBuf buf(n, S, colour_chunk_rows());
     const DeferredColourBuf::Regions r = buf.carve(extra);
-    if (hipMemsetAsync(r.counts, 0, sizeof(int) * buf.n_chunks, hs) != hipSuccess) { set_error("deferred colour: hipMemsetAsync failed"); return MI_EHIP; }
+    if (int rc = launch_clear_floats(buf.n_chunks, (float*)r.counts, hs)) return rc;
     MlpArgs args = {};
     args.packed = packed; args.n_samples = S; args.mode = 1;
     for (int64_t i = 0; i < buf.n_chunks; ++i) {

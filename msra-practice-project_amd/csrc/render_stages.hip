@@ -9,6 +9,7 @@
 //   sample_fine_kernel    sample_pdf + detach/cat/sort   nerf/render.py:27-56, 140-142
 //   sample_pdf_kernel     sample_pdf alone
 //   sample_coarse_bounds_kernel / sample_fine_kernel<true>   the two samplers over a range per ray (clipping to an occupancy grid)
+//   clear_floats_kernel   zeroes a buffer inside a call's launch sequence, where a captured memset node does not replay
 //
 // Each computation is stated once: every compositing kernel takes its weights and transmittances from composite_pass
 // (with sample_delta and ray_norm) under the G that dispatch_G picks, and both sampling kernels draw through
@@ -876,6 +877,24 @@ int launch_sample_fine_bounds(int64_t n, const float* bounds, int nc, int nf, co
                               const float* weights, float* z_samples, float* z_fine, int* pos, hipStream_t stream) {
     return launch_sample_fine_as<true>("sample_fine_bounds", n, 0.f, 0.f, nc, nf, bounds, u_lin, z_coarse, weights, z_samples,
                                        z_fine, pos, stream);
+}
+
+// ---------------------------------------------------------------------------------------
+// out[0, count) = 0.f - and zero bits are zero ints: the clear of every buffer that launches behind it add to (g_rays of
+// the occupancy backward) or count into (the live counts of the windowed coarse pass and of the deferred colour branch).
+// A kernel, not hipMemsetAsync: captured into a graph, a memset of more than 12 bytes, or one that crosses a 16-byte
+// line, cleared its bytes on the first replay only (tools/probes/graph_memset_probe.py, profiles/graph_memset_probe.log;
+// DESIGN.md 4.8 "In a graph").  Eager calls never showed it.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void clear_floats_kernel(int64_t count, float* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < count) out[i] = 0.f;
+}
+
+int launch_clear_floats(int64_t count, float* out, hipStream_t stream) {
+    if (count <= 0) return 0;
+    hipLaunchKernelGGL(clear_floats_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, count, out);
+    return check_launch("clear_floats");
 }
 
 }  // namespace mi
