@@ -603,14 +603,27 @@ struct PointIn {
 };
 
 // |d| of a ray direction with its roundings stated: the rounded d0 d0, d1 d1 added by one fma, then the rounded d2 d2 added.
-// This is what load_point's / load_window_point's norm compiles to in every instance (the compiler multiplies d0, d2 as a
-// pair and contracts the first sum only); a kernel that must reproduce their view direction from another code shape
-// (nerf_colour_kernel) cannot leave the contraction to the compiler - its own choice there was two fmas, one ulp away on one
-// ray in twenty.  tests/test_gpu_deferred_colour.py holds the two against each other bit for bit.
+// This is what load_point's / load_window_point's norm compiled to in every instance while it was left to the compiler (it
+// multiplied d0, d2 as a pair and contracted the first sum only), and what they call now; a kernel that must reproduce their
+// view direction from another code shape (nerf_colour_kernel) could not leave the contraction to the compiler either - its
+// own choice there was two fmas, one ulp away on one ray in twenty.  tests/test_gpu_deferred_colour.py holds the two against
+// each other bit for bit.
 __device__ __forceinline__ float dir_norm(float d0, float d1, float d2) {
 #pragma clang fp contract(off)
     const float s01 = __builtin_fmaf(d1, d1, d0 * d0);
     return sqrtf(s01 + d2 * d2);
+}
+
+// One coordinate of a point on a ray: fl(o + fl(d z)), a rounded product and a rounded sum like the reference's
+// rays_o + rays_d * z (render.py:134).  Written with the operators under contract(off): __fmul_rn / __fadd_rn are the plain
+// operators in HIP's headers, compiled there with the default contraction, and the compiler was free to fuse them into one
+// fma (it did in the NeRF kernels: a point one ulp beside the reference's on some coordinates, 2^9 ulp of angle in the
+// encoding's last frequency).  tests/test_gpu_prologue_gates.py holds the saved points to the two-rounding expression bit
+// for bit.
+__device__ __forceinline__ float ray_point(float o, float d, float z) {
+#pragma clang fp contract(off)
+    const float dz = d * z;
+    return o + dz;
 }
 
 // mode 0: x[M,6] points; mode 1: rays[N,2,3] + z[N,S].
@@ -629,10 +642,10 @@ __device__ __forceinline__ PointIn load_point(int mode, const float* __restrict_
         const float zz = zv[o.p];
         const float d0 = r[3], d1 = r[4], d2 = r[5];
         // render.py:134 pts = o + d*z (separate mul/add), :122 view = d / ||d||
-        o.px = __fadd_rn(r[0], __fmul_rn(d0, zz));
-        o.py = __fadd_rn(r[1], __fmul_rn(d1, zz));
-        o.pz = __fadd_rn(r[2], __fmul_rn(d2, zz));
-        const float nrm = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(d0, d0), __fmul_rn(d1, d1)), __fmul_rn(d2, d2)));
+        o.px = ray_point(r[0], d0, zz);
+        o.py = ray_point(r[1], d1, zz);
+        o.pz = ray_point(r[2], d2, zz);
+        const float nrm = dir_norm(d0, d1, d2);
         o.dx = d0 / nrm; o.dy = d1 / nrm; o.dz = d2 / nrm;
     }
     return o;
@@ -653,10 +666,10 @@ __device__ __forceinline__ PointIn load_window_point(const MlpArgs& a, int64_t t
     const float* r = a.a + ray * 6;
     const float zz = a.z[o.p];
     const float d0 = r[3], d1 = r[4], d2 = r[5];
-    o.px = __fadd_rn(r[0], __fmul_rn(d0, zz));
-    o.py = __fadd_rn(r[1], __fmul_rn(d1, zz));
-    o.pz = __fadd_rn(r[2], __fmul_rn(d2, zz));
-    const float nrm = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(d0, d0), __fmul_rn(d1, d1)), __fmul_rn(d2, d2)));
+    o.px = ray_point(r[0], d0, zz);
+    o.py = ray_point(r[1], d1, zz);
+    o.pz = ray_point(r[2], d2, zz);
+    const float nrm = dir_norm(d0, d1, d2);
     o.dx = d0 / nrm; o.dy = d1 / nrm; o.dz = d2 / nrm;
     return o;
 }

@@ -164,8 +164,16 @@ def test_field_grads_vs_oracle_autograd_injected(kind, n, nc, nf, sharp):
                              elem_tol=parity.GRAD_ELEM_TOL_SMOOTH if smooth else None, check=False) for name, t in pairs]
     bad = [r for r in recs if not r["passed"]]
     assert not bad, bad[0]
-    # most tensors see no flip at all and agree to fp32 rounding
-    assert sum(r["rel_l2_err"] <= 3e-4 for r in recs) >= len(pairs) // 2
+    # most tensors see no flip at all and agree to fp32 rounding: with the fp64 oracle, or - where the fp32 oracle itself sits
+    # further from it than that - with the fp32 oracle.  The kernels evaluate the oracle's fp32 points o + d z bit for bit
+    # (tests/test_gpu_prologue_gates.py), and the rounding of a point is 2^9 times larger in the encoding's last frequency
+    # than anything the layers add: on 300 rays the oracle's own fp32 gradients are 6e-4 .. 1.7e-3 from fp64 in 20 of 24
+    # tensors, and the HIP path's with them (measured: at most 2e-4 from the fp32 oracle's, 1.7e-3 from fp64 like its own).
+    for r, (name, t) in zip(recs, pairs):
+        r32 = refs[torch.float32][name].reshape(-1)
+        r["rel_l2_vs_oracle32"] = float(torch.linalg.norm(t.cpu().double().reshape(-1) - r32) / max(float(torch.linalg.norm(r32)), 1e-30))
+    assert sum(r["rel_l2_err"] <= 3e-4 or (r["oracle32_rel_l2_from_fp64"] > 3e-4 and r["rel_l2_vs_oracle32"] <= 3e-4)
+               for r in recs) >= len(pairs) // 2
     # the recompute path (above: nothing kept) gives the same gradients as the kept-activation path
     if not is_film:
         raw_s, saved = A._forward_pass(pf, rays_d, z_d, film_d, 1 << 40)
